@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- the headline metric of BASELINE.json on MI355X (and, with --config, its other configurations).
 
-  metric : SBS frames/s (+ achieved HBM GB/s) for 4K (3840x2160) forward warp + polylines_soft hole fill,
+  metric : SBS frames/s (--full: + achieved HBM GB/s) for 4K (3840x2160) forward warp + polylines_soft hole fill,
            divergence 8.0, left-right side-by-side, stepped synthetic depth, widget defaults otherwise
            (direction-aware depth blur ON: strength 20, threshold 20, falloff 2.0, vert 6).
   step   : one pass of the whole hot path (cs_generate: gray depth + min/max, depth blur, warp + fill +
@@ -10,18 +10,26 @@
            ends with the RCCL all-gather that reassembles the stereoscope tensor on every rank.
 
   python bench.py [--gpus N --steps K --warmup W] [--config metric|cfg2|cfg3|cfg4|cfg5] [--frames F] [--no-blur]
-                  [--no-cpu-baseline] [--verify]
+                  [--dump-outputs DIR] [--full [--no-cpu-baseline]] [--verify]
   N > 1:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task description) with extra objects:
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps, writes the outputs if asked and prints
+the headline (metric, value, unit, higher_is_better, dtype, ms_per_step: the milliseconds of one timed step).
+--dump-outputs DIR: after the timed steps, the arrays the last step handed its caller (stereoscope, depth_left, depth_right,
+mask; N > 1: what the rank-0 step returns) as DIR/<name>.npy in float32 -- whole arrays up to DUMP_SAMPLE elements, beyond that
+the same seeded sample of flat positions every run (the inputs are seeded too: two builds compare output for output).
+--full adds the extra objects below (each extra leg is timed over K steps of its own):
   roofline     : dominant kernel of the configuration -- algorithmic bytes per launch / its mean duration measured with HIP
-                 events on the launch stream inside the timed region
+                 events on the launch stream inside the timed region (the profiling hook is on only under --full)
+  diagnostics  : per-frame stats words of the timed plan (rows redone / replayed, kernel error flags)
   cpu_baseline : the CPU oracle (C port of the reference's D32 arithmetic) on a bounded sample of the same workload:
                  1 thread; all host cores as OpenMP over rows in one process (the analogue of the reference's numba prange);
                  64 single-threaded processes, a frame each
   value_blur_off (metric config, N = 1): the same workload with the depth blur switched off
   value_dialect_d64 (metric config, N = 1): the same workload under dialect D64 (what an install of the reference with numba computes)
+  value_other_depths (metric config, N = 1): the same workload on radial / blobs / scene8 depth
   split        (N > 1): kernels only / kernels + all-gather / end to end
+  ranks        (N > 1): what the collective library spans (an all-reduce of ones, every rank's device)
 """
 import argparse
 import ctypes
@@ -35,6 +43,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 HBM_PEAK_GBS = 8000.0
+# --dump-outputs: elements kept per output array (12 MiB of float32; the four outputs of a step stay under 64 MB together)
+DUMP_SAMPLE = 3 << 20
+DUMP_SEED = 20250101
 
 # BASELINE.json configs.  bytes_px: algorithmic bytes per source pixel at the float32 node boundary
 # (80: SBS + output-shaped mask, 76: gpu_warp SBS with the eye-shaped mask, 64: anaglyph).
@@ -133,6 +144,22 @@ def cpu_baseline(cfg, frames_sample, blur, seconds_budget=12.0):
                                     f"{os.cpu_count()} host cores, {dta:.1f} s ({mean_s:.2f} s per frame per core)"}}
 
 
+def dump_outputs(torch, outputs, out_dir):
+    """Write each device tensor of `outputs` ({name: tensor}) as out_dir/<name>.npy in float32: whole when it has at most
+    DUMP_SAMPLE elements, otherwise DUMP_SAMPLE flat positions drawn with a fixed seed (sorted; the same for every run of
+    the same shape), so that two runs with the same arguments write comparable files."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in outputs.items():
+        n = t.numel()
+        if n > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_SAMPLE, dtype=np.int64))
+            arr = t.reshape(-1)[torch.from_numpy(idx).to(t.device)].to(torch.float32).cpu().numpy()
+        else:
+            arr = t.to(torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}.npy"), arr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -145,14 +172,20 @@ def main():
                     help="replace the config's synthetic depth: clipped = saturated to exact 0 / 1 over large areas (exact closeness "
                          "ties: order-dependent rows, the stretch replay kernel), random8 = 8-bit noise (every row replayed whole), "
                          "scene8 = an 8-bit gradient with flat ellipses (quantised smooth depth with object silhouettes)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: roofline and diagnostics of the timed run, the "
+                         "blur-off / other-depth / D64 legs, the CPU baseline, the N > 1 split and rank report")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32; a seeded sample "
+                         f"of {DUMP_SAMPLE} elements of an array larger than that)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-frames", type=int, default=8)
     ap.add_argument("--verify", action="store_true", help="N > 1: check the reassembled float32 batch against a local float32 run")
     ap.add_argument("--gather", default="collective", choices=["collective", "p2p", "none"],
                     help="N > 1: all_gather_into_tensor (RCCL), the direct peer fan-out (batched send / recv to every peer), or none: "
                          "every rank keeps the float32 results of its own frame block (sharding.generate_sharded(..., gather=()), the "
                          "deployment form of DESIGN.md section 6) -- `value` is then the kernels-only rate and the config says so")
-    ap.add_argument("--no-other-depths", action="store_true", help="metric config, N = 1: skip the radial / blobs depth lines")
+    ap.add_argument("--no-other-depths", action="store_true", help="--full, metric config, N = 1: skip the radial / blobs depth lines")
     a = ap.parse_args()
     cfg = dict(CONFIGS[a.config])
     frames = a.frames or cfg["frames"]
@@ -232,6 +265,12 @@ def main():
         else:
             gathered_f32[0] = sharding.all_gather_frames(plan.run(image, depth)[0], bounds, method=a.gather)
 
+    def step_outputs():
+        """The arrays the last step handed its caller (N > 1: the reassembled stereoscope, or this rank's block with --gather none)."""
+        if world == 1 or no_gather:
+            return {"stereoscope": plan.stereo, "depth_left": plan.depth_l, "depth_right": plan.depth_r, "mask": plan.mask}
+        return {"stereoscope": job.gathered if job is not None else gathered_f32[0]}
+
     def fence():
         torch.cuda.synchronize()
         if world > 1:
@@ -252,7 +291,7 @@ def main():
         return dt
 
     ranks = None
-    if world > 1:   # what the collective library really spans: an all-reduce of ones, every rank's device
+    if world > 1 and a.full:   # what the collective library really spans: an all-reduce of ones, every rank's device
         ones = torch.ones(1, dtype=torch.int32, device=device)
         dist.all_reduce(ones)
         devs = [None] * world
@@ -264,17 +303,21 @@ def main():
     for _ in range(a.warmup):
         step()
     fence()
-    L.cs_profile(1)
+    if a.full:
+        L.cs_profile(1)
     dt = timed(step, a.steps)
-    tot_ms, launches = ctypes.c_double(), ctypes.c_int()
-    _native.check(L.cs_profile_read(ctypes.byref(tot_ms), ctypes.byref(launches)))
-    L.cs_profile(0)
-    fallback_rows = sum(int(q.stats()[:, 10].sum()) for q in plans)
-    tile_redo_rows = sum(int(q.stats()[:, 11].sum()) for q in plans)
-    err_flags = sum(int(q.stats()[:, 9].sum()) for q in plans)
+    if a.full:
+        tot_ms, launches = ctypes.c_double(), ctypes.c_int()
+        _native.check(L.cs_profile_read(ctypes.byref(tot_ms), ctypes.byref(launches)))
+        L.cs_profile(0)
+        fallback_rows = sum(int(q.stats()[:, 10].sum()) for q in plans)
+        tile_redo_rows = sum(int(q.stats()[:, 11].sum()) for q in plans)
+        err_flags = sum(int(q.stats()[:, 9].sum()) for q in plans)
+    if a.dump_outputs and rank == 0:   # (before any extra leg of --full reuses the buffers)
+        dump_outputs(torch, step_outputs(), a.dump_outputs)
 
     split = None
-    if world > 1 and not no_gather:  # kernels only / + all-gather / end to end, each timed like the headline
+    if world > 1 and not no_gather and a.full:  # kernels only / + all-gather / end to end, each timed like the headline
         dt_k = timed(compute_only, a.steps)
         dt_g = timed((lambda: step(expand=False)), a.steps) if job is not None else dt
         split = {"kernels_only_fps": frames * a.steps / dt_k, "kernels_plus_allgather_fps": frames * a.steps / dt_g,
@@ -283,14 +326,14 @@ def main():
                          if job is not None else "gpu_warp: float32 all-gather, no expansion step"}
 
     value_blur_off = None
-    if world == 1 and a.config == "metric" and blur:
+    if world == 1 and a.config == "metric" and blur and a.full:
         plan_off = engine.Plan(params(nloc, False), device)
         plan_off.run(image, depth)
         value_blur_off = frames * a.steps / timed(lambda: plan_off.run(image, depth), a.steps)
         del plan_off
 
     value_other_depths = None
-    if world == 1 and a.config == "metric" and not a.depth and not a.no_other_depths:
+    if world == 1 and a.config == "metric" and not a.depth and not a.no_other_depths and a.full:
         # the same workload on depth maps without plateaus (a gain that only exists on the stepped depth's flat
         # regions must be visible as such): radial = the stepped map before quantisation, blobs = smooth random hills
         value_other_depths = {}
@@ -311,7 +354,7 @@ def main():
     # the same workload under dialect D64 -- what an install of the reference WITH numba computes (float64 disparity chain + numba's typing
     # of the polylines sweep; derived typing): in the point kernel since round 6.  Reported next to the metric, never as it.
     value_dialect_d64 = None
-    if world == 1 and a.config == "metric" and not a.depth and not a.no_other_depths:
+    if world == 1 and a.config == "metric" and not a.depth and not a.no_other_depths and a.full:
         try:
             engine.DIALECT = "D64"
             plan64 = engine.Plan(params(nloc), device)
@@ -347,8 +390,9 @@ def main():
         # [verify] line of another rank landing inside it cost tests/test_gpu_sharded.py one run in ten sessions)
         sys.stdout.flush()
         dist.barrier()
-    if rank == 0:
-        fps = frames * a.steps / dt
+
+    def roofline_report():
+        """--full: the dominant kernel's bytes over its HIP-event time in the timed steps, against the HBM and issue roofs."""
         kern_ms = tot_ms.value / max(launches.value, 1)
         # launches of the dominant kernel per step: cs_generate cuts a batch into frame chunks (the pre-pass of chunk c + 1
         # runs under the warp of chunk c on a second stream), the sharded job into all-gather chunks
@@ -424,6 +468,10 @@ def main():
                     "achieved_own_bytes": achieved_own, "frac_own_bytes": achieved_own / HBM_PEAK_GBS, "own_bytes_per_launch": own_bytes,
                     "frac_node_bytes": achieved / HBM_PEAK_GBS,
                     "pipeline_achieved": pipeline, "pipeline_frac": pipeline / HBM_PEAK_GBS, "valu": valu}
+        return roofline
+
+    if rank == 0:
+        fps = frames * a.steps / dt
         line = {
             "metric": cfg["name"], "value": fps, "unit": "frames/s", "n_gpus": world,
             "steps": a.steps, "warmup": a.warmup, "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True,
@@ -436,10 +484,11 @@ def main():
                            "(gather=())); value = frames of all ranks / slowest rank's kernel time" if no_gather else
                            f"all_gather(stereoscope as uint8 codes) over RCCL in {job.n_chunks} chunk(s) overlapped with compute"
                            " + expand to float32 on every rank" if job is not None else "all_gather(stereoscope float32) over RCCL")},
-            "roofline": roofline,
-            "diagnostics": {"rows_redone_by_general_kernel": tile_redo_rows, "rows_replayed_sequentially": fallback_rows,
-                            "kernel_error_flags": err_flags},
         }
+        if a.full:
+            line["roofline"] = roofline_report()
+            line["diagnostics"] = {"rows_redone_by_general_kernel": tile_redo_rows, "rows_replayed_sequentially": fallback_rows,
+                                   "kernel_error_flags": err_flags}
         if value_blur_off is not None:
             line["value_blur_off"] = value_blur_off
         if value_other_depths is not None:
@@ -450,9 +499,9 @@ def main():
             line["split"] = split
         if ranks is not None:
             line["ranks"] = ranks
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(cfg, a.cpu_frames, blur)
-        elif not a.no_cpu_baseline:
+        elif a.full and not a.no_cpu_baseline:
             line["cpu_baseline"] = None
         print(json.dumps(line), flush=True)
     if world > 1:

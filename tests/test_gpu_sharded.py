@@ -124,7 +124,7 @@ def test_bench_two_ranks_verify(config, frames, gather):
     env = dict(os.environ, CS_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--config", config, "--frames", str(frames), "--verify", "--no-cpu-baseline", "--gather", gather]
+           "--config", config, "--frames", str(frames), "--verify", "--full", "--no-cpu-baseline", "--gather", gather]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert r.stdout.count("[verify] rank") == 2 and "MISMATCH" not in r.stdout
@@ -159,7 +159,7 @@ def test_bench_two_gpus_over_rccl_verify(config, frames, gather):
     env.pop("CS_BENCH_BACKEND", None)   # -> nccl
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--config", config, "--frames", str(frames), "--verify", "--no-cpu-baseline", "--gather", gather]
+           "--config", config, "--frames", str(frames), "--verify", "--full", "--no-cpu-baseline", "--gather", gather]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert r.stdout.count("[verify] rank") == 2 and "MISMATCH" not in r.stdout
