@@ -38,6 +38,19 @@ DEBUG = {"dbg": 0, "no_tile": 1, "pt_variant": 2, "blur_two_pass": 3, "blur_edge
          "blur_no_pre_edges": 8, "hybrid_unfused": 9, "gpuwarp_full_maps": 10,
          "hybrid_full_maps": 11}
 
+# stats word ST_WARP_PATH (Plan.stats()[:, 12]): the gpu_warp kernel instantiation that warped a frame (cs_common.h GW_PATH_*, the
+# list this mirrors; 0: no gpu_warp kernel ran).  Names: kernel<MINW, POW> (POW -1: exponent at run time); "node" -- the node's
+# interleaved layout compiled in, "gen" -- forward_warp_gpu's keyword parameters away from their defaults
+ST_WARP_PATH = 12
+WARP_PATH = {
+    "q<8,2>": 1, "q<8,-1>": 2, "q<6,2>": 3, "q<6,-1>": 4,
+    "k<8,2,node>": 5, "k<8,-1,node>": 6, "k<6,2,node>": 7, "k<6,-1,node>": 8,
+    "k<8,2>": 9, "k<8,-1>": 10, "k<6,2>": 11, "k<6,-1>": 12,
+    "k<8,gen>": 13, "k<6,gen>": 14,
+    "mesh<8>": 15, "mesh<6>": 16,
+}
+WARP_PATH_NAME = {v: k for k, v in WARP_PATH.items()}
+
 
 class Params(ctypes.Structure):
     """struct cs_params (include/comfystereo_amd.h)."""

@@ -24,7 +24,30 @@ enum {
     ST_ERROR = 9,  // set by kernels on internal capacity overflow (diagnostics)
     ST_FALLBACK_ROWS = 10,  // polylines: rows that took the sequential path (diagnostics)
     ST_TILE_REDO_ROWS = 11,  // polylines: rows the tiled fast path handed to the general row kernel
+    ST_WARP_PATH = 12,  // gpu_warp: the kernel instantiation that warped the frame (GW_PATH_* below; 0: no gpu_warp kernel ran)
     ST_WORDS = 16
+};
+
+// The gpu_warp kernel instantiations gw_launch chooses from (cs_gpuwarp.hip), as recorded in ST_WARP_PATH: one code per
+// kernel x MINW (waves per SIMD) x POW (2: exponent 2 compiled in, -1: exponent at run time) x layout.  The one list of them:
+// comfystereo_amd/_native.py WARP_PATH mirrors it (tests/test_abi_exports.py checks the two agree).
+enum {
+    GW_PATH_Q8_POW2 = 1,        // k_gpuwarp_q<8, 2>
+    GW_PATH_Q8_POWN = 2,        // k_gpuwarp_q<8, -1>
+    GW_PATH_Q6_POW2 = 3,        // k_gpuwarp_q<6, 2>
+    GW_PATH_Q6_POWN = 4,        // k_gpuwarp_q<6, -1>
+    GW_PATH_K8_POW2_NODE = 5,   // k_gpuwarp<8, 2, false, true>
+    GW_PATH_K8_POWN_NODE = 6,   // k_gpuwarp<8, -1, false, true>
+    GW_PATH_K6_POW2_NODE = 7,   // k_gpuwarp<6, 2, false, true>
+    GW_PATH_K6_POWN_NODE = 8,   // k_gpuwarp<6, -1, false, true>
+    GW_PATH_K8_POW2 = 9,        // k_gpuwarp<8, 2>  (generic layout)
+    GW_PATH_K8_POWN = 10,       // k_gpuwarp<8, -1>
+    GW_PATH_K6_POW2 = 11,       // k_gpuwarp<6, 2>
+    GW_PATH_K6_POWN = 12,       // k_gpuwarp<6, -1>
+    GW_PATH_K8_GEN = 13,        // k_gpuwarp<8, -1, true>  (forward_warp_gpu's keyword parameters away from their defaults)
+    GW_PATH_K6_GEN = 14,        // k_gpuwarp<6, -1, true>
+    GW_PATH_MESH8 = 15,         // k_meshwarp<8>
+    GW_PATH_MESH6 = 16,         // k_meshwarp<6>
 };
 
 namespace cs {

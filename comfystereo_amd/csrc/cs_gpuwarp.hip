@@ -1263,7 +1263,8 @@ __global__ void __launch_bounds__(1024, MINW) k_meshwarp(GwArgs A) {
 // refined reciprocals, the key decoding: ~170 of the 470 vector instructions a wave spent per eye on 3.75 columns): per frame
 // GWC_WORDS floats -- per eye {dmin, clamped range, its refined reciprocal, flags: bit 0 has_range, bit 1 range inside the division
 // core's reach, bit 2 divide by 255}, then the refined reciprocal of w - 1, the scale the kernel multiplies with, the frame's x255 flag.
-__global__ void k_gpuwarp_flags(uint32_t* stats, int n, int group, float* fconst, int w, int scale_from_stats) {
+// Also the frame's ST_WARP_PATH word: `path`, the instantiation gw_launch runs (GW_PATH_*; a diagnostics word that costs no launch).
+__global__ void k_gpuwarp_flags(uint32_t* stats, int n, int group, float* fconst, int w, int scale_from_stats, int path) {
     int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= n) return;
     int g0 = (f / group) * group, g1 = min(g0 + group, n);
@@ -1274,6 +1275,7 @@ __global__ void k_gpuwarp_flags(uint32_t* stats, int n, int group, float* fconst
     }
     stats[f * ST_WORDS + ST_WARP_DIV255_L] = fl;
     stats[f * ST_WORDS + ST_WARP_DIV255_R] = fr;
+    stats[f * ST_WORDS + ST_WARP_PATH] = (uint32_t)path;
     if (!fconst) return;
     float* C = fconst + (size_t)f * GWC_WORDS;
     for (int e = 0; e < 2; e++) {
@@ -1338,22 +1340,17 @@ static int gw_rounds(double gradient_threshold, int max_stretch) {
 }
 static int pow_mode_of(double e) { return e == 1.0 ? 0 : e == 0.5 ? 1 : e == 2.0 ? 2 : e == 3.0 ? 3 : e == 0.0 ? 5 : 4; }
 
-static int gw_launch(GwArgs& A, hipStream_t stream) {
+// The kernel instantiation of a call (GW_PATH_* in cs_common.h), its workgroup size and dynamic LDS: chosen on the host from the
+// arguments alone, before k_gpuwarp_flags, which records the code in every frame's ST_WARP_PATH word.
+struct GwPlan { int path, threads; size_t lds; };
+static int gw_select(GwArgs& A, GwPlan& P) {
     A.lin_step = A.h > 1 ? 2.0f / (float)(A.h - 1) : 0.0f;
     if (A.mesh) {
         if (A.h < 2 || A.w < 2) return CS_EINVAL;   // the reference divides by H - 1 and W - 1
         if (A.w > meshwarp_max_width()) return CS_ELIMIT;
-        const int ngroups = (A.n + A.group - 1) / A.group;
-        const int threads = A.w <= 1024 ? 256 : (A.w <= 2048 ? 512 : 1024);
-        size_t lk = mesh_keep_lds_bytes(A.w), lm = mesh_lds_bytes(A.w);
-        hipError_t e = hipFuncSetAttribute((const void*)k_mesh_keep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lk);
-        if (e != hipSuccess) return CS_EHIP;
-        e = hipFuncSetAttribute(threads > 512 ? (const void*)k_meshwarp<8> : (const void*)k_meshwarp<6>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lm);
-        if (e != hipSuccess) return CS_EHIP;
-        hipLaunchKernelGGL(k_mesh_keep, dim3(A.h - 1, ngroups, A.neyes), dim3(threads > 512 ? 512 : threads), lk, stream, A);
-        if (threads > 512) hipLaunchKernelGGL(k_meshwarp<8>, dim3(A.h, A.n), dim3(threads), lm, stream, A);
-        else hipLaunchKernelGGL(k_meshwarp<6>, dim3(A.h, A.n), dim3(threads), lm, stream, A);
+        P.threads = A.w <= 1024 ? 256 : (A.w <= 2048 ? 512 : 1024);
+        P.lds = mesh_lds_bytes(A.w);
+        P.path = P.threads > 512 ? GW_PATH_MESH8 : GW_PATH_MESH6;
         return CS_OK;
     }
     // forward_warp_gpu's keyword parameters away from their defaults: the general instantiation
@@ -1375,49 +1372,83 @@ static int gw_launch(GwArgs& A, hipStream_t stream) {
     // the node's layout (interleaved image and output, every eye writes the three channels) has instantiations of its own
     bool node = !gen && A.out && A.img_sc == 1 && A.img_sx == 3 && A.out_sc == 1 && A.out_sx == 3 && forced != 25;
     for (int e = 0; e < A.neyes; e++) node = node && A.eye[e].chan_mask == 7;
-    const void* fn = gen ? (wide ? (const void*)k_gpuwarp<8, -1, true> : (const void*)k_gpuwarp<6, -1, true>)
-                   : node ? (wide ? (pow2 ? (const void*)k_gpuwarp<8, 2, false, true> : (const void*)k_gpuwarp<8, -1, false, true>)
-                                  : (pow2 ? (const void*)k_gpuwarp<6, 2, false, true> : (const void*)k_gpuwarp<6, -1, false, true>))
-                          : wide ? (pow2 ? (const void*)k_gpuwarp<8, 2> : (const void*)k_gpuwarp<8, -1>)
-                                 : (pow2 ? (const void*)k_gpuwarp<6, 2> : (const void*)k_gpuwarp<6, -1>);
     // (round 6) the node's layout with four contiguous columns per lane: k_gpuwarp_q.  CS_DEBUG_PT_VARIANT 27: k_gpuwarp as before
     auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; };
     const bool quad = node && forced != 27 && A.neyes == 2 && A.eye[0].enabled && A.eye[1].enabled && (A.w & 3) == 0 && A.w >= 8 &&
                       A.depth_l && A.depth_r && A.mask_f32 && !A.mask_u8 && al16(A.out) && al16(A.depth_l) && al16(A.depth_r) &&
                       al16(A.mask_f32) && al16(A.eye[0].depth) && al16(A.eye[1].depth) && (!A.tilemap || al16(A.gray));
+    P.threads = threads;
     if (quad) {
         size_t lq = gwq_lds_bytes(A.w);
         if (A.pow_mode != 4) lq -= sizeof(csm::PowfTables) + 64;
         const bool four_q = threads == 512 && 4 * ((lq + 511) & ~(size_t)511) <= CS_LDS_BYTES && forced != 24;
         const bool wide_q = threads > 512 || four_q;
-        const void* fq = wide_q ? (pow2 ? (const void*)k_gpuwarp_q<8, 2> : (const void*)k_gpuwarp_q<8, -1>)
-                                : (pow2 ? (const void*)k_gpuwarp_q<6, 2> : (const void*)k_gpuwarp_q<6, -1>);
-        hipError_t eq = hipFuncSetAttribute(fq, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lq);
-        if (eq != hipSuccess) return CS_EHIP;
-        const dim3 grid(A.h, A.n), block(threads);
-        if (wide_q && pow2) hipLaunchKernelGGL((k_gpuwarp_q<8, 2>), grid, block, lq, stream, A);
-        else if (wide_q) hipLaunchKernelGGL((k_gpuwarp_q<8, -1>), grid, block, lq, stream, A);
-        else if (pow2) hipLaunchKernelGGL((k_gpuwarp_q<6, 2>), grid, block, lq, stream, A);
-        else hipLaunchKernelGGL((k_gpuwarp_q<6, -1>), grid, block, lq, stream, A);
+        P.lds = lq;
+        P.path = wide_q ? (pow2 ? GW_PATH_Q8_POW2 : GW_PATH_Q8_POWN) : (pow2 ? GW_PATH_Q6_POW2 : GW_PATH_Q6_POWN);
         return CS_OK;
     }
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    P.lds = lds;
+    P.path = gen ? (wide ? GW_PATH_K8_GEN : GW_PATH_K6_GEN)
+           : node ? (wide ? (pow2 ? GW_PATH_K8_POW2_NODE : GW_PATH_K8_POWN_NODE) : (pow2 ? GW_PATH_K6_POW2_NODE : GW_PATH_K6_POWN_NODE))
+                  : (wide ? (pow2 ? GW_PATH_K8_POW2 : GW_PATH_K8_POWN) : (pow2 ? GW_PATH_K6_POW2 : GW_PATH_K6_POWN));
+    return CS_OK;
+}
+
+static int gw_launch(const GwArgs& A, const GwPlan& P, hipStream_t stream) {
+    if (P.path == GW_PATH_MESH8 || P.path == GW_PATH_MESH6) {
+        const int ngroups = (A.n + A.group - 1) / A.group;
+        size_t lk = mesh_keep_lds_bytes(A.w);
+        hipError_t e = hipFuncSetAttribute((const void*)k_mesh_keep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lk);
+        if (e != hipSuccess) return CS_EHIP;
+        e = hipFuncSetAttribute(P.path == GW_PATH_MESH8 ? (const void*)k_meshwarp<8> : (const void*)k_meshwarp<6>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds);
+        if (e != hipSuccess) return CS_EHIP;
+        hipLaunchKernelGGL(k_mesh_keep, dim3(A.h - 1, ngroups, A.neyes), dim3(P.threads > 512 ? 512 : P.threads), lk, stream, A);
+        if (P.path == GW_PATH_MESH8) hipLaunchKernelGGL(k_meshwarp<8>, dim3(A.h, A.n), dim3(P.threads), P.lds, stream, A);
+        else hipLaunchKernelGGL(k_meshwarp<6>, dim3(A.h, A.n), dim3(P.threads), P.lds, stream, A);
+        return CS_OK;
+    }
+    const void* fn = nullptr;
+    switch (P.path) {
+    case GW_PATH_Q8_POW2: fn = (const void*)k_gpuwarp_q<8, 2>; break;
+    case GW_PATH_Q8_POWN: fn = (const void*)k_gpuwarp_q<8, -1>; break;
+    case GW_PATH_Q6_POW2: fn = (const void*)k_gpuwarp_q<6, 2>; break;
+    case GW_PATH_Q6_POWN: fn = (const void*)k_gpuwarp_q<6, -1>; break;
+    case GW_PATH_K8_POW2_NODE: fn = (const void*)k_gpuwarp<8, 2, false, true>; break;
+    case GW_PATH_K8_POWN_NODE: fn = (const void*)k_gpuwarp<8, -1, false, true>; break;
+    case GW_PATH_K6_POW2_NODE: fn = (const void*)k_gpuwarp<6, 2, false, true>; break;
+    case GW_PATH_K6_POWN_NODE: fn = (const void*)k_gpuwarp<6, -1, false, true>; break;
+    case GW_PATH_K8_POW2: fn = (const void*)k_gpuwarp<8, 2>; break;
+    case GW_PATH_K8_POWN: fn = (const void*)k_gpuwarp<8, -1>; break;
+    case GW_PATH_K6_POW2: fn = (const void*)k_gpuwarp<6, 2>; break;
+    case GW_PATH_K6_POWN: fn = (const void*)k_gpuwarp<6, -1>; break;
+    case GW_PATH_K8_GEN: fn = (const void*)k_gpuwarp<8, -1, true>; break;
+    case GW_PATH_K6_GEN: fn = (const void*)k_gpuwarp<6, -1, true>; break;
+    default: return CS_EINVAL;
+    }
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds);
     if (e != hipSuccess) return CS_EHIP;
 #ifdef GW_XCD_ROWS
-    const dim3 grid(8 * ((A.h + 7) / 8), A.n), block(threads);
+    const dim3 grid(P.path <= GW_PATH_Q6_POWN ? A.h : 8 * ((A.h + 7) / 8), A.n), block(P.threads);
 #else
-    const dim3 grid(A.h, A.n), block(threads);
+    const dim3 grid(A.h, A.n), block(P.threads);
 #endif
-    if (gen && wide) hipLaunchKernelGGL((k_gpuwarp<8, -1, true>), grid, block, lds, stream, A);
-    else if (gen) hipLaunchKernelGGL((k_gpuwarp<6, -1, true>), grid, block, lds, stream, A);
-    else if (node && wide && pow2) hipLaunchKernelGGL((k_gpuwarp<8, 2, false, true>), grid, block, lds, stream, A);
-    else if (node && wide) hipLaunchKernelGGL((k_gpuwarp<8, -1, false, true>), grid, block, lds, stream, A);
-    else if (node && pow2) hipLaunchKernelGGL((k_gpuwarp<6, 2, false, true>), grid, block, lds, stream, A);
-    else if (node) hipLaunchKernelGGL((k_gpuwarp<6, -1, false, true>), grid, block, lds, stream, A);
-    else if (wide && pow2) hipLaunchKernelGGL((k_gpuwarp<8, 2>), grid, block, lds, stream, A);
-    else if (wide) hipLaunchKernelGGL((k_gpuwarp<8, -1>), grid, block, lds, stream, A);
-    else if (pow2) hipLaunchKernelGGL((k_gpuwarp<6, 2>), grid, block, lds, stream, A);
-    else hipLaunchKernelGGL((k_gpuwarp<6, -1>), grid, block, lds, stream, A);
+    switch (P.path) {
+    case GW_PATH_Q8_POW2: hipLaunchKernelGGL((k_gpuwarp_q<8, 2>), grid, block, P.lds, stream, A); break;
+    case GW_PATH_Q8_POWN: hipLaunchKernelGGL((k_gpuwarp_q<8, -1>), grid, block, P.lds, stream, A); break;
+    case GW_PATH_Q6_POW2: hipLaunchKernelGGL((k_gpuwarp_q<6, 2>), grid, block, P.lds, stream, A); break;
+    case GW_PATH_Q6_POWN: hipLaunchKernelGGL((k_gpuwarp_q<6, -1>), grid, block, P.lds, stream, A); break;
+    case GW_PATH_K8_POW2_NODE: hipLaunchKernelGGL((k_gpuwarp<8, 2, false, true>), grid, block, P.lds, stream, A); break;
+    case GW_PATH_K8_POWN_NODE: hipLaunchKernelGGL((k_gpuwarp<8, -1, false, true>), grid, block, P.lds, stream, A); break;
+    case GW_PATH_K6_POW2_NODE: hipLaunchKernelGGL((k_gpuwarp<6, 2, false, true>), grid, block, P.lds, stream, A); break;
+    case GW_PATH_K6_POWN_NODE: hipLaunchKernelGGL((k_gpuwarp<6, -1, false, true>), grid, block, P.lds, stream, A); break;
+    case GW_PATH_K8_POW2: hipLaunchKernelGGL((k_gpuwarp<8, 2>), grid, block, P.lds, stream, A); break;
+    case GW_PATH_K8_POWN: hipLaunchKernelGGL((k_gpuwarp<8, -1>), grid, block, P.lds, stream, A); break;
+    case GW_PATH_K6_POW2: hipLaunchKernelGGL((k_gpuwarp<6, 2>), grid, block, P.lds, stream, A); break;
+    case GW_PATH_K6_POWN: hipLaunchKernelGGL((k_gpuwarp<6, -1>), grid, block, P.lds, stream, A); break;
+    case GW_PATH_K8_GEN: hipLaunchKernelGGL((k_gpuwarp<8, -1, true>), grid, block, P.lds, stream, A); break;
+    case GW_PATH_K6_GEN: hipLaunchKernelGGL((k_gpuwarp<6, -1, true>), grid, block, P.lds, stream, A); break;
+    }
     return CS_OK;
 }
 
@@ -1425,7 +1456,6 @@ int launch_gpuwarp_plain(const float* image, const float* depth, int n, int h, i
                          double exponent, double convergence, float* warped, uint8_t* gap_mask, uint32_t* stats,
                          void* extra, hipStream_t stream, int mesh, double grad_thr, int max_stretch) {
     float* const fconst = reinterpret_cast<float*>((uint8_t*)extra + 256);
-    hipLaunchKernelGGL(k_gpuwarp_flags, dim3((n + 63) / 64), dim3(64), 0, stream, stats, n, n, fconst, w, 0);
     GwArgs A;
     memset(&A, 0, sizeof(A));
     A.n = n; A.h = h; A.w = w;
@@ -1448,7 +1478,11 @@ int launch_gpuwarp_plain(const float* image, const float* depth, int n, int h, i
     A.mesh = mesh; A.grad_thr = (float)grad_thr; A.keep = (uint8_t*)extra + 256 + gw_const_bytes(n); A.group = n; A.fconst = fconst;
     A.rounds = gw_rounds(grad_thr, max_stretch);
     if (!mesh && A.rounds < 0) return CS_ELIMIT;
-    return gw_launch(A, stream);
+    GwPlan P;
+    const int rc = gw_select(A, P);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_gpuwarp_flags, dim3((n + 63) / 64), dim3(64), 0, stream, stats, n, n, fconst, w, 0, P.path);
+    return gw_launch(A, P, stream);
 }
 
 int launch_gpuwarp_node(const cs_params* p, const float* image, const float* dL, const float* dR, int scale_from_stats,
@@ -1457,7 +1491,6 @@ int launch_gpuwarp_node(const cs_params* p, const float* image, const float* dL,
     const int n = p->n, h = p->h, w = p->w;
     int group = p->batch_size > 0 ? (p->batch_size < n ? p->batch_size : n) : n;
     float* const fconst = reinterpret_cast<float*>((uint8_t*)extra + 256);
-    hipLaunchKernelGGL(k_gpuwarp_flags, dim3((n + 63) / 64), dim3(64), 0, stream, stats, n, group, fconst, w, scale_from_stats);
     GwArgs A;
     memset(&A, 0, sizeof(A));
     A.n = n; A.h = h; A.w = w;
@@ -1496,7 +1529,11 @@ int launch_gpuwarp_node(const cs_params* p, const float* image, const float* dL,
     A.mesh = (p->flags & 4) ? 1 : 0; A.grad_thr = 1.5f; A.rounds = 4; A.keep = (uint8_t*)extra + 256 + gw_const_bytes(n); A.group = group; A.fconst = fconst;   // (create_stereoimages_gpu calls the warp with its defaults, :1068-1083)
     if (tilemap && (A.mesh || w > gpuwarp_lazy_max_width())) return CS_EINVAL;   // (the caller asked gpuwarp_lazy_max_width)
     A.tilemap = tilemap; A.gray = gray; A.tm_words = tm_words;
-    return gw_launch(A, stream);
+    GwPlan P;
+    const int rc = gw_select(A, P);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_gpuwarp_flags, dim3((n + 63) / 64), dim3(64), 0, stream, stats, n, group, fconst, w, scale_from_stats, P.path);
+    return gw_launch(A, P, stream);
 }
 int gpuwarp_lazy_max_width() { return 4096; }   // two words of tile bits = 64 tiles of 64 columns
 

@@ -92,7 +92,8 @@ class Plan:
         return self.stereo, self.depth_l, self.depth_r, self.mask
 
     def stats(self):
-        """Per-frame diagnostics words (see cs_common.h ST_*), e.g. polylines rows replayed sequentially."""
+        """Per-frame diagnostics words (see cs_common.h ST_*), e.g. polylines rows replayed sequentially, or the gpu_warp kernel
+        instantiation that ran (column _native.ST_WARP_PATH, codes _native.WARP_PATH)."""
         return self.ws[: self.p.n * 64].view(torch.int32).view(self.p.n, 16).cpu()
 
 

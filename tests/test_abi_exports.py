@@ -35,6 +35,26 @@ def test_enums_match_header():
         assert int(re.search(name + r"\s*=\s*(\d+)", hdr).group(1)) == _native.MODE[key]
 
 
+def test_warp_path_codes_match_cs_common():
+    """The gpu_warp path codes of the diagnostics word (cs_common.h GW_PATH_*) and their Python names agree, one code per
+    kernel instantiation gw_launch can run."""
+    src = open(os.path.join(ROOT, "comfystereo_amd", "csrc", "cs_common.h")).read()
+    assert int(re.search(r"ST_WARP_PATH\s*=\s*(\d+)", src).group(1)) == _native.ST_WARP_PATH
+    codes = {}
+    for name, code, kern in re.findall(r"(GW_PATH_\w+)\s*=\s*(\d+),\s*//\s*(k_\w+<[^>]*>)", src):
+        codes[int(code)] = kern
+    assert sorted(codes) == sorted(_native.WARP_PATH.values()) == list(range(1, 17))
+    for code, kern in codes.items():
+        m = re.fullmatch(r"k_(gpuwarp_q|gpuwarp|meshwarp)<([^>]*)>", kern)
+        args = [a.strip() for a in m.group(2).split(",")]
+        short = {"gpuwarp_q": "q", "gpuwarp": "k", "meshwarp": "mesh"}[m.group(1)]
+        if short == "k" and args[2:] == ["false", "true"]:
+            args = args[:2] + ["node"]
+        elif short == "k" and args[2:] == ["true"]:
+            args = [args[0], "gen"]
+        assert _native.WARP_PATH_NAME[code] == f"{short}<{','.join(args)}>", (code, kern)
+
+
 def test_params_struct_layout():
     assert ctypes.sizeof(_native.Params) == 12 * 4 + 8 * 8
     assert _native.Params.divergence.offset == 48

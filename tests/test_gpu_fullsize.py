@@ -180,7 +180,7 @@ def test_naive_interpolating_tile_kernel_retrigger_chains(engine, hole):
 def test_gpu_warp_wide_gaps_and_empty_rows(engine, div):
     """k_gpuwarp's gap fill on bit rows (round 5): gaps wider than one and than two 32-bit words, gaps that start at column 0 (no
     filled column to the left), rows whose every pair is disconnected (nothing filled at all), next to ordinary rows.  Mask exact,
-    colours within the forward-warp tolerances, against the oracle."""
+    colours within 2e-6, against the oracle."""
     h, w = 12, 1500
     img = synth.image_f32(1, h, w, seed=77)
     depth = np.zeros((1, h, w, 3), np.float32)
@@ -194,7 +194,7 @@ def test_gpu_warp_wide_gaps_and_empty_rows(engine, div):
     got = [g.cpu().numpy() for g in got]
     assert np.array_equal(got[3], want[3])
     assert np.array_equal(got[1], want[1]) and np.array_equal(got[2], want[2])
-    assert np.abs(got[0] - want[0]).max() <= 1e-4
+    assert np.abs(got[0] - want[0]).max() <= 2e-6   # (the oracle follows the kernels' float32 arithmetic)
 
 
 def test_digests_at_baseline_sizes_on_the_gpu():
@@ -392,9 +392,10 @@ def test_8k_wide_rows_side_by_side(engine, fill):
     depth = synth.depth_batch("stepped", 1, h, w, channels=3)
     got = gen(engine, img, depth, fill, "left-right", blur=False, div=3.0)
     want = node_oracle.generate(img, depth, 3.0, 0.0, "left-right", 0.0, 0.5, 2.0, UI[fill], 20.0, 20.0, False, batch_size=12)
-    if fill == "gpu_warp":
-        assert np.array_equal(got[3], want[3])
-        assert np.abs(got[0] - want[0]).max() <= 1e-4
+    if fill == "gpu_warp":   # (two column passes per lane of k_gpuwarp_q)
+        for k in (1, 2, 3):
+            assert np.array_equal(got[k], want[k]), NAMES[k]
+        assert np.abs(got[0] - want[0]).max() <= 2e-6
     else:
         for g, w_, name in zip(got, want, ("stereoscope", "depth_left", "depth_right", "mask")):
             assert np.array_equal(g, w_), name
