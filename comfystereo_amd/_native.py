@@ -51,6 +51,16 @@ WARP_PATH = {
 }
 WARP_PATH_NAME = {v: k for k, v in WARP_PATH.items()}
 
+# the values of the development switch DEBUG["pt_variant"] (cs_common.h PTV_*, the list this mirrors, names without the prefix;
+# cs_debug_set refuses any other value)
+PT_VARIANT = {
+    "default": 0, "first_gen": 9,
+    "gw_threads_512": 21, "gw_threads_256_narrow": 22, "gw_threads_1024": 23, "gw_six_waves": 24, "gw_generic_layout": 25,
+    "gw_threads_256": 26, "gw_no_quad": 27,
+    "lean_whole_rows": 44, "replay_wave_only": 45, "naive_no_tier2": 47, "tiny_replay_pool": 48, "no_point_tier2": 49,
+    "soft_point_tier2": 50,
+}
+
 
 class Params(ctypes.Structure):
     """struct cs_params (include/comfystereo_amd.h)."""
@@ -170,7 +180,10 @@ def lib():
 
 
 def debug_set(key, value):
-    """cs_debug_set: development switch `key` (see DEBUG) := value.  Process-wide; reset it to 0 afterwards."""
+    """cs_debug_set: development switch `key` (see DEBUG) := value (pt_variant: a PT_VARIANT name).  Process-wide; reset it to 0
+    afterwards."""
+    if key == "pt_variant" and isinstance(value, str):
+        value = PT_VARIANT[value]
     check(lib().cs_debug_set(DEBUG[key], int(value)))
 
 

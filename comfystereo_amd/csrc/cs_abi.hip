@@ -70,12 +70,7 @@ __global__ void __launch_bounds__(256) k_gray(const float* __restrict__ depth, f
             g.y = (0.2989f * a.w + 0.5870f * b.x) + 0.1140f * b.y;
             g.z = (0.2989f * b.z + 0.5870f * b.w) + 0.1140f * cc.x;
             g.w = (0.2989f * cc.y + 0.5870f * cc.z) + 0.1140f * cc.w;
-#ifdef GRAY_NT_STORE   // (experiment, round 5: like k_gray_edges)
-            typedef float gr_v4 __attribute__((ext_vector_type(4)));
-            __builtin_nontemporal_store(gr_v4{g.x, g.y, g.z, g.w}, reinterpret_cast<gr_v4*>(d4 + q));
-#else
             d4[q] = g;
-#endif
             mn = fminf(fminf(mn, g.x), fminf(g.y, fminf(g.z, g.w)));
             mx = fmaxf(fmaxf(mx, g.x), fmaxf(g.y, fmaxf(g.z, g.w)));
         }
@@ -398,15 +393,27 @@ static bool ana_wide_fill(int fill) {
     return fill == CS_FILL_NONE || fill == CS_FILL_NAIVE || fill == CS_FILL_NAIVE_INTERPOLATING || fill == CS_FILL_INVERSE ||
            fill == CS_FILL_NONE_POST || fill == CS_FILL_INVERSE_POST;
 }
-static int stash_form_max_width(int fill) {   // widest row the row kernel takes in its own anaglyph form
+// widest row the LDS-resident row kernel takes, in its anaglyph form (two more bytes of LDS per column) or its side-by-side form
+static int row_form_max_width(int fill, int anaglyph) {
     int lo = 0, hi = 1 << 16;
     while (lo < hi) {
         const int mid = (lo + hi + 1) / 2;
-        if (rowwarp_lds_bytes(fill, mid, 1) <= CS_LDS_BYTES && poly_npt(mid, 1) < 65535) lo = mid; else hi = mid - 1;
+        if (rowwarp_lds_bytes(fill, mid, anaglyph) <= CS_LDS_BYTES && poly_npt(mid, 1) < 65535) lo = mid; else hi = mid - 1;
     }
     return lo;
 }
-static bool ana_wide_call(int fill, int anaglyph, int w) { return anaglyph && ana_wide_fill(fill) && w > stash_form_max_width(fill); }
+static bool ana_wide_call(int fill, int anaglyph, int w) { return anaglyph && ana_wide_fill(fill) && w > row_form_max_width(fill, 1); }
+
+// The ONE predicate of the polylines path choice: the tile kernels take a call of dialect `d64` (flags bits 3/4), `w` columns and
+// `halo` -- D32 up to k_polytile's halo; the float64 disparity chain (d64 & 1) and numba's typing of the sweep (d64 & 2, round 6:
+// k_polypoint<..., SW>, the point kernel's default geometry only) through the point kernel alone.  run_rows, width_refusal and
+// generate_chunk's lazy-tile choice all ask it.
+static bool polypoint_takes(int halo) { return halo <= polypoint_max_halo() && dev_switch(CS_DEBUG_PT_VARIANT) != PTV_FIRST_GEN; }
+static bool poly_tile_takes(int d64, int w, int halo) {
+    if (halo > polytile_max_halo() || dev_switch(CS_DEBUG_NO_TILE)) return false;
+    if (d64 == 0) return true;
+    return polypoint_takes(halo) && (d64 == 1 || polypoint_sweep64_ok(w, halo));
+}
 
 static int run_rows(int fill, RowArgs& A, int halo, uint8_t* rowflag, hipStream_t stream, uint8_t* ana_sbs = nullptr,
                     void* replay_scratch = nullptr, size_t replay_surplus = 0) {
@@ -417,17 +424,9 @@ static int run_rows(int fill, RowArgs& A, int halo, uint8_t* rowflag, hipStream_
     // the side-by-side modes: polylines_sharp 7 990 instead of 6 395 columns), and its order-dependent stretches go to the replay
     // kernel like those of the other modes.  (Rounds 2-4 let the row kernel write flagged rows in final anaglyph form.)
     // soft / sharp: the point-owner kernel (cs_polypoint.hip) unless the halo is too wide for it or the development switch
-    // CS_DEBUG_PT_VARIANT asks for the first generation (cs_polytile.hip)
-    const int variant = dev_switch(CS_DEBUG_PT_VARIANT);   // 0 / 3 .. 7: point-owner kernel; 41 - 43: tie-path what-ifs; other values: first generation
-    auto polypoint_takes = [&](int hl) {
-        return hl <= polypoint_max_halo() && (variant == 0 || (variant >= 3 && variant <= 7) || (variant >= 13 && variant <= 16) || (variant >= 41 && variant <= 50));
-    };
-    // (the tile kernels are dialect D32, plus -- round 5 -- the float64 disparity chain alone: k_polypoint<..., DIA>)
-    // (round 6: numba's typing of the sweep as well -- d64 & 2, k_polypoint<..., SW> -- in the point kernel's default geometry)
-    const bool tile_dialect = A.d64 == 0 || (A.d64 == 1 && polypoint_takes(halo)) ||
-                              ((A.d64 & 2) && polypoint_takes(halo) && polypoint_sweep64_ok(A.w, halo) && !dev_switch(CS_DEBUG_PT_VARIANT));
-    const bool ana_tiled = poly && tile_dialect && A.anaglyph && ana_sbs && A.image_f32 && !A.out_u8 && halo <= polytile_max_halo() && rowflag &&
-                           !dev_switch(CS_DEBUG_NO_TILE);
+    // PTV_FIRST_GEN asks for the first generation (cs_polytile.hip)
+    const bool tiled = poly && rowflag && poly_tile_takes(A.d64, A.w, halo);
+    const bool ana_tiled = tiled && A.anaglyph && ana_sbs && A.image_f32 && !A.out_u8;
     const bool ana_wide = ana_wide_call(fill, A.anaglyph, A.w) && ana_sbs && A.image_f32 && !A.out_u8;
     const RowArgs Afinal = A;
     if (ana_tiled || ana_wide) {
@@ -444,8 +443,7 @@ static int run_rows(int fill, RowArgs& A, int halo, uint8_t* rowflag, hipStream_
     bool cleared = false;   // the flagged-row block (row flags, counters, replay counters and retry flags) has been zeroed
     if (replay)
         (void)poly_replay_attach(A, fill == CS_FILL_POLYLINES_SHARP, replay_scratch, rowflag + al256((size_t)A.n * A.h) + 256, stream, replay_surplus);
-    if (poly && tile_dialect && !A.anaglyph && halo <= polytile_max_halo() && rowflag &&
-        !dev_switch(CS_DEBUG_NO_TILE)) {   // (anaglyph calls arrive here in their side-by-side form)
+    if (tiled && !A.anaglyph) {   // (anaglyph calls arrive here in their side-by-side form)
         // workspace: [n*h flag bytes][count, padded to 256][n*h list entries]
         const size_t rows = (size_t)A.n * A.h;
         uint32_t* count = (uint32_t*)(rowflag + al256(rows));
@@ -472,15 +470,16 @@ static int run_rows(int fill, RowArgs& A, int halo, uint8_t* rowflag, hipStream_
         if (e != hipSuccess) return fail_hip(e, "flagged-row collection");
         A.row_list = list; A.row_count = count;
         const uint32_t* hints = (const uint32_t*)(rowflag + rowflag_hint_off(rows));
-        // (round 6) second tier: the flagged rows through the point kernel once more with 512 instead of 160 slots for pixels under
-        // reversed segments and longer per-pixel lists (k_polypoint_listed); what THAT flags -- a second flag array and hint block,
-        // a third {count, cursor} pair -- is collected into the same list for the row kernel.  Depth maps with strong silhouettes
+        // (round 6) second tier: the flagged rows through the point kernel once more (k_polypoint_listed) with PP_DCAP2 = 192 instead
+        // of 160 slots for pixels under reversed segments and longer per-pixel lists (8 points / 12 segments sharp, 6 / 9 soft); what
+        // THAT flags -- a second flag array and hint block, a third {count, cursor} pair -- is collected into the same list for the row kernel.  Depth maps with strong silhouettes
         // (tools/synth.scene8) overflowed the first tier's lists in 15 % (soft) / 48 % (sharp) of the rows at the metric's divergence
         // and sent them to the row kernel: 4 200 / 1 060 frames/s against 5 380 / 4 050 on stepped depth.  polylines_sharp only:
         // for soft the lean row kernel on the hinted tiles' columns is the cheaper second stop (0.96 against 1.16 ms per 16 frames,
-        // tools/sessions/r06_s11.sh, s12: 4 100 against 3 750 frames/s; CS_DEBUG_PT_VARIANT 50 forces the tier for soft, 49: off)
+        // tools/sessions/r06_s11.sh, s12: 4 100 against 3 750 frames/s; PTV_SOFT_POINT_TIER2 forces the tier for soft, PTV_NO_POINT_TIER2: off)
         // (numba's sweep, d64 & 2: both techniques -- what the tier does not finish takes the dialect row kernel whole, there is no lean pass)
-        if (hint_T > 0 && (fill == CS_FILL_POLYLINES_SHARP || (A.d64 & 2) || dev_switch(CS_DEBUG_PT_VARIANT) == 50) && dev_switch(CS_DEBUG_PT_VARIANT) != 49) {
+        if (hint_T > 0 && (fill == CS_FILL_POLYLINES_SHARP || (A.d64 & 2) || dev_switch(CS_DEBUG_PT_VARIANT) == PTV_SOFT_POINT_TIER2) &&
+            dev_switch(CS_DEBUG_PT_VARIANT) != PTV_NO_POINT_TIER2) {
             uint8_t* flag2 = rowflag + rowflag_flag2_off(rows);
             uint32_t* hint2 = (uint32_t*)(rowflag + rowflag_hint2_off(rows));
             uint32_t* count3 = count + 16;
@@ -492,8 +491,8 @@ static int run_rows(int fill, RowArgs& A, int halo, uint8_t* rowflag, hipStream_
                 hints = hint2;
             } else if (e != hipErrorNotSupported) return fail_hip(e, "tiled polylines launch (second tier)");
         }
-        // (the lean first pass works on the flagged tiles' column ranges; CS_DEBUG_PT_VARIANT 44: whole rows as in round 4)
-        if (hint_T > 0 && dev_switch(CS_DEBUG_PT_VARIANT) != 44) {
+        // (the lean first pass works on the flagged tiles' column ranges; PTV_LEAN_WHOLE_ROWS: whole rows as in round 4)
+        if (hint_T > 0 && dev_switch(CS_DEBUG_PT_VARIANT) != PTV_LEAN_WHOLE_ROWS) {
             A.hint = hints; A.hint_T = hint_T; A.hint_S = halo;
         }
     }
@@ -517,7 +516,7 @@ static int run_rows(int fill, RowArgs& A, int halo, uint8_t* rowflag, hipStream_
             // naive_interpolating, second tier (round 5): the flagged rows through the tile kernel once more with a window that holds every
             // hole; what THAT flags (the retry-flag bytes of the block) is collected into the same list for the row kernel.  On depth
             // saturated to 0 / 1 the holes between a near and a far plateau outgrow the first window in most rows (1 830 frames/s at 4K)
-            if (fill == CS_FILL_NAIVE_INTERPOLATING && dev_switch(CS_DEBUG_PT_VARIANT) != 47) {
+            if (fill == CS_FILL_NAIVE_INTERPOLATING && dev_switch(CS_DEBUG_PT_VARIANT) != PTV_NAIVE_NO_TIER2) {
                 uint8_t* flag2 = rowflag + al256(rows) + 512;
                 uint32_t* count2 = count + 8;
                 e = launch_fwdtile(fill, A, halo, flag2, stream, list, count);
@@ -541,8 +540,8 @@ static int run_rows(int fill, RowArgs& A, int halo, uint8_t* rowflag, hipStream_
         if (e0 != hipSuccess) return fail_hip(e0, "rowflag memset");
     }
     // (polylines with the replay kernel attached: the lean instantiation first -- evaluation, stretch list, export; the rows it
-    // cannot export come back through the retry flags below.  CS_DEBUG_PT_VARIANT 43: the full kernel as in round 3)
-    hipError_t e = launch_rowwarp(fill, A, threads_for(fill, A.w), stream, 0, replay && dev_switch(CS_DEBUG_PT_VARIANT) != 43);
+    // cannot export come back through the retry flags below)
+    hipError_t e = launch_rowwarp(fill, A, threads_for(fill, A.w), stream, 0, replay);
     if (e != hipSuccess) return fail_hip(e, "row kernel launch");
     if (replay) {
         e = launch_poly_replay(fill == CS_FILL_POLYLINES_SHARP, A, halo, stream);
@@ -557,7 +556,7 @@ static int run_rows(int fill, RowArgs& A, int halo, uint8_t* rowflag, hipStream_
         R.rp_dump = nullptr; R.row_list = list; R.row_count = count2; R.hint = nullptr;
         // (one workgroup per CU: on saturated depth a few hundred rows per frame come back -- stretches whose list outgrows the
         // wave form's 64 entries --, 32 workgroups made them the tail of the call; an empty launch of 256 costs 0.03 ms)
-        e = launch_rowwarp(fill, R, threads_for(fill, A.w), stream, dev_switch(CS_DEBUG_PT_VARIANT) == 42 ? 32 : 256);
+        e = launch_rowwarp(fill, R, threads_for(fill, A.w), stream, 256);
         if (e != hipSuccess) return fail_hip(e, "row kernel launch (replay retry)");
     }
     if (ana_tiled || ana_wide) {   // R from one eye, G and B from the other, k / 255, the mask of the composite -- every row
@@ -599,23 +598,7 @@ static int max_width_for(int fill, int anaglyph) {
     if (fill == CS_FILL_GPU_WARP) return gpuwarp_max_width();   // (the mesh-quality variant, cs_params.flags bit 2: cs_forward_warp_mesh's limit)
     if (fill == CS_FILL_HYBRID_EDGE) return hybrid_max_width();
     if (fill < 0 || fill > CS_FILL_HYBRID_EDGE_PLUS) return 0;
-    int lo = 0, hi = 1 << 16;
-    while (lo < hi) {
-        int mid = (lo + hi + 1) / 2;
-        if (rowwarp_lds_bytes(fill, mid, anaglyph) <= CS_LDS_BYTES && poly_npt(mid, 1) < 65535) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-// widest row the row kernel takes in its own anaglyph form (two more bytes of LDS per column)
-static int row_form_max_width(int fill, int anaglyph) {
-    int lo = 0, hi = 1 << 16;
-    while (lo < hi) {
-        int mid = (lo + hi + 1) / 2;
-        if (rowwarp_lds_bytes(fill, mid, anaglyph) <= CS_LDS_BYTES && poly_npt(mid, 1) < 65535) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
+    return row_form_max_width(fill, anaglyph);
 }
 // polylines under the float64 disparity chain keep 8 more bytes per column in LDS (cs_rowwarp.hip Poly::xd)
 static bool dialect_width_ok(int fill, int w, int anaglyph, int d64) {
@@ -630,15 +613,11 @@ static const char* width_refusal(const cs_params* p, int w) {
     if (w > max_width_for(p->fill, ana) || !dialect_width_ok(p->fill, w, ana, (p->flags >> 3) & 3))
         return "frame too wide for the LDS-resident row kernel";
     if ((p->fill == CS_FILL_POLYLINES_SOFT || p->fill == CS_FILL_POLYLINES_SHARP) && ana && w > row_form_max_width(p->fill, 1)) {
-        // an anaglyph wider than the row kernel's anaglyph form: only through the tile kernels -- the predicate run_rows uses
-        // for its tiled anaglyph path (D32, or the float64 disparity chain alone with a halo within the point kernel's reach;
+        // an anaglyph wider than the row kernel's anaglyph form: only through the tile kernels (run_rows' tiled anaglyph path;
         // cs_generate's images are float32)
         const int halo = poly_halo(p->divergence * (1 + p->stereo_balance), p->divergence * (1 - p->stereo_balance), p->separation,
                                    p->stereo_offset_exponent, p->convergence_point, w);
-        const int d64 = (p->flags >> 3) & 3;
-        const bool tile_dialect = d64 == 0 || (d64 == 1 && halo <= polypoint_max_halo()) ||
-                                  ((d64 & 2) && halo <= polypoint_max_halo() && polypoint_sweep64_ok(w, halo) && !dev_switch(CS_DEBUG_PT_VARIANT));
-        if (!tile_dialect || halo > polytile_max_halo() || dev_switch(CS_DEBUG_NO_TILE))
+        if (!poly_tile_takes((p->flags >> 3) & 3, w, halo))
             return "frame too wide for the LDS-resident row kernel (anaglyph form)";
     }
     return nullptr;
@@ -831,7 +810,7 @@ static int generate_chunk(const cs_params* p, const float* image, const float* d
         // kernels keep complete maps: 0.94 of 17.1 ms per 64 frames under D64, profiles/r06_s39/)
         const int d64f = (p->flags >> 3) & 3;
         const bool poly_fill = p->fill == CS_FILL_POLYLINES_SOFT || p->fill == CS_FILL_POLYLINES_SHARP;
-        const bool dialect_lazy = d64f == 0 || (poly_fill && halo <= polypoint_max_halo() && (d64f == 1 || polypoint_sweep64_ok(w, halo)));
+        const bool dialect_lazy = d64f == 0 || (poly_fill && poly_tile_takes(d64f, w, halo));
         const bool want_lazy = (tile_fill || warp_lazy || hyb_lazy) && dialect_lazy && !dev_switch(CS_DEBUG_NO_TILE) && !dev_switch(CS_DEBUG_BLUR_FULL_COPY) &&
                                p->mode != CS_MODE_LEFT_ONLY && p->mode != CS_MODE_ONLY_RIGHT &&
                                al256((size_t)n * hw * 4) < (1ull << 32) - (1u << 20);
@@ -1220,6 +1199,14 @@ int cs_debug_set(int key, int value) {
     if (key == CS_DEBUG_DBG && value != 0 && value != 14 && value != 17 && value != 30 && value != 31)   // (30 / 31: column ranges of the polylines row kernel forced / off: same pixels)
         return fail(CS_EINVAL, "cs_debug_set: this CS_DEBUG_DBG value needs a -DCS_DEV build (phase cut-offs leave outputs unwritten)");
 #endif
+    if (key == CS_DEBUG_PT_VARIANT) {
+        switch (value) {
+        case PTV_DEFAULT: case PTV_FIRST_GEN: case PTV_GW_THREADS_512: case PTV_GW_THREADS_256_NARROW: case PTV_GW_THREADS_1024:
+        case PTV_GW_SIX_WAVES: case PTV_GW_GENERIC_LAYOUT: case PTV_GW_THREADS_256: case PTV_GW_NO_QUAD: case PTV_LEAN_WHOLE_ROWS:
+        case PTV_REPLAY_WAVE_ONLY: case PTV_NAIVE_NO_TIER2: case PTV_TINY_REPLAY_POOL: case PTV_NO_POINT_TIER2: case PTV_SOFT_POINT_TIER2: break;
+        default: return fail(CS_EINVAL, "cs_debug_set: unknown CS_DEBUG_PT_VARIANT value (PTV_* in cs_common.h)");
+        }
+    }
     g_dev[key].store(value, std::memory_order_relaxed);
     return CS_OK;
 }

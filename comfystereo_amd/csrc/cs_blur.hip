@@ -356,13 +356,7 @@ __global__ void __launch_bounds__(256) k_blur_edges4(BlurArgs A, unsigned long l
 #ifndef GE_RB
 #define GE_RB 32
 #endif
-#ifndef GE_WAVES
-#define GE_WAVES 0   // (development: > 0 = amdgpu_waves_per_eu)
-#endif
 static_assert(GE_RB % BLUR_ER4 == 0, "strips are whole summary blocks");
-#if GE_WAVES > 0
-__attribute__((amdgpu_waves_per_eu(GE_WAVES)))
-#endif
 __global__ void __launch_bounds__(64) k_gray_edges(const float* __restrict__ rgb, float* __restrict__ gray, int h, int w,
                                                    uint32_t* stats, float thr, unsigned long long* mask_l,
                                                    unsigned long long* mask_r, size_t plane, int MW, float4* blk, int HB) {
@@ -383,14 +377,7 @@ __global__ void __launch_bounds__(64) k_gray_edges(const float* __restrict__ rgb
         const bool rowok = yy >= 0 && yy < h;
         const float* r = src + ((size_t)(rowok ? yy : 0) * w) * 3;
         const float4* q = reinterpret_cast<const float4*>(r + (size_t)(incol ? x : 0) * 3);
-#ifdef GE_NT_LOAD   // (experiment, round 5: the RGB depth is read exactly once -- nontemporal loads)
-        typedef float ge_v4 __attribute__((ext_vector_type(4)));
-        const ge_v4* qv = reinterpret_cast<const ge_v4*>(q);
-        const ge_v4 va = __builtin_nontemporal_load(qv), vb = __builtin_nontemporal_load(qv + 1), vc = __builtin_nontemporal_load(qv + 2);
-        const float4 ta = make_float4(va.x, va.y, va.z, va.w), tb = make_float4(vb.x, vb.y, vb.z, vb.w), tc = make_float4(vc.x, vc.y, vc.z, vc.w);
-#else
         const float4 ta = q[0], tb = q[1], tc = q[2];
-#endif
         const bool ok = rowok && incol;
         a = make_float4(ok ? ta.x : 0.f, ok ? ta.y : 0.f, ok ? ta.z : 0.f, ok ? ta.w : 0.f);
         b = make_float4(ok ? tb.x : 0.f, ok ? tb.y : 0.f, ok ? tb.z : 0.f, ok ? tb.w : 0.f);
@@ -437,12 +424,9 @@ __global__ void __launch_bounds__(64) k_gray_edges(const float* __restrict__ rgb
             const int y = y0 + j;
             if (y < h && incol) {
                 const float4 q = G[1 + j].v;
-#ifndef GE_PLAIN_STORE   // (round 5: the gray map is not read back by this kernel -- nontemporal stores, -5 % on the kernel)
+                // (round 5: the gray map is not read back by this kernel -- nontemporal stores, -5 % on the kernel)
                 typedef float ge_v4s __attribute__((ext_vector_type(4)));
                 __builtin_nontemporal_store(ge_v4s{q.x, q.y, q.z, q.w}, reinterpret_cast<ge_v4s*>(dst + (size_t)y * w + x));
-#else
-                *reinterpret_cast<float4*>(dst + (size_t)y * w + x) = q;
-#endif
                 mn = fminf(fminf(mn, fminf(q.x, q.y)), fminf(q.z, q.w));
                 mx = fmaxf(fmaxf(mx, fmaxf(q.x, q.y)), fmaxf(q.z, q.w));
             }

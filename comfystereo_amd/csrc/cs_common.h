@@ -50,6 +50,27 @@ enum {
     GW_PATH_MESH6 = 16,         // k_meshwarp<6>
 };
 
+// The values cs_debug_set(CS_DEBUG_PT_VARIANT, v) accepts (any other: CS_EINVAL).  Each one reaches a reference path a test
+// compares against, or a kernel no default choice reaches.  comfystereo_amd/_native.py PT_VARIANT mirrors the list
+// (tests/test_abi_exports.py checks the two agree).
+enum {
+    PTV_DEFAULT = 0,
+    PTV_FIRST_GEN = 9,            // polylines: the first-generation tile kernel k_polytile at any halo
+    PTV_GW_THREADS_512 = 21,      // gpu_warp: 512-thread workgroups
+    PTV_GW_THREADS_256_NARROW = 22,   // gpu_warp: 256-thread workgroups for rows of at most 1024 columns
+    PTV_GW_THREADS_1024 = 23,     // gpu_warp: 1024-thread workgroups
+    PTV_GW_SIX_WAVES = 24,        // gpu_warp: the 6-waves-per-SIMD instantiation where the 8-wave one would fit
+    PTV_GW_GENERIC_LAYOUT = 25,   // gpu_warp: the generic-layout k_gpuwarp instead of the node-layout instantiations
+    PTV_GW_THREADS_256 = 26,      // gpu_warp: 256-thread workgroups
+    PTV_GW_NO_QUAD = 27,          // gpu_warp: k_gpuwarp instead of k_gpuwarp_q
+    PTV_LEAN_WHOLE_ROWS = 44,     // polylines: the lean row kernel on whole flagged rows, not the hinted tiles' columns
+    PTV_REPLAY_WAVE_ONLY = 45,    // polylines: order-dependent stretches replayed by the wave kernel alone
+    PTV_NAIVE_NO_TIER2 = 47,      // naive_interpolating: no second tier of the forward tile kernel
+    PTV_TINY_REPLAY_POOL = 48,    // polylines: a replay pool of ~100 bytes per row (most flagged rows find it full)
+    PTV_NO_POINT_TIER2 = 49,      // polylines: no second tier of the point kernel
+    PTV_SOFT_POINT_TIER2 = 50,    // polylines_soft: the second tier of the point kernel as for sharp
+};
+
 namespace cs {
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }

@@ -147,17 +147,10 @@ __global__ void __launch_bounds__(1024) k_gpuwarp(GwArgs A) {
     // Workgroup b runs on XCD b % 8 (observed dispatch order; a speed assumption only).  With row = blockIdx.x the rows y and
     // y + 1 -- whose image rows BOTH feed output row y through the 4-corner blend of the grid_sample round trip (:441-448) --
     // sit on different XCDs, and each fetches both rows from the fabric: 2.8 x the algorithmic reads (profiles/r03g_cfg4_pmc).
-    // -DGW_XCD_ROWS (measured in round 4, NOT the default): XCD k takes the rows [k * rpx, (k + 1) * rpx) in order, so the
-    // neighbour row is in that XCD's L2 -- FETCH_SIZE x 2 of the kernel 15.1 -> 9.0 GB per 128 1080p frames (-41 %), and the
-    // kernel is 1.3 % SLOWER at 1080p and at 4K (tools/sessions/r04_s7.sh): it is not the fabric that bounds this kernel.
-#ifdef GW_XCD_ROWS
-    const int rpx = (A.h + 7) >> 3;
-    const int y = (int)(blockIdx.x & 7u) * rpx + (int)(blockIdx.x >> 3);
-    if (y >= A.h) return;
-    const int frame = blockIdx.y, w = A.w, h = A.h;
-#else
+    // Measured in round 4 and dropped: XCD k taking the rows [k * rpx, (k + 1) * rpx) in order, so that the neighbour row is in
+    // that XCD's L2 -- FETCH_SIZE x 2 of the kernel 15.1 -> 9.0 GB per 128 1080p frames (-41 %), and the kernel is 1.3 % SLOWER
+    // at 1080p and at 4K (tools/sessions/r04_s7.sh): it is not the fabric that bounds this kernel.
     const int y = blockIdx.x, frame = blockIdx.y, w = A.w, h = A.h;
-#endif
     float* ndn = (float*)smem;     // normalised depth (not convergence-shifted); after the column pass: the left-nearest scan
     float* po = ndn + w;           // pixel offset; from the column pass on: the source map
     float* D = po + w;             // x + offset = dl of pair x = dr of pair x-1
@@ -260,14 +253,8 @@ __global__ void __launch_bounds__(1024) k_gpuwarp(GwArgs A) {
                                 A.image[frame * A.img_sf + y * A.img_sy + x * A.img_sx + c * A.img_sc];
             continue;
         }
-#ifdef GW_P1_RFL
-        const bool div255 = __builtin_amdgcn_readfirstlane((int)st[E.st_div]) != 0;
-        float dmin = csm::ord2f((uint32_t)__builtin_amdgcn_readfirstlane((int)st[E.st_min])),
-              dmax = csm::ord2f((uint32_t)__builtin_amdgcn_readfirstlane((int)st[E.st_max]));
-#else
         const bool div255 = st[E.st_div] != 0;
         float dmin = csm::ord2f(st[E.st_min]), dmax = csm::ord2f(st[E.st_max]);
-#endif
         if (div255) { dmin = dmin / 255.0f; dmax = dmax / 255.0f; }
         const float range = dmax - dmin;
         const float crange = fmaxf(range, (float)1e-6);
@@ -285,28 +272,15 @@ __global__ void __launch_bounds__(1024) k_gpuwarp(GwArgs A) {
         float* const depth_out = !A.depth_l ? nullptr : (e == 0 ? A.depth_l : A.depth_r) + (((size_t)frame * h + y) * w) * 3;
         for (int xb = tid; xb < w; xb += 4 * nt) {
             float dv[4], dm[4];
-            // (round 5, measured one by one, tools/sessions/r05_s7.sh: separate loops for the lazy / plain loads -DGW_P1_SPLIT - 1.4 %,
-            // the statistics words through readfirstlane -DGW_P1_RFL - 1.3 % -- fewer vector instructions, more scalar registers live
-            // across the eye loop at the 80-SGPR budget; both stay off.  32-bit offsets for the depth-map stores: + 0.4 %, on)
-#ifdef GW_P1_SPLIT
-            if (lazy) {
-#pragma unroll
-                for (int u = 0; u < 4; u++) dv[u] = lazy_load2(Z, Zhi, (uint32_t)min(xb + u * nt, w - 1), dm[u]);
-            } else {
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    dm[u] = scale;
-                    dv[u] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(drow) + 4u * (uint32_t)min(xb + u * nt, w - 1));
-                }
-            }
-#else
+            // (round 5, measured one by one, tools/sessions/r05_s7.sh: separate loops for the lazy / plain loads - 1.4 %, the
+            // statistics words through readfirstlane - 1.3 % -- fewer vector instructions, more scalar registers live across the eye
+            // loop at the 80-SGPR budget; both dropped.  32-bit offsets for the depth-map stores: + 0.4 %, kept)
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 const int x = min(xb + u * nt, w - 1);
                 dm[u] = scale;
                 dv[u] = lazy ? lazy_load2(Z, Zhi, (uint32_t)x, dm[u]) : drow[x];
             }
-#endif
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 const int x = xb + u * nt;
@@ -619,11 +593,7 @@ __global__ void __launch_bounds__(1024) k_gpuwarp(GwArgs A) {
 struct GwQuad { float x, y, z, w; };
 // a scheduling fence between the columns of a lane: the loads of the next column are not hoisted above the arithmetic of this one
 // (four columns' taps in flight do not fit the 64 registers of the 8-waves-per-SIMD instantiation)
-#ifndef GWQ_NO_FENCE
 #define GWQ_FENCE() asm volatile("" ::: "memory")
-#else
-#define GWQ_FENCE()
-#endif
 static size_t gwq_bit_words(int w) { return (size_t)((w + 127) >> 7) << 2; }   // one bit per column, padded to 16 bytes
 static size_t gwq_lds_bytes(int w) { return 4 * (size_t)w * 4 + ((size_t)w + 24) * 4 + 2 * gwq_bit_words(w) * 4 + 32 * 4 + sizeof(csm::PowfTables) + 64; }
 
@@ -1361,27 +1331,27 @@ static int gw_select(GwArgs& A, GwPlan& P) {
     // workgroup size: about 4 columns per thread (measured at 1080p: 512 threads 2.30 ms per 32 frames, 1024: 2.71, 256: 2.94)
     int threads = A.w <= 1024 ? 256 : (A.w <= 2048 ? 512 : 1024);
     const int forced = dev_switch(CS_DEBUG_PT_VARIANT);   // (development: workgroup size)
-    if (forced == 21) threads = 512;
-    if (forced == 22 && A.w <= 4 * 256) threads = 256;
-    if (forced == 23) threads = 1024;
-    if (forced == 26) threads = 256;   // (1080p: four workgroups of four waves per CU, 7.5 columns per lane)
+    if (forced == PTV_GW_THREADS_512) threads = 512;
+    if (forced == PTV_GW_THREADS_256_NARROW && A.w <= 4 * 256) threads = 256;
+    if (forced == PTV_GW_THREADS_1024) threads = 1024;
+    if (forced == PTV_GW_THREADS_256) threads = 256;   // (1080p: four workgroups of four waves per CU, 7.5 columns per lane)
     // 1080p: a row takes 40.5 KB without the tables -- FOUR 512-thread workgroups per CU instead of three if the kernel also
-    // fits 64 registers (the 8-waves-per-SIMD instantiation; development switch 24: the 6-wave one)
-    const bool four = threads == 512 && 4 * ((lds + 511) & ~(size_t)511) <= CS_LDS_BYTES && forced != 24;
+    // fits 64 registers (the 8-waves-per-SIMD instantiation; development switch PTV_GW_SIX_WAVES: the 6-wave one)
+    const bool four = threads == 512 && 4 * ((lds + 511) & ~(size_t)511) <= CS_LDS_BYTES && forced != PTV_GW_SIX_WAVES;
     const bool wide = threads > 512 || four, pow2 = A.pow_mode == 2 && !gen;
     // the node's layout (interleaved image and output, every eye writes the three channels) has instantiations of its own
-    bool node = !gen && A.out && A.img_sc == 1 && A.img_sx == 3 && A.out_sc == 1 && A.out_sx == 3 && forced != 25;
+    bool node = !gen && A.out && A.img_sc == 1 && A.img_sx == 3 && A.out_sc == 1 && A.out_sx == 3 && forced != PTV_GW_GENERIC_LAYOUT;
     for (int e = 0; e < A.neyes; e++) node = node && A.eye[e].chan_mask == 7;
-    // (round 6) the node's layout with four contiguous columns per lane: k_gpuwarp_q.  CS_DEBUG_PT_VARIANT 27: k_gpuwarp as before
+    // (round 6) the node's layout with four contiguous columns per lane: k_gpuwarp_q.  PTV_GW_NO_QUAD: k_gpuwarp as before
     auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; };
-    const bool quad = node && forced != 27 && A.neyes == 2 && A.eye[0].enabled && A.eye[1].enabled && (A.w & 3) == 0 && A.w >= 8 &&
+    const bool quad = node && forced != PTV_GW_NO_QUAD && A.neyes == 2 && A.eye[0].enabled && A.eye[1].enabled && (A.w & 3) == 0 && A.w >= 8 &&
                       A.depth_l && A.depth_r && A.mask_f32 && !A.mask_u8 && al16(A.out) && al16(A.depth_l) && al16(A.depth_r) &&
                       al16(A.mask_f32) && al16(A.eye[0].depth) && al16(A.eye[1].depth) && (!A.tilemap || al16(A.gray));
     P.threads = threads;
     if (quad) {
         size_t lq = gwq_lds_bytes(A.w);
         if (A.pow_mode != 4) lq -= sizeof(csm::PowfTables) + 64;
-        const bool four_q = threads == 512 && 4 * ((lq + 511) & ~(size_t)511) <= CS_LDS_BYTES && forced != 24;
+        const bool four_q = threads == 512 && 4 * ((lq + 511) & ~(size_t)511) <= CS_LDS_BYTES && forced != PTV_GW_SIX_WAVES;
         const bool wide_q = threads > 512 || four_q;
         P.lds = lq;
         P.path = wide_q ? (pow2 ? GW_PATH_Q8_POW2 : GW_PATH_Q8_POWN) : (pow2 ? GW_PATH_Q6_POW2 : GW_PATH_Q6_POWN);
@@ -1428,11 +1398,7 @@ static int gw_launch(const GwArgs& A, const GwPlan& P, hipStream_t stream) {
     }
     hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds);
     if (e != hipSuccess) return CS_EHIP;
-#ifdef GW_XCD_ROWS
-    const dim3 grid(P.path <= GW_PATH_Q6_POWN ? A.h : 8 * ((A.h + 7) / 8), A.n), block(P.threads);
-#else
     const dim3 grid(A.h, A.n), block(P.threads);
-#endif
     switch (P.path) {
     case GW_PATH_Q8_POW2: hipLaunchKernelGGL((k_gpuwarp_q<8, 2>), grid, block, P.lds, stream, A); break;
     case GW_PATH_Q8_POWN: hipLaunchKernelGGL((k_gpuwarp_q<8, -1>), grid, block, P.lds, stream, A); break;

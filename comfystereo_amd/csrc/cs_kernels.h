@@ -76,7 +76,8 @@ struct RowArgs {
 // Development switches (cs_debug_set, include/comfystereo_amd.h).  Release builds never read the environment; the
 // switches are explicit process-wide state that only tests and profiling tools set.  In a release build CS_DEBUG_DBG
 // only accepts the values that leave every output intact (14: count pixels per evaluation path, 17: no exponent
-// shortcuts); the phase cut-offs of the tile and blur kernels need a -DCS_DEV build.
+// shortcuts); the phase cut-offs of the tile and blur kernels need a -DCS_DEV build.  CS_DEBUG_PT_VARIANT only accepts the
+// PTV_* values of cs_common.h.
 int dev_switch(int key);
 
 

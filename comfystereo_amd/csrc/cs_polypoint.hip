@@ -133,23 +133,12 @@ struct PolyPointArgs {
 
 struct F3 { float x, y, z; };
 struct B3 { uint8_t x, y, z; };
-// the float32 output stores of the tile (stereoscope / depth map: 12 bytes per pixel, mask: 4).  -DPP_NT_STORES (experiment, round 5):
-// the nontemporal forms -- the outputs are never read back by this kernel
-typedef float pp_f3v __attribute__((ext_vector_type(3)));
+// the float32 output stores of the tile (stereoscope / depth map: 12 bytes per pixel, mask: 4)
 __device__ __forceinline__ void out_store3(char* p, float a, float b, float c) {
-#ifdef PP_NT_STORES
-    const pp_f3v v{a, b, c};
-    asm volatile("global_store_dwordx3 %0, %1, off nt" :: "v"(p), "v"(v) : "memory");
-#else
     *reinterpret_cast<F3*>(p) = F3{a, b, c};
-#endif
 }
 __device__ __forceinline__ void out_store1(char* p, float a) {
-#ifdef PP_NT_STORES
-    __builtin_nontemporal_store(a, reinterpret_cast<float*>(p));
-#else
     *reinterpret_cast<float*>(p) = a;
-#endif
 }
 
 // lane i receives lane i + 1's value, lane 63 +inf -- one DPP move instead of a ds_bpermute round trip
@@ -402,11 +391,7 @@ __device__ __forceinline__ void pp_tile(const float* __restrict__ hot_image, con
                        ((uint32_t)__builtin_amdgcn_fmed3f(cpre[k].z * 255.0f, 0.0f, 255.0f) << 16);
     }
     // this eye's depth-map output: (depth * 255).astype(uint8) wraps mod 256 (quirk Q7), value code / 255 on three channels
-#if defined(PP_SKELETON) && PP_SKELETON >= 3
-    if (false) {
-#else
     if (OUT != PO_ASD && !PP_DEV_IS(37)) {
-#endif
         float* const dd = eyei == 0 ? A.depth_l : A.depth_r;
         char* const dd_row = (char*)dd + (size_t)(rowpix + (uint32_t)o0) * 12;
         int code[SLOTS];
@@ -433,19 +418,6 @@ __device__ __forceinline__ void pp_tile(const float* __restrict__ hot_image, con
         }
         return;
     }
-#if defined(PP_SKELETON) && PP_SKELETON == 2
-    {   // (memory skeleton without the staging arithmetic: x = column + a cheap function of the depth; records as in production)
-        PQ* const Pw = P + 1 + tid;
-        float* const pzw = pz + 1 + tid;
-#pragma unroll
-        for (int k = 0; k < SLOTS; k++) {
-            const int j = tid + k * NT;
-            const float x = (float)(s0 + j) + 0.5f + dpre[k] * E.div32;
-            if (SLOTS * NT + 4 == NPT || 1 + j < NPT) { Pw[k * NT] = PQ{rgbk[k], x}; pzw[k * NT] = dpre[k] - dmin; }
-        }
-        if (tid == 0) P[0] = PQ{rgbk[0], (float)(-1.0 * w)};
-    }
-#else
     {
         const bool flat = dmax == dmin;
         const float range = dmax - dmin;
@@ -554,79 +526,8 @@ __device__ __forceinline__ void pp_tile(const float* __restrict__ hot_image, con
             if (SHARP && DIA) { float* const xq0 = const_cast<float*>(xq); xq0[0] = (float)(-1.0 * w); xq0[1] = (float)(-1.0 * w); }
         }
     }
-#endif
     __syncthreads();  // barrier 1: points staged, in-wave reversed segments marked
     if (PP_DEV_IS(31)) return;
-#ifdef PP_SKELETON
-    // (measurement, round 5: the kernel's MEMORY SKELETON -- every global load, the LDS point records and their read-back, every
-    // output store in today's form (lane = source slot: dwordx3 at the slot's tile pixel + the mask dword; the depth-map stores
-    // above) -- with the polyline arithmetic removed: a pixel's colour is a cheap function of the three records the fast path
-    // reads.  Results are meaningless; never defined in a release.  PP_SKELETON=2: without the staging arithmetic as well,
-    // PP_SKELETON=3: like 2 with the loads only (no output store at all), 4: like 2 without the depth-map stores)
-    {
-#pragma unroll
-        for (int k = 0; k < SLOTS; k++) {
-            const int j = min(tid + k * NT, ns - 1), o = 1 + j;
-            const PQ pm = P[o - 1], pc = P[o], pp = P[o + 1];
-            const int q = tid + k * NT + qoff;
-            const uint32_t mix = (pm.rgb + pp.rgb) ^ pc.rgb ^ (uint32_t)(pc.x > pm.x);
-#if PP_SKELETON == 3
-            if (mix == 0x12345678u && q == 77777) emit_k(0, 1.0f, 2.0f, 3.0f);
-#else
-            if ((unsigned)q < (unsigned)wt) emit_k(q, (float)(mix & 0xffu), (float)((mix >> 8) & 0xffu), (float)((mix >> 16) & 0xffu));
-#endif
-        }
-        return;
-    }
-#endif
-    // (model experiment, tools/r04_model.sh: -DPP_PAD_S=n / -DPP_PAD_V=n add n independent scalar / vector adds per wave here,
-    // so that the cost of one more instruction of either kind is measured on the production kernel; never defined in a release)
-#if defined(PP_PAD_S) || defined(PP_PAD_V)
-    {
-        int pa = tid, pb = row, pc = tile, pd = frame;
-#ifdef PP_PAD_S
-        int sa = __builtin_amdgcn_readfirstlane(pa), sb = __builtin_amdgcn_readfirstlane(pb), sc = __builtin_amdgcn_readfirstlane(pc),
-            sd = __builtin_amdgcn_readfirstlane(pd);
-#pragma unroll
-        for (int i = 0; i < PP_PAD_S / 4; i++)
-            asm volatile("s_add_u32 %0, %0, 1\n s_add_u32 %1, %1, 1\n s_add_u32 %2, %2, 1\n s_add_u32 %3, %3, 1" : "+s"(sa), "+s"(sb), "+s"(sc), "+s"(sd));
-        if (sa + sb + sc + sd == 0x7ffffff3) hazard = true;
-#endif
-#ifdef PP_PAD_V
-#pragma unroll
-        for (int i = 0; i < PP_PAD_V / 4; i++)
-            asm volatile("v_add_u32 %0, %0, 1\n v_add_u32 %1, %1, 1\n v_add_u32 %2, %2, 1\n v_add_u32 %3, %3, 1" : "+v"(pa), "+v"(pb), "+v"(pc), "+v"(pd));
-        if (pa + pb + pc + pd == 0x7ffffff3) hazard = true;
-#endif
-    }
-#endif
-#ifdef PP_PAD_P   // packed float32 adds (two results per instruction)
-    {
-        double pa = (double)tid, pb = (double)row;
-#pragma unroll
-        for (int i = 0; i < PP_PAD_P / 2; i++)
-            asm volatile("v_pk_add_f32 %0, %0, %0\n v_pk_add_f32 %1, %1, %1" : "+v"(pa), "+v"(pb));
-        if (pa + pb == 12345.678) hazard = true;
-    }
-#endif
-#ifdef PP_PAD_D   // ONE dependent chain of vector adds (every instruction waits for the previous one's result)
-    {
-        int pa = tid;
-#pragma unroll
-        for (int i = 0; i < PP_PAD_D / 4; i++)
-            asm volatile("v_add_u32 %0, %0, 1\n v_add_u32 %0, %0, 1\n v_add_u32 %0, %0, 1\n v_add_u32 %0, %0, 1" : "+v"(pa));
-        if (pa == 0x7ffffff3) hazard = true;
-    }
-#endif
-#ifdef PP_PAD_C   // the same with an instruction of the "4-cycle class" of tools/ubench (a conversion)
-    {
-        int pa = tid, pb = row, pc = tile, pd = frame;
-#pragma unroll
-        for (int i = 0; i < PP_PAD_C / 4; i++)
-            asm volatile("v_cvt_f32_ubyte0 %0, %0\n v_cvt_f32_ubyte0 %1, %1\n v_cvt_f32_ubyte0 %2, %2\n v_cvt_f32_ubyte0 %3, %3" : "+v"(pa), "+v"(pb), "+v"(pc), "+v"(pd));
-        if (pa + pb + pc + pd == 0x7ffffff3) hazard = true;
-    }
-#endif
 
     // ---- the segment pairs the staging loop could not see: lane 63 of every 64-point chunk (its right neighbour was staged
     // by another wave) and the left sentinel's pair.  Every wave checks the chunks IT staged -- lanes 0 .. SLOTS-1, one pair
@@ -1494,7 +1395,6 @@ static hipError_t polypoint_launch(PolyPointArgs& A, int out, hipStream_t stream
     const int tiles = (A.w + A.T - 1) / A.T;
     dim3 grid(tiles * 8, A.single >= 0 ? (A.h + 7) / 8 : eye_group_grid_y(A.h), A.n), block(NT);   // (see the kernel's prologue)
     size_t lds = polypoint_lds(NT, SLOTS, A.T, A.S, KP, KS, SHARP ? PP_DCAP_SHARP : PP_DCAP, SHARP);
-    // (development: CS_DEBUG_PT_VARIANT 13..16 pads the LDS request so that only 3..6 workgroups fit a CU -- occupancy what-if)
     const int npt = polypoint_npt(NT, SLOTS, A.T, A.S);
     const int off_dflag = 8 * npt + 4 * npt + 4 * polypoint_plcap(A.T, SHARP, SHARP ? PP_DCAP_SHARP : PP_DCAP), off_dcnt = off_dflag + ((2 * A.T + 3) & ~3);
     // sharp under the dialect: both points of every record, behind everything else
@@ -1508,8 +1408,6 @@ static hipError_t polypoint_launch(PolyPointArgs& A, int out, hipStream_t stream
         A.epk[e][2] = (unsigned long long)(uint32_t)E.st_min | ((unsigned long long)((uint32_t)E.st_max & 0xffffu) << 32) |
                       ((unsigned long long)(E.enabled ? 1u : 0u) << 48);
     }
-    const int occ = dev_switch(CS_DEBUG_PT_VARIANT) - 10;
-    if (occ >= 3 && occ <= 6) { const size_t pad = (size_t)(163840 / (occ + 1) + 1024) & ~(size_t)255; if (pad > lds) lds = pad; }
 #define PP_LAUNCH(O)                                                                                                         \
     {                                                                                                                        \
         hipError_t e = hipFuncSetAttribute((const void*)k_polypoint<NT, SLOTS, O, KP, KS, MINW, SHARP, DIA, SW>,                 \
@@ -1529,16 +1427,10 @@ static hipError_t polypoint_launch(PolyPointArgs& A, int out, hipStream_t stream
 // Launch for the eyes of `R` (SBS / TB / single-eye / uint8 outputs; no anaglyph).  `rowflag` must be zeroed by the caller;
 // afterwards the general kernel is run over the flagged rows.
 hipError_t launch_polypoint(const RowArgs& R, int S, uint8_t* rowflag, hipStream_t stream, int sharp, uint32_t* hint, int* tile_width) {
-    // workgroup geometry: threads x point slots per lane.  256 x 4 (7 workgroups per CU at the bench halo, 19.5 KB of LDS each) is
-    // the default; development switch CS_DEBUG_PT_VARIANT: 3 = 256 x 3 (the default until the end of round 3), 4 = 256 x 4,
-    // 5 = 384 x 3, 6 = 320 x 3
-    const int forced = dev_switch(CS_DEBUG_PT_VARIANT);
-    int geo = (forced >= 3 && forced <= 7) ? forced : 4;
-    if (sharp && geo != 5) geo = 4;
-    auto nt_of = [](int g) { return g == 5 ? 384 : (g == 6 ? 320 : 256); };
-    auto sl_of = [](int g) { return g == 4 ? 4 : (g == 7 ? 5 : 3); };
-    if (polypoint_tile(R.w, S, nt_of(geo) * sl_of(geo), nt_of(geo)) == 0 && (geo == 3 || geo == 4)) geo = 5;
-    const int nt = nt_of(geo), slots = sl_of(geo);
+    // workgroup geometry: threads x point slots per lane.  256 x 4 (7 workgroups per CU at the bench halo, 19.5 KB of LDS each);
+    // 384 x 3 (the wide-halo geometry) when that tile does not fit
+    const bool wide = polypoint_tile(R.w, S, 256 * 4, 256) == 0;
+    const int nt = wide ? 384 : 256, slots = wide ? 3 : 4;
     PolyPointArgs A;
     A.n = R.n; A.h = R.h; A.w = R.w; A.S = S;
     A.T = polypoint_tile(R.w, S, nt * slots, nt);
@@ -1559,7 +1451,7 @@ hipError_t launch_polypoint(const RowArgs& R, int S, uint8_t* rowflag, hipStream
     if (tile_width) *tile_width = A.T;
     // (dialect bits: 1 = the float64 disparity chain alone -- the sweep's typing stays D32; 2 / 3 = numba's typing of the sweep, without /
     // with the chain: the SW instantiations, default geometry only)
-    if ((R.d64 & 2) && geo != 4) return hipErrorInvalidValue;
+    if ((R.d64 & 2) && wide) return hipErrorInvalidValue;
     const int out = R.out_u8 ? PO_ASD : (R.stereo_is_u8 ? (R.no_mask ? PO_U8NM : PO_U8) : PO_F32);
     if ((out == PO_ASD) != (R.image_u8 != nullptr)) return hipErrorInvalidValue;  // uint8 image in <=> uint8 image out
     if ((size_t)A.n * A.h * A.w >= (1ull << 31) || (size_t)A.n * A.out_h * A.out_w >= (1ull << 31) || A.h > 4 * 65535 - 512 || A.n > 65535)
@@ -1569,22 +1461,16 @@ hipError_t launch_polypoint(const RowArgs& R, int S, uint8_t* rowflag, hipStream
         return polypoint_launch<256, 4, PP_SW_MINW_SOFT, 0, 1, 1>(A, out, stream);
     }
     if (R.d64) {   // the float64 disparity chain (one geometry per form: the default one, or the wide-halo one)
-        if (sharp) return geo == 5 ? polypoint_launch<384, 3, 5, 1, 1>(A, out, stream) : polypoint_launch<256, 4, 5, 1, 1>(A, out, stream);
-        if (geo == 5) return polypoint_launch<384, 3, 7, 0, 1>(A, out, stream);
+        if (sharp) return wide ? polypoint_launch<384, 3, 5, 1, 1>(A, out, stream) : polypoint_launch<256, 4, 5, 1, 1>(A, out, stream);
+        if (wide) return polypoint_launch<384, 3, 7, 0, 1>(A, out, stream);
         return polypoint_launch<256, 4, PP_MINW, 0, 1>(A, out, stream);
     }
     if (sharp) {   // (two geometries: the default and the wide-halo one)
-        if (geo == 5) return polypoint_launch<384, 3, 7, 1>(A, out, stream);
+        if (wide) return polypoint_launch<384, 3, 7, 1>(A, out, stream);
         return polypoint_launch<256, 4, PP_SHARP_MINW, 1>(A, out, stream);
     }
-    switch (geo) {
-    case 3: return polypoint_launch<256, 3, PP_MINW, 0>(A, out, stream);
-    case 4: return polypoint_launch<256, 4, PP_MINW, 0>(A, out, stream);
-    case 5: return polypoint_launch<384, 3, 7, 0>(A, out, stream);
-    case 6: return polypoint_launch<320, 3, 6, 0>(A, out, stream);
-    case 7: return polypoint_launch<256, 5, PP_MINW, 0>(A, out, stream);
-    default: return polypoint_launch<256, 4, PP_MINW, 0>(A, out, stream);
-    }
+    if (wide) return polypoint_launch<384, 3, 7, 0>(A, out, stream);
+    return polypoint_launch<256, 4, PP_MINW, 0>(A, out, stream);
 }
 
 // Second tier (k_polypoint_listed): the flagged rows of `list` / `count` (k_collect_rows) once more, with PP_DCAP2 slots and longer

@@ -37,21 +37,12 @@
 namespace cs {
 
 #define PT_T 512      // output pixels per tile
-// -DCS_PT_TIMESTAMPS=1: development build with per-phase timestamps of sampled workgroups (CS_DBG=20).
 // PT_DEV_CUTOFF(n): CS_DBG=n returns after that phase (8 image staged, 9 LDS set up, 11 disparity staged, 12 registered,
 // 18 pass 1, 13 before the stores).  The cut-offs stay in release builds on purpose: each is one scalar compare, and the
 // basic-block boundaries they create keep the register allocator from spilling scalar state that is live across the
 // phases (measured: 8 instead of 30 spilled VGPRs, all of them then in the rare general search; 6.2 vs 6.8 ms per
-// 16 frames).  PT_DEV_IS(n): development-only behaviours (15 skips the evaluation, 41 memory-only pass).
-#ifndef CS_PT_TIMESTAMPS
-#define CS_PT_TIMESTAMPS 0
-#endif
+// 16 frames).
 #define PT_DEV_CUTOFF(n) if (A.dbg == (n)) return
-#if CS_PT_TIMESTAMPS
-#define PT_DEV_IS(n) (A.dbg == (n))
-#else
-#define PT_DEV_IS(n) false
-#endif
 #define PT_THREADS 256  // == the 256 entries of the byte -> float table, one per thread
 
 __constant__ csm::PowfTables c_pt_powf_tables = CS_POWF_TABLES_INIT;
@@ -100,7 +91,7 @@ struct PolyTileArgs {
     uint8_t* rowflag;  // [n][h] set to 1 when the row must be redone by the general kernel
     const uint32_t* tilemap; const float* gray; int tm_words;   // lazy depth-blur tiles (cs_common.h) or null
     int dbg;           // env CS_DBG: 14 = count the pixels per evaluation path into the spare stats words, 17 = no exponent
-                       // shortcuts (tests compare the two); more in development builds, see CS_PT_TIMESTAMPS
+                       // shortcuts (tests compare the two); more in development builds, see PT_DEV_CUTOFF
 };
 
 // PT_KP / PT_KS: polyline points / forward segments per output pixel the fast path can hold (more -> row redo)
@@ -112,23 +103,6 @@ k_polytile(const float* __restrict__ hot_image, const float* __restrict__ hot_de
            int hot_w, int hot_h, int hot_S, int hot_single, PolyTileArgs A) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
-    // development (-DCS_PT_TIMESTAMPS=1 and CS_DBG=20): per-phase latency of sampled workgroups, summed into the spare stats
-    // words of frame `phase`.  Compiled out by default: even the untaken branches delay the kernel-argument loads.
-#if CS_PT_TIMESTAMPS
-    const bool rec_wg = A.dbg == 20 && blockIdx.x % 61 == 0;  // sampled: the hot atomics perturb
-    long long t_prev = wall_clock64();
-    auto stamp = [&](int phase) {
-        if (rec_wg && A.stats_rw && threadIdx.x == 0) {
-            long long t = wall_clock64();
-            atomicAdd(&A.stats_rw[(size_t)(phase % A.n) * ST_WORDS + 12], (unsigned)(t - t_prev));
-            atomicAdd(&A.stats_rw[(size_t)(phase % A.n) * ST_WORDS + 13], 1u);
-            t_prev = t;
-        }
-    };
-#else
-    constexpr bool rec_wg = false;
-    auto stamp = [](int) {};
-#endif
     const int tiles = (hot_w + PT_T - 1) / PT_T;
     // (eye = slowest grid dimension: pairing the two eyes of a tile on one XCD so that the second finds the image row in
     // that L2 was measured 13 % SLOWER -- the eyes' output streams then hit the same HBM channels at the same time)
@@ -154,7 +128,7 @@ k_polytile(const float* __restrict__ hot_image, const float* __restrict__ hot_de
     E.st_max = eyei ? A.eye[1].st_max : A.eye[0].st_max;
     E.xoff = eyei ? A.eye[1].xoff : A.eye[0].xoff;
     E.yoff = eyei ? A.eye[1].yoff : A.eye[0].yoff;
-    const bool eye_on = E.enabled && !PT_DEV_IS(41);
+    const bool eye_on = E.enabled;
     const int w = hot_w, h = hot_h;
     const int o0 = tile * PT_T, wt = min(PT_T, w - o0);
     const int s0 = max(0, (o0 - hot_S - 1) & ~3), s1 = min(w, o0 + wt + hot_S + 1), ns = s1 - s0;  // s0 % 4 == 0: float4 staging
@@ -210,8 +184,6 @@ k_polytile(const float* __restrict__ hot_image, const float* __restrict__ hot_de
     const float4* s4 = reinterpret_cast<const float4*>(hot_image + (rowpix + s0) * 3);
     float4 q0 = make_float4(0.f, 0.f, 0.f, 0.f), q1 = q0, q2 = q0;
     if (tid < nq) { q0 = s4[3 * tid]; q1 = s4[3 * tid + 1]; q2 = s4[3 * tid + 2]; }
-    stamp(10);  // (development) loads issued
-    if (rec_wg) { __builtin_amdgcn_s_waitcnt(0); stamp(11); }  // loads arrived
     const float scale = (A.scale_from_stats && st[ST_SCALE255]) ? 255.0f : 1.0f;
     const float dmin = eye_on ? csm::ord2f(st[E.st_min]) : 0.0f, dmax = eye_on ? csm::ord2f(st[E.st_max]) : 0.0f;
 
@@ -255,7 +227,6 @@ k_polytile(const float* __restrict__ hot_image, const float* __restrict__ hot_de
             img[j] = (uint32_t)src[3 * j] | ((uint32_t)src[3 * j + 1] << 8) | ((uint32_t)src[3 * j + 2] << 16);
     }
     __syncthreads();  // tables ready
-    stamp(1);
     PT_DEV_CUTOFF(8);
     if (!eye_on) {
         for (int q = tid; q < wt; q += PT_THREADS) dep8[q] = csm::f32_to_u8_wrap((depth_at(o0 + q - s0) * scale) * 255.0f);
@@ -359,7 +330,6 @@ k_polytile(const float* __restrict__ hot_image, const float* __restrict__ hot_de
         if (fold) flags[3] = 1;
     }
     __syncthreads();
-    stamp(2);
 
     PT_DEV_CUTOFF(11);
     lut[tid] = (float)tid / 255.0f;  // (PT_THREADS == 256) the powf tables underneath are dead now; read in the store phase
@@ -464,7 +434,6 @@ k_polytile(const float* __restrict__ hot_image, const float* __restrict__ hot_de
         }
     }
     __syncthreads();
-    stamp(mono ? 4 : 3);  // fold tiles are accounted separately
 
     // ---- EVALUATE ----------------------------------------------------------------------------------------
     // per-pixel constants of the float64 ("Python float") branch of the sub-interval arithmetic
@@ -812,7 +781,7 @@ k_polytile(const float* __restrict__ hot_image, const float* __restrict__ hot_de
         if (SHARP) return mono ? (c >> 12) == 2u : c == 0x0302u;
         return mono ? (c >> 12) == 1u : c == 0x0201u;
     };
-    if (!eye_on || PT_DEV_IS(15)) {
+    if (!eye_on) {
         for (int q = tid; q < wt; q += PT_THREADS) put(q, img[o0 + q - s0]);
     } else {
         for (int qa = tid; qa < wt; qa += 2 * PT_THREADS) {
@@ -859,7 +828,6 @@ k_polytile(const float* __restrict__ hot_image, const float* __restrict__ hot_de
         __syncthreads();
         // the leftovers below usually fit one wave; the other three write the depth-map output meanwhile
         if (tid >= 64) store_depth(tid - 64, PT_THREADS - 64);
-        stamp(mono ? 5 : 8);
         // ---- pass 2 (soft): the chain path over the listed pixels, the general search for those it cannot do
         const int nlist = flags[2];
         for (int base = tid & ~63; base < nlist; base += PT_THREADS) {
@@ -893,7 +861,6 @@ k_polytile(const float* __restrict__ hot_image, const float* __restrict__ hot_de
     }
     if (hazard) flags[0] = 1;
     __syncthreads();
-    stamp(mono ? 7 : 6);
     if (flags[0]) {
         // the general kernel redoes this row (both eyes) and overwrites whatever is stored below
         if (tid == 0) A.rowflag[(size_t)frame * h + row] = 1;
@@ -940,8 +907,6 @@ k_polytile(const float* __restrict__ hot_image, const float* __restrict__ hot_de
                 m[q] = ((int)res[3 * q] + (int)res[3 * q + 1] + (int)res[3 * q + 2]) == 0 ? 1.0f : 0.0f;
         }
     }
-    if (rec_wg) __builtin_amdgcn_s_waitcnt(0);
-    stamp(9);
 }
 
 static size_t polytile_lds(int S, int sharp, int PT_KP, int PT_KS) {
@@ -975,7 +940,6 @@ hipError_t launch_polytile(int sharp, const RowArgs& R, int S, uint8_t* rowflag,
     A.tilemap = R.tilemap; A.gray = R.lazy_gray; A.tm_words = R.tm_words;
     const int tiles = (A.w + PT_T - 1) / PT_T;
     dim3 grid(tiles * 8, A.single >= 0 ? (A.h + 7) / 8 : eye_group_grid_y(A.h), A.n), block(PT_THREADS);
-    const int variant = dev_switch(CS_DEBUG_PT_VARIANT);
 #define PT_LAUNCH(SH, KP, KS, MW)                                                                                   \
     {                                                                                                               \
         size_t lds = polytile_lds(S, SH, KP, KS);                                                                   \
@@ -986,15 +950,9 @@ hipError_t launch_polytile(int sharp, const RowArgs& R, int S, uint8_t* rowflag,
                            A.eye[1].depth, A.w, A.h, A.S, A.single, A);                              \
     }
     // soft default: 4 points / 5 segments per pixel in the lists -> 21.6 KB of LDS at the bench halo, 72 VGPRs: 7 workgroups
-    // per CU (LDS is handed out in 2 KB granules; 6 segments would be 128 bytes over).  CS_PT_VARIANT: development.
+    // per CU (LDS is handed out in 2 KB granules; 6 segments would be 128 bytes over).
     // sharp (two points per source pixel): 5 points / 7 segments per pixel (+16 % over 6 / 8 at the same redo rate on the bench)
-    if (sharp && variant == 1) PT_LAUNCH(1, 6, 8, 4)
-    else if (sharp && variant == 2) PT_LAUNCH(1, 4, 6, 5)
-    else if (sharp) PT_LAUNCH(1, 5, 7, 5)
-    else if (variant == 1) PT_LAUNCH(0, 4, 6, 6)
-    else if (variant == 9) PT_LAUNCH(0, 4, 5, 7)
-    else if (variant == 2) PT_LAUNCH(0, 3, 4, 7)
-    else if (variant == 13) PT_LAUNCH(0, 6, 8, 6)
+    if (sharp) PT_LAUNCH(1, 5, 7, 5)
     else PT_LAUNCH(0, 4, 5, 7)
 #undef PT_LAUNCH
     return hipGetLastError();

@@ -1058,9 +1058,6 @@ __device__ __forceinline__ void poly_seg_pixels(const Poly& P, int o, int& p0, i
 #ifndef RPL_K
 #define RPL_K 16   // list entries a lane of k_poly_replay_lanes holds (18 B each in LDS)
 #endif
-#ifndef RPL_KL
-#define RPL_KL 64  // ... of its second instantiation (lists of dozens: noise depth; 74 KB of LDS per wave, two waves per CU)
-#endif
 struct RpCtx {      // where a row exports its stretches to (dump == null: replay inside the row kernel)
     uint8_t* dump; uint32_t* list; uint32_t* ctr; uint32_t pool16, cap; uint32_t rowid; int eye;   // pool16: dump bytes / 16
     uint8_t* retry;   // LEAN: one byte per row, set when the row needs the full kernel (its inline replay)
@@ -1601,9 +1598,9 @@ __device__ void technique_polylines(const Lds& L, int w, const EyeArgs& E, float
                     const bool good = c0 == 0 || seg0 >= 0;   // (always: the pixel before was marked because one segment is active)
                     if (!good) *rp_ok = 0;
                     uint32_t* q = sinfo + RP_DESC * si;
-                    // (bit 31: not for the 16-entry lane kernel; bit 30 with it: for the 64-entry one -- lists of up to ~56, or unknown)
+                    // (bit 31: not for the 16-entry lane kernel)
                     q[1] = slist[si]; q[2] = (uint32_t)seg0;
-                    q[3] = (uint32_t)sgp0 | (longest > RPL_K - 3 ? 0x80000000u : 0u) | ((longest > RPL_K - 3 && (longest <= RPL_KL - 8 || longest == 0x7fff)) ? 0x40000000u : 0u);
+                    q[3] = (uint32_t)sgp0 | (longest > RPL_K - 3 ? 0x80000000u : 0u);
                     q[4] = (uint32_t)pw0 | ((uint32_t)pw1 << 16);
                     q[5] = (uint32_t)cmin | ((uint32_t)cmax << 16); q[6] = X->rowid | ((uint32_t)X->eye << 31); q[7] = (uint32_t)P.binoff[c0];
                 }
@@ -1866,19 +1863,6 @@ struct Px3f { float x, y, z; };
 struct Px3b { uint8_t x, y, z; };
 __device__ __forceinline__ float ax32_of(float nd) { return fabsf(nd); }
 
-// -DHYB_WTAB (experiment, round 5): the Gaussian weight of a contribution is exp((double)(-(diff * diff) / 2.0f))
-// with diff = dest_x - (float)column, an EXACT float32 difference (reference :1643-1644).  For dest_x >= 512 the float32 dest_x is
-// a multiple of 2^-14, so |diff| < 2 is one of 32 768 multiples of 2^-14 (coarser binades use a subset): ONE table of the
-// libm-exact doubles, indexed by (int)(|diff| * 2^14), replaces the ~25-instruction float64 evaluation by a gather.
-#ifdef HYB_WTAB
-__device__ double d_hyb_wtab[32768];
-__global__ void __launch_bounds__(256) k_hyb_wtab_init() {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    const float d = (float)i * 0x1p-14f;
-    const float arg = -(d * d) / 2.0f;
-    d_hyb_wtab[i] = csm::exp_exact_small((double)arg, d_hyb_exp_tab);
-}
-#endif
 
 // The same splat for an output TILE of one eye row (node path, float32 image): only the sources within S + 2 columns of
 // the tile can touch it, so a 256-thread workgroup stages them three per lane and runs the counting sort, the in-bin
@@ -2093,17 +2077,10 @@ __global__ void __launch_bounds__(HYT_NT) k_hybrid_splat_tile(RowArgs A, int S, 
         int p2 = e1, e2 = mono ? binoff[q + 3] : binoff[q + 2];
         float acc0 = 0.0f, acc1 = 0.0f, acc2 = 0.0f, ws = 0.0f;
         bool touched = false;
-#ifdef HYB_WTAB
-        const bool wtab = o0 - 1 >= 512;   // every dest_x that can touch the tile is >= o0 - 1 (tile-uniform)
-#endif
         auto contribute = [&](int j) {
             const float diff = destx[j] - (float)jcol;
             const float arg = -(diff * diff) / 2.0f;
-#ifdef HYB_WTAB
-            double wg = wtab ? d_hyb_wtab[(uint32_t)(fabsf(diff) * 16384.0f)] : csm::exp_exact_small((double)arg, etab);
-#else
             double wg = csm::exp_exact_small((double)arg, etab);   // (-8 < arg <= 0: no range test, cs_math.h)
-#endif
             if (f64chain) {
                 const double d64v = destx64[j] - (double)jcol;
                 wg = csm::exp_exact_small(-(d64v * d64v) / 2.0, etab);
@@ -2711,9 +2688,7 @@ __device__ __forceinline__ void rowwarp_row(const RowArgs& A, const int row, con
                 // LDS base re-read through an opaque move per eye -- what the compiler derives from them is recomputed instead of
                 // carried across the eye loop: 336 -> 278 scalar, 77 -> 48 vector spills; the same trick as in k_gpuwarp)
                 int we = w, l0 = 0;
-#ifndef RW_NO_LAUNDER
                 if (LEAN) asm volatile("" : "+s"(we), "+s"(l0));
-#endif
                 const Lds Le = carve(smem + l0, FILL, we, A.anaglyph);
                 technique_polylines<FILL == CS_FILL_POLYLINES_SHARP ? 1 : 0, DIALECT, decltype(out), LEAN>(Le, we, E, A.e32, st_rw, out, A.dbg, &X, A.d64, A.e64, RG);
             }
@@ -2993,7 +2968,6 @@ __global__ void __launch_bounds__(64) k_poly_replay_lanes(RowArgs A) {
     extern __shared__ __attribute__((aligned(16))) char lane_smem[];
     float4* const ent_all = reinterpret_cast<float4*>(lane_smem);                 // {x0, x1, z0, z1} of entry k of lane l at [64 k + l]
     uint16_t* const csg_all = reinterpret_cast<uint16_t*>(lane_smem + (size_t)K * 64 * 16);   // its segment id
-    constexpr bool LONG = K > RPL_K;   // the second instantiation: the stretches flagged for it (bits 31 + 30 of word 3), its own cursor
     const int lane = threadIdx.x;
     const uint32_t count = min(A.rp_ctr[1], A.rp_cap);
     if (count == 0) return;
@@ -3002,14 +2976,14 @@ __global__ void __launch_bounds__(64) k_poly_replay_lanes(RowArgs A) {
     float4* const ent = ent_all + lane;
     for (;;) {
         uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(&A.rp_ctr[LONG ? 0 : 3], 64u);
+        if (lane == 0) base = atomicAdd(&A.rp_ctr[3], 64u);
         base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
         if (base >= count) break;
         const uint32_t idx = base + (uint32_t)lane;
         if (idx >= count) continue;
         uint32_t* const q = A.rp_list + (size_t)idx * RP_DESC;
         const uint32_t slot = q[0];
-        if (slot == 0xffffffffu || (LONG ? (q[3] >> 30) != 3u : (q[3] >> 31) != 0u)) continue;   // (done / another kernel's)
+        if (slot == 0xffffffffu || (q[3] >> 31) != 0u) continue;   // (done / the wave kernel's)
         const int c0 = (int)(q[1] & 0xffffu), c1 = (int)(q[1] >> 16), seg0 = (int)q[2], sgp0 = (int)(q[3] & 0x3fffffffu);
         const int pw0 = (int)(q[4] & 0xffffu), pw1 = (int)(q[4] >> 16), cmin = (int)(q[5] & 0xffffu), cmax = (int)(q[5] >> 16);
         const uint32_t rowid = q[6] & 0x7fffffffu;
@@ -3154,14 +3128,12 @@ __global__ void __launch_bounds__(64) k_poly_replay_lanes(RowArgs A) {
 // the host pipeline are eight), larger ones the 4 KB per row; a row that finds the pool (or the descriptor list) full takes the
 // second pass (in-row replay), and a caller can always give more (workspace beyond cs_workspace_bytes extends the pool).
 static size_t rp_pool_bytes(size_t rows, int w, int sharp) {
-    // (development: CS_DEBUG_PT_VARIANT 41 quadruples the per-row budget -- does a workload run out of pool?)
-    // (48: a deliberately tiny pool -- most flagged rows find it full: tests/test_gpu_stress.py exercises the refund path)
-    const int variant = dev_switch(CS_DEBUG_PT_VARIANT);
-    const size_t per_row = variant == 41 ? 16384 : 4096;
-    const size_t every_row = rows * 2 * ((size_t)rp_win16(poly_npt(w, sharp), w) << 4), budget = rows * per_row + (64u << 10);
+    // (development: PTV_TINY_REPLAY_POOL, a deliberately tiny pool -- most flagged rows find it full: tests/test_gpu_fullsize.py
+    // exercises the refund path)
+    const size_t every_row = rows * 2 * ((size_t)rp_win16(poly_npt(w, sharp), w) << 4), budget = rows * 4096 + (64u << 10);
     const size_t cap = (size_t)1 << 30;
     size_t pool = every_row <= cap ? every_row : (budget > cap ? budget : cap);
-    if (variant == 48) pool = rows * 96 + 8192;
+    if (dev_switch(CS_DEBUG_PT_VARIANT) == PTV_TINY_REPLAY_POOL) pool = rows * 96 + 8192;
     if (pool > every_row) pool = every_row;
     return (pool + 15) & ~(size_t)15;
 }
@@ -3191,24 +3163,13 @@ hipError_t launch_poly_replay(int sharp, const RowArgs& A, int halo, hipStream_t
     const dim3 grid(256 * (wide ? 5 : 19)), block(64);   // (resident waves per CU: 29 KB / 8.3 KB of LDS each)
     uint8_t* retry = poly_replay_retry_flags(A);
     // first a lane per stretch (short lists: saturated depth), then a wave per stretch for what that kernel gave up
-    // (CS_DEBUG_PT_VARIANT 45: the wave kernel alone, as in round 4)
-    if (dev_switch(CS_DEBUG_PT_VARIANT) != 45) {
+    // (PTV_REPLAY_WAVE_ONLY: the wave kernel alone, as in round 4.  A 64-entry lane instantiation for the long lists of noise
+    // depth finished them all, bit-exact, and was 2.4 x SLOWER than the wave kernel: DESIGN section 10)
+    if (dev_switch(CS_DEBUG_PT_VARIANT) != PTV_REPLAY_WAVE_ONLY) {
         const dim3 lgrid(256 * 8);
-        const size_t lds16 = (size_t)RPL_K * 64 * 18, lds64 = (size_t)RPL_KL * 64 * 18;
+        const size_t lds16 = (size_t)RPL_K * 64 * 18;
         if (sharp) hipLaunchKernelGGL((k_poly_replay_lanes<1, RPL_K>), lgrid, block, lds16, stream, A);
         else hipLaunchKernelGGL((k_poly_replay_lanes<0, RPL_K>), lgrid, block, lds16, stream, A);
-        // ... then, ONLY under CS_DEBUG_PT_VARIANT 46, the stretches with lists of dozens (noise depth) by the 64-entry instantiation, two
-        // waves per CU.  Measured (tools/sessions/r05_s26.sh): it finishes them all, bit-exact, and is 2.4 x SLOWER than the wave kernel
-        // (8 noise frames: 263 against 110 ms) -- one wave per SIMD walks two 40-entry loops of dependent LDS reads per step, 23 us
-        // a step.  The scalar-bound wave kernel stays the path for long lists.
-        if (dev_switch(CS_DEBUG_PT_VARIANT) == 46) {
-            hipError_t e = sharp ? hipFuncSetAttribute((const void*)k_poly_replay_lanes<1, RPL_KL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds64)
-                                 : hipFuncSetAttribute((const void*)k_poly_replay_lanes<0, RPL_KL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds64);
-            if (e != hipSuccess) return e;
-            const dim3 g64(256 * 2);
-            if (sharp) hipLaunchKernelGGL((k_poly_replay_lanes<1, RPL_KL>), g64, block, lds64, stream, A);
-            else hipLaunchKernelGGL((k_poly_replay_lanes<0, RPL_KL>), g64, block, lds64, stream, A);
-        }
     }
     if (sharp && wide) hipLaunchKernelGGL((k_poly_replay<1, RP_PWS, RP_CWS_WIDE>), grid, block, 0, stream, A, retry, halo + 2);
     else if (sharp) hipLaunchKernelGGL((k_poly_replay<1, RP_PWS, RP_CWS>), grid, block, 0, stream, A, retry, halo + 2);
@@ -3372,9 +3333,6 @@ int launch_hybrid(const RowArgs& A0, void* workspace, hipStream_t stream, int pl
             uint16_t* lst = (uint16_t*)((char*)cnt + hybrid_count_bytes(A.n, A.h));
             e = hipMemsetAsync(cnt, 0, (size_t)A.n * A.neyes * A.h * 4, stream);
             if (e != hipSuccess) return CS_EHIP;
-#ifdef HYB_WTAB
-            hipLaunchKernelGGL(k_hyb_wtab_init, dim3(128), dim3(256), 0, stream);   // (experiment: every call; a product would do it once)
-#endif
             if (A.d64) hipLaunchKernelGGL((k_hybrid_splat_tile<true, true>), grid, dim3(HYT_NT), 0, stream, A, halo, T, cnt, lst);
             else hipLaunchKernelGGL(k_hybrid_splat_tile<true>, grid, dim3(HYT_NT), 0, stream, A, halo, T, cnt, lst);
             hipLaunchKernelGGL(k_hybrid_gaps<true>, dim3(A.h, A.neyes, A.n), dim3(64), 0, stream, A, (const uint32_t*)cnt, (const uint16_t*)lst);

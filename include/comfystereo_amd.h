@@ -274,7 +274,7 @@ CS_API int cs_profile_tiles(double *fraction);
 enum cs_debug_key {
     CS_DEBUG_DBG = 0,               /* 14: count pixels per evaluation path into spare stats words; 17: no exponent shortcuts */
     CS_DEBUG_NO_TILE = 1,           /* polylines: general row kernel for every row instead of the tiled path */
-    CS_DEBUG_PT_VARIANT = 2,        /* tile kernel: other list capacities / the previous kernel generation */
+    CS_DEBUG_PT_VARIANT = 2,        /* reference paths of the polylines and gpu_warp kernels: the PTV_* values of cs_common.h */
     CS_DEBUG_BLUR_TWO_PASS = 3,     /* depth blur: two-pass row kernels */
     CS_DEBUG_BLUR_EDGES_SCALAR = 4, /* depth blur: one-column-per-lane edge kernel */
     CS_DEBUG_BLUR_FULL_COPY = 5,    /* depth blur: write the edge-free tiles as well (no lazy tile map for the warp kernel) */

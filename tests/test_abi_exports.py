@@ -1,6 +1,7 @@
 """The C-ABI library loads on a GPU-less host and exports every symbol include/comfystereo_amd.h declares;
 argument validation that needs no device work behaves as documented (not gpu)."""
 import ctypes
+import json
 import os
 import re
 
@@ -37,7 +38,7 @@ def test_enums_match_header():
 
 def test_warp_path_codes_match_cs_common():
     """The gpu_warp path codes of the diagnostics word (cs_common.h GW_PATH_*) and their Python names agree, one code per
-    kernel instantiation gw_launch can run."""
+    kernel instantiation gw_launch can run; so do the pt_variant values (PTV_*) and their Python names."""
     src = open(os.path.join(ROOT, "comfystereo_amd", "csrc", "cs_common.h")).read()
     assert int(re.search(r"ST_WARP_PATH\s*=\s*(\d+)", src).group(1)) == _native.ST_WARP_PATH
     codes = {}
@@ -53,6 +54,9 @@ def test_warp_path_codes_match_cs_common():
         elif short == "k" and args[2:] == ["true"]:
             args = [args[0], "gen"]
         assert _native.WARP_PATH_NAME[code] == f"{short}<{','.join(args)}>", (code, kern)
+    # ... and the values of the development switch pt_variant (cs_common.h PTV_*)
+    ptv = {name.lower(): int(code) for name, code in re.findall(r"\bPTV_(\w+)\s*=\s*(\d+)", src)}
+    assert ptv and ptv == _native.PT_VARIANT
 
 
 def test_params_struct_layout():
@@ -127,15 +131,44 @@ def test_max_width_params_is_the_predicate_cs_generate_applies():
                     assert rc in want, (fill, mode, flags, div, w, rc, L.cs_last_error())
     assert seen_lower > 0   # (the cases the advisor named exist: a pre-validation with cs_max_width_mode alone would have passed them)
     assert L.cs_max_width_params(None) == 0
+    # ... and every answer of the host-side limits is the one recorded before the polylines path choice was single-sourced
+    with open(os.path.join(ROOT, "tests", "golden", "width_limits.json")) as f:
+        assert width_limits(L) == json.load(f)
+
+
+def width_limits(L):
+    """The host-side limits (no GPU): cs_max_width_params over the grid above, cs_max_width_mode for every technique x mode,
+    cs_workspace_bytes for a few shapes x techniques x modes x blur; keyed by their arguments (tests/golden/width_limits.json)."""
+    from comfystereo_amd import engine
+    out = {"max_width_params": {}, "max_width_mode": {}, "workspace_bytes": {}}
+    for fill in sorted(_native.FILL):
+        for mode in ("left-right", "red-cyan-anaglyph", "top-bottom"):
+            for flags, div, conv in ((0, 3.0, 0.5), (8, 3.0, 0.5), (24, 3.0, 0.5), (0, 15.0, 1.0), (8, 15.0, 1.0)):
+                p = engine.make_params(1, 4, 64, 4, 64, 3, fill, mode, div, 0.0, 0.0, conv, 2.0, False, 20.0, 20.0, 1.0, 0, 12)
+                p.flags = flags
+                out["max_width_params"][f"{fill}/{mode}/{flags}/{div}/{conv}"] = L.cs_max_width_params(ctypes.byref(p))
+        for mode in sorted(_native.MODE):
+            out["max_width_mode"][f"{fill}/{mode}"] = L.cs_max_width_mode(_native.FILL[fill], _native.MODE[mode])
+        for n, h, w in ((1, 4, 64), (3, 720, 1283), (4, 1080, 1920), (8, 2160, 3840)):
+            for mode in ("left-right", "red-cyan-anaglyph", "top-bottom", "left-only"):
+                for blur in (False, True):
+                    p = engine.make_params(n, h, w, h, w, 3, fill, mode, 6.0, 0.3, 0.0, 0.1, 2.0, blur, 20.0, 20.0, 2.0, 6, 12)
+                    out["workspace_bytes"][f"{fill}/{n}x{h}x{w}/{mode}/{int(blur)}"] = L.cs_workspace_bytes(ctypes.byref(p))
+    return out
 
 
 def test_debug_switches_are_explicit_and_release_builds_reject_the_phase_cutoffs():
     """cs_debug_set is the only way to reach the development switches (the library never reads the environment); a
-    release build refuses the CS_DEBUG_DBG values that would leave outputs unwritten."""
+    release build refuses the CS_DEBUG_DBG values that would leave outputs unwritten, and every build the pt_variant values
+    that are not in cs_common.h's PTV_* list."""
     L = _native.lib()
     assert L.cs_debug_set(_native.DEBUG["dbg"], 17) == _native.CS_OK
     assert L.cs_debug_set(_native.DEBUG["dbg"], 0) == _native.CS_OK
     assert L.cs_debug_set(_native.DEBUG["dbg"], 12) == _native.CS_EINVAL and b"CS_DEV" in L.cs_last_error()
+    for v in range(-1, 64):
+        want = _native.CS_OK if v in _native.PT_VARIANT.values() else _native.CS_EINVAL
+        assert L.cs_debug_set(_native.DEBUG["pt_variant"], v) == want, v
+    assert L.cs_debug_set(_native.DEBUG["pt_variant"], 0) == _native.CS_OK
     assert L.cs_debug_set(99, 1) == _native.CS_EINVAL
     src = os.path.join(ROOT, "comfystereo_amd", "csrc")
     for f in os.listdir(src):

@@ -746,14 +746,14 @@ def test_replay_pool_nearly_full_never_hands_out_overlapping_windows(engine, dev
     refunding around a successful one could hand a later row a window inside the successful row's live region (its stretches
     were then replayed from another row's sorted points: silently wrong, nondeterministic pixels).  The refund is now one
     compare-and-swap that only succeeds while the failed reservation is the topmost one.  A deliberately tiny pool
-    (cs_debug_set pt_variant 48: ~100 bytes per row) on saturated depth -- hundreds of flagged rows reserving at once, most of
+    (cs_debug_set pt_variant tiny_replay_pool: ~100 bytes per row) on saturated depth -- hundreds of flagged rows reserving at once, most of
     them failing -- must give the oracle's bits, several runs in a row (the interleaving differs from run to run)."""
     n, h, w = 4, 160, 2048
     img = synth.image_f32(n, h, w, seed=77)
     depth = np.stack([synth.clipped(1200, w, seed=s)[500:500 + h] for s in range(n)])[..., None].repeat(3, -1)
     want = node_oracle.generate(img, depth, 7.0, 0.0, "left-right", 0.0, 0.5, 2.0, ui, 20.0, 20.0, False, batch_size=12)
     p = engine.make_params(n, h, w, h, w, 3, fill, "left-right", 7.0, 0.0, 0.0, 0.5, 2.0, False, 20.0, 20.0, 1.0, 0, 12)
-    dev_switch("pt_variant", 48)
+    dev_switch("pt_variant", "tiny_replay_pool")
     plan = engine.Plan(p, torch.device("cuda"))
     dimg, ddepth = cuda(img), cuda(depth)
     for rep in range(6):
@@ -769,7 +769,7 @@ def test_lean_pass_on_the_flagged_tiles_column_ranges(engine, dev_switch, fill, 
     stages, sorts, lists and evaluates only those tiles' columns plus a margin (technique_polylines, PolyRange) -- the rest of the row
     keeps the tile kernel's pixels.  4K-wide rows, smooth depth with saturated patches (exact ties) at the left end, in the middle and
     at the right end of the row, so that ranges touch either sentinel and rows have one, two or three flagged tiles; against the
-    oracle, and the same bits as the whole-row form of round 4 (cs_debug_set pt_variant 44)."""
+    oracle, and the same bits as the whole-row form of round 4 (cs_debug_set pt_variant lean_whole_rows)."""
     n, h, w = 2, 40, 3840
     img = synth.image_f32(n, h, w, seed=41)
     ramp = np.linspace(0.2, 0.8, w, dtype=np.float32)[None, None, :] + 0.05 * np.sin(np.arange(h, dtype=np.float32))[None, :, None]
@@ -787,12 +787,12 @@ def test_lean_pass_on_the_flagged_tiles_column_ranges(engine, dev_switch, fill, 
         got = [t.cpu().numpy() for t in plan.run(cuda(img), cuda(depth))]
         st = plan.stats()
         assert int(st[:, 11].sum()) > 0 and int(st[:, 9].sum()) == 0   # rows went back to the row kernel; no kernel error flags
-        dev_switch("pt_variant", 44)
+        dev_switch("pt_variant", "lean_whole_rows")
         whole = [t.cpu().numpy() for t in engine.Plan(p, torch.device("cuda")).run(cuda(img), cuda(depth))]
-        # (... and the stretches replayed by a lane each, k_poly_replay_lanes, against a wave each alone: pt_variant 45)
-        dev_switch("pt_variant", 45)
+        # (... and the stretches replayed by a lane each, k_poly_replay_lanes, against a wave each alone: pt_variant replay_wave_only)
+        dev_switch("pt_variant", "replay_wave_only")
         waves = [t.cpu().numpy() for t in engine.Plan(p, torch.device("cuda")).run(cuda(img), cuda(depth))]
-        dev_switch("pt_variant", 0)
+        dev_switch("pt_variant", "default")
         for g, r, v, w_, name in zip(got, whole, waves, want, NAMES):
             assert np.array_equal(g, r), (mode, "column ranges vs whole rows", name)
             assert np.array_equal(g, v), (mode, "lane replay vs wave replay", name)
@@ -804,7 +804,7 @@ def test_naive_interpolating_second_tier_on_saturated_depth(engine, dev_switch):
     saturated to 0 / 1 are up to twice the halo wide) no longer go to the whole-row kernel but through the tile kernel once more with a
     window of 2 halo + 16 (persistent workgroups over the flagged-row list); what that flags -- intervals lengthened by black pixels --
     still does.  4K-wide rows of saturated depth with black patches, SBS and anaglyph, blur off and on: the oracle's bits, and the same
-    bits without the second tier (cs_debug_set pt_variant 47)."""
+    bits without the second tier (cs_debug_set pt_variant naive_no_tier2)."""
     n, h, w = 2, 48, 3840
     img = synth.image_f32(n, h, w, seed=51)
     img[:, 5:9, 1000:1400] = 0.0                      # black pixels lengthen intervals: beyond any window
@@ -815,11 +815,11 @@ def test_naive_interpolating_second_tier_on_saturated_depth(engine, dev_switch):
                                     depth_blur_falloff=2.0, depth_blur_vert_smooth=6, batch_size=12)
         p = engine.make_params(n, h, w, h, w, 3, "naive_interpolating", mode, 8.0, 0.0, 0.0, 0.5, 2.0, blur, 20.0, 20.0, 2.0, 6, 12)
         got = [t.cpu().numpy() for t in engine.Plan(p, torch.device("cuda")).run(cuda(img), cuda(depth))]
-        dev_switch("pt_variant", 47)
+        dev_switch("pt_variant", "naive_no_tier2")
         plan1 = engine.Plan(p, torch.device("cuda"))
         one = [t.cpu().numpy() for t in plan1.run(cuda(img), cuda(depth))]
         rows_one_tier = int(plan1.stats()[:, 11].sum())
-        dev_switch("pt_variant", 0)
+        dev_switch("pt_variant", "default")
         plan2 = engine.Plan(p, torch.device("cuda"))
         plan2.run(cuda(img), cuda(depth))
         rows_two_tiers = int(plan2.stats()[:, 11].sum())

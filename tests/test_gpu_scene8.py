@@ -86,17 +86,18 @@ def test_scene8_4k_wide_bands_vs_oracle(engine, fill, blur):
 
 @pytest.mark.parametrize("fill", ["polylines_sharp", "polylines_soft"])
 def test_second_tier_of_the_point_kernel_on_soft_silhouettes(engine, dev_switch, fill):
-    """Round 6: the rows k_polypoint flags go through k_polypoint_listed -- the same tile function with 512 slots for pixels under
-    reversed segments and longer per-pixel lists -- before the row kernel (polylines_sharp by default; cs_debug_set pt_variant 50 forces
-    it for soft, 49 switches it off).  Softened silhouettes at divergence 8 overflow the first tier's lists in many rows: with the
-    second tier fewer rows reach the row kernel, and all three settings give the oracle's bits."""
+    """Round 6: the rows k_polypoint flags go through k_polypoint_listed -- the same tile function with PP_DCAP2 = 192 instead of 160
+    slots for pixels under reversed segments and longer per-pixel lists (8 points / 12 segments sharp, 6 / 9 soft) -- before the row
+    kernel (polylines_sharp by default; cs_debug_set pt_variant soft_point_tier2 forces it for soft, no_point_tier2 switches it off).
+    Softened silhouettes at divergence 8 overflow the first tier's lists in many rows: with the second tier fewer rows reach the
+    row kernel, and all three settings give the oracle's bits."""
     n, h, w = 2, 64, 3840
     img = synth.image_f32(n, h, w, seed=71)
     depth = np.stack([synth.scene8(2160, w, seed=s, soften=True)[y0:y0 + h] for s, y0 in ((2, 700), (5, 1500))])[..., None].repeat(3, -1)
     want = node_oracle.generate(img, depth, 8.0, 0.0, "left-right", 0.0, 0.5, 2.0, UI[fill], 20.0, 20.0, False, batch_size=12)
     p = engine.make_params(n, h, w, h, w, 3, fill, "left-right", 8.0, 0.0, 0.0, 0.5, 2.0, False, 20.0, 20.0, 1.0, 0, 12)
     redone = {}
-    for variant in (49, 50, 0):
+    for variant in ("no_point_tier2", "soft_point_tier2", "default"):
         dev_switch("pt_variant", variant)
         plan = engine.Plan(p, torch.device("cuda"))
         got = [t.cpu().numpy() for t in plan.run(cuda(img), cuda(depth))]
@@ -105,6 +106,6 @@ def test_second_tier_of_the_point_kernel_on_soft_silhouettes(engine, dev_switch,
         redone[variant] = int(st[:, 11].sum())
         for g_, w_, name in zip(got, want, NAMES):
             assert np.array_equal(g_, w_), (fill, variant, name)
-    assert redone[49] > 0, "no row was flagged: the test does not reach the second tier"
-    assert redone[50] < redone[49]
-    assert redone[0] == (redone[50] if fill == "polylines_sharp" else redone[49])
+    assert redone["no_point_tier2"] > 0, "no row was flagged: the test does not reach the second tier"
+    assert redone["soft_point_tier2"] < redone["no_point_tier2"]
+    assert redone["default"] == (redone["soft_point_tier2"] if fill == "polylines_sharp" else redone["no_point_tier2"])

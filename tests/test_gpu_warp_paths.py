@@ -2,9 +2,10 @@
 
 gw_launch (cs_gpuwarp.hip) picks one of the k_gpuwarp_q / k_gpuwarp instantiations per call from the width, the exponent, the
 layout, the eyes and the buffers' alignment, and records the pick in every frame's ST_WARP_PATH stats word (_native.WARP_PATH).
-Each case below names the path it is built to reach under the default choice and under the development switch pt_variant:
-27 k_gpuwarp in the node layout, 25 the generic layout, 21 / 22 / 23 / 26 the workgroup sizes 512 / 256 (rows of at most 1024) /
-1024 / 256, 24 the 6-wave instantiation at 512 threads.  Every run is checked
+Each case below names the path it is built to reach under the default choice and under the development switch pt_variant
+(_native.PT_VARIANT): gw_no_quad k_gpuwarp in the node layout, gw_generic_layout the generic layout, gw_threads_512 /
+gw_threads_256_narrow / gw_threads_1024 / gw_threads_256 the workgroup sizes 512 / 256 (rows of at most 1024) / 1024 / 256,
+gw_six_waves the 6-wave instantiation at 512 threads.  Every run is checked
   * path: the recorded code is the expected one (a shape that quietly leaves the k_gpuwarp_q predicate fails here);
   * against node_oracle.generate: all four outputs array_equal.  The oracle follows the kernels' float32 arithmetic operation for
     operation, and every path has been measured bit-equal to it; the 2e-6 the other node-level tests allow (and the 1e-4 of
@@ -55,71 +56,71 @@ def case_id(c):
 # take k_gpuwarp.  Four 512-thread workgroups per CU (the 8-wave instantiations) fit up to ~1940 columns for k_gpuwarp and ~2010 for
 # k_gpuwarp_q; 1.3 is the exponent that adds the powf tables to the LDS, which moves that cut (1920, 1984).
 WIDTHS = [
-    C(8, 3, 2.0, "random8", div=8.0, paths={0: "q<6,2>", 27: "k<6,2,node>", 25: "k<6,2>", 21: "q<8,2>", 22: "q<6,2>", 23: "q<8,2>", 26: "q<6,2>", 24: "q<6,2>"}),
-    C(12, 2, 1.3, "stepped", div=8.0, paths={0: "q<6,-1>", 27: "k<6,-1,node>", 25: "k<6,-1>", 21: "q<8,-1>", 22: "q<6,-1>", 23: "q<8,-1>", 26: "q<6,-1>", 24: "q<6,-1>"}),
-    C(248, 5, 2.0, "blobs", div=12.0, paths={0: "q<6,2>", 27: "k<6,2,node>", 25: "k<6,2>", 21: "q<8,2>", 22: "q<6,2>", 23: "q<8,2>", 26: "q<6,2>", 24: "q<6,2>"}),
-    C(252, 3, 0.5, "stepped", div=8.0, paths={0: "q<6,-1>", 27: "k<6,-1,node>", 25: "k<6,-1>", 21: "q<8,-1>", 22: "q<6,-1>", 23: "q<8,-1>", 26: "q<6,-1>", 24: "q<6,-1>"}),
-    C(256, 2, 2.0, "noisy_ramp", div=8.0, paths={0: "q<6,2>", 27: "k<6,2,node>", 25: "k<6,2>", 21: "q<8,2>", 22: "q<6,2>", 23: "q<8,2>", 26: "q<6,2>", 24: "q<6,2>"}),
-    C(508, 5, 3.0, "clipped", div=8.0, paths={0: "q<6,-1>", 27: "k<6,-1,node>", 25: "k<6,-1>", 21: "q<8,-1>", 22: "q<6,-1>", 23: "q<8,-1>", 26: "q<6,-1>", 24: "q<6,-1>"}),
-    C(1008, 3, 2.0, "stepped", div=8.0, paths={0: "q<6,2>", 27: "k<6,2,node>", 25: "k<6,2>", 21: "q<8,2>", 22: "q<6,2>", 23: "q<8,2>", 26: "q<6,2>", 24: "q<6,2>"}),
-    C(1012, 1, 0.0, "blobs", div=8.0, paths={0: "q<6,-1>", 27: "k<6,-1,node>", 25: "k<6,-1>", 21: "q<8,-1>", 22: "q<6,-1>", 23: "q<8,-1>", 26: "q<6,-1>", 24: "q<6,-1>"}),
-    C(1020, 5, 2.0, "random8", div=8.0, paths={0: "q<6,2>", 27: "k<6,2,node>", 25: "k<6,2>", 21: "q<8,2>", 22: "q<6,2>", 23: "q<8,2>", 26: "q<6,2>", 24: "q<6,2>"}),
-    C(1024, 2, 1.0, "stepped", div=8.0, paths={0: "q<6,-1>", 27: "k<6,-1,node>", 25: "k<6,-1>", 21: "q<8,-1>", 22: "q<6,-1>", 23: "q<8,-1>", 26: "q<6,-1>", 24: "q<6,-1>"}),
-    C(1028, 3, 2.0, "stepped", div=8.0, paths={0: "q<8,2>", 27: "k<8,2,node>", 25: "k<8,2>", 21: "q<8,2>", 23: "q<8,2>", 26: "q<6,2>", 24: "q<6,2>"}),
-    C(1028, 3, 1.3, "blobs", div=8.0, paths={0: "q<8,-1>", 27: "k<8,-1,node>", 25: "k<8,-1>", 21: "q<8,-1>", 23: "q<8,-1>", 26: "q<6,-1>", 24: "q<6,-1>"}),
-    C(1920, 3, 1.3, "radial", div=4.5, paths={0: "q<8,-1>", 27: "k<6,-1,node>", 25: "k<6,-1>", 21: "q<8,-1>", 23: "q<8,-1>", 26: "q<6,-1>", 24: "q<6,-1>"}),
-    C(1940, 3, 2.0, "blobs", paths={0: "q<8,2>", 27: "k<6,2,node>", 25: "k<6,2>", 21: "q<8,2>", 23: "q<8,2>", 26: "q<6,2>", 24: "q<6,2>"}),
-    C(1984, 2, 1.3, "blobs", paths={0: "q<6,-1>", 27: "k<6,-1,node>", 25: "k<6,-1>", 21: "q<6,-1>", 23: "q<8,-1>", 26: "q<6,-1>", 24: "q<6,-1>"}),
-    C(1984, 5, 2.0, "blobs", paths={0: "q<8,2>", 27: "k<6,2,node>", 25: "k<6,2>", 21: "q<8,2>", 23: "q<8,2>", 26: "q<6,2>", 24: "q<6,2>"}),
-    C(2016, 2, 2.0, "stepped", div=8.0, paths={0: "q<6,2>", 27: "k<6,2,node>", 25: "k<6,2>", 21: "q<6,2>", 23: "q<8,2>", 26: "q<6,2>", 24: "q<6,2>"}),
-    C(2020, 5, 1.3, "blobs", div=8.0, paths={0: "q<6,-1>", 27: "k<6,-1,node>", 25: "k<6,-1>", 21: "q<6,-1>", 23: "q<8,-1>", 26: "q<6,-1>", 24: "q<6,-1>"}),
-    C(2044, 1, 2.0, "clipped", div=8.0, paths={0: "q<6,2>", 27: "k<6,2,node>", 25: "k<6,2>", 21: "q<6,2>", 23: "q<8,2>", 26: "q<6,2>", 24: "q<6,2>"}),
-    C(2048, 3, 2.0, "stepped", div=8.0, blur=True, paths={0: "q<6,2>", 27: "k<6,2,node>", 25: "k<6,2>", 21: "q<6,2>", 23: "q<8,2>", 26: "q<6,2>", 24: "q<6,2>"}),
-    C(2052, 2, 1.0, "blobs", div=8.0, blur=True, paths={0: "q<8,-1>", 27: "k<8,-1,node>", 25: "k<8,-1>", 21: "q<6,-1>", 23: "q<8,-1>", 26: "q<6,-1>", 24: "q<8,-1>"}),
-    C(4032, 3, 2.0, "stepped", div=8.0, paths={0: "q<8,2>", 27: "k<8,2,node>", 25: "k<8,2>", 21: "q<6,2>", 23: "q<8,2>", 26: "q<6,2>", 24: "q<8,2>"}),
-    C(4036, 1, 0.5, "random8", div=8.0, paths={0: "q<8,-1>", 27: "k<8,-1,node>", 25: "k<8,-1>", 21: "q<6,-1>", 23: "q<8,-1>", 26: "q<6,-1>", 24: "q<8,-1>"}),
-    C(4092, 5, 2.0, "blobs", div=8.0, paths={0: "q<8,2>", 27: "k<8,2,node>", 25: "k<8,2>", 21: "q<6,2>", 23: "q<8,2>", 26: "q<6,2>", 24: "q<8,2>"}),
-    C(4096, 2, 2.0, "stepped", div=8.0, blur=True, paths={0: "q<8,2>", 27: "k<8,2,node>", 25: "k<8,2>", 21: "q<6,2>", 23: "q<8,2>", 26: "q<6,2>", 24: "q<8,2>"}),
-    C(4100, 3, 1.3, "blobs", div=8.0, blur=True, paths={0: "q<8,-1>", 27: "k<8,-1,node>", 25: "k<8,-1>", 21: "q<6,-1>", 23: "q<8,-1>", 26: "q<6,-1>", 24: "q<8,-1>"}),
-    C(7760, 5, 2.0, "stepped", div=3.0, paths={0: "q<8,2>", 27: "k<8,2,node>", 25: "k<8,2>", 21: "q<6,2>", 23: "q<8,2>", 26: "q<6,2>", 24: "q<8,2>"}),
-    C(7760, 2, 1.3, "blobs", div=8.0, paths={0: "q<8,-1>", 27: "k<8,-1,node>", 25: "k<8,-1>", 21: "q<6,-1>", 23: "q<8,-1>", 26: "q<6,-1>", 24: "q<8,-1>"}),
-    C(9, 3, 2.0, "random8", div=8.0, paths={0: "k<6,2,node>", 27: "k<6,2,node>", 25: "k<6,2>", 21: "k<8,2,node>", 22: "k<6,2,node>", 23: "k<8,2,node>", 26: "k<6,2,node>", 24: "k<6,2,node>"}),
-    C(1023, 2, 1.3, "stepped", div=8.0, paths={0: "k<6,-1,node>", 27: "k<6,-1,node>", 25: "k<6,-1>", 21: "k<8,-1,node>", 22: "k<6,-1,node>", 23: "k<8,-1,node>", 26: "k<6,-1,node>", 24: "k<6,-1,node>"}),
-    C(2049, 5, 2.0, "blobs", div=8.0, blur=True, paths={0: "k<8,2,node>", 27: "k<8,2,node>", 25: "k<8,2>", 21: "k<6,2,node>", 23: "k<8,2,node>", 26: "k<6,2,node>", 24: "k<8,2,node>"}),
-    C(7763, 3, 2.0, "stepped", div=3.0, paths={0: "k<8,2,node>", 27: "k<8,2,node>", 25: "k<8,2>", 21: "k<6,2,node>", 23: "k<8,2,node>", 26: "k<6,2,node>", 24: "k<8,2,node>"}),
+    C(8, 3, 2.0, "random8", div=8.0, paths={"default": "q<6,2>", "gw_no_quad": "k<6,2,node>", "gw_generic_layout": "k<6,2>", "gw_threads_512": "q<8,2>", "gw_threads_256_narrow": "q<6,2>", "gw_threads_1024": "q<8,2>", "gw_threads_256": "q<6,2>", "gw_six_waves": "q<6,2>"}),
+    C(12, 2, 1.3, "stepped", div=8.0, paths={"default": "q<6,-1>", "gw_no_quad": "k<6,-1,node>", "gw_generic_layout": "k<6,-1>", "gw_threads_512": "q<8,-1>", "gw_threads_256_narrow": "q<6,-1>", "gw_threads_1024": "q<8,-1>", "gw_threads_256": "q<6,-1>", "gw_six_waves": "q<6,-1>"}),
+    C(248, 5, 2.0, "blobs", div=12.0, paths={"default": "q<6,2>", "gw_no_quad": "k<6,2,node>", "gw_generic_layout": "k<6,2>", "gw_threads_512": "q<8,2>", "gw_threads_256_narrow": "q<6,2>", "gw_threads_1024": "q<8,2>", "gw_threads_256": "q<6,2>", "gw_six_waves": "q<6,2>"}),
+    C(252, 3, 0.5, "stepped", div=8.0, paths={"default": "q<6,-1>", "gw_no_quad": "k<6,-1,node>", "gw_generic_layout": "k<6,-1>", "gw_threads_512": "q<8,-1>", "gw_threads_256_narrow": "q<6,-1>", "gw_threads_1024": "q<8,-1>", "gw_threads_256": "q<6,-1>", "gw_six_waves": "q<6,-1>"}),
+    C(256, 2, 2.0, "noisy_ramp", div=8.0, paths={"default": "q<6,2>", "gw_no_quad": "k<6,2,node>", "gw_generic_layout": "k<6,2>", "gw_threads_512": "q<8,2>", "gw_threads_256_narrow": "q<6,2>", "gw_threads_1024": "q<8,2>", "gw_threads_256": "q<6,2>", "gw_six_waves": "q<6,2>"}),
+    C(508, 5, 3.0, "clipped", div=8.0, paths={"default": "q<6,-1>", "gw_no_quad": "k<6,-1,node>", "gw_generic_layout": "k<6,-1>", "gw_threads_512": "q<8,-1>", "gw_threads_256_narrow": "q<6,-1>", "gw_threads_1024": "q<8,-1>", "gw_threads_256": "q<6,-1>", "gw_six_waves": "q<6,-1>"}),
+    C(1008, 3, 2.0, "stepped", div=8.0, paths={"default": "q<6,2>", "gw_no_quad": "k<6,2,node>", "gw_generic_layout": "k<6,2>", "gw_threads_512": "q<8,2>", "gw_threads_256_narrow": "q<6,2>", "gw_threads_1024": "q<8,2>", "gw_threads_256": "q<6,2>", "gw_six_waves": "q<6,2>"}),
+    C(1012, 1, 0.0, "blobs", div=8.0, paths={"default": "q<6,-1>", "gw_no_quad": "k<6,-1,node>", "gw_generic_layout": "k<6,-1>", "gw_threads_512": "q<8,-1>", "gw_threads_256_narrow": "q<6,-1>", "gw_threads_1024": "q<8,-1>", "gw_threads_256": "q<6,-1>", "gw_six_waves": "q<6,-1>"}),
+    C(1020, 5, 2.0, "random8", div=8.0, paths={"default": "q<6,2>", "gw_no_quad": "k<6,2,node>", "gw_generic_layout": "k<6,2>", "gw_threads_512": "q<8,2>", "gw_threads_256_narrow": "q<6,2>", "gw_threads_1024": "q<8,2>", "gw_threads_256": "q<6,2>", "gw_six_waves": "q<6,2>"}),
+    C(1024, 2, 1.0, "stepped", div=8.0, paths={"default": "q<6,-1>", "gw_no_quad": "k<6,-1,node>", "gw_generic_layout": "k<6,-1>", "gw_threads_512": "q<8,-1>", "gw_threads_256_narrow": "q<6,-1>", "gw_threads_1024": "q<8,-1>", "gw_threads_256": "q<6,-1>", "gw_six_waves": "q<6,-1>"}),
+    C(1028, 3, 2.0, "stepped", div=8.0, paths={"default": "q<8,2>", "gw_no_quad": "k<8,2,node>", "gw_generic_layout": "k<8,2>", "gw_threads_512": "q<8,2>", "gw_threads_1024": "q<8,2>", "gw_threads_256": "q<6,2>", "gw_six_waves": "q<6,2>"}),
+    C(1028, 3, 1.3, "blobs", div=8.0, paths={"default": "q<8,-1>", "gw_no_quad": "k<8,-1,node>", "gw_generic_layout": "k<8,-1>", "gw_threads_512": "q<8,-1>", "gw_threads_1024": "q<8,-1>", "gw_threads_256": "q<6,-1>", "gw_six_waves": "q<6,-1>"}),
+    C(1920, 3, 1.3, "radial", div=4.5, paths={"default": "q<8,-1>", "gw_no_quad": "k<6,-1,node>", "gw_generic_layout": "k<6,-1>", "gw_threads_512": "q<8,-1>", "gw_threads_1024": "q<8,-1>", "gw_threads_256": "q<6,-1>", "gw_six_waves": "q<6,-1>"}),
+    C(1940, 3, 2.0, "blobs", paths={"default": "q<8,2>", "gw_no_quad": "k<6,2,node>", "gw_generic_layout": "k<6,2>", "gw_threads_512": "q<8,2>", "gw_threads_1024": "q<8,2>", "gw_threads_256": "q<6,2>", "gw_six_waves": "q<6,2>"}),
+    C(1984, 2, 1.3, "blobs", paths={"default": "q<6,-1>", "gw_no_quad": "k<6,-1,node>", "gw_generic_layout": "k<6,-1>", "gw_threads_512": "q<6,-1>", "gw_threads_1024": "q<8,-1>", "gw_threads_256": "q<6,-1>", "gw_six_waves": "q<6,-1>"}),
+    C(1984, 5, 2.0, "blobs", paths={"default": "q<8,2>", "gw_no_quad": "k<6,2,node>", "gw_generic_layout": "k<6,2>", "gw_threads_512": "q<8,2>", "gw_threads_1024": "q<8,2>", "gw_threads_256": "q<6,2>", "gw_six_waves": "q<6,2>"}),
+    C(2016, 2, 2.0, "stepped", div=8.0, paths={"default": "q<6,2>", "gw_no_quad": "k<6,2,node>", "gw_generic_layout": "k<6,2>", "gw_threads_512": "q<6,2>", "gw_threads_1024": "q<8,2>", "gw_threads_256": "q<6,2>", "gw_six_waves": "q<6,2>"}),
+    C(2020, 5, 1.3, "blobs", div=8.0, paths={"default": "q<6,-1>", "gw_no_quad": "k<6,-1,node>", "gw_generic_layout": "k<6,-1>", "gw_threads_512": "q<6,-1>", "gw_threads_1024": "q<8,-1>", "gw_threads_256": "q<6,-1>", "gw_six_waves": "q<6,-1>"}),
+    C(2044, 1, 2.0, "clipped", div=8.0, paths={"default": "q<6,2>", "gw_no_quad": "k<6,2,node>", "gw_generic_layout": "k<6,2>", "gw_threads_512": "q<6,2>", "gw_threads_1024": "q<8,2>", "gw_threads_256": "q<6,2>", "gw_six_waves": "q<6,2>"}),
+    C(2048, 3, 2.0, "stepped", div=8.0, blur=True, paths={"default": "q<6,2>", "gw_no_quad": "k<6,2,node>", "gw_generic_layout": "k<6,2>", "gw_threads_512": "q<6,2>", "gw_threads_1024": "q<8,2>", "gw_threads_256": "q<6,2>", "gw_six_waves": "q<6,2>"}),
+    C(2052, 2, 1.0, "blobs", div=8.0, blur=True, paths={"default": "q<8,-1>", "gw_no_quad": "k<8,-1,node>", "gw_generic_layout": "k<8,-1>", "gw_threads_512": "q<6,-1>", "gw_threads_1024": "q<8,-1>", "gw_threads_256": "q<6,-1>", "gw_six_waves": "q<8,-1>"}),
+    C(4032, 3, 2.0, "stepped", div=8.0, paths={"default": "q<8,2>", "gw_no_quad": "k<8,2,node>", "gw_generic_layout": "k<8,2>", "gw_threads_512": "q<6,2>", "gw_threads_1024": "q<8,2>", "gw_threads_256": "q<6,2>", "gw_six_waves": "q<8,2>"}),
+    C(4036, 1, 0.5, "random8", div=8.0, paths={"default": "q<8,-1>", "gw_no_quad": "k<8,-1,node>", "gw_generic_layout": "k<8,-1>", "gw_threads_512": "q<6,-1>", "gw_threads_1024": "q<8,-1>", "gw_threads_256": "q<6,-1>", "gw_six_waves": "q<8,-1>"}),
+    C(4092, 5, 2.0, "blobs", div=8.0, paths={"default": "q<8,2>", "gw_no_quad": "k<8,2,node>", "gw_generic_layout": "k<8,2>", "gw_threads_512": "q<6,2>", "gw_threads_1024": "q<8,2>", "gw_threads_256": "q<6,2>", "gw_six_waves": "q<8,2>"}),
+    C(4096, 2, 2.0, "stepped", div=8.0, blur=True, paths={"default": "q<8,2>", "gw_no_quad": "k<8,2,node>", "gw_generic_layout": "k<8,2>", "gw_threads_512": "q<6,2>", "gw_threads_1024": "q<8,2>", "gw_threads_256": "q<6,2>", "gw_six_waves": "q<8,2>"}),
+    C(4100, 3, 1.3, "blobs", div=8.0, blur=True, paths={"default": "q<8,-1>", "gw_no_quad": "k<8,-1,node>", "gw_generic_layout": "k<8,-1>", "gw_threads_512": "q<6,-1>", "gw_threads_1024": "q<8,-1>", "gw_threads_256": "q<6,-1>", "gw_six_waves": "q<8,-1>"}),
+    C(7760, 5, 2.0, "stepped", div=3.0, paths={"default": "q<8,2>", "gw_no_quad": "k<8,2,node>", "gw_generic_layout": "k<8,2>", "gw_threads_512": "q<6,2>", "gw_threads_1024": "q<8,2>", "gw_threads_256": "q<6,2>", "gw_six_waves": "q<8,2>"}),
+    C(7760, 2, 1.3, "blobs", div=8.0, paths={"default": "q<8,-1>", "gw_no_quad": "k<8,-1,node>", "gw_generic_layout": "k<8,-1>", "gw_threads_512": "q<6,-1>", "gw_threads_1024": "q<8,-1>", "gw_threads_256": "q<6,-1>", "gw_six_waves": "q<8,-1>"}),
+    C(9, 3, 2.0, "random8", div=8.0, paths={"default": "k<6,2,node>", "gw_no_quad": "k<6,2,node>", "gw_generic_layout": "k<6,2>", "gw_threads_512": "k<8,2,node>", "gw_threads_256_narrow": "k<6,2,node>", "gw_threads_1024": "k<8,2,node>", "gw_threads_256": "k<6,2,node>", "gw_six_waves": "k<6,2,node>"}),
+    C(1023, 2, 1.3, "stepped", div=8.0, paths={"default": "k<6,-1,node>", "gw_no_quad": "k<6,-1,node>", "gw_generic_layout": "k<6,-1>", "gw_threads_512": "k<8,-1,node>", "gw_threads_256_narrow": "k<6,-1,node>", "gw_threads_1024": "k<8,-1,node>", "gw_threads_256": "k<6,-1,node>", "gw_six_waves": "k<6,-1,node>"}),
+    C(2049, 5, 2.0, "blobs", div=8.0, blur=True, paths={"default": "k<8,2,node>", "gw_no_quad": "k<8,2,node>", "gw_generic_layout": "k<8,2>", "gw_threads_512": "k<6,2,node>", "gw_threads_1024": "k<8,2,node>", "gw_threads_256": "k<6,2,node>", "gw_six_waves": "k<8,2,node>"}),
+    C(7763, 3, 2.0, "stepped", div=3.0, paths={"default": "k<8,2,node>", "gw_no_quad": "k<8,2,node>", "gw_generic_layout": "k<8,2>", "gw_threads_512": "k<6,2,node>", "gw_threads_1024": "k<8,2,node>", "gw_threads_256": "k<6,2,node>", "gw_six_waves": "k<8,2,node>"}),
 ]
 # the eight modes (anaglyphs and single-eye modes: the generic layout), stereo_balance (+-1: one eye is the source image), divergence
 # of both signs (negative: both eyes are the source image) and up to gaps of 200 columns, convergence 0 / 0.5 / 1
 MODES = [
-    C(516, 3, 2.0, "blobs", mode="left-right", paths={0: "q<6,2>", 27: "k<6,2,node>", 25: "k<6,2>", 21: "q<8,2>", 22: "q<6,2>", 23: "q<8,2>", 26: "q<6,2>", 24: "q<6,2>"}),
-    C(516, 3, 2.0, "blobs", mode="right-left", paths={0: "q<6,2>", 27: "k<6,2,node>", 25: "k<6,2>", 21: "q<8,2>", 22: "q<6,2>", 23: "q<8,2>", 26: "q<6,2>", 24: "q<6,2>"}),
-    C(516, 3, 2.0, "blobs", mode="top-bottom", paths={0: "q<6,2>", 27: "k<6,2,node>", 25: "k<6,2>", 21: "q<8,2>", 22: "q<6,2>", 23: "q<8,2>", 26: "q<6,2>", 24: "q<6,2>"}),
-    C(516, 3, 2.0, "blobs", mode="bottom-top", paths={0: "q<6,2>", 27: "k<6,2,node>", 25: "k<6,2>", 21: "q<8,2>", 22: "q<6,2>", 23: "q<8,2>", 26: "q<6,2>", 24: "q<6,2>"}),
-    C(516, 3, 2.0, "blobs", mode="red-cyan-anaglyph", paths={0: "k<6,2>", 27: "k<6,2>", 25: "k<6,2>", 21: "k<8,2>", 22: "k<6,2>", 23: "k<8,2>", 26: "k<6,2>", 24: "k<6,2>"}),
-    C(516, 3, 2.0, "blobs", mode="cyan-red-reverseanaglyph", paths={0: "k<6,2>", 27: "k<6,2>", 25: "k<6,2>", 21: "k<8,2>", 22: "k<6,2>", 23: "k<8,2>", 26: "k<6,2>", 24: "k<6,2>"}),
-    C(516, 3, 2.0, "blobs", mode="left-only", paths={0: "k<6,2>", 27: "k<6,2>", 25: "k<6,2>", 21: "k<8,2>", 22: "k<6,2>", 23: "k<8,2>", 26: "k<6,2>", 24: "k<6,2>"}),
-    C(516, 3, 2.0, "blobs", mode="only-right", paths={0: "k<6,2>", 27: "k<6,2>", 25: "k<6,2>", 21: "k<8,2>", 22: "k<6,2>", 23: "k<8,2>", 26: "k<6,2>", 24: "k<6,2>"}),
-    C(516, 3, 1.3, "clipped", mode="red-cyan-anaglyph", paths={0: "k<6,-1>", 27: "k<6,-1>", 25: "k<6,-1>", 21: "k<8,-1>", 22: "k<6,-1>", 23: "k<8,-1>", 26: "k<6,-1>", 24: "k<6,-1>"}),
-    C(1028, 3, 2.0, "stepped", bal=0.5, paths={0: "q<8,2>", 27: "k<8,2,node>", 25: "k<8,2>", 21: "q<8,2>", 23: "q<8,2>", 26: "q<6,2>", 24: "q<6,2>"}),
-    C(1028, 3, 2.0, "stepped", bal=-0.5, paths={0: "q<8,2>", 27: "k<8,2,node>", 25: "k<8,2>", 21: "q<8,2>", 23: "q<8,2>", 26: "q<6,2>", 24: "q<6,2>"}),
-    C(1028, 3, 2.0, "stepped", bal=1.0, paths={0: "k<8,2,node>", 27: "k<8,2,node>", 25: "k<8,2>", 21: "k<8,2,node>", 23: "k<8,2,node>", 26: "k<6,2,node>", 24: "k<6,2,node>"}),
-    C(1028, 3, 2.0, "stepped", bal=-1.0, paths={0: "k<8,2,node>", 27: "k<8,2,node>", 25: "k<8,2>", 21: "k<8,2,node>", 23: "k<8,2,node>", 26: "k<6,2,node>", 24: "k<6,2,node>"}),
-    C(1028, 3, 2.0, "stepped", div=-6.0, conv=0.5, paths={0: "k<8,2,node>", 27: "k<8,2,node>", 25: "k<8,2>", 21: "k<8,2,node>", 23: "k<8,2,node>", 26: "k<6,2,node>", 24: "k<6,2,node>"}),
-    C(1028, 3, 2.0, "stepped", div=12.0, conv=0.0, paths={0: "q<8,2>", 27: "k<8,2,node>", 25: "k<8,2>", 21: "q<8,2>", 23: "q<8,2>", 26: "q<6,2>", 24: "q<6,2>"}),
-    C(1028, 3, 1.3, "stepped", div=12.0, conv=1.0, paths={0: "q<8,-1>", 27: "k<8,-1,node>", 25: "k<8,-1>", 21: "q<8,-1>", 23: "q<8,-1>", 26: "q<6,-1>", 24: "q<6,-1>"}),
-    C(1028, 3, 1.0, "stepped", div=20.0, conv=0.5, paths={0: "q<8,-1>", 27: "k<8,-1,node>", 25: "k<8,-1>", 21: "q<8,-1>", 23: "q<8,-1>", 26: "q<6,-1>", 24: "q<6,-1>"}),
-    C(1028, 3, 1.0, "stepped", div=-20.0, conv=0.5, paths={0: "k<8,-1,node>", 27: "k<8,-1,node>", 25: "k<8,-1>", 21: "k<8,-1,node>", 23: "k<8,-1,node>", 26: "k<6,-1,node>", 24: "k<6,-1,node>"}),
-    C(1028, 3, 1.3, "stepped", div=-12.0, bal=-1.5, paths={0: "k<8,-1,node>", 27: "k<8,-1,node>", 25: "k<8,-1>", 21: "k<8,-1,node>", 23: "k<8,-1,node>", 26: "k<6,-1,node>", 24: "k<6,-1,node>"}),
+    C(516, 3, 2.0, "blobs", mode="left-right", paths={"default": "q<6,2>", "gw_no_quad": "k<6,2,node>", "gw_generic_layout": "k<6,2>", "gw_threads_512": "q<8,2>", "gw_threads_256_narrow": "q<6,2>", "gw_threads_1024": "q<8,2>", "gw_threads_256": "q<6,2>", "gw_six_waves": "q<6,2>"}),
+    C(516, 3, 2.0, "blobs", mode="right-left", paths={"default": "q<6,2>", "gw_no_quad": "k<6,2,node>", "gw_generic_layout": "k<6,2>", "gw_threads_512": "q<8,2>", "gw_threads_256_narrow": "q<6,2>", "gw_threads_1024": "q<8,2>", "gw_threads_256": "q<6,2>", "gw_six_waves": "q<6,2>"}),
+    C(516, 3, 2.0, "blobs", mode="top-bottom", paths={"default": "q<6,2>", "gw_no_quad": "k<6,2,node>", "gw_generic_layout": "k<6,2>", "gw_threads_512": "q<8,2>", "gw_threads_256_narrow": "q<6,2>", "gw_threads_1024": "q<8,2>", "gw_threads_256": "q<6,2>", "gw_six_waves": "q<6,2>"}),
+    C(516, 3, 2.0, "blobs", mode="bottom-top", paths={"default": "q<6,2>", "gw_no_quad": "k<6,2,node>", "gw_generic_layout": "k<6,2>", "gw_threads_512": "q<8,2>", "gw_threads_256_narrow": "q<6,2>", "gw_threads_1024": "q<8,2>", "gw_threads_256": "q<6,2>", "gw_six_waves": "q<6,2>"}),
+    C(516, 3, 2.0, "blobs", mode="red-cyan-anaglyph", paths={"default": "k<6,2>", "gw_no_quad": "k<6,2>", "gw_generic_layout": "k<6,2>", "gw_threads_512": "k<8,2>", "gw_threads_256_narrow": "k<6,2>", "gw_threads_1024": "k<8,2>", "gw_threads_256": "k<6,2>", "gw_six_waves": "k<6,2>"}),
+    C(516, 3, 2.0, "blobs", mode="cyan-red-reverseanaglyph", paths={"default": "k<6,2>", "gw_no_quad": "k<6,2>", "gw_generic_layout": "k<6,2>", "gw_threads_512": "k<8,2>", "gw_threads_256_narrow": "k<6,2>", "gw_threads_1024": "k<8,2>", "gw_threads_256": "k<6,2>", "gw_six_waves": "k<6,2>"}),
+    C(516, 3, 2.0, "blobs", mode="left-only", paths={"default": "k<6,2>", "gw_no_quad": "k<6,2>", "gw_generic_layout": "k<6,2>", "gw_threads_512": "k<8,2>", "gw_threads_256_narrow": "k<6,2>", "gw_threads_1024": "k<8,2>", "gw_threads_256": "k<6,2>", "gw_six_waves": "k<6,2>"}),
+    C(516, 3, 2.0, "blobs", mode="only-right", paths={"default": "k<6,2>", "gw_no_quad": "k<6,2>", "gw_generic_layout": "k<6,2>", "gw_threads_512": "k<8,2>", "gw_threads_256_narrow": "k<6,2>", "gw_threads_1024": "k<8,2>", "gw_threads_256": "k<6,2>", "gw_six_waves": "k<6,2>"}),
+    C(516, 3, 1.3, "clipped", mode="red-cyan-anaglyph", paths={"default": "k<6,-1>", "gw_no_quad": "k<6,-1>", "gw_generic_layout": "k<6,-1>", "gw_threads_512": "k<8,-1>", "gw_threads_256_narrow": "k<6,-1>", "gw_threads_1024": "k<8,-1>", "gw_threads_256": "k<6,-1>", "gw_six_waves": "k<6,-1>"}),
+    C(1028, 3, 2.0, "stepped", bal=0.5, paths={"default": "q<8,2>", "gw_no_quad": "k<8,2,node>", "gw_generic_layout": "k<8,2>", "gw_threads_512": "q<8,2>", "gw_threads_1024": "q<8,2>", "gw_threads_256": "q<6,2>", "gw_six_waves": "q<6,2>"}),
+    C(1028, 3, 2.0, "stepped", bal=-0.5, paths={"default": "q<8,2>", "gw_no_quad": "k<8,2,node>", "gw_generic_layout": "k<8,2>", "gw_threads_512": "q<8,2>", "gw_threads_1024": "q<8,2>", "gw_threads_256": "q<6,2>", "gw_six_waves": "q<6,2>"}),
+    C(1028, 3, 2.0, "stepped", bal=1.0, paths={"default": "k<8,2,node>", "gw_no_quad": "k<8,2,node>", "gw_generic_layout": "k<8,2>", "gw_threads_512": "k<8,2,node>", "gw_threads_1024": "k<8,2,node>", "gw_threads_256": "k<6,2,node>", "gw_six_waves": "k<6,2,node>"}),
+    C(1028, 3, 2.0, "stepped", bal=-1.0, paths={"default": "k<8,2,node>", "gw_no_quad": "k<8,2,node>", "gw_generic_layout": "k<8,2>", "gw_threads_512": "k<8,2,node>", "gw_threads_1024": "k<8,2,node>", "gw_threads_256": "k<6,2,node>", "gw_six_waves": "k<6,2,node>"}),
+    C(1028, 3, 2.0, "stepped", div=-6.0, conv=0.5, paths={"default": "k<8,2,node>", "gw_no_quad": "k<8,2,node>", "gw_generic_layout": "k<8,2>", "gw_threads_512": "k<8,2,node>", "gw_threads_1024": "k<8,2,node>", "gw_threads_256": "k<6,2,node>", "gw_six_waves": "k<6,2,node>"}),
+    C(1028, 3, 2.0, "stepped", div=12.0, conv=0.0, paths={"default": "q<8,2>", "gw_no_quad": "k<8,2,node>", "gw_generic_layout": "k<8,2>", "gw_threads_512": "q<8,2>", "gw_threads_1024": "q<8,2>", "gw_threads_256": "q<6,2>", "gw_six_waves": "q<6,2>"}),
+    C(1028, 3, 1.3, "stepped", div=12.0, conv=1.0, paths={"default": "q<8,-1>", "gw_no_quad": "k<8,-1,node>", "gw_generic_layout": "k<8,-1>", "gw_threads_512": "q<8,-1>", "gw_threads_1024": "q<8,-1>", "gw_threads_256": "q<6,-1>", "gw_six_waves": "q<6,-1>"}),
+    C(1028, 3, 1.0, "stepped", div=20.0, conv=0.5, paths={"default": "q<8,-1>", "gw_no_quad": "k<8,-1,node>", "gw_generic_layout": "k<8,-1>", "gw_threads_512": "q<8,-1>", "gw_threads_1024": "q<8,-1>", "gw_threads_256": "q<6,-1>", "gw_six_waves": "q<6,-1>"}),
+    C(1028, 3, 1.0, "stepped", div=-20.0, conv=0.5, paths={"default": "k<8,-1,node>", "gw_no_quad": "k<8,-1,node>", "gw_generic_layout": "k<8,-1>", "gw_threads_512": "k<8,-1,node>", "gw_threads_1024": "k<8,-1,node>", "gw_threads_256": "k<6,-1,node>", "gw_six_waves": "k<6,-1,node>"}),
+    C(1028, 3, 1.3, "stepped", div=-12.0, bal=-1.5, paths={"default": "k<8,-1,node>", "gw_no_quad": "k<8,-1,node>", "gw_generic_layout": "k<8,-1>", "gw_threads_512": "k<8,-1,node>", "gw_threads_1024": "k<8,-1,node>", "gw_threads_256": "k<6,-1,node>", "gw_six_waves": "k<6,-1,node>"}),
 ]
 # depth that forces rare branches: a flat frame (no range), a range just above / just below 1e-6, a range beyond 2^40 (the IEEE
 # division instead of the division core) with numerators beyond 2^60, 13 frames in sub-batches of 12 mixing maxima <= 1 and > 1
 DEPTHS = [
-    C(1028, 3, 2.0, "flat", paths={0: "q<8,2>", 27: "k<8,2,node>", 25: "k<8,2>", 21: "q<8,2>", 23: "q<8,2>", 26: "q<6,2>", 24: "q<6,2>"}),
-    C(1028, 3, 2.0, "range_above", paths={0: "q<8,2>", 27: "k<8,2,node>", 25: "k<8,2>", 21: "q<8,2>", 23: "q<8,2>", 26: "q<6,2>", 24: "q<6,2>"}),
-    C(1028, 3, 1.3, "range_below", paths={0: "q<8,-1>", 27: "k<8,-1,node>", 25: "k<8,-1>", 21: "q<8,-1>", 23: "q<8,-1>", 26: "q<6,-1>", 24: "q<6,-1>"}),
-    C(1028, 3, 1.0, "huge", paths={0: "q<8,-1>", 27: "k<8,-1,node>", 25: "k<8,-1>", 21: "q<8,-1>", 23: "q<8,-1>", 26: "q<6,-1>", 24: "q<6,-1>"}),
-    C(2052, 2, 1.3, "huge", paths={0: "q<8,-1>", 27: "k<8,-1,node>", 25: "k<8,-1>", 21: "q<6,-1>", 23: "q<8,-1>", 26: "q<6,-1>", 24: "q<8,-1>"}),
-    C(516, 2, 2.0, "mixed13", paths={0: "q<6,2>", 27: "k<6,2,node>", 25: "k<6,2>", 21: "q<8,2>", 22: "q<6,2>", 23: "q<8,2>", 26: "q<6,2>", 24: "q<6,2>"}),
+    C(1028, 3, 2.0, "flat", paths={"default": "q<8,2>", "gw_no_quad": "k<8,2,node>", "gw_generic_layout": "k<8,2>", "gw_threads_512": "q<8,2>", "gw_threads_1024": "q<8,2>", "gw_threads_256": "q<6,2>", "gw_six_waves": "q<6,2>"}),
+    C(1028, 3, 2.0, "range_above", paths={"default": "q<8,2>", "gw_no_quad": "k<8,2,node>", "gw_generic_layout": "k<8,2>", "gw_threads_512": "q<8,2>", "gw_threads_1024": "q<8,2>", "gw_threads_256": "q<6,2>", "gw_six_waves": "q<6,2>"}),
+    C(1028, 3, 1.3, "range_below", paths={"default": "q<8,-1>", "gw_no_quad": "k<8,-1,node>", "gw_generic_layout": "k<8,-1>", "gw_threads_512": "q<8,-1>", "gw_threads_1024": "q<8,-1>", "gw_threads_256": "q<6,-1>", "gw_six_waves": "q<6,-1>"}),
+    C(1028, 3, 1.0, "huge", paths={"default": "q<8,-1>", "gw_no_quad": "k<8,-1,node>", "gw_generic_layout": "k<8,-1>", "gw_threads_512": "q<8,-1>", "gw_threads_1024": "q<8,-1>", "gw_threads_256": "q<6,-1>", "gw_six_waves": "q<6,-1>"}),
+    C(2052, 2, 1.3, "huge", paths={"default": "q<8,-1>", "gw_no_quad": "k<8,-1,node>", "gw_generic_layout": "k<8,-1>", "gw_threads_512": "q<6,-1>", "gw_threads_1024": "q<8,-1>", "gw_threads_256": "q<6,-1>", "gw_six_waves": "q<8,-1>"}),
+    C(516, 2, 2.0, "mixed13", paths={"default": "q<6,2>", "gw_no_quad": "k<6,2,node>", "gw_generic_layout": "k<6,2>", "gw_threads_512": "q<8,2>", "gw_threads_256_narrow": "q<6,2>", "gw_threads_1024": "q<8,2>", "gw_threads_256": "q<6,2>", "gw_six_waves": "q<6,2>"}),
 ]
 
 
@@ -157,7 +158,7 @@ def make_depth(c):
     return synth.depth_batch(kind, n, h, w, channels=3)
 
 
-def run(engine, dev_switch, img, depth, c, variant=0, views=None):
+def run(engine, dev_switch, img, depth, c, variant="default", views=None):
     """One node call through a Plan (-> outputs as numpy, the path names recorded per frame).  views: output tensors to use instead
     of the Plan's own (the alignment test)."""
     n, h, w = img.shape[:3]
@@ -171,7 +172,7 @@ def run(engine, dev_switch, img, depth, c, variant=0, views=None):
         out = [t.cpu().numpy().copy() for t in plan.run(img, depth)]
         codes = plan.stats()[:, _native.ST_WARP_PATH].numpy()
     finally:
-        dev_switch("pt_variant", 0)
+        dev_switch("pt_variant", "default")
     return out, [_native.WARP_PATH_NAME.get(int(k), int(k)) for k in codes]
 
 
@@ -234,8 +235,8 @@ def kind_of(path):
 @pytest.mark.parametrize("seed", range(4))
 def test_plateaus_spikes_and_ties_every_path(engine, dev_switch, seed):
     """The hostile depth of test_gpu_fuzz.make_case (plateaus, two-level patterns, ramps with jumps, spikes: exact ties in the scatter
-    rounds), widened to a multiple of 4 and to one column less: the default path, k_gpuwarp in the node layout (27) and the generic
-    layout (25), each against the oracle and bit-identical to the others."""
+    rounds), widened to a multiple of 4 and to one column less: the default path, k_gpuwarp in the node layout (gw_no_quad) and the generic
+    layout (gw_generic_layout), each against the oracle and bit-identical to the others."""
     from test_gpu_fuzz import make_case
     rng = np.random.default_rng(4400 + seed)
     for _ in range(4):
@@ -254,7 +255,7 @@ def test_plateaus_spikes_and_ties_every_path(engine, dev_switch, seed):
             it, dt = cuda(img), cuda(depth)
             first = None
             # (divergence > 0, balance 0, left-right: both eyes run, the node layout -- k_gpuwarp_q exactly when w % 4 == 0)
-            for variant, kind in ((0, "q" if q else "k node"), (27, "k node"), (25, "k generic")):
+            for variant, kind in (("default", "q" if q else "k node"), ("gw_no_quad", "k node"), ("gw_generic_layout", "k generic")):
                 got, seen = run(engine, dev_switch, it, dt, c, variant)
                 assert kind_of(seen[0]) == kind, (case_id(c), variant, seen)
                 err = check_vs_oracle(got, want, (case_id(c), variant))
@@ -268,21 +269,21 @@ def test_plateaus_spikes_and_ties_every_path(engine, dev_switch, seed):
 NODE_LAYOUT = {"q<8,2>", "q<8,-1>", "q<6,2>", "q<6,-1>", "k<8,2,node>", "k<8,-1,node>", "k<6,2,node>", "k<6,-1,node>"}
 GENERIC = {"k<8,2>", "k<8,-1>", "k<6,2>", "k<6,-1>"}
 COVERAGE = [   # (width, exponent, pt_variant) -> the instantiation it reaches
-    (1024, 2.0, 0, "q<6,2>"), (1024, 1.3, 0, "q<6,-1>"), (1028, 2.0, 0, "q<8,2>"), (1028, 1.0, 0, "q<8,-1>"),
-    (1024, 2.0, 27, "k<6,2,node>"), (1023, 0.5, 0, "k<6,-1,node>"), (1028, 2.0, 27, "k<8,2,node>"), (2049, 3.0, 0, "k<8,-1,node>"),
-    (1024, 2.0, 25, "k<6,2>"), (1024, 0.0, 25, "k<6,-1>"), (4100, 2.0, 25, "k<8,2>"), (2052, 1.3, 25, "k<8,-1>"),
+    (1024, 2.0, "default", "q<6,2>"), (1024, 1.3, "default", "q<6,-1>"), (1028, 2.0, "default", "q<8,2>"), (1028, 1.0, "default", "q<8,-1>"),
+    (1024, 2.0, "gw_no_quad", "k<6,2,node>"), (1023, 0.5, "default", "k<6,-1,node>"), (1028, 2.0, "gw_no_quad", "k<8,2,node>"), (2049, 3.0, "default", "k<8,-1,node>"),
+    (1024, 2.0, "gw_generic_layout", "k<6,2>"), (1024, 0.0, "gw_generic_layout", "k<6,-1>"), (4100, 2.0, "gw_generic_layout", "k<8,2>"), (2052, 1.3, "gw_generic_layout", "k<8,-1>"),
 ]
 
 
 def test_designed_cases_reach_every_instantiation(engine, dev_switch):
-    """A short walk over designed cases reaches every node-layout instantiation gw_launch can choose and, through pt_variant 25, every
+    """A short walk over designed cases reaches every node-layout instantiation gw_launch can choose and, through pt_variant gw_generic_layout, every
     generic one; each agrees with the default path's bits of its case."""
     seen = set()
     for w, e, variant, path in COVERAGE:
         c = C(w, 2, e, "blobs", n=2)
         img = synth.image_f32(2, 2, w, seed=w)
         it, dt = cuda(img), cuda(make_depth(c))
-        base, _ = run(engine, dev_switch, it, dt, c, 0)
+        base, _ = run(engine, dev_switch, it, dt, c, "default")
         got, codes = run(engine, dev_switch, it, dt, c, variant)
         assert codes == [path, path], (w, e, variant, codes)
         seen.add(codes[0])
@@ -347,7 +348,7 @@ def test_non_finite_pixel_in_the_zero_weight_row(engine, dev_switch):
         depth = make_depth(c)
         want = oracle_of(img, depth, c)
         it, dt = cuda(img), cuda(depth)
-        k, kc = run(engine, dev_switch, it, dt, c, 27)
+        k, kc = run(engine, dev_switch, it, dt, c, "gw_no_quad")
         assert kc == ["k<8,2,node>"]
         for a, b in ((k, want),):
             assert np.array_equal(np.isnan(a[0]), np.isnan(b[0])) and np.array_equal(np.isinf(a[0]), np.isinf(b[0]))
@@ -356,7 +357,7 @@ def test_non_finite_pixel_in_the_zero_weight_row(engine, dev_switch):
             for j in (1, 2, 3):
                 assert np.array_equal(a[j], b[j]), NAMES[j]
         assert np.isnan(want[0][0, r - 1]).any() and (~np.isfinite(want[0][0, r])).sum() >= 2
-        d, dc = run(engine, dev_switch, it, dt, c, 0)
+        d, dc = run(engine, dev_switch, it, dt, c, "default")
         if w % 4:
             assert dc == ["k<8,2,node>"]
             for j in range(4):
@@ -376,7 +377,7 @@ def test_non_finite_pixel_in_the_zero_weight_row(engine, dev_switch):
 @pytest.mark.parametrize("seed", range(8))
 def test_node_fuzz_hostile_depth(engine, dev_switch, seed):
     """Seeded node-level fuzz of gpu_warp on the hostile generators (saturated and 8-bit-noise depth, test_gpu_fuzz.make_case
-    plateaus), random shapes, modes, balance, exponents and blur: the default path and k_gpuwarp (pt_variant 27) against the oracle
+    plateaus), random shapes, modes, balance, exponents and blur: the default path and k_gpuwarp (pt_variant gw_no_quad) against the oracle
     and against each other: bit-identical."""
     from test_gpu_fuzz import make_case
     rng = np.random.default_rng(7100 + seed)
@@ -399,8 +400,8 @@ def test_node_fuzz_hostile_depth(engine, dev_switch, seed):
         img = synth.image_f32(n, h, w, seed=seed * 10 + w)
         want = oracle_of(img, depth, c)
         it, dt = cuda(img), cuda(depth)
-        a, pa = run(engine, dev_switch, it, dt, c, 0)
-        b, pb = run(engine, dev_switch, it, dt, c, 27)
+        a, pa = run(engine, dev_switch, it, dt, c, "default")
+        b, pb = run(engine, dev_switch, it, dt, c, "gw_no_quad")
         for got, path in ((a, pa[0]), (b, pb[0])):
             err = check_vs_oracle(got, want, (seed, case_id(c), path))
             MAX_ERR[path] = max(MAX_ERR.get(path, 0.0), err)

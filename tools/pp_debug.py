@@ -1,5 +1,5 @@
 """Development aid: the point-owner polylines kernel (cs_polypoint.hip) against the CPU oracle and against the first
-generation (cs_polytile.hip, cs_debug_set(PT_VARIANT, 9)) on a spread of inputs; mismatches are listed with the geometry
+generation (cs_polytile.hip, cs_debug_set pt_variant first_gen) on a spread of inputs; mismatches are listed with the geometry
 of their pixel (points in the pixel, reversed segments over it) so that a failing path can be named.  GPU only."""
 import os
 import sys
@@ -42,11 +42,11 @@ for kind, h, w, div, sep, e, conv in cases:
     depth = synth.DEPTHS[kind](h, w) * np.float32(255)
     want = oracle.apply_stereo_divergence(img, depth, div, sep, e, "polylines_soft", conv)
     ti, td = torch.from_numpy(img).cuda(), torch.from_numpy(depth).cuda()
-    _native.debug_set("pt_variant", 0)
+    _native.debug_set("pt_variant", "default")
     got = engine.apply_stereo_divergence(ti, td, div, sep, e, "polylines_soft", conv).cpu().numpy()
-    _native.debug_set("pt_variant", 9)
+    _native.debug_set("pt_variant", "first_gen")
     old = engine.apply_stereo_divergence(ti, td, div, sep, e, "polylines_soft", conv).cpu().numpy()
-    _native.debug_set("pt_variant", 0)
+    _native.debug_set("pt_variant", "default")
     bad = np.nonzero((got != want).any(-1))
     badold = int((old != want).any(-1).sum())
     tag = f"{kind:10s} {h}x{w} div {div} sep {sep} e {e} conv {conv}"
