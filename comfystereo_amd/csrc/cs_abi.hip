@@ -1118,6 +1118,60 @@ int cs_forward_warp_mesh(const float* image, const float* depth, int n, int h, i
                                gradient_threshold, warped, gap_mask, workspace, workspace_bytes, (hipStream_t)stream_);
 }
 
+size_t cs_grid_warp_workspace_bytes(int n, int h, int w) {
+    (void)h; (void)w;
+    return n <= 0 ? 0 : al256((size_t)n * ST_WORDS * 4) + al256((size_t)n * 16);
+}
+int cs_grid_warp_max_width(int op) {
+    if (op == CS_GRID_MASK || op == CS_GRID_STRETCH) return gridwarp_max_width();
+    return (op == CS_GRID_WARP || op == CS_GRID_FILL) ? 0x7fffffff : 0;
+}
+
+int cs_grid_warp(const float* image, const float* depth, int n, int c, int h, int w, double divergence_px, double separation_px,
+                 double exponent, double convergence, int op, int padding, float* warped, uint8_t* mask, void* workspace,
+                 size_t workspace_bytes, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (op < CS_GRID_WARP || op > CS_GRID_STRETCH) return fail(CS_EINVAL, "cs_grid_warp: unknown operation (CS_GRID_*)");
+    if (padding < CS_GRID_PAD_BORDER || padding > CS_GRID_PAD_REFLECTION) return fail(CS_EINVAL, "cs_grid_warp: unknown padding (CS_GRID_PAD_*)");
+    if (op != CS_GRID_FILL && padding != CS_GRID_PAD_BORDER) return fail(CS_EINVAL, "cs_grid_warp: only CS_GRID_FILL takes a padding mode");
+    if (op == CS_GRID_MASK) warped = nullptr;
+    if (op == CS_GRID_WARP) mask = nullptr;
+    if (!depth || !workspace || (warped && !image)) return fail(CS_EINVAL, "null pointer");
+    if (n <= 0 || h <= 0 || w <= 0 || (warped && c <= 0)) return fail(CS_EINVAL, "non-positive size");
+    if (n > 65535) return fail(CS_ELIMIT, "cs_grid_warp: more than 65535 frames in one call");
+    if ((size_t)h * w >= (1ull << 31)) return fail(CS_ELIMIT, "cs_grid_warp: frame of 2^31 pixels or more");
+    if ((op == CS_GRID_MASK || op == CS_GRID_STRETCH) && w > gridwarp_max_width())
+        return fail(CS_ELIMIT, "cs_grid_warp: frame too wide for the LDS-resident row (cs_grid_warp_max_width)");
+    if (workspace_bytes < cs_grid_warp_workspace_bytes(n, h, w)) return fail(CS_EWORKSPACE, "workspace too small");
+    if (!warped && !mask) return CS_OK;
+    uint32_t* stats = (uint32_t*)workspace;
+    float* fconst = (float*)((char*)workspace + al256((size_t)n * ST_WORDS * 4));
+    hipLaunchKernelGGL(k_stats_init, dim3((n * ST_WORDS + 255) / 256), dim3(256), 0, stream, stats, n);
+    hipLaunchKernelGGL(k_minmax, dim3(grid_for((size_t)h * w, 256), n), dim3(256), 0, stream, depth, h * w, stats, ST_L_MIN, ST_L_MAX);
+    hipError_t e = launch_gridwarp(image, depth, n, c, h, w, divergence_px, separation_px, exponent, convergence, op, padding,
+                                   warped, mask, stats, fconst, stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_grid_warp");
+}
+
+int cs_interpolate_fill(const float* image, const uint8_t* mask, int n, int c, int h, int w, float* out, void* stream) {
+    if (!image || !mask || !out) return fail(CS_EINVAL, "null pointer");
+    if (n <= 0 || c <= 0 || h <= 0 || w <= 0) return fail(CS_EINVAL, "non-positive size");
+    if (n > 65535) return fail(CS_ELIMIT, "cs_interpolate_fill: more than 65535 frames in one call");
+    if ((size_t)w > (1u << 24)) return fail(CS_ELIMIT, "cs_interpolate_fill: rows of more than 2^24 columns");
+    if (image == out) return fail(CS_EINVAL, "cs_interpolate_fill: out must not alias image");
+    hipError_t e = launch_interp_fill(image, mask, n, c, h, w, out, (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_interpolate_fill");
+}
+
+int cs_detect_disocclusions(const float* depth, const float* grid, const float* grid_x_warped, int h, int w, double threshold,
+                            uint8_t* out, void* stream) {
+    if (!depth || !grid || !grid_x_warped || !out) return fail(CS_EINVAL, "null pointer");
+    if (h <= 0 || w <= 0) return fail(CS_EINVAL, "non-positive size");
+    if (w < 2) return fail(CS_EINVAL, "cs_detect_disocclusions: w >= 2 (the last column takes the step before it)");
+    hipError_t e = launch_detect_disocc(depth, grid, grid_x_warped, h, w, threshold, out, (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_detect_disocclusions");
+}
+
 int cs_expand_u8(const uint8_t* codes, float* out, size_t count, void* stream) {
     if (!codes || !out) return fail(CS_EINVAL, "null pointer");
     if (((uintptr_t)codes & 3) || ((uintptr_t)out & 15)) return fail(CS_EINVAL, "cs_expand_u8 needs 4-/16-byte aligned buffers");

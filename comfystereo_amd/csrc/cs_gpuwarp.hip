@@ -16,6 +16,7 @@
 // a stated tolerance against torch's vectorised bilinear kernel (tests).
 #include "cs_common.h"
 #include "cs_kernels.h"
+#include "cs_warpmath.h"
 #include <string.h>
 
 namespace cs {
@@ -69,16 +70,6 @@ struct Px3 { float x, y, z; };
 
 __constant__ csm::PowfTables c_gw_powf_tables = CS_POWF_TABLES_INIT;
 
-__device__ __forceinline__ float torch_pow(float x, int mode, float e32, const csm::PowfTables* T) {
-    switch (mode) {
-    case 0: return x;
-    case 1: return sqrtf(x);
-    case 2: return x * x;
-    case 3: return (x * x) * x;
-    case 5: return 1.0f;
-    default: return csm::powf_exact(x, e32, T);
-    }
-}
 
 // a / b, correctly rounded: the FMA core of the IEEE expansion hipcc emits for `a / b` without its range scaling
 // (v_div_scale / v_div_fixup), which only acts near the range limits.  Callers guarantee a == 0 or 2^-60 <= |a| < 2^60
@@ -180,9 +171,9 @@ __global__ void __launch_bounds__(1024) k_gpuwarp(GwArgs A) {
     float gy;
     {
         float step = h > 1 ? 2.0f / (float)(h - 1) : 0.0f;
-        gy = y < h / 2 ? fmaf(step, (float)y, -1.0f) : fmaf(-step, (float)(h - y - 1), 1.0f);
+        gy = torch_linspace_m11(y, h, step);
     }
-    float yy = (gy + 1.0f) * ((float)(h - 1) / 2.0f);
+    float yy = gs_unnormalize(gy, h);
     yy = fminf(fmaxf(yy, 0.0f), (float)(h - 1));
     const float yn = floorf(yy);
     const float wn = yy - yn, wsth = 1.0f - wn;
@@ -650,8 +641,8 @@ __global__ void __launch_bounds__(1024) k_gpuwarp_q(GwArgs A) {
         for (int q = tid; q < ((w + 3 * NR) >> 2) + (2 * L.nbw >> 2); q += nt) reinterpret_cast<int4*>(L.M)[q] = make_int4(0, 0, 0, 0);   // M, W0, W1, fbits, gbits
         // torch.linspace(-1, 1, H)[y] and its unnormalisation (as in k_gpuwarp; the step is an IEEE division on the host)
         const float step = A.lin_step;
-        const float gy = y < h / 2 ? fmaf(step, (float)y, -1.0f) : fmaf(-step, (float)(h - y - 1), 1.0f);
-        float yy = (gy + 1.0f) * ((float)(h - 1) / 2.0f);
+        const float gy = torch_linspace_m11(y, h, step);
+        float yy = gs_unnormalize(gy, h);
         yy = fminf(fmaxf(yy, 0.0f), (float)(h - 1));
         const float yn = floorf(yy);
         wn = uni(yy - yn); wsth = uni(1.0f - wn);
@@ -1308,7 +1299,6 @@ static int gw_rounds(double gradient_threshold, int max_stretch) {
     const int rounds = kv < (double)max_stretch ? (int)kv : max_stretch;
     return rounds > 16 ? -1 : rounds;
 }
-static int pow_mode_of(double e) { return e == 1.0 ? 0 : e == 0.5 ? 1 : e == 2.0 ? 2 : e == 3.0 ? 3 : e == 0.0 ? 5 : 4; }
 
 // The kernel instantiation of a call (GW_PATH_* in cs_common.h), its workgroup size and dynamic LDS: chosen on the host from the
 // arguments alone, before k_gpuwarp_flags, which records the code in every frame's ST_WARP_PATH word.

@@ -161,6 +161,14 @@ int launch_gpuwarp_node(const cs_params* p, const float* image, const float* dL,
                         uint32_t* stats, float* stereo, float* depth_l, float* depth_r, float* mask, int out_h,
                         int out_w, void* workspace, hipStream_t stream, const uint32_t* tilemap = nullptr,
                         const float* gray = nullptr, int tm_words = 0);
+// cs_gridwarp.hip (the grid-sample warps: cs_grid_warp, cs_interpolate_fill, cs_detect_disocclusions)
+int gridwarp_max_width();   // CS_GRID_MASK / CS_GRID_STRETCH (the row in LDS)
+hipError_t launch_gridwarp(const float* image, const float* depth, int n, int c, int h, int w, double div_px, double sep_px,
+                           double exponent, double convergence, int op, int padding, float* out, uint8_t* mask,
+                           const uint32_t* stats, float* fconst, hipStream_t stream);
+hipError_t launch_interp_fill(const float* image, const uint8_t* mask, int n, int c, int h, int w, float* out, hipStream_t stream);
+hipError_t launch_detect_disocc(const float* depth, const float* grid, const float* gxw, int h, int w, double threshold,
+                                uint8_t* out, hipStream_t stream);
 // lazy depth-blur tiles in k_gpuwarp (tilemap != nullptr): rows of at most this many columns, not the mesh-quality warp
 int gpuwarp_lazy_max_width();
 

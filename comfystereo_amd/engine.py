@@ -251,3 +251,84 @@ def test_exp(x):
     out = torch.empty_like(x)
     _native.check(L.cs_test_exp(_ptr(x), _ptr(out), x.numel(), _stream()))
     return out
+
+
+# ---- the reference's grid-sample warps (cs_grid_warp, cs_interpolate_fill, cs_detect_disocclusions) -------------------------
+def _grid_input(t, name, dims):
+    """A float32, contiguous, device-resident tensor of `dims` dimensions, or ValueError."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name} must be a torch.Tensor")
+    if t.dim() != dims:
+        raise ValueError(f"{name} must have {dims} dimensions, got shape {tuple(t.shape)}")
+    if not (t.is_floating_point() or t.dtype in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)):
+        raise ValueError(f"{name}: unsupported dtype {t.dtype}")
+    return _dev(t).to(torch.float32).contiguous()
+
+
+def grid_warp(image, depth, divergence_px, separation_px, stereo_offset_exponent, convergence_point, op, padding="border"):
+    """cs_grid_warp on device tensors: image [B,C,H,W] (ignored for op "mask"), depth [B,H,W] ->
+    (warped float32 [B,C,H,W] or None, mask bool [B,H,W] or None).  op: "warp" (apply_stereo_divergence_gpu), "fill"
+    (apply_stereo_divergence_gpu_with_fill: mask = valid), "mask" (compute_forward_mask_gpu), "stretch" (warp_and_fill_gpu)."""
+    L = _native.lib()
+    if op not in _native.GRID_OP or padding not in _native.GRID_PADDING:
+        raise ValueError(f"unknown grid operation {op!r} / padding {padding!r}")
+    depth = _grid_input(depth, "depth", 3)
+    b, h, w = depth.shape
+    c = 0
+    if op != "mask":
+        image = _grid_input(image, "image", 4)
+        if image.device != depth.device:
+            raise ValueError("image and depth must be on the same device")
+        if image.shape[0] != b or tuple(image.shape[2:]) != (h, w):
+            raise ValueError(f"image {tuple(image.shape)} and depth {tuple(depth.shape)} do not match ([B,C,H,W] / [B,H,W])")
+        c = image.shape[1]
+        if c < 1:
+            raise ValueError("image has no channels")
+    if b == 0 or h == 0 or w == 0:
+        raise ValueError(f"empty depth {tuple(depth.shape)}")
+    # (a frame wider than cs_grid_warp_max_width: the native call refuses it, NativeError CS_ELIMIT)
+    warped = torch.empty((b, c, h, w), dtype=torch.float32, device=depth.device) if op != "mask" else None
+    mask = torch.empty((b, h, w), dtype=torch.uint8, device=depth.device) if op != "warp" else None
+    nb = L.cs_grid_warp_workspace_bytes(b, h, w)
+    ws = torch.empty((max(nb, 256),), dtype=torch.uint8, device=depth.device)
+    _native.check(L.cs_grid_warp(_ptr(image) if warped is not None else None, _ptr(depth), b, c, h, w, float(divergence_px),
+                                 float(separation_px), float(stereo_offset_exponent), float(convergence_point),
+                                 _native.GRID_OP[op], _native.GRID_PADDING[padding],
+                                 _ptr(warped) if warped is not None else None, _ptr(mask) if mask is not None else None,
+                                 _ptr(ws), nb, _stream()))
+    return warped, (mask.bool() if mask is not None else None)
+
+
+def interpolate_fill(image, mask):
+    """cs_interpolate_fill: image [B,C,H,W], mask bool [B,H,W] (True = fill) -> filled float32 [B,C,H,W]."""
+    L = _native.lib()
+    image = _grid_input(image, "image", 4)
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool:
+        raise ValueError("mask must be a bool tensor")
+    if mask.dim() != 3 or mask.shape[0] != image.shape[0] or tuple(mask.shape[1:]) != tuple(image.shape[2:]):
+        raise ValueError(f"mask {tuple(mask.shape)} does not match image {tuple(image.shape)} ([B,H,W] / [B,C,H,W])")
+    mask = _dev(mask).to(image.device).contiguous().view(torch.uint8)
+    b, c, h, w = image.shape
+    if image.numel() == 0:
+        raise ValueError(f"empty image {tuple(image.shape)}")
+    out = torch.empty_like(image)
+    _native.check(L.cs_interpolate_fill(_ptr(image), _ptr(mask), b, c, h, w, _ptr(out), _stream()))
+    return out
+
+
+def detect_disocclusions(depth, grid, grid_x_warped, threshold=0.02):
+    """cs_detect_disocclusions: depth [H,W], grid [1,H,W,2], grid_x_warped [H,W] -> bool [H,W]."""
+    L = _native.lib()
+    depth = _grid_input(depth, "depth", 2)
+    grid = _grid_input(grid, "grid", 4)
+    gxw = _grid_input(grid_x_warped, "grid_x_warped", 2)
+    h, w = depth.shape
+    if tuple(grid.shape) != (1, h, w, 2) or tuple(gxw.shape) != (h, w):
+        raise ValueError(f"grid {tuple(grid.shape)} / grid_x_warped {tuple(gxw.shape)} do not match depth {(h, w)}")
+    if grid.device != depth.device or gxw.device != depth.device:
+        raise ValueError("depth, grid and grid_x_warped must be on the same device")
+    if h == 0 or w < 2:
+        raise ValueError(f"detect_disocclusions needs H >= 1 and W >= 2, got {(h, w)}")
+    out = torch.empty((h, w), dtype=torch.uint8, device=depth.device)
+    _native.check(L.cs_detect_disocclusions(_ptr(depth), _ptr(grid), _ptr(gxw), h, w, float(threshold), _ptr(out), _stream()))
+    return out.bool()

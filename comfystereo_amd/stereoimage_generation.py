@@ -7,7 +7,9 @@
 Same names, argument order, defaults, return types and error behaviour; the arithmetic runs in the
 HIP kernels behind the C ABI (there is no CPU fallback: without a GPU these functions raise).
 Extras kept for callers of the reference's building blocks: apply_stereo_divergence (:1576-1620),
-directional_motion_blur_gpu (:1171-1251), forward_warp_gpu (:277-450), forward_warp_mesh (:453-689).
+directional_motion_blur_gpu (:1171-1251), forward_warp_gpu (:277-450), forward_warp_mesh (:453-689), and the grid-sample
+warps apply_stereo_divergence_gpu (:52-119), warp_and_fill_gpu (:122-274), compute_forward_mask_gpu (:692-757),
+detect_disocclusions_gpu (:807-857), interpolate_fill_gpu (:860-920), apply_stereo_divergence_gpu_with_fill (:923-1002).
 """
 import numpy as np
 import torch
@@ -221,3 +223,68 @@ def forward_warp_mesh(image_tensor, depth_tensor, divergence_px, separation_px, 
     dev = _device()
     return engine.forward_warp_mesh(image_tensor.to(dev, torch.float32), depth_tensor.to(dev, torch.float32), divergence_px,
                                     separation_px, stereo_offset_exponent, convergence_point, gradient_threshold)
+
+
+# ---- the grid-sample warps (cs_grid_warp, cs_interpolate_fill, cs_detect_disocclusions) ---------
+# Inputs are taken as float32 and moved to the device; results are float32 / bool device tensors.  `device` is accepted and ignored.
+def apply_stereo_divergence_gpu(image_tensor, depth_tensor, divergence_px, separation_px,
+                                stereo_offset_exponent, convergence_point=0.5):
+    """reference :52-119: image [B,C,H,W], depth [B,H,W] -> warped [B,C,H,W] (bilinear grid_sample, border padding)."""
+    dev = _device()
+    warped, _ = engine.grid_warp(image_tensor.to(dev), depth_tensor.to(dev), divergence_px, separation_px,
+                                 stereo_offset_exponent, convergence_point, "warp")
+    return warped
+
+
+def warp_and_fill_gpu(image_tensor, depth_tensor, divergence_px, separation_px,
+                      stereo_offset_exponent, convergence_point=0.5):
+    """reference :122-274: the warp with edge-stretch fill -> (warped [B,C,H,W], gap_mask bool [B,H,W])."""
+    dev = _device()
+    return engine.grid_warp(image_tensor.to(dev), depth_tensor.to(dev), divergence_px, separation_px, stereo_offset_exponent,
+                            convergence_point, "stretch")
+
+
+def compute_forward_mask_gpu(depth_tensor, divergence_px, separation_px,
+                             stereo_offset_exponent, convergence_point, device):
+    """reference :692-757: depth [B,H,W] -> forward gap mask bool [B,H,W] (dilated by one column at offset steps above 1.5)."""
+    dev = _device()
+    return engine.grid_warp(None, depth_tensor.to(dev), divergence_px, separation_px, stereo_offset_exponent,
+                            convergence_point, "mask")[1]
+
+
+def detect_disocclusions_gpu(depth_tensor, grid, grid_x_warped, device, threshold=0.02):
+    """reference :807-857: depth [H,W], grid [1,H,W,2], grid_x_warped [H,W] -> bool [H,W].  W == 1 raises IndexError, as the
+    reference's `warp_grad[:, -2]` does."""
+    dev = _device()
+    if isinstance(depth_tensor, torch.Tensor) and depth_tensor.dim() == 2 and depth_tensor.shape[1] == 1:
+        raise IndexError("index -2 is out of bounds for dimension 1 with size 1")
+    return engine.detect_disocclusions(depth_tensor.to(dev), grid.to(dev), grid_x_warped.to(dev), threshold)
+
+
+def interpolate_fill_gpu(image_tensor, mask, device):
+    """reference :860-920: image [B,C,H,W], mask bool [B,H,W] (True = fill) -> filled [B,C,H,W]."""
+    dev = _device()
+    return engine.interpolate_fill(image_tensor.to(dev), mask.to(dev))
+
+
+def apply_stereo_divergence_gpu_with_fill(image_tensor, depth_tensor, divergence_px, separation_px,
+                                          stereo_offset_exponent, convergence_point=0.5, fill_mode='border'):
+    """reference :923-1002: one frame -> (warped [C,H,W], valid_mask bool [H,W]).  A 3-D image whose last dimension is 1, 3 or 4
+    is read as HWC (so a CHW image with W in {1, 3, 4} is misread, as in the reference); depth is squeezed; fill_mode 'border',
+    'zeros' or 'reflection' is the padding, anything else means 'border'."""
+    dev = _device()
+    img = image_tensor.to(dev)
+    if img.dim() == 3 and img.shape[2] in [1, 3, 4]:
+        img = img.permute(2, 0, 1)
+    if img.dim() != 3:
+        raise ValueError(f"image must be [C,H,W] or [H,W,C], got shape {tuple(img.shape)}")
+    c, h, w = img.shape
+    depth = depth_tensor.to(dev)
+    if depth.dim() == 3:
+        depth = depth.squeeze()
+    if depth.shape not in (torch.Size([h, w]), torch.empty((h, w), device="meta").squeeze().shape):   # (H or W of 1: squeezed)
+        raise ValueError(f"depth {tuple(depth_tensor.shape)} does not match the image's {h} x {w}")
+    padding = fill_mode if fill_mode in ('border', 'zeros', 'reflection') else 'border'
+    warped, valid = engine.grid_warp(img[None], depth.reshape(1, h, w), divergence_px, separation_px, stereo_offset_exponent,
+                                     convergence_point, "fill", padding)
+    return warped[0], valid[0]

@@ -200,6 +200,40 @@ CS_API int cs_forward_warp2(const float *image, const float *depth, int n, int h
                      int max_stretch, float *warped, uint8_t *gap_mask, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * The reference's grid-sample warps (stereoimage_generation.py), one bilinear grid_sample (align_corners=True) at
+ * grid x = linspace(-1, 1, w) - offset / (w / 2), grid y = linspace(-1, 1, h), offsets from forward_warp_gpu's depth chain
+ * (the batch is divided by 255 when any frame's maximum is above 1; each frame normalised by its own min / max).
+ *   CS_GRID_WARP     apply_stereo_divergence_gpu (:52-119): warped, border padding; no mask output
+ *   CS_GRID_FILL     apply_stereo_divergence_gpu_with_fill (:923-1002) for n frames: warped with `padding` (CS_GRID_PAD_*),
+ *                    mask = valid (the source x inside [-1, 1])
+ *   CS_GRID_MASK     compute_forward_mask_gpu (:692-757): mask = the forward gap mask (dilated at offset steps above 1.5);
+ *                    image and warped are not read / written
+ *   CS_GRID_STRETCH  warp_and_fill_gpu (:122-274): the gap pixels' grid x stretched from the border grid values, mask = the gap mask
+ * image [n][c][h][w] float32, depth [n][h][w] float32 -> warped [n][c][h][w] float32, mask [n][h][w] uint8 (0 / 1).
+ * A null warped or mask skips that output.  padding must be CS_GRID_PAD_BORDER for every operation but CS_GRID_FILL.
+ * workspace: cs_grid_warp_workspace_bytes(n, h, w).  CS_GRID_MASK and CS_GRID_STRETCH keep a row in LDS: frames wider than
+ * cs_grid_warp_max_width(op) (19 486 columns) are refused with CS_ELIMIT; CS_GRID_WARP and CS_GRID_FILL have no width limit.
+ * At most 65 535 frames per call.
+ */
+enum cs_grid_op { CS_GRID_WARP = 0, CS_GRID_FILL = 1, CS_GRID_MASK = 2, CS_GRID_STRETCH = 3 };
+enum cs_grid_padding { CS_GRID_PAD_BORDER = 0, CS_GRID_PAD_ZEROS = 1, CS_GRID_PAD_REFLECTION = 2 };
+CS_API size_t cs_grid_warp_workspace_bytes(int n, int h, int w);
+CS_API int cs_grid_warp_max_width(int op);
+CS_API int cs_grid_warp(const float *image, const float *depth, int n, int c, int h, int w, double divergence_px,
+                        double separation_px, double stereo_offset_exponent, double convergence_point, int op, int padding,
+                        float *warped, uint8_t *mask, void *workspace, size_t workspace_bytes, void *stream);
+/* interpolate_fill_gpu (reference :860-920): image [n][c][h][w] float32, mask [n][h][w] uint8 (non-zero = fill) -> out
+ * [n][c][h][w]: a masked pixel takes left * (1 - t) + right * t, left = the nearest unmasked column before it, right = the
+ * row's LAST unmasked column if it lies after it; t = distance to left / max(distance to left + distance to right, 1), 1
+ * without a left, 0 without a right border (a row with nothing unmasked takes column 0).  out must not alias image. */
+CS_API int cs_interpolate_fill(const float *image, const uint8_t *mask, int n, int c, int h, int w, float *out, void *stream);
+/* detect_disocclusions_gpu (reference :807-857): depth [h][w], grid [h][w][2] (x, y), grid_x_warped [h][w] float32 -> out
+ * [h][w] uint8: depth sampled at the grid (nearest, border padding, align_corners=True) minus depth above `threshold`, or
+ * |grid_x_warped[x + 1] - grid_x_warped[x]| above 3 * 2 / w (the last column takes the step before it).  w >= 2. */
+CS_API int cs_detect_disocclusions(const float *depth, const float *grid, const float *grid_x_warped, int h, int w,
+                                   double threshold, uint8_t *out, void *stream);
+
+/*
  * forward_warp_mesh (reference stereoimage_generation.py:453-689), the mesh-quality warp the reference uses whenever
  * `moderngl` is importable (:1068-1071): same tensors as cs_forward_warp plus the culling threshold (reference
  * default 1.5).  The reference rasterises through OpenGL; the parts OpenGL leaves to the implementation are fixed as
