@@ -26,6 +26,8 @@ MODE = {
 # enum cs_grid_op / cs_grid_padding (the reference's grid-sample warps, cs_grid_warp)
 GRID_OP = {"warp": 0, "fill": 1, "mask": 2, "stretch": 3}
 GRID_PADDING = {"border": 0, "zeros": 1, "reflection": 2}
+# enum cs_gauss_op (the reference's Gaussian depth blurs, cs_gaussian_blur)
+GAUSS_OP = {"plain": 0, "edge_selective": 1, "left": 2, "right": 3}
 
 # the ABI version the ctypes signatures below were written for (include/comfystereo_amd.h CS_ABI_VERSION)
 ABI_VERSION = 4
@@ -36,6 +38,7 @@ EXPORTS = [
     "cs_warp_workspace_bytes", "cs_forward_warp", "cs_forward_warp2", "cs_warp_mesh_workspace_bytes", "cs_forward_warp_mesh", "cs_expand_u8", "cs_pack_u8", "cs_host_expand_u8", "cs_host_copy", "cs_take_f32", "cs_host_replicate_f32", "cs_stereo_shift_workspace_bytes", "cs_stereo_shift", "cs_profile", "cs_profile_read", "cs_profile_tiles", "cs_debug_set",
     "cs_test_powf", "cs_test_exp", "cs_test_edge_threshold",
     "cs_grid_warp_workspace_bytes", "cs_grid_warp_max_width", "cs_grid_warp", "cs_interpolate_fill", "cs_detect_disocclusions",
+    "cs_gaussian_blur_workspace_bytes", "cs_gaussian_blur_max_taps", "cs_gaussian_blur",
 ]
 
 # enum cs_debug_key (development switches; tests and profiling tools only)
@@ -191,6 +194,12 @@ def lib():
     L.cs_interpolate_fill.argtypes = [vp, vp, c_int, c_int, c_int, c_int, vp, vp]
     L.cs_detect_disocclusions.restype = c_int
     L.cs_detect_disocclusions.argtypes = [vp, vp, vp, c_int, c_int, c_double, vp, vp]
+    L.cs_gaussian_blur_workspace_bytes.restype = c_size
+    L.cs_gaussian_blur_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int]
+    L.cs_gaussian_blur_max_taps.restype = c_int
+    L.cs_gaussian_blur_max_taps.argtypes = []
+    L.cs_gaussian_blur.restype = c_int
+    L.cs_gaussian_blur.argtypes = [c_int, vp, vp, c_int, c_double, c_int, c_int, c_int, vp, vp, c_size, vp]
     _lib = L
     return L
 

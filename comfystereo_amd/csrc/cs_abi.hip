@@ -1172,6 +1172,31 @@ int cs_detect_disocclusions(const float* depth, const float* grid, const float* 
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_detect_disocclusions");
 }
 
+size_t cs_gaussian_blur_workspace_bytes(int n, int h, int w, int n_taps) {
+    (void)n_taps;
+    return (n <= 0 || h <= 0 || w <= 0) ? 0 : al256((size_t)n * h * w * 4);
+}
+int cs_gaussian_blur_max_taps(void) { return gaussblur_max_taps(); }
+
+int cs_gaussian_blur(int op, const float* depth, const double* taps, int n_taps, double edge_threshold, int n, int h, int w,
+                     float* out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (op < CS_GAUSS_PLAIN || op > CS_GAUSS_RIGHT) return fail(CS_EINVAL, "cs_gaussian_blur: unknown operation (CS_GAUSS_*)");
+    if (!depth || !taps || !out || !workspace) return fail(CS_EINVAL, "null pointer");
+    if (n_taps <= 0 || (n_taps & 1) == 0) return fail(CS_EINVAL, "cs_gaussian_blur: n_taps must be odd and positive (2 * radius + 1)");
+    if (n <= 0 || h <= 0 || w <= 0) return fail(CS_EINVAL, "non-positive size");
+    if (((uintptr_t)depth & 3) || ((uintptr_t)out & 3) || ((uintptr_t)workspace & 3) || ((uintptr_t)taps & 7))
+        return fail(CS_EINVAL, "cs_gaussian_blur: float32 buffers need 4-byte, the taps 8-byte alignment");
+    if (out == depth || (void*)out == workspace || (const void*)depth == workspace)
+        return fail(CS_EINVAL, "cs_gaussian_blur: depth, out and workspace must not alias");
+    if (n_taps > gaussblur_max_taps()) return fail(CS_ELIMIT, "cs_gaussian_blur: more taps than cs_gaussian_blur_max_taps()");
+    // one workgroup per 1024 columns of a row / per 256 columns of a 16-row band: grids of fewer than 2^24 workgroups
+    if ((size_t)n * h * ((w + 1023) / 1024) >= (1u << 24) || (size_t)n * ((h + 15) / 16) * ((w + 255) / 256) >= (1u << 24))
+        return fail(CS_ELIMIT, "cs_gaussian_blur: more than 2^24 workgroups in one call (split the batch)");
+    if (workspace_bytes < cs_gaussian_blur_workspace_bytes(n, h, w, n_taps)) return fail(CS_EWORKSPACE, "workspace too small");
+    hipError_t e = launch_gaussblur(op, depth, taps, n_taps, edge_threshold, n, h, w, out, (float*)workspace, (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_gaussian_blur");
+}
+
 int cs_expand_u8(const uint8_t* codes, float* out, size_t count, void* stream) {
     if (!codes || !out) return fail(CS_EINVAL, "null pointer");
     if (((uintptr_t)codes & 3) || ((uintptr_t)out & 15)) return fail(CS_EINVAL, "cs_expand_u8 needs 4-/16-byte aligned buffers");

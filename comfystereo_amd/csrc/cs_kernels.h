@@ -169,6 +169,10 @@ hipError_t launch_gridwarp(const float* image, const float* depth, int n, int c,
 hipError_t launch_interp_fill(const float* image, const uint8_t* mask, int n, int c, int h, int w, float* out, hipStream_t stream);
 hipError_t launch_detect_disocc(const float* depth, const float* grid, const float* gxw, int h, int w, double threshold,
                                 uint8_t* out, hipStream_t stream);
+// cs_gaussblur.hip (the Gaussian depth blurs: cs_gaussian_blur).  tmp: [n][h][w] float32, the row pass's output
+int gaussblur_max_taps();   // the row pass keeps a 1024-column segment plus 2 * radius halo columns in LDS
+hipError_t launch_gaussblur(int op, const float* depth, const double* taps, int n_taps, double edge_threshold, int n, int h, int w,
+                            float* out, float* tmp, hipStream_t stream);
 // lazy depth-blur tiles in k_gpuwarp (tilemap != nullptr): rows of at most this many columns, not the mesh-quality warp
 int gpuwarp_lazy_max_width();
 

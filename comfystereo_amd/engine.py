@@ -5,6 +5,7 @@ PyTorch only provides the memory and the stream -- the arithmetic is in the HIP 
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _native
@@ -332,3 +333,50 @@ def detect_disocclusions(depth, grid, grid_x_warped, threshold=0.02):
     out = torch.empty((h, w), dtype=torch.uint8, device=depth.device)
     _native.check(L.cs_detect_disocclusions(_ptr(depth), _ptr(grid), _ptr(gxw), h, w, float(threshold), _ptr(out), _stream()))
     return out.bool()
+
+
+# ---- the reference's Gaussian depth blurs (cs_gaussian_blur) ------------------------------------------
+def gaussian_taps(sigma):
+    """The reference's tap array (stereoimage_generation.py:1261-1264) for sigma > 0: 2 * int(3 * sigma) + 1 float64 values.
+    Evaluated by numpy on the host, as the reference does: numpy's float64 exp is a SIMD routine that need not equal libm's or
+    the device's, so the library takes the taps as data and never recomputes them."""
+    sigma = float(sigma)
+    if not sigma > 0:
+        raise ValueError(f"gaussian_taps needs sigma > 0, got {sigma}")
+    radius = int(3 * sigma)
+    x = np.arange(-radius, radius + 1)
+    k = np.exp(-(x ** 2) / (2 * sigma * sigma))
+    k /= k.sum()
+    return k
+
+
+def gaussian_blur(depth, sigma, op="plain", edge_threshold=None):
+    """cs_gaussian_blur on a float32 device tensor [H,W] or [B,H,W] (every frame on its own) -> float32 tensor of that shape.
+    op: "plain" (blur_depth_map), "edge_selective", "left", "right" (the three blends of depth and blur, which need
+    edge_threshold).  sigma <= 0 blurs nothing: "plain" returns a copy, the blends blend the depth with itself, as the
+    reference does.  More taps than cs_gaussian_blur_max_taps(): NativeError CS_ELIMIT."""
+    L = _native.lib()
+    if op not in _native.GAUSS_OP:
+        raise ValueError(f"unknown Gaussian blur operation {op!r}")
+    if not isinstance(depth, torch.Tensor):
+        raise ValueError("depth must be a torch.Tensor")
+    if depth.dim() not in (2, 3):
+        raise ValueError(f"depth must be [H,W] or [B,H,W], got shape {tuple(depth.shape)}")
+    if depth.dtype != torch.float32:
+        raise ValueError(f"depth must be float32, got {depth.dtype}")
+    if depth.numel() == 0:
+        raise ValueError(f"empty depth {tuple(depth.shape)}")
+    if op != "plain" and edge_threshold is None:
+        raise ValueError(f"operation {op!r} needs an edge_threshold")
+    depth = _dev(depth).contiguous()
+    taps = gaussian_taps(sigma) if sigma > 0 else np.ones(1)
+    d3 = depth.reshape((-1,) + tuple(depth.shape[-2:]))
+    n, h, w = d3.shape
+    taps_dev = torch.from_numpy(np.ascontiguousarray(taps, dtype=np.float64)).to(depth.device)
+    out = torch.empty_like(d3)
+    nb = L.cs_gaussian_blur_workspace_bytes(n, h, w, taps.shape[0])
+    ws = torch.empty((max(nb, 256),), dtype=torch.uint8, device=depth.device)
+    _native.check(L.cs_gaussian_blur(_native.GAUSS_OP[op], _ptr(d3), _ptr(taps_dev), taps.shape[0],
+                                     float(edge_threshold) if edge_threshold is not None else 0.0, n, h, w, _ptr(out), _ptr(ws),
+                                     nb, _stream()))
+    return out.reshape(depth.shape)

@@ -9,7 +9,9 @@ HIP kernels behind the C ABI (there is no CPU fallback: without a GPU these func
 Extras kept for callers of the reference's building blocks: apply_stereo_divergence (:1576-1620),
 directional_motion_blur_gpu (:1171-1251), forward_warp_gpu (:277-450), forward_warp_mesh (:453-689), and the grid-sample
 warps apply_stereo_divergence_gpu (:52-119), warp_and_fill_gpu (:122-274), compute_forward_mask_gpu (:692-757),
-detect_disocclusions_gpu (:807-857), interpolate_fill_gpu (:860-920), apply_stereo_divergence_gpu_with_fill (:923-1002).
+detect_disocclusions_gpu (:807-857), interpolate_fill_gpu (:860-920), apply_stereo_divergence_gpu_with_fill (:923-1002),
+and the Gaussian depth blurs blur_depth_map (:1253-1281), edge_selective_blur_depth_map (:1283-1309),
+left_direction_aware_blur_depth_map (:1311-1327), right_direction_aware_blur_depth_map (:1329-1344).
 """
 import numpy as np
 import torch
@@ -288,3 +290,41 @@ def apply_stereo_divergence_gpu_with_fill(image_tensor, depth_tensor, divergence
     warped, valid = engine.grid_warp(img[None], depth.reshape(1, h, w), divergence_px, separation_px, stereo_offset_exponent,
                                      convergence_point, "fill", padding)
     return warped[0], valid[0]
+
+
+# ---- the Gaussian depth blurs (cs_gaussian_blur) --------------------------------------------------
+# numpy (or anything np.asarray takes) [H,W] in, float32 numpy [H,W] out, bit for bit the reference on float32 input.  The one
+# deviation: input of another dtype is converted to float32 first (the reference would convolve float64 samples as they are).
+def _gaussian(depth, sigma, op, edge_threshold=None):
+    dev = _device()
+    d = np.asarray(depth)
+    if d.ndim != 2:
+        raise ValueError(f"depth must be a 2-D map [H,W], got shape {d.shape}")
+    d = torch.from_numpy(np.ascontiguousarray(d, dtype=np.float32)).to(dev)
+    return engine.gaussian_blur(d, sigma, op, edge_threshold).cpu().numpy()
+
+
+def blur_depth_map(depth, sigma):
+    """reference :1253-1281: separable Gaussian, radius int(3 * sigma), replicate borders, rows then columns -> float32 [H,W].
+    sigma <= 0 returns `depth` itself.  Input that is not float32 is converted to float32 first."""
+    if sigma <= 0:
+        return depth
+    return _gaussian(depth, sigma, "plain")
+
+
+def edge_selective_blur_depth_map(depth, sigma, edge_threshold):
+    """reference :1283-1309: (1 - w) * depth + w * blur with w = min(|3x3 Sobel gradient| / edge_threshold, 1) -> float32 [H,W].
+    sigma <= 0 blends the depth with itself.  Input that is not float32 is converted to float32 first."""
+    return _gaussian(depth, sigma, "edge_selective", edge_threshold)
+
+
+def left_direction_aware_blur_depth_map(depth, sigma, edge_threshold):
+    """reference :1311-1327: the blend with w = min(g / edge_threshold, 1) where the central horizontal difference g is
+    positive, else 0 -> float32 [H,W].  Input that is not float32 is converted to float32 first."""
+    return _gaussian(depth, sigma, "left", edge_threshold)
+
+
+def right_direction_aware_blur_depth_map(depth, sigma, edge_threshold):
+    """reference :1329-1344: the blend with w = min(|g| / edge_threshold, 1) where g is negative, else 0 -> float32 [H,W].
+    Input that is not float32 is converted to float32 first."""
+    return _gaussian(depth, sigma, "right", edge_threshold)

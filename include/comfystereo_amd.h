@@ -234,6 +234,30 @@ CS_API int cs_detect_disocclusions(const float *depth, const float *grid, const 
                                    double threshold, uint8_t *out, void *stream);
 
 /*
+ * The reference's Gaussian depth blurs (stereoimage_generation.py): a separable filter with replicate borders, rows then
+ * columns, and a per-pixel blend of the depth with its blur.
+ *   CS_GAUSS_PLAIN           blur_depth_map (:1253-1281): out = the blurred map
+ *   CS_GAUSS_EDGE_SELECTIVE  edge_selective_blur_depth_map (:1283-1309): weight min(|3x3 Sobel gradient| / edge_threshold, 1)
+ *   CS_GAUSS_LEFT            left_direction_aware_blur_depth_map (:1311-1327): weight min(g / edge_threshold, 1) where the
+ *                            central horizontal difference g is positive, else 0
+ *   CS_GAUSS_RIGHT           right_direction_aware_blur_depth_map (:1329-1344): the same where g is negative (|g|)
+ * and out = (1 - weight) * depth + weight * blurred for the last three (float32, unfused).
+ * depth [n][h][w] float32 -> out [n][h][w] float32.  taps: n_taps = 2 * radius + 1 float64 values in DEVICE memory (8-byte
+ * aligned), applied as np.convolve(np.pad(line, radius, 'edge'), taps, 'valid'): float32 samples times float64 taps, the
+ * products added in float64 one at a time in the order of the flipped tap array, the sum rounded to float32; the column pass
+ * reads the float32 result of the row pass.  The library never computes taps: the caller evaluates the reference's numpy
+ * expression (comfystereo_amd.engine.gaussian_taps).  edge_threshold is rounded to float32; CS_GAUSS_PLAIN ignores it.
+ * workspace: cs_gaussian_blur_workspace_bytes(n, h, w, n_taps).  depth, out and workspace must not overlap.  Any h, w >= 1;
+ * n_taps at most cs_gaussian_blur_max_taps() (4097: radius 2048), CS_ELIMIT beyond, and for calls of 2^24 workgroups or more
+ * (one per 1024 columns of a row).
+ */
+enum cs_gauss_op { CS_GAUSS_PLAIN = 0, CS_GAUSS_EDGE_SELECTIVE = 1, CS_GAUSS_LEFT = 2, CS_GAUSS_RIGHT = 3 };
+CS_API size_t cs_gaussian_blur_workspace_bytes(int n, int h, int w, int n_taps);
+CS_API int cs_gaussian_blur_max_taps(void);
+CS_API int cs_gaussian_blur(int op, const float *depth, const double *taps, int n_taps, double edge_threshold, int n, int h,
+                            int w, float *out, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * forward_warp_mesh (reference stereoimage_generation.py:453-689), the mesh-quality warp the reference uses whenever
  * `moderngl` is importable (:1068-1071): same tensors as cs_forward_warp plus the culling threshold (reference
  * default 1.5).  The reference rasterises through OpenGL; the parts OpenGL leaves to the implementation are fixed as
