@@ -39,6 +39,7 @@ EXPORTS = [
     "cs_test_powf", "cs_test_exp", "cs_test_edge_threshold",
     "cs_grid_warp_workspace_bytes", "cs_grid_warp_max_width", "cs_grid_warp", "cs_interpolate_fill", "cs_detect_disocclusions",
     "cs_gaussian_blur_workspace_bytes", "cs_gaussian_blur_max_taps", "cs_gaussian_blur",
+    "cs_inpaint_prepare_workspace_bytes", "cs_inpaint_prepare_max_width", "cs_inpaint_prepare",
 ]
 
 # enum cs_debug_key (development switches; tests and profiling tools only)
@@ -200,6 +201,12 @@ def lib():
     L.cs_gaussian_blur_max_taps.argtypes = []
     L.cs_gaussian_blur.restype = c_int
     L.cs_gaussian_blur.argtypes = [c_int, vp, vp, c_int, c_double, c_int, c_int, c_int, vp, vp, c_size, vp]
+    L.cs_inpaint_prepare_workspace_bytes.restype = c_size
+    L.cs_inpaint_prepare_workspace_bytes.argtypes = [c_int, c_int, c_int]
+    L.cs_inpaint_prepare_max_width.restype = c_int
+    L.cs_inpaint_prepare_max_width.argtypes = []
+    L.cs_inpaint_prepare.restype = c_int
+    L.cs_inpaint_prepare.argtypes = [vp, vp, c_int, c_int, c_int, c_double, c_double, vp, vp, vp, vp, vp, vp, c_size, vp]
     _lib = L
     return L
 

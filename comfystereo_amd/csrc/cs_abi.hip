@@ -1172,6 +1172,35 @@ int cs_detect_disocclusions(const float* depth, const float* grid, const float* 
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_detect_disocclusions");
 }
 
+size_t cs_inpaint_prepare_workspace_bytes(int n, int h, int w) {
+    if (n <= 0 || h <= 0 || w <= 0) return 0;
+    return al256((size_t)n * ST_WORDS * 4) + 2 * al256(inpaint_prep_bits_bytes(n, h, w));
+}
+int cs_inpaint_prepare_max_width(void) { return inpaint_prep_max_width(); }
+
+int cs_inpaint_prepare(const float* image, const float* depth, int n, int h, int w, double divergence_px, double threshold,
+                       float* warped, float* filled, uint8_t* mask, uint8_t* warped_u8, uint8_t* filled_u8, void* workspace,
+                       size_t workspace_bytes, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!image || !depth || !workspace) return fail(CS_EINVAL, "null pointer");
+    if (n <= 0 || h <= 0 || w <= 0) return fail(CS_EINVAL, "non-positive size");
+    if (n > 65535) return fail(CS_ELIMIT, "cs_inpaint_prepare: more than 65535 frames in one call");
+    if ((size_t)h * w >= (1ull << 31)) return fail(CS_ELIMIT, "cs_inpaint_prepare: frame of 2^31 pixels or more");
+    if (w > inpaint_prep_max_width())
+        return fail(CS_ELIMIT, "cs_inpaint_prepare: frame too wide for the LDS-resident bit row (cs_inpaint_prepare_max_width)");
+    if (workspace_bytes < cs_inpaint_prepare_workspace_bytes(n, h, w)) return fail(CS_EWORKSPACE, "workspace too small");
+    if (!warped && !filled && !mask && !warped_u8 && !filled_u8) return CS_OK;
+    uint32_t* stats = (uint32_t*)workspace;
+    const size_t bits = al256(inpaint_prep_bits_bytes(n, h, w));
+    uint32_t* nvb = (uint32_t*)((char*)workspace + al256((size_t)n * ST_WORDS * 4));
+    uint32_t* disb = (uint32_t*)((char*)nvb + bits);
+    hipLaunchKernelGGL(k_stats_init, dim3((n * ST_WORDS + 255) / 256), dim3(256), 0, stream, stats, n);
+    hipLaunchKernelGGL(k_minmax, dim3(grid_for((size_t)h * w, 256), n), dim3(256), 0, stream, depth, h * w, stats, ST_L_MIN, ST_L_MAX);
+    hipError_t e = launch_inpaint_prep(image, depth, n, h, w, divergence_px, threshold, warped, filled, mask, warped_u8, filled_u8,
+                                       stats, nvb, disb, stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_inpaint_prepare");
+}
+
 size_t cs_gaussian_blur_workspace_bytes(int n, int h, int w, int n_taps) {
     (void)n_taps;
     return (n <= 0 || h <= 0 || w <= 0) ? 0 : al256((size_t)n * h * w * 4);

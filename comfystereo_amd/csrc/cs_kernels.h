@@ -169,6 +169,13 @@ hipError_t launch_gridwarp(const float* image, const float* depth, int n, int c,
 hipError_t launch_interp_fill(const float* image, const uint8_t* mask, int n, int c, int h, int w, float* out, hipStream_t stream);
 hipError_t launch_detect_disocc(const float* depth, const float* grid, const float* gxw, int h, int w, double threshold,
                                 uint8_t* out, hipStream_t stream);
+// cs_inpaintprep.hip (StereoDiffusion Fast mode's warp, inpaint mask and gap pre-fill: cs_inpaint_prepare).  nvb / disb: the
+// two bit-row planes of inpaint_prep_bits_bytes(n, h, w) bytes each; stats: ST_L_MIN / ST_L_MAX = each frame's raw depth min / max
+int inpaint_prep_max_width();
+size_t inpaint_prep_bits_bytes(int n, int h, int w);
+hipError_t launch_inpaint_prep(const float* image, const float* depth, int n, int h, int w, double div_px, double threshold,
+                               float* warped, float* filled, uint8_t* mask, uint8_t* warped_u8, uint8_t* filled_u8,
+                               const uint32_t* stats, uint32_t* nvb, uint32_t* disb, hipStream_t stream);
 // cs_gaussblur.hip (the Gaussian depth blurs: cs_gaussian_blur).  tmp: [n][h][w] float32, the row pass's output
 int gaussblur_max_taps();   // the row pass keeps a 1024-column segment plus 2 * radius halo columns in LDS
 hipError_t launch_gaussblur(int op, const float* depth, const double* taps, int n_taps, double edge_threshold, int n, int h, int w,

@@ -380,3 +380,36 @@ def gaussian_blur(depth, sigma, op="plain", edge_threshold=None):
                                      float(edge_threshold) if edge_threshold is not None else 0.0, n, h, w, _ptr(out), _ptr(ws),
                                      nb, _stream()))
     return out.reshape(depth.shape)
+
+
+# ---- StereoDiffusion Fast mode's warp, inpaint mask and gap pre-fill (cs_inpaint_prepare) ---------------
+def inpaint_prepare(image, depth, scale_factor, threshold=0.05, codes=False):
+    """cs_inpaint_prepare on device tensors: image [B,3,H,W] (values k / 255), depth [B,H,W], every frame on its own ->
+    (warped float32 [B,3,H,W], filled float32 [B,3,H,W], mask bool [B,H,W]), with codes=True followed by
+    (warped_u8, filled_u8), uint8 [B,H,W,3]: trunc(value * 255), the images the reference hands to its inpainting model and
+    blends the model's answer into.  scale_factor is the reference's (divergence_px = scale_factor / 100 * W).
+    A frame wider than cs_inpaint_prepare_max_width(): NativeError CS_ELIMIT."""
+    L = _native.lib()
+    image = _grid_input(image, "image", 4)
+    depth = _grid_input(depth, "depth", 3)
+    if image.device != depth.device:
+        raise ValueError("image and depth must be on the same device")
+    b, h, w = depth.shape
+    if image.shape[1] != 3 or image.shape[0] != b or tuple(image.shape[2:]) != (h, w):
+        raise ValueError(f"image {tuple(image.shape)} and depth {tuple(depth.shape)} do not match ([B,3,H,W] / [B,H,W])")
+    if b == 0 or h == 0 or w == 0:
+        raise ValueError(f"empty depth {tuple(depth.shape)}")
+    dev = depth.device
+    warped = torch.empty((b, 3, h, w), dtype=torch.float32, device=dev)
+    filled = torch.empty((b, 3, h, w), dtype=torch.float32, device=dev)
+    mask = torch.empty((b, h, w), dtype=torch.uint8, device=dev)
+    wu8 = torch.empty((b, h, w, 3), dtype=torch.uint8, device=dev) if codes else None
+    fu8 = torch.empty((b, h, w, 3), dtype=torch.uint8, device=dev) if codes else None
+    nb = L.cs_inpaint_prepare_workspace_bytes(b, h, w)
+    ws = torch.empty((max(nb, 256),), dtype=torch.uint8, device=dev)
+    divergence_px = (float(scale_factor) / 100.0) * w
+    _native.check(L.cs_inpaint_prepare(_ptr(image), _ptr(depth), b, h, w, divergence_px, float(threshold), _ptr(warped),
+                                       _ptr(filled), _ptr(mask), _ptr(wu8) if codes else None, _ptr(fu8) if codes else None,
+                                       _ptr(ws), nb, _stream()))
+    out = (warped, filled, mask.bool())
+    return out + (wu8, fu8) if codes else out

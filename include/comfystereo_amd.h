@@ -234,6 +234,32 @@ CS_API int cs_detect_disocclusions(const float *depth, const float *grid, const 
                                    double threshold, uint8_t *out, void *stream);
 
 /*
+ * The front half of StereoDiffusion's Fast mode (reference stereodiffusion_nodes.py:425-571, _generate_stereo_fast_single
+ * around its inpainting model), n independent frames: image [n][3][h][w] float32 (values k / 255), depth [n][h][w] float32.
+ *   depth chain (:432-440)  d / 255 when THAT FRAME's maximum is above 1; (d - min) / (max - min) of the frame when the range
+ *                           is above 1e-6, else 0; minus 0.5 (no exponent, no convergence point)
+ *   warped (:442-454)       one bilinear grid_sample (border padding, align_corners=True) at grid x = linspace(-1, 1, w) -
+ *                           (d * -divergence_px) / (w / 2), grid y = linspace(-1, 1, h)
+ *   mask (:456-491)         dilate3x3(grid x outside [-1, 1]  |  dilate3x3(nearest sample of d + 0.5 at the grid minus d + 0.5
+ *                           above `threshold`, reference 0.05)); an empty mask stays empty (the early return, :478)
+ *   filled (:493-542)       a masked pixel takes left * (1 - t) + right * t (float32, unfused) of the warped colours at the
+ *                           NEAREST unmasked column on either side (0 where there is none), t = distance to left / max(distance
+ *                           to left + distance to right, 1), distances counted from 1 with the frame edge one step beyond the
+ *                           last column; a row with nothing unmasked is 0.  Unmasked pixels keep warped.
+ *   warped_u8 / filled_u8   trunc(value * 255) (:546, :564) as [n][h][w][3] uint8, the images the reference hands to the model
+ *                           and blends its answer into (:563-571); defined for values in [0, 1]
+ * -> warped, filled [n][3][h][w] float32, mask [n][h][w] uint8 (0 / 1).  Any null output is skipped.  divergence_px is the
+ * reference's scale_factor / 100 * w (:430).  workspace: cs_inpaint_prepare_workspace_bytes(n, h, w).  The mask of a row is
+ * kept in LDS: frames wider than cs_inpaint_prepare_max_width() (16 384 columns) are refused with CS_ELIMIT before any device
+ * work.  Any h, w >= 1; at most 65 535 frames per call.
+ */
+CS_API size_t cs_inpaint_prepare_workspace_bytes(int n, int h, int w);
+CS_API int cs_inpaint_prepare_max_width(void);
+CS_API int cs_inpaint_prepare(const float *image, const float *depth, int n, int h, int w, double divergence_px,
+                              double threshold, float *warped, float *filled, uint8_t *mask, uint8_t *warped_u8,
+                              uint8_t *filled_u8, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * The reference's Gaussian depth blurs (stereoimage_generation.py): a separable filter with replicate borders, rows then
  * columns, and a per-pixel blend of the depth with its blur.
  *   CS_GAUSS_PLAIN           blur_depth_map (:1253-1281): out = the blurred map

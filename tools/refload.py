@@ -53,6 +53,21 @@ def load_node():
     return importlib.import_module("refpkg.GenerateStereo")
 
 
+def load_sd_nodes():
+    """stereodiffusion_nodes.py as a submodule of the same synthetic package.  model_wrappers and model_loader need `diffusers`,
+    which this image lacks: both get empty stand-ins (the three names the module imports from them, never called on the Fast
+    mode's per-frame path)."""
+    if "refpkg.stereodiffusion_nodes" in sys.modules:
+        return sys.modules["refpkg.stereodiffusion_nodes"]
+    load_node()
+    mw, ml = types.ModuleType("refpkg.model_wrappers"), types.ModuleType("refpkg.model_loader")
+    mw.ComfyUIModelWrapper = type("ComfyUIModelWrapper", (), {})
+    ml.load_sd_model = ml.load_inpainting_model = None
+    sys.modules.setdefault("refpkg.model_wrappers", mw)
+    sys.modules.setdefault("refpkg.model_loader", ml)
+    return importlib.import_module("refpkg.stereodiffusion_nodes")
+
+
 def quiet():
     """The D32 dialect (no numba, NumPy 2) emits an expected uint8-overflow warning per pixel sum."""
     warnings.filterwarnings("ignore", category=RuntimeWarning)
