@@ -28,6 +28,8 @@ GRID_OP = {"warp": 0, "fill": 1, "mask": 2, "stretch": 3}
 GRID_PADDING = {"border": 0, "zeros": 1, "reflection": 2}
 # enum cs_gauss_op (the reference's Gaussian depth blurs, cs_gaussian_blur)
 GAUSS_OP = {"plain": 0, "edge_selective": 1, "left": 2, "right": 3}
+# enum cs_pil_flags (Pillow's bicubic resize with the Fast mode's code conversions, cs_pil_resize)
+PIL_FLAG = {"in_f32": 1, "gray": 2, "out_planar": 4}
 
 # the ABI version the ctypes signatures below were written for (include/comfystereo_amd.h CS_ABI_VERSION)
 ABI_VERSION = 4
@@ -40,6 +42,7 @@ EXPORTS = [
     "cs_grid_warp_workspace_bytes", "cs_grid_warp_max_width", "cs_grid_warp", "cs_interpolate_fill", "cs_detect_disocclusions",
     "cs_gaussian_blur_workspace_bytes", "cs_gaussian_blur_max_taps", "cs_gaussian_blur",
     "cs_inpaint_prepare_workspace_bytes", "cs_inpaint_prepare_max_width", "cs_inpaint_prepare",
+    "cs_pil_resize_workspace_bytes", "cs_pil_resize_max_taps", "cs_pil_resize",
 ]
 
 # enum cs_debug_key (development switches; tests and profiling tools only)
@@ -207,6 +210,12 @@ def lib():
     L.cs_inpaint_prepare_max_width.argtypes = []
     L.cs_inpaint_prepare.restype = c_int
     L.cs_inpaint_prepare.argtypes = [vp, vp, c_int, c_int, c_int, c_double, c_double, vp, vp, vp, vp, vp, vp, c_size, vp]
+    L.cs_pil_resize_workspace_bytes.restype = c_size
+    L.cs_pil_resize_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int, c_int]
+    L.cs_pil_resize_max_taps.restype = c_int
+    L.cs_pil_resize_max_taps.argtypes = []
+    L.cs_pil_resize.restype = c_int
+    L.cs_pil_resize.argtypes = [vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, vp, vp, c_size, vp, c_size, vp]
     _lib = L
     return L
 

@@ -1201,6 +1201,52 @@ int cs_inpaint_prepare(const float* image, const float* depth, int n, int h, int
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_inpaint_prepare");
 }
 
+size_t cs_pil_resize_workspace_bytes(int n, int h, int w, int c, int oh, int ow) {
+    if (n <= 0 || h <= 0 || w <= 0 || oh <= 0 || ow <= 0 || (c != 1 && c != 3)) return 0;
+    if (!pilresize_fits(h, w, oh, ow)) return 0;
+    return pilresize_workspace_bytes(n, h, w, c, oh, ow) + 256;
+}
+int cs_pil_resize_max_taps(void) { return pilresize_max_taps(); }
+
+static bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return a && b && pa < pb + nb && pb < pa + na;
+}
+
+int cs_pil_resize(const void* in, int n, int h, int w, int c, int oh, int ow, int flags, uint8_t* out_u8, float* out_f32,
+                  size_t f32_row_pitch, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!in || !workspace) return fail(CS_EINVAL, "null pointer");
+    if (n <= 0 || h <= 0 || w <= 0 || oh <= 0 || ow <= 0) return fail(CS_EINVAL, "non-positive size");
+    if (flags & ~(CS_PIL_IN_F32 | CS_PIL_GRAY | CS_PIL_OUT_PLANAR)) return fail(CS_EINVAL, "cs_pil_resize: unknown flag (CS_PIL_*)");
+    if (c != 1 && c != 3) return fail(CS_EINVAL, "cs_pil_resize: 1 or 3 channels (modes L and RGB)");
+    if ((flags & CS_PIL_GRAY) && c != 3) return fail(CS_EINVAL, "cs_pil_resize: CS_PIL_GRAY takes 3 channels");
+    const int in_f32 = (flags & CS_PIL_IN_F32) != 0, gray = (flags & CS_PIL_GRAY) != 0, planar = (flags & CS_PIL_OUT_PLANAR) != 0;
+    const int co = gray ? 1 : c;
+    const size_t dense = (size_t)ow * co;
+    if (!planar && f32_row_pitch != 0 && f32_row_pitch < dense) return fail(CS_EINVAL, "cs_pil_resize: f32_row_pitch below ow * channels");
+    if (in_f32 && ((uintptr_t)in & 3)) return fail(CS_EINVAL, "cs_pil_resize: float32 input needs 4-byte alignment");
+    if ((uintptr_t)out_f32 & 3) return fail(CS_EINVAL, "cs_pil_resize: out_f32 needs 4-byte alignment");
+    if ((uintptr_t)workspace & 7) return fail(CS_EINVAL, "cs_pil_resize: workspace needs 8-byte alignment");
+    if (n > 65535) return fail(CS_ELIMIT, "cs_pil_resize: more than 65535 frames in one call");
+    if (h > pilresize_max_size() || w > pilresize_max_size() || oh > pilresize_max_size() || ow > pilresize_max_size())
+        return fail(CS_ELIMIT, "cs_pil_resize: a side of more than 65535 samples");
+    if (!pilresize_fits(h, w, oh, ow))
+        return fail(CS_ELIMIT, "cs_pil_resize: reduction too strong for the LDS-resident input span (cs_pil_resize_max_taps)");
+    const size_t pitch = planar ? 0 : (f32_row_pitch ? f32_row_pitch : dense);
+    const size_t in_bytes = (size_t)n * h * w * c * (in_f32 ? 4 : 1), u8_bytes = (size_t)n * oh * dense;
+    const size_t f32_bytes = planar ? u8_bytes * 4 : ((size_t)n * oh - 1) * pitch * 4 + dense * 4;
+    const size_t need = cs_pil_resize_workspace_bytes(n, h, w, c, oh, ow);
+    if (overlaps(in, in_bytes, out_u8, u8_bytes) || overlaps(in, in_bytes, out_f32, f32_bytes) ||
+        overlaps(out_u8, u8_bytes, out_f32, f32_bytes) || overlaps(workspace, need, in, in_bytes) ||
+        overlaps(workspace, need, out_u8, u8_bytes) || overlaps(workspace, need, out_f32, f32_bytes))
+        return fail(CS_EINVAL, "cs_pil_resize: in, out_u8, out_f32 and workspace must not overlap");
+    if (workspace_bytes < need) return fail(CS_EWORKSPACE, "workspace too small");
+    if (!out_u8 && !out_f32) return CS_OK;
+    void* ws = (void*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    hipError_t e = launch_pilresize(in, in_f32, gray, n, h, w, c, oh, ow, out_u8, out_f32, planar, pitch, ws, (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_pil_resize");
+}
+
 size_t cs_gaussian_blur_workspace_bytes(int n, int h, int w, int n_taps) {
     (void)n_taps;
     return (n <= 0 || h <= 0 || w <= 0) ? 0 : al256((size_t)n * h * w * 4);

@@ -180,6 +180,14 @@ hipError_t launch_inpaint_prep(const float* image, const float* depth, int n, in
 int gaussblur_max_taps();   // the row pass keeps a 1024-column segment plus 2 * radius halo columns in LDS
 hipError_t launch_gaussblur(int op, const float* depth, const double* taps, int n_taps, double edge_threshold, int n, int h, int w,
                             float* out, float* tmp, hipStream_t stream);
+// cs_pilresize.hip (Pillow's 8-bit bicubic resize with the Fast mode's code conversions: cs_pil_resize).  c_in: channels of `in`
+// (gray: 3 in, 1 out); pitch: floats per row of an NHWC out_f32
+int pilresize_max_taps();
+int pilresize_max_size();
+bool pilresize_fits(int h, int w, int oh, int ow);
+size_t pilresize_workspace_bytes(int n, int h, int w, int c_out, int oh, int ow);
+hipError_t launch_pilresize(const void* in, int in_f32, int gray, int n, int h, int w, int c_in, int oh, int ow, uint8_t* out_u8,
+                            float* out_f32, int planar, size_t pitch, void* workspace, hipStream_t stream);
 // lazy depth-blur tiles in k_gpuwarp (tilemap != nullptr): rows of at most this many columns, not the mesh-quality warp
 int gpuwarp_lazy_max_width();
 

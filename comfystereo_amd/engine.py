@@ -413,3 +413,62 @@ def inpaint_prepare(image, depth, scale_factor, threshold=0.05, codes=False):
                                        _ptr(ws), nb, _stream()))
     out = (warped, filled, mask.bool())
     return out + (wu8, fu8) if codes else out
+
+
+# ---- Pillow's 8-bit bicubic resize with the Fast mode's code conversions (cs_pil_resize) ----------------
+def pil_resize(x, size, gray=False, f32=None, codes=True, f32_out=None):
+    """cs_pil_resize on a device tensor: x [N,H,W,C] (C 1 or 3) or [N,H,W], uint8 codes or float32 (codes
+    trunc(clip(255 * x, 0, 255))); size = (width, height), PIL's order -> the uint8 codes [N,oh,ow,C] of
+    PIL.Image.resize(size) (Pillow 12.2, all defaults), byte for byte.  gray=True: x has 3 channels, the result one, the
+    Fast mode's gray of a coloured depth taken before the resize.
+    f32: None, "nhwc" ([N,oh,ow,C]) or "planar" ([N,C,oh,ow]): also return code / 255 as float32 -> (codes, floats).
+    codes=False: no uint8 result (None in its place).  f32_out: a float32 [N,oh,ow,C] destination for "nhwc" whose rows may be
+    a slice of wider rows (one eye of a side-by-side frame).
+    A reduction by more than a factor of 64, or a side above 65 535: NativeError CS_ELIMIT."""
+    L = _native.lib()
+    if not isinstance(x, torch.Tensor):
+        raise ValueError("x must be a torch.Tensor")
+    if x.dtype not in (torch.uint8, torch.float32):
+        raise ValueError(f"x must be uint8 or float32, got {x.dtype}")
+    if x.dim() == 3:
+        x = x.unsqueeze(-1)
+    if x.dim() != 4 or x.shape[-1] not in (1, 3):
+        raise ValueError(f"x must be [N,H,W,C] with C 1 or 3, or [N,H,W]; got shape {tuple(x.shape)}")
+    if gray and x.shape[-1] != 3:
+        raise ValueError("gray=True takes 3 channels")
+    if f32 not in (None, "nhwc", "planar"):
+        raise ValueError(f"f32 must be None, 'nhwc' or 'planar', got {f32!r}")
+    if f32_out is not None and f32 != "nhwc":
+        raise ValueError("f32_out needs f32='nhwc'")
+    if not codes and f32 is None:
+        raise ValueError("nothing asked for: codes=False without f32")
+    ow, oh = (int(v) for v in size)
+    if ow <= 0 or oh <= 0 or x.numel() == 0:
+        raise ValueError(f"empty image: {tuple(x.shape)} -> {(oh, ow)}")
+    x = _dev(x).contiguous()
+    n, h, w, c = x.shape
+    co = 1 if gray else c
+    dev = x.device
+    out = torch.empty((n, oh, ow, co), dtype=torch.uint8, device=dev) if codes else None
+    flt, pitch = None, 0
+    if f32 == "planar":
+        flt = torch.empty((n, co, oh, ow), dtype=torch.float32, device=dev)
+    elif f32_out is not None:
+        flt = f32_out
+        if (not isinstance(flt, torch.Tensor) or flt.dtype != torch.float32 or flt.device != dev
+                or tuple(flt.shape) != (n, oh, ow, co)):
+            raise ValueError(f"f32_out must be a float32 tensor {(n, oh, ow, co)} on {dev}")
+        st = flt.stride()
+        pitch = st[1] if oh > 1 else (st[0] if n > 1 else ow * co)
+        dense_pixels = (co == 1 or st[3] == 1) and (ow == 1 or st[2] == co)
+        if not dense_pixels or pitch < ow * co or (n > 1 and oh > 1 and st[0] != oh * pitch):
+            raise ValueError("f32_out must have dense pixels, and rows and frames one row pitch apart")
+    elif f32 == "nhwc":
+        flt = torch.empty((n, oh, ow, co), dtype=torch.float32, device=dev)
+    flags = (_native.PIL_FLAG["in_f32"] if x.dtype == torch.float32 else 0) | (_native.PIL_FLAG["gray"] if gray else 0) | \
+        (_native.PIL_FLAG["out_planar"] if f32 == "planar" else 0)
+    nb = L.cs_pil_resize_workspace_bytes(n, h, w, c, oh, ow)
+    ws = torch.empty((max(nb, 256),), dtype=torch.uint8, device=dev)
+    _native.check(L.cs_pil_resize(_ptr(x), n, h, w, c, oh, ow, flags, _ptr(out) if codes else None,
+                                  _ptr(flt) if flt is not None else None, pitch, _ptr(ws), max(nb, 256), _stream()))
+    return out if f32 is None else (out, flt)

@@ -260,6 +260,36 @@ CS_API int cs_inpaint_prepare(const float *image, const float *depth, int n, int
                               uint8_t *filled_u8, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * Pillow's 8-bit bicubic resize, byte for byte: out = PIL.Image.resize((ow, oh)) of Pillow 12.2 with all defaults on modes L
+ * (c = 1) and RGB (c = 3), n independent frames of interleaved codes [n][h][w][c] -> [n][oh][ow][c].  What StereoDiffusion's
+ * Fast mode does around its 512 x 512 working size (reference stereodiffusion_nodes.py:415-423, :481-484, :569-573).
+ *   passes   horizontal first, then vertical, whatever the direction of scaling; a pass whose input and output size agree is
+ *            skipped (an exact copy).  The image between the passes is uint8 [h][ow][c]: its rounding and clipping count.
+ *   taps     per axis, float64: scale = in / out, fs = max(scale, 1), support = 2 * fs; output sample xx has center =
+ *            (xx + 0.5) * scale, xmin = max((int)(center - support + 0.5), 0), xmax = min((int)(center + support + 0.5), in);
+ *            k[x] = bicubic((x + xmin - center + 0.5) * (1 / fs)), the Keys kernel with a = -0.5, divided by their left-to-right
+ *            sum; fixed point (int)(k * 2^22 + 0.5), (int)(k * 2^22 - 0.5) for a negative k.  Built on the device.
+ *   sample   clip8((2^21 + sum pixel * tap) >> 22) in int32, arithmetic shift
+ * flags (enum cs_pil_flags):
+ *   CS_PIL_IN_F32      `in` is float32 [n][h][w][c]; its codes are trunc(clip(255 * x, 0, 255)) (float32 product, :55)
+ *   CS_PIL_GRAY        c = 3 in, ONE channel out: gray = trunc((r * 0.2989 + g * 0.5870) + b * 0.1140) in float64, in this
+ *                      order (:419), before the resize.  Equal to the reference on every depth with three equal channels; its
+ *                      own BLAS product differs from this order, and from itself between array shapes, on a few hundred of
+ *                      the 2^24 colours.
+ *   CS_PIL_OUT_PLANAR  out_f32 is planar [n][c][oh][ow] (what cs_inpaint_prepare takes) instead of [n][oh][ow][c]
+ * out_u8: the codes, or null.  out_f32: code / 255.0f (a true division, :61), or null; interleaved rows start f32_row_pitch
+ * floats apart (0: ow * channels; lets two eyes be written into one side-by-side frame).  Both null: nothing is done.
+ * workspace: cs_pil_resize_workspace_bytes(n, h, w, c, oh, ow), 8-byte aligned.  in, out_u8, out_f32 and workspace must not
+ * overlap (CS_EINVAL).  CS_ELIMIT before any device work: more than 65 535 frames, a side above 65 535, or a reduction whose
+ * window has more than cs_pil_resize_max_taps() (257: a factor of 64) taps on an axis that is resampled.
+ */
+enum cs_pil_flags { CS_PIL_IN_F32 = 1, CS_PIL_GRAY = 2, CS_PIL_OUT_PLANAR = 4 };
+CS_API size_t cs_pil_resize_workspace_bytes(int n, int h, int w, int c, int oh, int ow);
+CS_API int cs_pil_resize_max_taps(void);
+CS_API int cs_pil_resize(const void *in, int n, int h, int w, int c, int oh, int ow, int flags, uint8_t *out_u8,
+                         float *out_f32, size_t f32_row_pitch, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * The reference's Gaussian depth blurs (stereoimage_generation.py): a separable filter with replicate borders, rows then
  * columns, and a per-pixel blend of the depth with its blur.
  *   CS_GAUSS_PLAIN           blur_depth_map (:1253-1281): out = the blurred map
