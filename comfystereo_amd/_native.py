@@ -30,6 +30,8 @@ GRID_PADDING = {"border": 0, "zeros": 1, "reflection": 2}
 GAUSS_OP = {"plain": 0, "edge_selective": 1, "left": 2, "right": 3}
 # enum cs_pil_flags (Pillow's bicubic resize with the Fast mode's code conversions, cs_pil_resize)
 PIL_FLAG = {"in_f32": 1, "gray": 2, "out_planar": 4}
+# enum cs_attn_mode (the reference's stereo attention, cs_stereo_attention)
+ATTN_MODE = {"self": 0, "uni": 1, "bi": 2}
 
 # the ABI version the ctypes signatures below were written for (include/comfystereo_amd.h CS_ABI_VERSION)
 ABI_VERSION = 4
@@ -43,12 +45,13 @@ EXPORTS = [
     "cs_gaussian_blur_workspace_bytes", "cs_gaussian_blur_max_taps", "cs_gaussian_blur",
     "cs_inpaint_prepare_workspace_bytes", "cs_inpaint_prepare_max_width", "cs_inpaint_prepare",
     "cs_pil_resize_workspace_bytes", "cs_pil_resize_max_taps", "cs_pil_resize",
+    "cs_stereo_attention_max_head_dim", "cs_stereo_attention",
 ]
 
 # enum cs_debug_key (development switches; tests and profiling tools only)
 DEBUG = {"dbg": 0, "no_tile": 1, "pt_variant": 2, "blur_two_pass": 3, "blur_edges_scalar": 4, "blur_full_copy": 5, "chunks": 6, "no_replay_kernel": 7,
          "blur_no_pre_edges": 8, "hybrid_unfused": 9, "gpuwarp_full_maps": 10,
-         "hybrid_full_maps": 11}
+         "hybrid_full_maps": 11, "attn_waves": 12}
 
 # stats word ST_WARP_PATH (Plan.stats()[:, 12]): the gpu_warp kernel instantiation that warped a frame (cs_common.h GW_PATH_*, the
 # list this mirrors; 0: no gpu_warp kernel ran).  Names: kernel<MINW, POW> (POW -1: exponent at run time); "node" -- the node's
@@ -216,6 +219,10 @@ def lib():
     L.cs_pil_resize_max_taps.argtypes = []
     L.cs_pil_resize.restype = c_int
     L.cs_pil_resize.argtypes = [vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, vp, vp, c_size, vp, c_size, vp]
+    L.cs_stereo_attention_max_head_dim.restype = c_int
+    L.cs_stereo_attention_max_head_dim.argtypes = []
+    L.cs_stereo_attention.restype = c_int
+    L.cs_stereo_attention.argtypes = [vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_int, vp]
     _lib = L
     return L
 

@@ -1335,6 +1335,31 @@ int cs_stereo_shift(const float* input, const float* depth, int b, int c, int h,
     return er == hipSuccess ? CS_OK : fail_hip(er, "cs_stereo_shift");
 }
 
+int cs_stereo_attention_max_head_dim(void) { return stereo_attention_max_head_dim(); }
+
+int cs_stereo_attention(const float* q, const float* k, const float* v, float* out, int c, int s, int b, int h, int n, int n_k,
+                        int d, double scale, int mode, void* stream) {
+    if (!q || !k || !v || !out) return fail(CS_EINVAL, "null pointer");
+    if (c <= 0 || s <= 0 || b <= 0 || h <= 0 || n <= 0 || n_k <= 0 || d <= 0) return fail(CS_EINVAL, "non-positive size");
+    if (mode < CS_ATTN_SELF || mode > CS_ATTN_BI) return fail(CS_EINVAL, "cs_stereo_attention: unknown mode (CS_ATTN_*)");
+    if (mode != CS_ATTN_SELF && (s != 2 || n_k != n))
+        return fail(CS_EINVAL, "cs_stereo_attention: CS_ATTN_UNI / CS_ATTN_BI take two views (s = 2) with n_k = n");
+    if (!(scale == scale) || scale - scale != 0.0) return fail(CS_EINVAL, "cs_stereo_attention: scale must be finite");
+    if ((d & 3) || d > stereo_attention_max_head_dim())
+        return fail(CS_ELIMIT, "cs_stereo_attention: head dimension must be a multiple of 4 up to cs_stereo_attention_max_head_dim()");
+    if (((uintptr_t)q & 15) || ((uintptr_t)k & 15) || ((uintptr_t)v & 15) || ((uintptr_t)out & 15))
+        return fail(CS_EINVAL, "cs_stereo_attention: q, k, v and out need 16-byte alignment");
+    // one workgroup per 32 * waves queries of a (c, s, b, h); token and key indices in 32-bit ints
+    const long long bhn = (long long)c * s * b * h;
+    if (n > (1 << 24) || n_k > (1 << 24) || bhn >= (1ll << 31) || bhn * ((n + 31) / 32) >= (1ll << 31))
+        return fail(CS_ELIMIT, "cs_stereo_attention: more than 2^24 tokens per view or 2^31 workgroups in one call");
+    const size_t q_bytes = (size_t)bhn * n * d * 4, k_bytes = (size_t)bhn * n_k * d * 4;
+    if (overlaps(out, q_bytes, q, q_bytes) || overlaps(out, q_bytes, k, k_bytes) || overlaps(out, q_bytes, v, k_bytes))
+        return fail(CS_EINVAL, "cs_stereo_attention: out must not overlap q, k or v");
+    hipError_t e = launch_stereo_attention(q, k, v, out, c, s, b, h, n, n_k, d, (float)scale, mode, (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_stereo_attention");
+}
+
 int cs_profile(int enable) {
     std::lock_guard<std::mutex> lock(g_prof_mu);
     g_prof_on.store(enable != 0);
@@ -1361,6 +1386,8 @@ int cs_debug_set(int key, int value) {
         default: return fail(CS_EINVAL, "cs_debug_set: unknown CS_DEBUG_PT_VARIANT value (PTV_* in cs_common.h)");
         }
     }
+    if (key == CS_DEBUG_ATTN_WAVES && value != 0 && value != 1 && value != 2 && value != 4)
+        return fail(CS_EINVAL, "cs_debug_set: CS_DEBUG_ATTN_WAVES takes 0 (the launcher's choice), 1, 2 or 4");
     g_dev[key].store(value, std::memory_order_relaxed);
     return CS_OK;
 }

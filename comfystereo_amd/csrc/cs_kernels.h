@@ -188,6 +188,11 @@ bool pilresize_fits(int h, int w, int oh, int ow);
 size_t pilresize_workspace_bytes(int n, int h, int w, int c_out, int oh, int ow);
 hipError_t launch_pilresize(const void* in, int in_f32, int gray, int n, int h, int w, int c_in, int oh, int ow, uint8_t* out_u8,
                             float* out_f32, int planar, size_t pitch, void* workspace, hipStream_t stream);
+// cs_attention.hip (the reference's stereo attention, BNAttention: cs_stereo_attention).  mode: enum cs_attn_mode
+int stereo_attention_max_head_dim();
+int stereo_attention_waves(long long batch_heads, int n);   // waves per workgroup the launcher picks (32 queries each)
+hipError_t launch_stereo_attention(const float* q, const float* k, const float* v, float* out, int c, int s, int b, int h, int n,
+                                   int n_k, int d, float scale, int mode, hipStream_t stream);
 // lazy depth-blur tiles in k_gpuwarp (tilemap != nullptr): rows of at most this many columns, not the mesh-quality warp
 int gpuwarp_lazy_max_width();
 

@@ -4,6 +4,7 @@ Everything here takes and returns tensors that live on the MI355X (`cuda` device
 PyTorch only provides the memory and the stream -- the arithmetic is in the HIP kernels.
 """
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -472,3 +473,61 @@ def pil_resize(x, size, gray=False, f32=None, codes=True, f32_out=None):
     _native.check(L.cs_pil_resize(_ptr(x), n, h, w, c, oh, ow, flags, _ptr(out) if codes else None,
                                   _ptr(flt) if flt is not None else None, pitch, _ptr(ws), max(nb, 256), _stream()))
     return out if f32 is None else (out, flt)
+
+
+# ---- the reference's stereo attention (cs_stereo_attention) ---------------------------------------------
+def stereo_attention(q, k, v, heads, scale, mode, chunks=1, out=None):
+    """cs_stereo_attention on float32 device tensors: q [(c s b h), n, d], k and v [(c s b h), n_k, d] -> [(c s b), n, h * d],
+    softmax(scale * q k^T) v over the keys `mode` selects, in one fused kernel (no score matrix is ever written).
+    mode: "self" (every batch entry sees its own keys; n_k may differ from n), "uni" (both views see the left view's keys) or
+    "bi" (both views see both views' keys); "uni" / "bi" take two views (s = 2) and `chunks` = c CFG chunks, "self" takes
+    the batch as it is.  heads = h.  out: an optional float32 destination of the result's shape.
+    d must be a multiple of 4 up to cs_stereo_attention_max_head_dim(): ValueError before anything is launched."""
+    if mode not in _native.ATTN_MODE:
+        raise ValueError(f"unknown attention mode {mode!r} (self, uni, bi)")
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch.Tensor")
+        if t.dim() != 3:
+            raise ValueError(f"{name} must be [(c s b h), tokens, d], got shape {tuple(t.shape)}")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name} must be float32, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+        if t.requires_grad:
+            raise ValueError(f"{name} requires grad: cs_stereo_attention is forward only")
+    heads, chunks = int(heads), int(chunks)
+    bh, n, d = q.shape
+    if k.shape != v.shape or k.shape[0] != bh or k.shape[2] != d:
+        raise ValueError(f"q {tuple(q.shape)}, k {tuple(k.shape)} and v {tuple(v.shape)} do not match")
+    n_k = k.shape[1]
+    if bh == 0 or n == 0 or n_k == 0 or d == 0:
+        raise ValueError(f"empty attention: q {tuple(q.shape)}, k {tuple(k.shape)}")
+    views = 1 if mode == "self" else 2
+    if mode == "self":
+        chunks = 1
+    if heads <= 0 or chunks <= 0 or bh % (heads * views * chunks):
+        raise ValueError(f"batch {bh} is not chunks * views * samples * heads = {chunks} * {views} * b * {heads}")
+    if mode != "self" and n_k != n:
+        raise ValueError(f"mode {mode!r} needs as many keys as queries per view, got {n_k} and {n}")
+    d_max = _native.lib().cs_stereo_attention_max_head_dim()   # (host only: no device work)
+    if d % 4 or d > d_max:
+        raise ValueError(f"head dimension {d}: cs_stereo_attention takes multiples of 4 up to {d_max}")
+    if not math.isfinite(float(scale)):
+        raise ValueError(f"scale must be finite, got {scale}")
+    samples = bh // (heads * views * chunks)
+    shape = (bh // heads, n, heads * d)
+    if out is not None:
+        if (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous()
+                or out.device != q.device):
+            raise ValueError(f"out must be a contiguous float32 tensor {shape} on {q.device}")
+    _dev(q)
+    if k.device != q.device or v.device != q.device:
+        raise ValueError("q, k and v must be on the same device")
+    L = _native.lib()
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=q.device)
+    with torch.cuda.device(q.device):
+        _native.check(L.cs_stereo_attention(_ptr(q), _ptr(k), _ptr(v), _ptr(out), chunks, views, samples, heads, n, n_k, d,
+                                            float(scale), _native.ATTN_MODE[mode], _stream()))
+    return out

@@ -1,8 +1,16 @@
-"""Drop-in for the one function of the reference's stereo_utils.py that lies on the depth-to-stereo path:
-`stereo_shift_torch` (reference stereo_utils.py:15-88; called on diffusion latents by stereodiffusion_nodes.py:650, :664).
-Same name, argument order, defaults and return shape; the shift runs in a HIP kernel behind the C ABI (cs_stereo_shift) --
-no CPU fallback.  The attention-editing half of that file (BNAttention, ...) is diffusion plumbing and out of scope."""
+"""Drop-in for the reference's stereo_utils.py.
+
+`stereo_shift_torch` (reference stereo_utils.py:15-88; called on diffusion latents by stereodiffusion_nodes.py:650, :664): same
+name, argument order, defaults and return shape; the shift runs in a HIP kernel behind the C ABI (cs_stereo_shift).
+
+`BNAttention`, `register_attention_editor_diffusers`, `restore_attention` (reference :91-393), the attention editing of
+StereoDiffusion's Standard mode: the same classes, names, signatures and step bookkeeping; the attention itself is one fused
+HIP kernel behind the C ABI (cs_stereo_attention) that never materialises the score matrix -- the reference builds
+`sim` and `softmax(sim)` twice per layer, [heads, 2n, 2n] float32 the second time.
+
+No CPU fallback anywhere: without a GPU the calls raise RuntimeError."""
 import torch
+import torch.nn as nn
 
 from . import engine
 
@@ -22,3 +30,167 @@ def stereo_shift_torch(input_images: torch.Tensor, depthmaps: torch.Tensor, scal
                               stereo_offset_exponent)
     out = out.to(input_images.dtype)
     return out if input_images.is_cuda else out.to(input_images.device)
+
+
+def _need_gpu():
+    if not torch.cuda.is_available():
+        raise RuntimeError("comfystereo_amd needs an MI355X (PyTorch-ROCm `cuda` device); there is no CPU fallback")
+
+
+def _attention(q, k, v, num_heads, scale, mode, chunks=1):
+    """engine.stereo_attention on q, k, v as the reference holds them ([(c s b h), n, d]).  float16 / bfloat16 inputs are upcast
+    to float32 and the result is cast back: the products, the softmax and the sums are float32 throughout, which is MORE
+    accurate than the reference's arithmetic in the tensors' own half precision (its result differs by half-precision
+    rounding errors; only float32, the Standard pipeline's dtype -- reference model_loader.py:63-65 -- is pinned)."""
+    _need_gpu()
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if not isinstance(t, torch.Tensor) or not t.is_floating_point():
+            raise TypeError(f"BNAttention: {name} must be a floating-point tensor")
+        if t.requires_grad:
+            raise RuntimeError(f"BNAttention: {name} requires grad; the fused attention is forward only (run under torch.no_grad(), "
+                               "as the reference's pipeline does, stereodiffusion_nodes.py:575)")
+    if scale is None:
+        raise ValueError("BNAttention needs the keyword argument scale")
+    dev = q.device if q.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    q32, k32, v32 = (t.detach().to(dev, torch.float32).contiguous() for t in (q, k, v))
+    out = engine.stereo_attention(q32, k32, v32, num_heads, float(scale), mode, chunks).to(q.dtype)
+    return out if q.is_cuda else out.to(q.device)
+
+
+class BNAttention:
+    """The reference's attention editor (stereo_utils.py:91-188): from `start_step` on, every self-attention lets the right
+    view's queries see the left view's keys ('uni') or both views see both ('bi').  Same constructor, attributes and call
+    signatures; `sim` and `attn` are accepted for compatibility and ignored (they may be None): the fused kernel recomputes
+    the scores tile by tile and never stores them."""
+
+    def __init__(self, start_step: int = 4, total_steps: int = 50, direction: str = 'uni', use_cfg: bool = True):
+        # the editor's whole state: four settings and two counters; register_attention_editor_diffusers fills in the layer count
+        self.start_step, self.total_steps = start_step, total_steps
+        self.direction, self.use_cfg = direction, use_cfg
+        self.cur_step = self.cur_att_layer = 0
+        self.num_att_layers = 0
+
+    def attn_batch(self, q, k, v, sim, attn, is_cross, place_in_unet, num_heads, **kwargs):
+        """One CFG half in stereo mode (:119-133): q [(s b h), n, d] over the keys of both views, or -- k, v [(b h), n, d],
+        the left view's half, as the reference's `forward` passes them for 'uni' -- over the left view's.  That second form
+        costs a copy of k and v (the kernel addresses the left view inside a two-view tensor); `forward` here never takes it."""
+        if k.shape[0] == q.shape[0]:
+            return _attention(q, k, v, num_heads, kwargs.get("scale"), "bi")
+        if 2 * k.shape[0] != q.shape[0]:
+            raise ValueError(f"attn_batch: {q.shape[0]} query and {k.shape[0]} key batch entries")
+        # the kernel addresses the left view inside a [(s b h)] tensor: hand it one whose view 0 is k, v (view 1 is not read)
+        return _attention(q, torch.cat([k, k]), torch.cat([v, v]), num_heads, kwargs.get("scale"), "uni")
+
+    def forward(self, q, k, v, sim, attn, is_cross, place_in_unet, num_heads, **kwargs):
+        if is_cross or (self.cur_step < self.start_step):
+            return _attention(q, k, v, num_heads, kwargs.get("scale"), "self")   # (:137-140)
+        if not self.use_cfg:
+            return _attention(q, k, v, num_heads, kwargs.get("scale"), "bi")     # (:142-146) [left, right]
+        # CFG: the batch is [uncond_left, uncond_right, cond_left, cond_right] (:148-176)
+        if self.direction not in ('bi', 'uni'):
+            raise ValueError(f"Unknown direction: {self.direction}")
+        return _attention(q, k, v, num_heads, kwargs.get("scale"), self.direction, chunks=2)
+
+    def __call__(self, q, k, v, sim, attn, is_cross, place_in_unet, num_heads, **kwargs):
+        out = self.forward(q, k, v, sim, attn, is_cross, place_in_unet, num_heads, **kwargs)
+        # one call per attention layer: the step is the number of complete passes over the registered layers (over 32 layers,
+        # SD 1.x's count, for an editor nobody registered)
+        self.cur_att_layer += 1
+        self.cur_step = self.cur_att_layer // (self.num_att_layers if self.num_att_layers > 0 else 32)
+        return out
+
+
+_SAVED_FORWARD = "_comfystereo_saved_forward"
+
+
+def _get_unet(model):
+    """Where the reference looks for the UNet (:284-307), in its order: a ComfyUI wrapper's `comfy_model.model.diffusion_model`,
+    a diffusers pipeline's `unet`, a raw ComfyUI model's `model.diffusion_model`; anything else is taken to be the UNet."""
+    for path in (("comfy_model", "model", "diffusion_model"), ("unet",), ("model", "diffusion_model")):
+        if path[0] == "comfy_model" and hasattr(model, "comfy_model"):
+            return model.comfy_model.model.diffusion_model   # (no fall-through: the reference does not probe further here)
+        node = model
+        for name in path:
+            node = getattr(node, name, None)
+            if node is None:
+                break
+        else:
+            return node
+    return model
+
+
+def _walk_attention(model, visit):
+    """The reference's walk (:258-281): the UNet's children whose name says down / input, mid, up / output, and below them
+    every module whose class name contains 'Attention' and that has children.  visit(module, place_in_unet); returns the count."""
+    def walk(net, count, place_in_unet):
+        for _name, subnet in net.named_children():
+            if 'Attention' in net.__class__.__name__:
+                visit(net, place_in_unet)
+                return count + 1
+            elif hasattr(net, 'children'):
+                count = walk(subnet, count, place_in_unet)
+        return count
+
+    total = 0
+    for net_name, net in _get_unet(model).named_children():
+        if "down" in net_name or "input" in net_name:
+            total += walk(net, 0, "down")
+        elif "mid" in net_name:
+            total += walk(net, 0, "mid")
+        elif "up" in net_name or "output" in net_name:
+            total += walk(net, 0, "up")
+    return total
+
+
+def register_attention_editor_diffusers(model, editor: BNAttention):
+    """Install `editor` on every attention module of the model's UNet (reference :190-281: the same walk, the same names) and
+    count the modules into editor.num_att_layers.  The installed forward computes q, k, v with the module's own linear layers
+    and calls the editor with sim = attn = None: no score matrix is built.  The original forwards are saved on the modules;
+    restore_attention puts them back.
+    An attention mask other than None is refused with ValueError: Stable Diffusion's UNet never passes one, and the fused
+    kernel has no mask input."""
+    def install(net, place_in_unet):
+        if not hasattr(net, _SAVED_FORWARD):
+            # an instance attribute shadows the class's forward: remember whether there was one
+            setattr(net, _SAVED_FORWARD, net.__dict__.get("forward"))
+        scale = net.scale if hasattr(net, 'scale') else net.dim_head ** -0.5
+
+        def forward(x, encoder_hidden_states=None, attention_mask=None, context=None, mask=None, value=None,
+                    transformer_options=None, **kwargs):
+            # diffusers' and ComfyUI's names for the same two things; the first of each pair wins, as in the reference
+            context = encoder_hidden_states if encoder_hidden_states is not None else context
+            mask = attention_mask if attention_mask is not None else mask
+            if mask is not None:
+                raise ValueError("the fused stereo attention takes no attention mask")
+            is_cross = context is not None
+            source = context if is_cross else x
+            heads = net.heads
+
+            def split(t):   # [b, n, heads * d] -> [(b heads), n, d]
+                b, n, hd = t.shape
+                return t.reshape(b, n, heads, hd // heads).permute(0, 2, 1, 3).reshape(b * heads, n, hd // heads)
+
+            q, k = split(net.to_q(x)), split(net.to_k(source))
+            v = split(net.to_v(source if value is None else value))
+            out = editor(q, k, v, None, None, is_cross, place_in_unet, heads, scale=scale)
+            project = net.to_out[0] if isinstance(net.to_out, nn.ModuleList) else net.to_out
+            return project(out)
+
+        net.forward = forward
+
+    editor.num_att_layers = _walk_attention(model, install)
+
+
+def restore_attention(model):
+    """Put back the forwards register_attention_editor_diffusers replaced (reference :310-393 installs a plain attention
+    forward instead; here the modules get their own forward back, which computes the same thing)."""
+    def uninstall(net, place_in_unet):
+        if hasattr(net, _SAVED_FORWARD):
+            saved = getattr(net, _SAVED_FORWARD)
+            delattr(net, _SAVED_FORWARD)
+            if saved is None:
+                net.__dict__.pop("forward", None)
+            else:
+                net.forward = saved
+
+    _walk_attention(model, uninstall)

@@ -368,6 +368,25 @@ CS_API int cs_stereo_shift(const float *input, const float *depth, int b, int c,
                     void *stream);
 
 /*
+ * Stereo attention (reference stereo_utils.py BNAttention :91-188, the hot path of StereoDiffusion's Standard mode): one fused
+ * flash-style forward attention, float32 in and out, float32 accumulation on the f32-input MFMA; no score matrix is written,
+ * there is no workspace, nothing is allocated, everything runs on the caller's stream.
+ *   q [(c s b h)][n][d], k and v [(c s b h)][n_k][d], out [(c s b)][n][(h d)] -- c: CFG chunks (1 or 2), s: views (1 or 2),
+ *   b: samples, h: heads, n / n_k: query / key tokens per view; all contiguous float32, 16-byte aligned.
+ *   out = softmax(scale * q . k^T) . v over the keys `mode` selects for the query (c, s, b, h, i):
+ *     CS_ATTN_SELF  (c, s, b, h, 0..n_k-1): ordinary attention, n_k may differ from n (:137-140)
+ *     CS_ATTN_UNI   (c, 0, b, h, 0..n-1): both views see the left view's keys (:163-171)
+ *     CS_ATTN_BI    (c, 0, b, h, .) followed by (c, 1, b, h, .), 2 n keys (:156-162; the no-CFG path :142-146 with c = 1)
+ * CS_EINVAL: null or misaligned pointers, non-positive sizes, unknown mode, UNI / BI with s != 2 or n_k != n, out aliasing an
+ * input.  CS_ELIMIT: d not a multiple of 4 or above cs_stereo_attention_max_head_dim() (160), sizes beyond 32-bit grids.
+ * Forward only.
+ */
+enum cs_attn_mode { CS_ATTN_SELF = 0, CS_ATTN_UNI = 1, CS_ATTN_BI = 2 };
+CS_API int cs_stereo_attention_max_head_dim(void);
+CS_API int cs_stereo_attention(const float *q, const float *k, const float *v, float *out, int c, int s, int b, int h, int n,
+                        int n_k, int d, double scale, int mode, void *stream);
+
+/*
  * Measurement hook for bench.py: while enabled, cs_generate brackets the launch of its dominant
  * kernel (the row warp + fill kernel of the selected technique) with HIP events on the caller's
  * stream.  cs_profile_read waits for the recorded events, returns the summed kernel time in
@@ -398,7 +417,8 @@ enum cs_debug_key {
     CS_DEBUG_HYBRID_UNFUSED = 9,    /* hybrid_edge: splat result -> node outputs in a streaming pass of its own (k_hybrid_out4) */
     CS_DEBUG_GPUWARP_FULL_MAPS = 10, /* gpu_warp with the depth blur: complete blurred maps (k_blur_copy_tiles) instead of the tile map */
     CS_DEBUG_HYBRID_FULL_MAPS = 11, /* hybrid_edge with the depth blur: complete blurred maps instead of the tile map */
-    CS_DEBUG_KEYS = 12
+    CS_DEBUG_ATTN_WAVES = 12,       /* cs_stereo_attention: 1, 2 or 4 waves per workgroup instead of the launcher's choice (tile-size sweeps) */
+    CS_DEBUG_KEYS = 13
 };
 CS_API int cs_debug_set(int key, int value);
 
