@@ -32,6 +32,8 @@ GAUSS_OP = {"plain": 0, "edge_selective": 1, "left": 2, "right": 3}
 PIL_FLAG = {"in_f32": 1, "gray": 2, "out_planar": 4}
 # enum cs_attn_mode (the reference's stereo attention, cs_stereo_attention)
 ATTN_MODE = {"self": 0, "uni": 1, "bi": 2}
+# enum cs_attn_dtype (the element type of cs_stereo_attention_half)
+ATTN_DTYPE = {"float16": 0, "bfloat16": 1}
 
 # the ABI version the ctypes signatures below were written for (include/comfystereo_amd.h CS_ABI_VERSION)
 ABI_VERSION = 4
@@ -45,7 +47,7 @@ EXPORTS = [
     "cs_gaussian_blur_workspace_bytes", "cs_gaussian_blur_max_taps", "cs_gaussian_blur",
     "cs_inpaint_prepare_workspace_bytes", "cs_inpaint_prepare_max_width", "cs_inpaint_prepare",
     "cs_pil_resize_workspace_bytes", "cs_pil_resize_max_taps", "cs_pil_resize",
-    "cs_stereo_attention_max_head_dim", "cs_stereo_attention",
+    "cs_stereo_attention_max_head_dim", "cs_stereo_attention", "cs_stereo_attention_half",
 ]
 
 # enum cs_debug_key (development switches; tests and profiling tools only)
@@ -223,6 +225,8 @@ def lib():
     L.cs_stereo_attention_max_head_dim.argtypes = []
     L.cs_stereo_attention.restype = c_int
     L.cs_stereo_attention.argtypes = [vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_int, vp]
+    L.cs_stereo_attention_half.restype = c_int
+    L.cs_stereo_attention_half.argtypes = [vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_int, vp]
     _lib = L
     return L
 

@@ -1360,6 +1360,29 @@ int cs_stereo_attention(const float* q, const float* k, const float* v, float* o
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_stereo_attention");
 }
 
+int cs_stereo_attention_half(const void* q, const void* k, const void* v, void* out, int dtype, int c, int s, int b, int h, int n,
+                             int n_k, int d, double scale, int mode, void* stream) {
+    if (!q || !k || !v || !out) return fail(CS_EINVAL, "null pointer");
+    if (dtype != CS_ATTN_F16 && dtype != CS_ATTN_BF16) return fail(CS_EINVAL, "cs_stereo_attention_half: unknown dtype (CS_ATTN_F16, CS_ATTN_BF16)");
+    if (c <= 0 || s <= 0 || b <= 0 || h <= 0 || n <= 0 || n_k <= 0 || d <= 0) return fail(CS_EINVAL, "non-positive size");
+    if (mode < CS_ATTN_SELF || mode > CS_ATTN_BI) return fail(CS_EINVAL, "cs_stereo_attention_half: unknown mode (CS_ATTN_*)");
+    if (mode != CS_ATTN_SELF && (s != 2 || n_k != n))
+        return fail(CS_EINVAL, "cs_stereo_attention_half: CS_ATTN_UNI / CS_ATTN_BI take two views (s = 2) with n_k = n");
+    if (!(scale == scale) || scale - scale != 0.0) return fail(CS_EINVAL, "cs_stereo_attention_half: scale must be finite");
+    if ((d & 7) || d > stereo_attention_max_head_dim())
+        return fail(CS_ELIMIT, "cs_stereo_attention_half: head dimension must be a multiple of 8 up to cs_stereo_attention_max_head_dim()");
+    if (((uintptr_t)q & 15) || ((uintptr_t)k & 15) || ((uintptr_t)v & 15) || ((uintptr_t)out & 15))
+        return fail(CS_EINVAL, "cs_stereo_attention_half: q, k, v and out need 16-byte alignment");
+    const long long bhn = (long long)c * s * b * h;
+    if (n > (1 << 24) || n_k > (1 << 24) || bhn >= (1ll << 31) || bhn * ((n + 31) / 32) >= (1ll << 31))
+        return fail(CS_ELIMIT, "cs_stereo_attention_half: more than 2^24 tokens per view or 2^31 workgroups in one call");
+    const size_t q_bytes = (size_t)bhn * n * d * 2, k_bytes = (size_t)bhn * n_k * d * 2;
+    if (overlaps(out, q_bytes, q, q_bytes) || overlaps(out, q_bytes, k, k_bytes) || overlaps(out, q_bytes, v, k_bytes))
+        return fail(CS_EINVAL, "cs_stereo_attention_half: out must not overlap q, k or v");
+    hipError_t e = launch_stereo_attention_half(q, k, v, out, dtype, c, s, b, h, n, n_k, d, (float)scale, mode, (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_stereo_attention_half");
+}
+
 int cs_profile(int enable) {
     std::lock_guard<std::mutex> lock(g_prof_mu);
     g_prof_on.store(enable != 0);

@@ -1,0 +1,276 @@
+// cs_attention_half.hip -- cs_attention.hip's stereo attention with float16 / bfloat16 q, k, v and output, on the half-input MFMA
+// (v_mfma_f32_32x32x16_f16 / _bf16).  Same routing, index maps and decomposition as k_stereo_attention; scores, the online
+// softmax (running maximum, sum, rescale) and both accumulators are float32, only the MFMA operands (Q, K, V, and P after the
+// exponential) are half.  No score matrix, no workspace.
+//
+// One wave owns 32 queries; a workgroup of NW waves shares the 32-key K / V tiles in LDS.  Per tile a wave computes
+//   S^T = K . Q^T   lane (r, h) (r = l & 31, h = l >> 5) holds K[key r][d = 16 g + 8 h + j], j = 0..7, of k-step g (one
+//                   ds_read_b128) and the matching eight Q elements of its query in registers; d is zero-padded to a multiple
+//                   of 16.  The accumulator has the query on the lane and key sa_row(reg, h) in register reg, as in the
+//                   float32 kernel: the softmax reductions are in-lane plus one exchange with lane l ^ 32.
+//   O^T += V^T . P^T  registers 8 s .. 8 s + 7 of the S^T accumulator, converted to half, ARE the B fragment of k-step s
+//                   (s = 0, 1): element j stands for key sa_row(8 s + j, h) = 16 s + 8 (j >> 2) + 4 h + (j & 3).  The A fragment
+//                   is V of those eight keys at output column 32 blk + r: V is staged TRANSPOSED and key-permuted,
+//                   Vt[column][slot 16 s + 8 h + j], so that the fragment is one ds_read_b128.
+// LDS banking (16-byte slots, 16 per 256-byte bank row; ds_read_b128 is served in 16-lane groups {0-3, 12-15, 20-27},
+// {4-11, 16-19, 28-31} of either wave half, i.e. one h and 16 rows that are pairwise distinct mod 16):
+//   K rows are 32 ND + 8 halves = (4 ND + 1) slots apart, Vt rows 40 halves = 5 slots: an odd slot stride times 16 rows distinct
+//   mod 16 gives 16 distinct slots, every fragment read is conflict-free.
+//   The transposing V store is a ds_write_b32 of the pair (key 2 m, key 2 m + 1) -- adjacent slots -- per column: a wave half is
+//   16 pairs x two 8-column chunks; the 16 pairs fill 16 consecutive dwords of a Vt row, rows are 20 dwords apart, 8 rows are
+//   160 = 0 (mod 32) dwords apart, so the lanes of the odd chunk take their columns in the order i ^ 4 (4 rows = 80 = 16 mod 32):
+//   the two chunks land on disjoint halves of the 32 write banks.
+// The next tile's K / V are loaded into registers before this tile's products and stored to LDS after them.
+#include "cs_common.h"
+#include "cs_kernels.h"
+
+namespace cs {
+
+enum { SAH_KT = 32, SAH_SVT = SAH_KT + 8 };   // keys per tile; halves per row of the transposed V image (80 bytes)
+
+typedef float sah_acc __attribute__((ext_vector_type(16)));
+typedef _Float16 sah_f16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 sah_bf16x8 __attribute__((ext_vector_type(8)));
+
+template <typename T> struct sah_frag;
+template <> struct sah_frag<_Float16> {
+    typedef sah_f16x8 type;
+    static __device__ __forceinline__ sah_acc mfma(type a, type b, sah_acc c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+};
+template <> struct sah_frag<__bf16> {
+    typedef sah_bf16x8 type;
+    static __device__ __forceinline__ sah_acc mfma(type a, type b, sah_acc c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+};
+
+// accumulator register r of lane half hi <-> row of the 32 x 32 tile (cs_attention.hip sa_row)
+__device__ __forceinline__ int sah_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
+// key of a tile -> its position in a row of the transposed V image: the inverse of sah_row(8 s + j, h) -> 16 s + 8 h + j
+__device__ __forceinline__ int sah_slot(int key) { return (key & 16) + 8 * ((key >> 2) & 1) + 4 * ((key >> 3) & 1) + (key & 3); }
+
+// half element i (0..7) of a 16-byte chunk
+__device__ __forceinline__ unsigned sah_elem(const uint4& c, int i) {
+    const unsigned w = (i >> 1) == 0 ? c.x : (i >> 1) == 1 ? c.y : (i >> 1) == 2 ? c.z : c.w;
+    return (i & 1) ? (w >> 16) : (w & 0xffffu);
+}
+
+template <typename T, int ND, int NW>
+__global__ void __launch_bounds__(NW * 64) k_stereo_attention_half(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v,
+                                                                   T* __restrict__ out, int S, int B, int H, int n, int n_k, int d,
+                                                                   float scale, int mode, int qtiles) {
+    typedef typename sah_frag<T>::type frag;
+    constexpr int SK = ND * 32 + 8, NT = NW * 64;
+    constexpr int KI = (SAH_KT * ND * 4 + NT - 1) / NT;         // 16-byte K chunks of a tile per thread
+    constexpr int VI = (SAH_KT / 2 * ND * 4 + NT - 1) / NT;     // (key pair, 8-column chunk) tasks of a V tile per thread
+    __shared__ __attribute__((aligned(16))) T Ks[SAH_KT * SK];
+    __shared__ __attribute__((aligned(16))) T Vt[ND * 32 * SAH_SVT];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, hi = lane >> 5;
+    const int bh = blockIdx.x / qtiles, qt = blockIdx.x - bh * qtiles;
+    // (c s b h) -> the key set: view 0 of the same (c, b, h) for UNI / BI, followed by view 1 for BI
+    const int hh = bh % H, sb = bh / H, s = (sb / B) % S;
+    const size_t kset = mode == CS_ATTN_SELF ? (size_t)bh : (size_t)bh - (size_t)s * B * H;
+    const int nkeys = mode == CS_ATTN_BI ? 2 * n_k : n_k;
+    const size_t view_rows = (size_t)(B * H - 1) * n_k;   // BI: rows between the end of view 0's keys and the start of view 1's
+    const T* kb = k + kset * n_k * d;
+    const T* vb = v + kset * n_k * d;
+    const int d8 = d >> 3;
+
+    // K's pad columns (d .. SK) are multiplied by Q's zero pad, Vt's rows past d feed output columns nobody stores, keys past
+    // the set are multiplied by p = 0: all of them must be finite
+    for (int i = tid; i < SAH_KT * SK / 2; i += NT) ((unsigned*)Ks)[i] = 0u;
+    for (int i = tid; i < ND * 32 * SAH_SVT / 2; i += NT) ((unsigned*)Vt)[i] = 0u;
+
+    // Q fragment: query `col` of this wave, d = 16 g + 8 hi .. + 7 in qf[g]; zero past d and past n
+    const int qi = (qt * NW + wave) * 32 + col;
+    const bool q_ok = qi < n;
+    const T* qrow = q + ((size_t)bh * n + (q_ok ? qi : 0)) * d;
+    frag qf[ND * 2];
+#pragma unroll
+    for (int g = 0; g < ND * 2; g++) {
+        const int c0 = 16 * g + 8 * hi;
+        uint4 raw = make_uint4(0u, 0u, 0u, 0u);
+        if (q_ok && c0 < d) raw = *(const uint4*)(qrow + c0);
+        qf[g] = __builtin_bit_cast(frag, raw);
+    }
+
+    sah_acc o[ND];
+#pragma unroll
+    for (int b = 0; b < ND; b++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) o[b][r] = 0.0f;
+    float m_run = -INFINITY, l_run = 0.0f;
+    const float sc2 = scale * 1.44269504088896340736f;   // scores in units of log2: p = exp2(s - m)
+
+    // a tile's K and V in registers: K chunk e = (row e / d8, 8 columns e % d8); V task e = (key pair e & 15, 8 columns e >> 4)
+    uint4 kr[KI], va[VI], vc[VI];
+    auto fetch = [&](int kt) {
+#pragma unroll
+        for (int it = 0; it < KI; it++) {
+            const int e = tid + it * NT;
+            const int row = e / d8, c8 = e - row * d8;
+            const int j = kt * SAH_KT + row;
+            kr[it] = make_uint4(0u, 0u, 0u, 0u);
+            if (row < SAH_KT && j < nkeys) kr[it] = *(const uint4*)(kb + ((size_t)j + (j >= n_k ? view_rows : 0)) * d + 8 * c8);
+        }
+#pragma unroll
+        for (int it = 0; it < VI; it++) {
+            const int e = tid + it * NT;
+            const int c8 = e >> 4, j = kt * SAH_KT + 2 * (e & 15);
+            va[it] = vc[it] = make_uint4(0u, 0u, 0u, 0u);
+            if (c8 < d8) {
+                if (j < nkeys) va[it] = *(const uint4*)(vb + ((size_t)j + (j >= n_k ? view_rows : 0)) * d + 8 * c8);
+                if (j + 1 < nkeys) vc[it] = *(const uint4*)(vb + ((size_t)(j + 1) + (j + 1 >= n_k ? view_rows : 0)) * d + 8 * c8);
+            }
+        }
+    };
+    auto stage = [&]() {
+#pragma unroll
+        for (int it = 0; it < KI; it++) {
+            const int e = tid + it * NT;
+            const int row = e / d8, c8 = e - row * d8;
+            if (row < SAH_KT) *(uint4*)(Ks + row * SK + 8 * c8) = kr[it];
+        }
+#pragma unroll
+        for (int it = 0; it < VI; it++) {
+            const int e = tid + it * NT;
+            const int c8 = e >> 4, slot = sah_slot(2 * (e & 15));
+            const bool odd = c8 & 1;
+            if (c8 < d8) {
+#pragma unroll
+                for (int i = 0; i < 8; i++) {
+                    const unsigned lo = odd ? sah_elem(va[it], i ^ 4) : sah_elem(va[it], i);
+                    const unsigned up = odd ? sah_elem(vc[it], i ^ 4) : sah_elem(vc[it], i);
+                    const int c = 8 * c8 + (odd ? (i ^ 4) : i);
+                    *(unsigned*)(Vt + c * SAH_SVT + slot) = lo | (up << 16);
+                }
+            }
+        }
+    };
+
+    const int ntiles = (nkeys + SAH_KT - 1) / SAH_KT;
+    fetch(0);
+    for (int kt = 0; kt < ntiles; kt++) {
+        __syncthreads();   // the previous tile's readers (first pass: the zero fill) are done
+        stage();
+        __syncthreads();
+        if (kt + 1 < ntiles) fetch(kt + 1);
+
+        // S^T = K . Q^T
+        sah_acc st;
+#pragma unroll
+        for (int r = 0; r < 16; r++) st[r] = 0.0f;
+#pragma unroll
+        for (int g = 0; g < ND * 2; g++) {
+            if (16 * g < d) {
+                const frag kf = *(const frag*)(Ks + col * SK + 16 * g + 8 * hi);
+                st = sah_frag<T>::mfma(kf, qf[g], st);
+            }
+        }
+        // keys past the set: -inf BEFORE the running maximum is updated (tile 0 always holds key 0, so the maximum is
+        // finite from the first tile on and exp2(-inf - m) = 0 is the only form -inf takes)
+        const int key0 = kt * SAH_KT;
+        const bool tail = key0 + SAH_KT > nkeys;
+        float m_tile = -INFINITY;
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            float sv = st[r] * sc2;
+            if (tail && key0 + sah_row(r, hi) >= nkeys) sv = -INFINITY;
+            st[r] = sv;
+            m_tile = fmaxf(m_tile, sv);
+        }
+        m_tile = fmaxf(m_tile, __shfl_xor(m_tile, 32));
+        const float m_new = fmaxf(m_run, m_tile);
+        const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);   // first tile: exp2(-inf) = 0
+        m_run = m_new;
+        float psum = 0.0f;
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            st[r] = __builtin_amdgcn_exp2f(st[r] - m_new);
+            psum += st[r];
+        }
+        l_run = l_run * alpha + psum;   // this lane half's 16 keys; the halves are added after the last tile
+#pragma unroll
+        for (int b = 0; b < ND; b++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) o[b][r] *= alpha;
+
+        // O^T += V^T . P^T
+#pragma unroll
+        for (int ks = 0; ks < 2; ks++) {
+            frag pf;
+#pragma unroll
+            for (int j = 0; j < 8; j++) pf[j] = (T)st[8 * ks + j];
+#pragma unroll
+            for (int b = 0; b < ND; b++) {
+                const frag vf = *(const frag*)(Vt + (b * 32 + col) * SAH_SVT + 16 * ks + 8 * hi);
+                o[b] = sah_frag<T>::mfma(vf, pf, o[b]);
+            }
+        }
+    }
+
+    const float l_all = l_run + __shfl_xor(l_run, 32);
+    if (!q_ok) return;
+    // out [(c s b)][n][(h d)]: lane (query, hi) holds columns 32 blk + 8 g + 4 hi .. + 3 in registers 4 g .. 4 g + 3
+    T* orow = out + ((size_t)sb * n + qi) * ((size_t)H * d) + (size_t)hh * d;
+#pragma unroll
+    for (int b = 0; b < ND; b++) {
+#pragma unroll
+        for (int g = 0; g < 4; g++) {
+            const int c0 = b * 32 + 8 * g + 4 * hi;
+            if (c0 < d) {
+                typedef T t4 __attribute__((ext_vector_type(4)));
+                t4 r4;
+#pragma unroll
+                for (int j = 0; j < 4; j++) r4[j] = (T)(o[b][4 * g + j] / l_all);
+                *(t4*)(orow + c0) = r4;
+            }
+        }
+    }
+}
+
+template <typename T, int ND>
+static hipError_t sah_launch(int nw, int blocks, const T* q, const T* k, const T* v, T* out, int S, int B, int H, int n, int n_k, int d,
+                             float scale, int mode, int qtiles, hipStream_t stream) {
+    if (nw == 4)
+        hipLaunchKernelGGL((k_stereo_attention_half<T, ND, 4>), dim3(blocks), dim3(256), 0, stream, q, k, v, out, S, B, H, n, n_k, d, scale, mode, qtiles);
+    else if (nw == 2)
+        hipLaunchKernelGGL((k_stereo_attention_half<T, ND, 2>), dim3(blocks), dim3(128), 0, stream, q, k, v, out, S, B, H, n, n_k, d, scale, mode, qtiles);
+    else
+        hipLaunchKernelGGL((k_stereo_attention_half<T, ND, 1>), dim3(blocks), dim3(64), 0, stream, q, k, v, out, S, B, H, n, n_k, d, scale, mode, qtiles);
+    return hipGetLastError();
+}
+
+// Waves per workgroup: 4, as in the float32 kernel, until tools/attention_bench.py --dtype ... --sweep says otherwise; 1 and 2
+// stay selectable with CS_DEBUG_ATTN_WAVES.
+int stereo_attention_half_waves(long long batch_heads, int n) {
+    (void)batch_heads; (void)n;
+    const int forced = dev_switch(CS_DEBUG_ATTN_WAVES);
+    return (forced == 1 || forced == 2) ? forced : 4;
+}
+
+template <typename T>
+static hipError_t sah_dispatch(const void* q, const void* k, const void* v, void* out, int c, int s, int b, int h, int n, int n_k, int d,
+                               float scale, int mode, hipStream_t stream) {
+    const long long bhn = (long long)c * s * b * h;
+    const int nw = stereo_attention_half_waves(bhn, n);
+    const int qtiles = (n + 32 * nw - 1) / (32 * nw);
+    const int blocks = (int)(bhn * qtiles);
+    const T *tq = (const T*)q, *tk = (const T*)k, *tv = (const T*)v;
+    T* to = (T*)out;
+    switch ((d + 31) / 32) {
+    case 1: return sah_launch<T, 1>(nw, blocks, tq, tk, tv, to, s, b, h, n, n_k, d, scale, mode, qtiles, stream);
+    case 2: return sah_launch<T, 2>(nw, blocks, tq, tk, tv, to, s, b, h, n, n_k, d, scale, mode, qtiles, stream);
+    case 3: return sah_launch<T, 3>(nw, blocks, tq, tk, tv, to, s, b, h, n, n_k, d, scale, mode, qtiles, stream);
+    case 4: return sah_launch<T, 4>(nw, blocks, tq, tk, tv, to, s, b, h, n, n_k, d, scale, mode, qtiles, stream);
+    case 5: return sah_launch<T, 5>(nw, blocks, tq, tk, tv, to, s, b, h, n, n_k, d, scale, mode, qtiles, stream);
+    }
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_stereo_attention_half(const void* q, const void* k, const void* v, void* out, int dtype, int c, int s, int b, int h,
+                                        int n, int n_k, int d, float scale, int mode, hipStream_t stream) {
+    if (dtype == CS_ATTN_F16) return sah_dispatch<_Float16>(q, k, v, out, c, s, b, h, n, n_k, d, scale, mode, stream);
+    if (dtype == CS_ATTN_BF16) return sah_dispatch<__bf16>(q, k, v, out, c, s, b, h, n, n_k, d, scale, mode, stream);
+    return hipErrorInvalidValue;
+}
+
+}  // namespace cs

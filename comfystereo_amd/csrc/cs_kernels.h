@@ -193,6 +193,10 @@ int stereo_attention_max_head_dim();
 int stereo_attention_waves(long long batch_heads, int n);   // waves per workgroup the launcher picks (32 queries each)
 hipError_t launch_stereo_attention(const float* q, const float* k, const float* v, float* out, int c, int s, int b, int h, int n,
                                    int n_k, int d, float scale, int mode, hipStream_t stream);
+// cs_attention_half.hip (the same attention on float16 / bfloat16 tensors: cs_stereo_attention_half).  dtype: enum cs_attn_dtype
+int stereo_attention_half_waves(long long batch_heads, int n);
+hipError_t launch_stereo_attention_half(const void* q, const void* k, const void* v, void* out, int dtype, int c, int s, int b, int h,
+                                        int n, int n_k, int d, float scale, int mode, hipStream_t stream);
 // lazy depth-blur tiles in k_gpuwarp (tilemap != nullptr): rows of at most this many columns, not the mesh-quality warp
 int gpuwarp_lazy_max_width();
 

@@ -481,8 +481,10 @@ def stereo_attention(q, k, v, heads, scale, mode, chunks=1, out=None):
     softmax(scale * q k^T) v over the keys `mode` selects, in one fused kernel (no score matrix is ever written).
     mode: "self" (every batch entry sees its own keys; n_k may differ from n), "uni" (both views see the left view's keys) or
     "bi" (both views see both views' keys); "uni" / "bi" take two views (s = 2) and `chunks` = c CFG chunks, "self" takes
-    the batch as it is.  heads = h.  out: an optional float32 destination of the result's shape.
-    d must be a multiple of 4 up to cs_stereo_attention_max_head_dim(): ValueError before anything is launched."""
+    the batch as it is.  heads = h.  out: an optional destination of the result's shape and the inputs' dtype.
+    d must be a multiple of 4 up to cs_stereo_attention_max_head_dim(): ValueError before anything is launched.
+    q, k, v all float16 or all bfloat16 go to cs_stereo_attention_half (half matrix operands, float32 scores, softmax and
+    accumulators; the result has the inputs' dtype); there d must be a multiple of 8.  Mixed dtypes are a ValueError."""
     if mode not in _native.ATTN_MODE:
         raise ValueError(f"unknown attention mode {mode!r} (self, uni, bi)")
     for name, t in (("q", q), ("k", k), ("v", v)):
@@ -490,12 +492,15 @@ def stereo_attention(q, k, v, heads, scale, mode, chunks=1, out=None):
             raise ValueError(f"{name} must be a torch.Tensor")
         if t.dim() != 3:
             raise ValueError(f"{name} must be [(c s b h), tokens, d], got shape {tuple(t.shape)}")
-        if t.dtype != torch.float32:
-            raise ValueError(f"{name} must be float32, got {t.dtype}")
+        if t.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise ValueError(f"{name} must be float32, float16 or bfloat16, got {t.dtype}")
+        if t.dtype != q.dtype:
+            raise ValueError(f"q, k and v must share one dtype, got {q.dtype} and {t.dtype} ({name})")
         if not t.is_contiguous():
             raise ValueError(f"{name} must be contiguous")
         if t.requires_grad:
             raise ValueError(f"{name} requires grad: cs_stereo_attention is forward only")
+    half = q.dtype != torch.float32
     heads, chunks = int(heads), int(chunks)
     bh, n, d = q.shape
     if k.shape != v.shape or k.shape[0] != bh or k.shape[2] != d:
@@ -511,23 +516,29 @@ def stereo_attention(q, k, v, heads, scale, mode, chunks=1, out=None):
     if mode != "self" and n_k != n:
         raise ValueError(f"mode {mode!r} needs as many keys as queries per view, got {n_k} and {n}")
     d_max = _native.lib().cs_stereo_attention_max_head_dim()   # (host only: no device work)
-    if d % 4 or d > d_max:
-        raise ValueError(f"head dimension {d}: cs_stereo_attention takes multiples of 4 up to {d_max}")
+    if d % (8 if half else 4) or d > d_max:
+        raise ValueError(f"head dimension {d}: cs_stereo_attention takes multiples of 4 (float16 / bfloat16: of 8) up to {d_max}")
     if not math.isfinite(float(scale)):
         raise ValueError(f"scale must be finite, got {scale}")
     samples = bh // (heads * views * chunks)
     shape = (bh // heads, n, heads * d)
     if out is not None:
-        if (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous()
+        if (not isinstance(out, torch.Tensor) or out.dtype != q.dtype or tuple(out.shape) != shape or not out.is_contiguous()
                 or out.device != q.device):
-            raise ValueError(f"out must be a contiguous float32 tensor {shape} on {q.device}")
+            raise ValueError(f"out must be a contiguous {q.dtype} tensor {shape} on {q.device}")
     _dev(q)
     if k.device != q.device or v.device != q.device:
         raise ValueError("q, k and v must be on the same device")
     L = _native.lib()
     if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=q.device)
+        out = torch.empty(shape, dtype=q.dtype, device=q.device)
     with torch.cuda.device(q.device):
+        if half:
+            _native.check(L.cs_stereo_attention_half(_ptr(q), _ptr(k), _ptr(v), _ptr(out),
+                                                     _native.ATTN_DTYPE["float16" if q.dtype == torch.float16 else "bfloat16"],
+                                                     chunks, views, samples, heads, n, n_k, d, float(scale),
+                                                     _native.ATTN_MODE[mode], _stream()))
+            return out
         _native.check(L.cs_stereo_attention(_ptr(q), _ptr(k), _ptr(v), _ptr(out), chunks, views, samples, heads, n, n_k, d,
                                             float(scale), _native.ATTN_MODE[mode], _stream()))
     return out

@@ -8,6 +8,13 @@ StereoDiffusion's Standard mode: the same classes, names, signatures and step bo
 HIP kernel behind the C ABI (cs_stereo_attention) that never materialises the score matrix -- the reference builds
 `sim` and `softmax(sim)` twice per layer, [heads, 2n, 2n] float32 the second time.
 
+float16 / bfloat16 q, k, v: by default they are upcast to float32, run through the float32 kernel and the result is cast back
+(three conversion passes in, one out, at the f32-input MFMA's rate).  `HALF_ATTENTION = True` (a module switch, like
+engine.MESH_WARP / engine.DIALECT) sends them to cs_stereo_attention_half instead, with no conversion pass: the matrix
+operands (q, k, v, and the probabilities after the exponential) stay half on the half-input MFMA, the scores, the softmax and
+the accumulators are float32 -- the reference's own arithmetic in that dtype rounds more, not less.  float32 inputs take the
+float32 kernel either way.
+
 No CPU fallback anywhere: without a GPU the calls raise RuntimeError."""
 import torch
 import torch.nn as nn
@@ -32,6 +39,10 @@ def stereo_shift_torch(input_images: torch.Tensor, depthmaps: torch.Tensor, scal
     return out if input_images.is_cuda else out.to(input_images.device)
 
 
+# float16 / bfloat16 q, k, v of BNAttention: False = upcast, float32 kernel, cast back; True = cs_stereo_attention_half
+HALF_ATTENTION = False
+
+
 def _need_gpu():
     if not torch.cuda.is_available():
         raise RuntimeError("comfystereo_amd needs an MI355X (PyTorch-ROCm `cuda` device); there is no CPU fallback")
@@ -41,7 +52,9 @@ def _attention(q, k, v, num_heads, scale, mode, chunks=1):
     """engine.stereo_attention on q, k, v as the reference holds them ([(c s b h), n, d]).  float16 / bfloat16 inputs are upcast
     to float32 and the result is cast back: the products, the softmax and the sums are float32 throughout, which is MORE
     accurate than the reference's arithmetic in the tensors' own half precision (its result differs by half-precision
-    rounding errors; only float32, the Standard pipeline's dtype -- reference model_loader.py:63-65 -- is pinned)."""
+    rounding errors; only float32, the Standard pipeline's dtype -- reference model_loader.py:63-65 -- is pinned).
+    With HALF_ATTENTION set, float16 / bfloat16 q, k, v of one dtype go to the half kernel as they are (a head dimension that
+    is no multiple of 8, which that kernel does not take, keeps the upcast)."""
     _need_gpu()
     for name, t in (("q", q), ("k", k), ("v", v)):
         if not isinstance(t, torch.Tensor) or not t.is_floating_point():
@@ -52,6 +65,10 @@ def _attention(q, k, v, num_heads, scale, mode, chunks=1):
     if scale is None:
         raise ValueError("BNAttention needs the keyword argument scale")
     dev = q.device if q.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    if HALF_ATTENTION and q.dtype in (torch.float16, torch.bfloat16) and k.dtype == q.dtype and v.dtype == q.dtype and q.shape[-1] % 8 == 0:
+        qh, kh, vh = (t.detach().to(dev).contiguous() for t in (q, k, v))
+        out = engine.stereo_attention(qh, kh, vh, num_heads, float(scale), mode, chunks)
+        return out if q.is_cuda else out.to(q.device)
     q32, k32, v32 = (t.detach().to(dev, torch.float32).contiguous() for t in (q, k, v))
     out = engine.stereo_attention(q32, k32, v32, num_heads, float(scale), mode, chunks).to(q.dtype)
     return out if q.is_cuda else out.to(q.device)

@@ -387,6 +387,18 @@ CS_API int cs_stereo_attention(const float *q, const float *k, const float *v, f
                         int n_k, int d, double scale, int mode, void *stream);
 
 /*
+ * The same attention on float16 or bfloat16 tensors (the dtypes diffusion pipelines run in), on the half-input MFMA: q, k, v
+ * and out are all `dtype` (enum cs_attn_dtype), in cs_stereo_attention's layouts and with its modes.  The scores, the online
+ * softmax and both accumulators are float32; only the matrix operands (q, k, v, and the probabilities after the exponential)
+ * are half; the final division is float32 and the store rounds to nearest-even.  No score matrix, no workspace, the caller's
+ * stream.  Refusals are cs_stereo_attention's, and nothing is written on a refusal; in addition CS_EINVAL: unknown dtype;
+ * CS_ELIMIT: d not a multiple of 8 (every row 16-byte aligned).  Forward only.
+ */
+enum cs_attn_dtype { CS_ATTN_F16 = 0, CS_ATTN_BF16 = 1 };
+CS_API int cs_stereo_attention_half(const void *q, const void *k, const void *v, void *out, int dtype, int c, int s, int b, int h,
+                             int n, int n_k, int d, double scale, int mode, void *stream);
+
+/*
  * Measurement hook for bench.py: while enabled, cs_generate brackets the launch of its dominant
  * kernel (the row warp + fill kernel of the selected technique) with HIP events on the caller's
  * stream.  cs_profile_read waits for the recorded events, returns the summed kernel time in
@@ -417,7 +429,7 @@ enum cs_debug_key {
     CS_DEBUG_HYBRID_UNFUSED = 9,    /* hybrid_edge: splat result -> node outputs in a streaming pass of its own (k_hybrid_out4) */
     CS_DEBUG_GPUWARP_FULL_MAPS = 10, /* gpu_warp with the depth blur: complete blurred maps (k_blur_copy_tiles) instead of the tile map */
     CS_DEBUG_HYBRID_FULL_MAPS = 11, /* hybrid_edge with the depth blur: complete blurred maps instead of the tile map */
-    CS_DEBUG_ATTN_WAVES = 12,       /* cs_stereo_attention: 1, 2 or 4 waves per workgroup instead of the launcher's choice (tile-size sweeps) */
+    CS_DEBUG_ATTN_WAVES = 12,       /* cs_stereo_attention, cs_stereo_attention_half: 1, 2 or 4 waves per workgroup instead of the launcher's choice (tile-size sweeps) */
     CS_DEBUG_KEYS = 13
 };
 CS_API int cs_debug_set(int key, int value);

@@ -5,9 +5,13 @@
 F.scaled_dot_product_attention in float32 on the rearranged tensors.  Prints one JSON line per level and direction; TFLOP/s
 counts 4 * queries * keys * d per head (the two products), against the 157 TFLOP/s f32-matrix peak.
 
-  python tools/attention_bench.py [--iters 20] [--warmup 3] [--sweep]
+  python tools/attention_bench.py [--iters 20] [--warmup 3] [--sweep] [--dtype f16|bf16]
 --sweep: the kernel alone with 1, 2 and 4 waves per workgroup forced (development switch attn_waves) next to the launcher's
-choice: the measurement behind stereo_attention_waves() in cs_attention.hip.
+choice: the measurement behind stereo_attention_waves() in cs_attention.hip (with --dtype: stereo_attention_half_waves()).
+--dtype f16|bf16: cs_stereo_attention_half on random float16 / bfloat16 operands next to (a) the upcast path for the same
+inputs (three casts to float32, the float32 kernel, one cast back: stereo_utils.HALF_ATTENTION = False) and (b)
+F.scaled_dot_product_attention in that dtype on the routed keys.  The three are timed alternately, round by round, in one
+process; the medians and the ratio to the upcast path are printed per level and direction.  TFLOP/s as above.
 """
 import argparse
 import json
@@ -71,18 +75,61 @@ def timed(fn, iters, warmup):
     return ms[len(ms) // 2], ms[0]
 
 
+def timed_alternately(fns, iters, warmup):
+    """{name: fn} -> {name: (median ms, min ms)}; one call of each per round, so that clock and cache state drift alike."""
+    for _ in range(warmup):
+        for fn in fns.values():
+            fn()
+    torch.cuda.synchronize()
+    ms = {name: [] for name in fns}
+    for _ in range(iters):
+        for name, fn in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            ms[name].append(a.elapsed_time(b))
+    return {name: (sorted(t)[len(t) // 2], min(t)) for name, t in ms.items()}
+
+
+def half_rows(dtype, iters, warmup):
+    dt = {"f16": torch.float16, "bf16": torch.bfloat16}[dtype]
+    for level, n, d, heads in LEVELS:
+        bh = 2 * 2 * heads
+        q, k, v = (torch.randn(bh, n, d, device="cuda").to(dt) for _ in range(3))
+        scale = d ** -0.5
+        for mode in ("uni", "bi"):
+            upcast = lambda: engine.stereo_attention(q.float(), k.float(), v.float(), heads, scale, mode, chunks=2).to(dt)  # noqa: E731
+            got = engine.stereo_attention(q, k, v, heads, scale, mode, chunks=2)
+            err = float((got.float() - upcast().float()).abs().max())
+            t = timed_alternately({"kernel": lambda: engine.stereo_attention(q, k, v, heads, scale, mode, chunks=2),
+                                   "upcast": upcast, "sdpa": lambda: sdpa(q, k, v, mode, heads, scale)}, iters, warmup)
+            flop = 4.0 * bh * n * (2 * n if mode == "bi" else n) * d
+            print(json.dumps(dict(dtype=dtype, level=level, n=n, d=d, heads=heads, mode=mode, kernel_ms=round(t["kernel"][0], 4),
+                                  kernel_min_ms=round(t["kernel"][1], 4), upcast_ms=round(t["upcast"][0], 4),
+                                  sdpa_ms=round(t["sdpa"][0], 4), kernel_tflops=round(flop / t["kernel"][0] / 1e9, 2),
+                                  speedup_vs_upcast=round(t["upcast"][0] / t["kernel"][0], 2),
+                                  speedup_vs_sdpa=round(t["sdpa"][0] / t["kernel"][0], 2), max_abs_diff_vs_upcast=err)), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--sweep", action="store_true")
+    ap.add_argument("--dtype", choices=("f32", "f16", "bf16"), default="f32")
     args = ap.parse_args()
     torch.manual_seed(0)
+    if args.dtype != "f32" and not args.sweep:
+        half_rows(args.dtype, args.iters, args.warmup)
+        return
     if args.sweep:
+        dt = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}[args.dtype]
         for level, n, d, heads in LEVELS:
-            q, k, v = (torch.randn(4 * heads, n, d, device="cuda") for _ in range(3))
+            q, k, v = (torch.randn(4 * heads, n, d, device="cuda").to(dt) for _ in range(3))
             for mode in ("uni", "bi"):
-                row = dict(level=level, n=n, d=d, mode=mode)
+                row = dict(dtype=args.dtype, level=level, n=n, d=d, mode=mode)
                 for waves in (0, 1, 2, 4):
                     _native.debug_set("attn_waves", waves)
                     try:
