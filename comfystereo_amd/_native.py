@@ -48,6 +48,7 @@ EXPORTS = [
     "cs_inpaint_prepare_workspace_bytes", "cs_inpaint_prepare_max_width", "cs_inpaint_prepare",
     "cs_pil_resize_workspace_bytes", "cs_pil_resize_max_taps", "cs_pil_resize",
     "cs_stereo_attention_max_head_dim", "cs_stereo_attention", "cs_stereo_attention_half",
+    "cs_attention_fwd_lse", "cs_attention_bwd_workspace_bytes", "cs_attention_bwd",
 ]
 
 # enum cs_debug_key (development switches; tests and profiling tools only)
@@ -227,6 +228,12 @@ def lib():
     L.cs_stereo_attention.argtypes = [vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_int, vp]
     L.cs_stereo_attention_half.restype = c_int
     L.cs_stereo_attention_half.argtypes = [vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_int, vp]
+    L.cs_attention_fwd_lse.restype = c_int
+    L.cs_attention_fwd_lse.argtypes = [vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_double, vp]
+    L.cs_attention_bwd_workspace_bytes.restype = c_size
+    L.cs_attention_bwd_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int]
+    L.cs_attention_bwd.restype = c_int
+    L.cs_attention_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_double, vp, c_size, vp]
     _lib = L
     return L
 

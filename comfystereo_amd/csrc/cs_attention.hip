@@ -32,10 +32,13 @@ typedef float sa_f16 __attribute__((ext_vector_type(16)));
 // accumulator register r of lane half hi <-> row of the 32 x 32 tile
 __device__ __forceinline__ int sa_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
 
-template <int ND, int NW>
+// LSE (cs_attention_fwd_lse, the forward of the differentiable attention): besides `out`, the log-sum-exp of every query's scaled
+// scores goes to lse [(c s b h)][n], in log2 units like sc2: p(i, j) = exp2(sc2 * s(i, j) - lse(i)).  Nothing else differs.
+template <int ND, int NW, bool LSE = false>
 __global__ void __launch_bounds__(NW * 64) k_stereo_attention(const float* __restrict__ q, const float* __restrict__ k,
                                                               const float* __restrict__ v, float* __restrict__ out, int S, int B,
-                                                              int H, int n, int n_k, int d, float scale, int mode, int qtiles) {
+                                                              int H, int n, int n_k, int d, float scale, int mode, int qtiles,
+                                                              float* __restrict__ lse = nullptr) {
     constexpr int SK = ND * 32 + 4, SV = ND * 32, NT = NW * 64;
     __shared__ __attribute__((aligned(16))) float Ks[SA_KT * SK];
     __shared__ __attribute__((aligned(16))) float Vs[SA_KT * SV];
@@ -145,6 +148,7 @@ __global__ void __launch_bounds__(NW * 64) k_stereo_attention(const float* __res
 
     const float l_all = l_run + __shfl_xor(l_run, 32);
     if (!q_ok) return;
+    if (LSE && hi == 0) lse[(size_t)bh * n + qi] = m_run + __builtin_amdgcn_logf(l_all);   // (v_log_f32 is log2; l_all >= 1)
     // out [(c s b)][n][(h d)]: lane (query, hi) holds columns 32 blk + 8 g + 4 hi .. + 3 in registers 4 g .. 4 g + 3
     float* orow = out + ((size_t)sb * n + qi) * ((size_t)H * d) + (size_t)hh * d;
 #pragma unroll
@@ -174,6 +178,18 @@ static hipError_t sa_launch(int nw, int blocks, const float* q, const float* k, 
 // Waves per workgroup, by measurement on the four SD 1.5 levels (tools/attention_bench.py --sweep): 4 everywhere.
 // A wave's share of the cooperative K / V tile load, not its MFMAs, bounds the tile loop, so four waves per tile win even where
 // they leave CUs idle (n = 256: 64 workgroups) or have no query of their own (n = 64).  1 and 2 stay selectable for sweeps.
+template <int ND>
+static hipError_t sa_launch_lse(int nw, int blocks, const float* q, const float* k, const float* v, float* out, float* lse, int B, int H,
+                                int n, int n_k, int d, float scale, int qtiles, hipStream_t stream) {
+    if (nw == 4)
+        hipLaunchKernelGGL((k_stereo_attention<ND, 4, true>), dim3(blocks), dim3(256), 0, stream, q, k, v, out, 1, B, H, n, n_k, d, scale, (int)CS_ATTN_SELF, qtiles, lse);
+    else if (nw == 2)
+        hipLaunchKernelGGL((k_stereo_attention<ND, 2, true>), dim3(blocks), dim3(128), 0, stream, q, k, v, out, 1, B, H, n, n_k, d, scale, (int)CS_ATTN_SELF, qtiles, lse);
+    else
+        hipLaunchKernelGGL((k_stereo_attention<ND, 1, true>), dim3(blocks), dim3(64), 0, stream, q, k, v, out, 1, B, H, n, n_k, d, scale, (int)CS_ATTN_SELF, qtiles, lse);
+    return hipGetLastError();
+}
+
 int stereo_attention_waves(long long batch_heads, int n) {
     (void)batch_heads; (void)n;
     const int forced = dev_switch(CS_DEBUG_ATTN_WAVES);
@@ -192,6 +208,23 @@ hipError_t launch_stereo_attention(const float* q, const float* k, const float* 
     case 3: return sa_launch<3>(nw, blocks, q, k, v, out, s, b, h, n, n_k, d, scale, mode, qtiles, stream);
     case 4: return sa_launch<4>(nw, blocks, q, k, v, out, s, b, h, n, n_k, d, scale, mode, qtiles, stream);
     case 5: return sa_launch<5>(nw, blocks, q, k, v, out, s, b, h, n, n_k, d, scale, mode, qtiles, stream);
+    }
+    return hipErrorInvalidValue;
+}
+
+// the same launch as launch_stereo_attention(..., CS_ATTN_SELF) with c = s = 1: `out` is bit for bit that call's
+hipError_t launch_attention_fwd_lse(const float* q, const float* k, const float* v, float* out, float* lse, int b, int h, int n, int n_k,
+                                    int d, float scale, hipStream_t stream) {
+    const long long bhn = (long long)b * h;
+    const int nw = stereo_attention_waves(bhn, n);
+    const int qtiles = (n + 32 * nw - 1) / (32 * nw);
+    const int blocks = (int)(bhn * qtiles);
+    switch ((d + 31) / 32) {
+    case 1: return sa_launch_lse<1>(nw, blocks, q, k, v, out, lse, b, h, n, n_k, d, scale, qtiles, stream);
+    case 2: return sa_launch_lse<2>(nw, blocks, q, k, v, out, lse, b, h, n, n_k, d, scale, qtiles, stream);
+    case 3: return sa_launch_lse<3>(nw, blocks, q, k, v, out, lse, b, h, n, n_k, d, scale, qtiles, stream);
+    case 4: return sa_launch_lse<4>(nw, blocks, q, k, v, out, lse, b, h, n, n_k, d, scale, qtiles, stream);
+    case 5: return sa_launch_lse<5>(nw, blocks, q, k, v, out, lse, b, h, n, n_k, d, scale, qtiles, stream);
     }
     return hipErrorInvalidValue;
 }

@@ -1,0 +1,90 @@
+"""Drop-in for the attention hook of the reference's diffusion_utils.py.
+
+`register_attention_control(model, controller)` (reference diffusion_utils.py:158-292; its one caller is NullInversion.invert,
+inversion.py:216, with controller = None): the same UNet lookup, the same walk over the modules whose class is named
+`CrossAttention`, the same `place_in_unet` names and layer count.  The forward it installs computes q, k, v with the module's own
+linear layers and runs the attention in the fused HIP kernels: under autograd (null-text optimisation differentiates through
+every layer, inversion.py:184-212) through engine.differentiable_attention, whose backward recomputes the probabilities from one
+saved float per query instead of keeping [(b h), n, n_k] of them; without autograd through engine.stereo_attention.
+
+The reference hands a controller the [(b h), n, n_k] probabilities, which the fused kernels never form: a controller other than
+None is refused with TypeError, an attention mask with ValueError (Stable Diffusion's UNet passes neither).
+
+The replaced forwards are saved the way stereo_utils.register_attention_editor_diffusers saves them: stereo_utils.restore_attention
+undoes this hook too, and an editor registered later stacks on top of it.
+
+No CPU fallback: without a GPU the installed forward raises RuntimeError."""
+import torch
+import torch.nn as nn
+
+from . import engine, stereo_utils
+
+
+def _attend(q, k, v, heads, scale):
+    """q [(b h), n, d], k and v [(b h), n_k, d] -> [(b), n, h * d] in q's dtype, on the fused kernels."""
+    stereo_utils._need_gpu()
+    dev = q.device if q.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+        out = engine.differentiable_attention(q.to(dev), k.to(dev), v.to(dev), heads, scale)
+    else:
+        q32, k32, v32 = (t.detach().to(dev, torch.float32).contiguous() for t in (q, k, v))
+        out = engine.stereo_attention(q32, k32, v32, heads, scale, "self").to(q.dtype)
+    return out if q.is_cuda else out.to(q.device)
+
+
+def register_attention_control(model, controller):
+    """Install the fused attention on every `CrossAttention` module of the model's UNet.  controller must be None (TypeError
+    otherwise, before the model is touched)."""
+    if controller is not None:
+        raise TypeError("register_attention_control: a controller receives the [(b h), n, n_k] attention probabilities, which the "
+                        "fused attention never forms; only controller=None (the reference's own use, inversion.py:216) is supported")
+    is_comfyui = hasattr(model, 'comfy_model')
+
+    def make_forward(net, place_in_unet):
+        scale = net.scale if hasattr(net, 'scale') else net.dim_head ** -0.5
+
+        def attention(x, context, value, mask):
+            if mask is not None:
+                raise ValueError("the fused attention takes no attention mask")
+            source = x if context is None else context
+            heads = net.heads
+
+            def split(t):   # [b, n, heads * d] -> [(b heads), n, d]
+                b, n, hd = t.shape
+                return t.reshape(b, n, heads, hd // heads).permute(0, 2, 1, 3).reshape(b * heads, n, hd // heads)
+
+            q, k = split(net.to_q(x)), split(net.to_k(source))
+            v = split(net.to_v(source if value is None else value))
+            project = net.to_out[0] if isinstance(net.to_out, nn.ModuleList) else net.to_out
+            return project(_attend(q, k, v, heads, float(scale)))
+
+        # the two call conventions differ in their third positional argument, as in the reference (:180, :220)
+        if is_comfyui:
+            def forward(x, context=None, value=None, mask=None, transformer_options=None, **kwargs):
+                return attention(x, context, value, mask)
+        else:
+            def forward(x, context=None, mask=None, value=None, transformer_options=None, **kwargs):
+                return attention(x, context, value, mask)
+        return forward
+
+    def walk(net, count, place_in_unet):
+        if net.__class__.__name__ == 'CrossAttention':
+            if not hasattr(net, stereo_utils._SAVED_FORWARD):
+                # an instance attribute shadows the class's forward: remember whether there was one
+                setattr(net, stereo_utils._SAVED_FORWARD, net.__dict__.get("forward"))
+            net.forward = make_forward(net, place_in_unet)
+            return count + 1
+        if hasattr(net, 'children'):
+            for child in net.children():
+                count = walk(child, count, place_in_unet)
+        return count
+
+    total = 0
+    for name, net in stereo_utils._get_unet(model).named_children():
+        if "down" in name or "input" in name:
+            total += walk(net, 0, "down")
+        elif "up" in name or "output" in name:
+            total += walk(net, 0, "up")
+        elif "mid" in name:
+            total += walk(net, 0, "mid")
+    return total

@@ -542,3 +542,100 @@ def stereo_attention(q, k, v, heads, scale, mode, chunks=1, out=None):
         _native.check(L.cs_stereo_attention(_ptr(q), _ptr(k), _ptr(v), _ptr(out), chunks, views, samples, heads, n, n_k, d,
                                             float(scale), _native.ATTN_MODE[mode], _stream()))
     return out
+
+
+# ---- the differentiable fused attention (cs_attention_fwd_lse / cs_attention_bwd) -------------------
+def _attention_grad_args(heads, scale, **tensors):
+    """The checks of stereo_attention for the float32 'self' form: q [(b h), n, d], k and v [(b h), n_k, d] and, where given,
+    out / d_out [(b), n, h * d] and lse [(b h), n].  ValueError before anything is launched.  -> (b, h, n, n_k, d)"""
+    for name, t in tensors.items():
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch.Tensor")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name} must be float32, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    q, k, v = tensors["q"], tensors["k"], tensors["v"]
+    for name in ("q", "k", "v"):
+        if tensors[name].dim() != 3:
+            raise ValueError(f"{name} must be [(b h), tokens, d], got shape {tuple(tensors[name].shape)}")
+    heads = int(heads)
+    bh, n, d = q.shape
+    if k.shape != v.shape or k.shape[0] != bh or k.shape[2] != d:
+        raise ValueError(f"q {tuple(q.shape)}, k {tuple(k.shape)} and v {tuple(v.shape)} do not match")
+    n_k = k.shape[1]
+    if bh == 0 or n == 0 or n_k == 0 or d == 0:
+        raise ValueError(f"empty attention: q {tuple(q.shape)}, k {tuple(k.shape)}")
+    if heads <= 0 or bh % heads:
+        raise ValueError(f"batch {bh} is not samples * heads = b * {heads}")
+    d_max = _native.lib().cs_stereo_attention_max_head_dim()   # (host only: no device work)
+    if d % 4 or d > d_max:
+        raise ValueError(f"head dimension {d}: the fused attention takes multiples of 4 up to {d_max}")
+    if not math.isfinite(float(scale)):
+        raise ValueError(f"scale must be finite, got {scale}")
+    for name, shape in (("out", (bh // heads, n, heads * d)), ("d_out", (bh // heads, n, heads * d)), ("lse", (bh, n))):
+        if name in tensors and tuple(tensors[name].shape) != shape:
+            raise ValueError(f"{name} must have shape {shape}, got {tuple(tensors[name].shape)}")
+    _dev(q)
+    if any(t.device != q.device for t in tensors.values()):
+        raise ValueError("all tensors must be on the same device")
+    return bh // heads, heads, n, n_k, d
+
+
+def attention_lse(q, k, v, heads, scale):
+    """cs_attention_fwd_lse: stereo_attention(q, k, v, heads, scale, "self") -- the same kernel, `out` bit for bit the same -- that
+    also returns lse [(b h), n], the log-sum-exp of every query's scaled scores in log2 units: what attention_backward needs
+    instead of the [(b h), n, n_k] probabilities.  float32 only; argument checks as in stereo_attention.  -> (out, lse)"""
+    b, h, n, n_k, d = _attention_grad_args(heads, scale, q=q, k=k, v=v)
+    out = torch.empty((b, n, h * d), dtype=torch.float32, device=q.device)
+    lse = torch.empty((b * h, n), dtype=torch.float32, device=q.device)
+    with torch.cuda.device(q.device):
+        _native.check(_native.lib().cs_attention_fwd_lse(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), b, h, n, n_k, d,
+                                                         float(scale), _stream()))
+    return out, lse
+
+
+def attention_backward(q, k, v, out, lse, d_out, heads, scale):
+    """cs_attention_bwd: the gradients of sum(out * d_out) with respect to q, k and v, from attention_lse's out and lse.  The
+    probabilities are recomputed tile by tile; the only scratch is one float per query.  No atomics: two calls on the same inputs
+    return bit-identical tensors.  -> (dq, dk, dv), shaped like q, k, v"""
+    b, h, n, n_k, d = _attention_grad_args(heads, scale, q=q, k=k, v=v, out=out, lse=lse, d_out=d_out)
+    L = _native.lib()
+    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+    nb = L.cs_attention_bwd_workspace_bytes(b, h, n, n_k, d)
+    ws = torch.empty((nb,), dtype=torch.uint8, device=q.device)
+    with torch.cuda.device(q.device):
+        _native.check(L.cs_attention_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(d_out), _ptr(dq), _ptr(dk), _ptr(dv),
+                                         b, h, n, n_k, d, float(scale), _ptr(ws), nb, _stream()))
+    return dq, dk, dv
+
+
+class _DifferentiableAttention(torch.autograd.Function):
+    """Saves q, k, v, out and lse -- O(n d), never the O(n n_k) probabilities autograd keeps for einsum / softmax / einsum."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, heads, scale):
+        out, lse = attention_lse(q, k, v, heads, scale)
+        ctx.save_for_backward(q, k, v, out, lse)
+        ctx.heads, ctx.scale = heads, scale
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out):
+        q, k, v, out, lse = ctx.saved_tensors
+        dq, dk, dv = attention_backward(q, k, v, out, lse, d_out.contiguous(), ctx.heads, ctx.scale)
+        return dq, dk, dv, None, None
+
+
+def differentiable_attention(q, k, v, heads, scale):
+    """stereo_attention(q, k, v, heads, scale, "self") that autograd can differentiate: q [(b h), n, d], k and v [(b h), n_k, d] ->
+    [(b), n, h * d].  float16 / bfloat16 q, k, v are upcast to float32 before the fused kernels and the result is cast back to q's
+    dtype, as BNAttention's default path does (autograd differentiates the casts).  Gradients of gradients are not supported."""
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch.Tensor")
+        if t.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise ValueError(f"{name} must be float32, float16 or bfloat16, got {t.dtype}")
+    out = _DifferentiableAttention.apply(q.float().contiguous(), k.float().contiguous(), v.float().contiguous(), int(heads), float(scale))
+    return out.to(q.dtype)

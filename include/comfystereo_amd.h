@@ -379,7 +379,7 @@ CS_API int cs_stereo_shift(const float *input, const float *depth, int b, int c,
  *     CS_ATTN_BI    (c, 0, b, h, .) followed by (c, 1, b, h, .), 2 n keys (:156-162; the no-CFG path :142-146 with c = 1)
  * CS_EINVAL: null or misaligned pointers, non-positive sizes, unknown mode, UNI / BI with s != 2 or n_k != n, out aliasing an
  * input.  CS_ELIMIT: d not a multiple of 4 or above cs_stereo_attention_max_head_dim() (160), sizes beyond 32-bit grids.
- * Forward only.
+ * Forward only (the differentiable CS_ATTN_SELF form is cs_attention_fwd_lse / cs_attention_bwd below).
  */
 enum cs_attn_mode { CS_ATTN_SELF = 0, CS_ATTN_UNI = 1, CS_ATTN_BI = 2 };
 CS_API int cs_stereo_attention_max_head_dim(void);
@@ -397,6 +397,30 @@ CS_API int cs_stereo_attention(const float *q, const float *k, const float *v, f
 enum cs_attn_dtype { CS_ATTN_F16 = 0, CS_ATTN_BF16 = 1 };
 CS_API int cs_stereo_attention_half(const void *q, const void *k, const void *v, void *out, int dtype, int c, int s, int b, int h,
                              int n, int n_k, int d, double scale, int mode, void *stream);
+
+/*
+ * The fused attention with a backward pass (reference diffusion_utils.py register_attention_control :158-292, the attention
+ * the UNet runs under NullInversion.invert, inversion.py:214-262, whose null-text optimisation differentiates through every
+ * layer).  float32, CS_ATTN_SELF semantics only: q, dq [(b h)][n][d]; k, v, dk, dv [(b h)][n_k][d] (n_k may differ from n);
+ * out, d_out [(b)][n][(h d)]; lse [(b h)][n]; all contiguous, 16-byte aligned.
+ *   cs_attention_fwd_lse  cs_stereo_attention(..., c = 1, s = 1, CS_ATTN_SELF) -- `out` is bit for bit that call's -- which also
+ *     stores lse(i) = log2 sum_j exp2(scale * log2(e) * q_i . k_j): the log-sum-exp of the scaled scores in LOG2 units
+ *     (natural-log value = lse * ln 2), the unit the kernels' exponentials work in.
+ *   cs_attention_bwd      dq, dk, dv of sum(out * d_out) from q, k, v and the forward's out and lse.  The probabilities are
+ *     recomputed tile by tile as exp2(scale * log2(e) * s - lse); nothing of size n x n_k is stored.  Three kernels on the
+ *     caller's stream (row sums of d_out * out into the workspace; dk and dv; dq); every gradient element is accumulated by one
+ *     lane in a fixed order, there are no atomics, and results are bit-identical from run to run.
+ * No allocation.  Refusals are cs_stereo_attention's, and nothing is written on a refusal.  CS_EINVAL: null or misaligned
+ * pointers, non-positive sizes, non-finite scale, an output (out, lse; dq, dk, dv, the workspace) overlapping an input or another
+ * output.  CS_ELIMIT: d not a multiple of 4 or above cs_stereo_attention_max_head_dim() (160), sizes beyond 32-bit grids.
+ * CS_EWORKSPACE: workspace_bytes < cs_attention_bwd_workspace_bytes (which is 0 for non-positive sizes).
+ */
+CS_API int cs_attention_fwd_lse(const float *q, const float *k, const float *v, float *out, float *lse, int b, int h, int n,
+                         int n_k, int d, double scale, void *stream);
+CS_API size_t cs_attention_bwd_workspace_bytes(int b, int h, int n, int n_k, int d);
+CS_API int cs_attention_bwd(const float *q, const float *k, const float *v, const float *out, const float *lse, const float *d_out,
+                     float *dq, float *dk, float *dv, int b, int h, int n, int n_k, int d, double scale, void *workspace,
+                     size_t workspace_bytes, void *stream);
 
 /*
  * Measurement hook for bench.py: while enabled, cs_generate brackets the launch of its dominant
@@ -429,7 +453,7 @@ enum cs_debug_key {
     CS_DEBUG_HYBRID_UNFUSED = 9,    /* hybrid_edge: splat result -> node outputs in a streaming pass of its own (k_hybrid_out4) */
     CS_DEBUG_GPUWARP_FULL_MAPS = 10, /* gpu_warp with the depth blur: complete blurred maps (k_blur_copy_tiles) instead of the tile map */
     CS_DEBUG_HYBRID_FULL_MAPS = 11, /* hybrid_edge with the depth blur: complete blurred maps instead of the tile map */
-    CS_DEBUG_ATTN_WAVES = 12,       /* cs_stereo_attention, cs_stereo_attention_half: 1, 2 or 4 waves per workgroup instead of the launcher's choice (tile-size sweeps) */
+    CS_DEBUG_ATTN_WAVES = 12,       /* cs_stereo_attention, cs_stereo_attention_half, cs_attention_fwd_lse, cs_attention_bwd: 1, 2 or 4 waves per workgroup instead of the launcher's choice (tile-size sweeps) */
     CS_DEBUG_KEYS = 13
 };
 CS_API int cs_debug_set(int key, int value);

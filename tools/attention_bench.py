@@ -5,7 +5,12 @@
 F.scaled_dot_product_attention in float32 on the rearranged tensors.  Prints one JSON line per level and direction; TFLOP/s
 counts 4 * queries * keys * d per head (the two products), against the 157 TFLOP/s f32-matrix peak.
 
-  python tools/attention_bench.py [--iters 20] [--warmup 3] [--sweep] [--dtype f16|bf16]
+  python tools/attention_bench.py [--iters 20] [--warmup 3] [--sweep] [--dtype f16|bf16] [--backward]
+--backward: forward + backward of the plain attention that diffusion_utils.register_attention_control installs (batch 2 x 8 heads,
+float32): self-attention at the four levels and cross-attention on 77 keys, engine.differentiable_attention next to (a) the
+stock-torch composition of the reference's arithmetic (einsum, softmax, einsum; diffusion_utils.py:192-203) under autograd and
+(b) F.scaled_dot_product_attention, all on the same GPU in one process, timed alternately.  Per row: median milliseconds of
+forward + backward and the peak of torch.cuda.max_memory_allocated above the inputs, for each of the three.
 --sweep: the kernel alone with 1, 2 and 4 waves per workgroup forced (development switch attn_waves) next to the launcher's
 choice: the measurement behind stereo_attention_waves() in cs_attention.hip (with --dtype: stereo_attention_half_waves()).
 --dtype f16|bf16: cs_stereo_attention_half on random float16 / bfloat16 operands next to (a) the upcast path for the same
@@ -113,14 +118,66 @@ def half_rows(dtype, iters, warmup):
                                   speedup_vs_sdpa=round(t["sdpa"][0] / t["kernel"][0], 2), max_abs_diff_vs_upcast=err)), flush=True)
 
 
+def backward_rows(iters, warmup):
+    heads, batch = 8, 2
+    bh = batch * heads
+
+    def fold(o):   # '(b h) n d -> b n (h d)'
+        return o.reshape(batch, heads, o.shape[1], o.shape[2]).permute(0, 2, 1, 3).reshape(batch, o.shape[1], heads * o.shape[2])
+
+    for level, n, d, _ in LEVELS:
+        for kind, n_k in (("self", n), ("cross", 77)):
+            scale = d ** -0.5
+            q = torch.randn(bh, n, d, device="cuda", requires_grad=True)
+            k, v = (torch.randn(bh, n_k, d, device="cuda", requires_grad=True) for _ in range(2))
+            d_out = torch.randn(batch, n, heads * d, device="cuda")
+
+            def run(fwd):
+                q.grad = k.grad = v.grad = None
+                fwd().backward(d_out)
+
+            fns = {
+                "kernel": lambda: run(lambda: engine.differentiable_attention(q, k, v, heads, scale)),
+                "stock": lambda: run(lambda: fold(torch.einsum("b i j, b j d -> b i d",
+                                                               (torch.einsum("b i d, b j d -> b i j", q, k) * scale).softmax(dim=-1), v))),
+                "sdpa": lambda: run(lambda: fold(F.scaled_dot_product_attention(q, k, v, scale=scale))),
+            }
+            grads, peak = {}, {}
+            for name, fn in fns.items():
+                fn()
+                grads[name] = (q.grad.clone(), k.grad.clone(), v.grad.clone())
+                q.grad = k.grad = v.grad = None
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats()
+                base = torch.cuda.max_memory_allocated()
+                fn()
+                torch.cuda.synchronize()
+                peak[name] = torch.cuda.max_memory_allocated() - base
+            err = max(float((a - b).abs().max()) for a, b in zip(grads["kernel"], grads["stock"]))
+            del grads
+            t = timed_alternately(fns, iters, warmup)
+            flop = (4.0 + 10.0) * bh * n * n_k * d   # forward 2 products, backward 5 (S, dP, dV, dK, dQ), 2 flop per multiply-add
+            print(json.dumps(dict(backward=True, level=level, kind=kind, n=n, n_k=n_k, d=d, heads=heads, batch=batch,
+                                  kernel_ms=round(t["kernel"][0], 4), kernel_min_ms=round(t["kernel"][1], 4),
+                                  stock_ms=round(t["stock"][0], 4), sdpa_ms=round(t["sdpa"][0], 4),
+                                  kernel_peak_mib=round(peak["kernel"] / 2 ** 20, 2), stock_peak_mib=round(peak["stock"] / 2 ** 20, 2),
+                                  sdpa_peak_mib=round(peak["sdpa"] / 2 ** 20, 2), kernel_tflops=round(flop / t["kernel"][0] / 1e9, 2),
+                                  speedup_vs_stock=round(t["stock"][0] / t["kernel"][0], 2),
+                                  speedup_vs_sdpa=round(t["sdpa"][0] / t["kernel"][0], 2), max_abs_grad_diff_vs_stock=err)), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--dtype", choices=("f32", "f16", "bf16"), default="f32")
+    ap.add_argument("--backward", action="store_true")
     args = ap.parse_args()
     torch.manual_seed(0)
+    if args.backward:
+        backward_rows(args.iters, args.warmup)
+        return
     if args.dtype != "f32" and not args.sweep:
         half_rows(args.dtype, args.iters, args.warmup)
         return
