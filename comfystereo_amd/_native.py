@@ -32,7 +32,7 @@ GAUSS_OP = {"plain": 0, "edge_selective": 1, "left": 2, "right": 3}
 PIL_FLAG = {"in_f32": 1, "gray": 2, "out_planar": 4}
 # enum cs_attn_mode (the reference's stereo attention, cs_stereo_attention)
 ATTN_MODE = {"self": 0, "uni": 1, "bi": 2}
-# enum cs_attn_dtype (the element type of cs_stereo_attention_half)
+# enum cs_attn_dtype (the element type of cs_stereo_attention_half, cs_attention_half_fwd_lse and cs_attention_half_bwd)
 ATTN_DTYPE = {"float16": 0, "bfloat16": 1}
 
 # the ABI version the ctypes signatures below were written for (include/comfystereo_amd.h CS_ABI_VERSION)
@@ -49,6 +49,7 @@ EXPORTS = [
     "cs_pil_resize_workspace_bytes", "cs_pil_resize_max_taps", "cs_pil_resize",
     "cs_stereo_attention_max_head_dim", "cs_stereo_attention", "cs_stereo_attention_half",
     "cs_attention_fwd_lse", "cs_attention_bwd_workspace_bytes", "cs_attention_bwd",
+    "cs_attention_half_fwd_lse", "cs_attention_half_bwd_workspace_bytes", "cs_attention_half_bwd",
 ]
 
 # enum cs_debug_key (development switches; tests and profiling tools only)
@@ -234,6 +235,12 @@ def lib():
     L.cs_attention_bwd_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int]
     L.cs_attention_bwd.restype = c_int
     L.cs_attention_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_double, vp, c_size, vp]
+    L.cs_attention_half_fwd_lse.restype = c_int
+    L.cs_attention_half_fwd_lse.argtypes = [vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, c_double, vp]
+    L.cs_attention_half_bwd_workspace_bytes.restype = c_size
+    L.cs_attention_half_bwd_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int]
+    L.cs_attention_half_bwd.restype = c_int
+    L.cs_attention_half_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, c_double, vp, c_size, vp]
     _lib = L
     return L
 

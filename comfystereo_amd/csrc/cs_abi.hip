@@ -1383,10 +1383,13 @@ int cs_stereo_attention_half(const void* q, const void* k, const void* v, void* 
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_stereo_attention_half");
 }
 
-// the checks cs_attention_fwd_lse and cs_attention_bwd share with cs_stereo_attention (SELF mode, c = s = 1)
-static int attn_grad_args(int b, int h, int n, int n_k, int d, double scale) {
+// the checks cs_attention_fwd_lse and cs_attention_bwd share with cs_stereo_attention (SELF mode, c = s = 1); half: the
+// float16 / bfloat16 pair, whose rows need d to be a multiple of 8
+static int attn_grad_args(int b, int h, int n, int n_k, int d, double scale, bool half = false) {
     if (b <= 0 || h <= 0 || n <= 0 || n_k <= 0 || d <= 0) return fail(CS_EINVAL, "non-positive size");
     if (!(scale == scale) || scale - scale != 0.0) return fail(CS_EINVAL, "attention: scale must be finite");
+    if (half && ((d & 7) || d > stereo_attention_max_head_dim()))
+        return fail(CS_ELIMIT, "attention: float16 / bfloat16 head dimension must be a multiple of 8 up to cs_stereo_attention_max_head_dim()");
     if ((d & 3) || d > stereo_attention_max_head_dim())
         return fail(CS_ELIMIT, "attention: head dimension must be a multiple of 4 up to cs_stereo_attention_max_head_dim()");
     const long long bhn = (long long)b * h;
@@ -1434,6 +1437,51 @@ int cs_attention_bwd(const float* q, const float* k, const float* v, const float
                 return fail(CS_EINVAL, "cs_attention_bwd: dq, dk, dv and the workspace must not overlap an input or each other");
     hipError_t e = launch_attention_bwd(q, k, v, out, lse, d_out, dq, dk, dv, b, h, n, n_k, d, (float)scale, workspace, (hipStream_t)stream);
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_attention_bwd");
+}
+
+int cs_attention_half_fwd_lse(const void* q, const void* k, const void* v, void* out, float* lse, int dtype, int b, int h, int n, int n_k,
+                              int d, double scale, void* stream) {
+    if (!q || !k || !v || !out || !lse) return fail(CS_EINVAL, "null pointer");
+    if (dtype != CS_ATTN_F16 && dtype != CS_ATTN_BF16) return fail(CS_EINVAL, "cs_attention_half_fwd_lse: unknown dtype (CS_ATTN_F16, CS_ATTN_BF16)");
+    if (int rc = attn_grad_args(b, h, n, n_k, d, scale, true)) return rc;
+    if (((uintptr_t)q & 15) || ((uintptr_t)k & 15) || ((uintptr_t)v & 15) || ((uintptr_t)out & 15) || ((uintptr_t)lse & 15))
+        return fail(CS_EINVAL, "cs_attention_half_fwd_lse: q, k, v, out and lse need 16-byte alignment");
+    const size_t bhn = (size_t)b * h, q_bytes = bhn * n * d * 2, k_bytes = bhn * n_k * d * 2, l_bytes = bhn * n * 4;
+    const void* in[3] = {q, k, v};
+    const size_t in_bytes[3] = {q_bytes, k_bytes, k_bytes};
+    for (int i = 0; i < 3; i++)
+        if (overlaps(out, q_bytes, in[i], in_bytes[i]) || overlaps(lse, l_bytes, in[i], in_bytes[i]))
+            return fail(CS_EINVAL, "cs_attention_half_fwd_lse: out and lse must not overlap q, k or v");
+    if (overlaps(out, q_bytes, lse, l_bytes)) return fail(CS_EINVAL, "cs_attention_half_fwd_lse: out and lse must not overlap");
+    hipError_t e = launch_attention_half_fwd_lse(q, k, v, out, lse, dtype, b, h, n, n_k, d, (float)scale, (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_attention_half_fwd_lse");
+}
+
+size_t cs_attention_half_bwd_workspace_bytes(int b, int h, int n, int n_k, int d) {
+    return attention_half_bwd_workspace_bytes(b, h, n, n_k, d);
+}
+
+int cs_attention_half_bwd(const void* q, const void* k, const void* v, const void* out, const float* lse, const void* d_out, void* dq,
+                          void* dk, void* dv, int dtype, int b, int h, int n, int n_k, int d, double scale, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+    if (!q || !k || !v || !out || !lse || !d_out || !dq || !dk || !dv || !workspace) return fail(CS_EINVAL, "null pointer");
+    if (dtype != CS_ATTN_F16 && dtype != CS_ATTN_BF16) return fail(CS_EINVAL, "cs_attention_half_bwd: unknown dtype (CS_ATTN_F16, CS_ATTN_BF16)");
+    if (int rc = attn_grad_args(b, h, n, n_k, d, scale, true)) return rc;
+    const size_t bhn = (size_t)b * h, q_bytes = bhn * n * d * 2, k_bytes = bhn * n_k * d * 2, l_bytes = bhn * n * 4;
+    const size_t need = attention_half_bwd_workspace_bytes(b, h, n, n_k, d);
+    // inputs 0..5, then the regions that are written: dq, dk, dv and the workspace
+    const void* p[10] = {q, k, v, out, lse, d_out, dq, dk, dv, workspace};
+    const size_t bytes[10] = {q_bytes, k_bytes, k_bytes, q_bytes, l_bytes, q_bytes, q_bytes, k_bytes, k_bytes, need};
+    for (int i = 0; i < 10; i++)
+        if ((uintptr_t)p[i] & 15) return fail(CS_EINVAL, "cs_attention_half_bwd: every pointer needs 16-byte alignment");
+    if (workspace_bytes < need) return fail(CS_EWORKSPACE, "cs_attention_half_bwd: workspace too small (cs_attention_half_bwd_workspace_bytes)");
+    for (int w = 6; w < 10; w++)
+        for (int i = 0; i < w; i++)
+            if (overlaps(p[w], bytes[w], p[i], bytes[i]))
+                return fail(CS_EINVAL, "cs_attention_half_bwd: dq, dk, dv and the workspace must not overlap an input or each other");
+    hipError_t e = launch_attention_half_bwd(q, k, v, out, lse, d_out, dq, dk, dv, dtype, b, h, n, n_k, d, (float)scale, workspace,
+                                             (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_attention_half_bwd");
 }
 
 int cs_profile(int enable) {

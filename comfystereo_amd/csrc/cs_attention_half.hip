@@ -21,42 +21,19 @@
 //   160 = 0 (mod 32) dwords apart, so the lanes of the odd chunk take their columns in the order i ^ 4 (4 rows = 80 = 16 mod 32):
 //   the two chunks land on disjoint halves of the 32 write banks.
 // The next tile's K / V are loaded into registers before this tile's products and stored to LDS after them.
+#include "cs_attention_half.h"
 #include "cs_common.h"
 #include "cs_kernels.h"
 
 namespace cs {
 
-enum { SAH_KT = 32, SAH_SVT = SAH_KT + 8 };   // keys per tile; halves per row of the transposed V image (80 bytes)
-
-typedef float sah_acc __attribute__((ext_vector_type(16)));
-typedef _Float16 sah_f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 sah_bf16x8 __attribute__((ext_vector_type(8)));
-
-template <typename T> struct sah_frag;
-template <> struct sah_frag<_Float16> {
-    typedef sah_f16x8 type;
-    static __device__ __forceinline__ sah_acc mfma(type a, type b, sah_acc c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-};
-template <> struct sah_frag<__bf16> {
-    typedef sah_bf16x8 type;
-    static __device__ __forceinline__ sah_acc mfma(type a, type b, sah_acc c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-};
-
-// accumulator register r of lane half hi <-> row of the 32 x 32 tile (cs_attention.hip sa_row)
-__device__ __forceinline__ int sah_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
-// key of a tile -> its position in a row of the transposed V image: the inverse of sah_row(8 s + j, h) -> 16 s + 8 h + j
-__device__ __forceinline__ int sah_slot(int key) { return (key & 16) + 8 * ((key >> 2) & 1) + 4 * ((key >> 3) & 1) + (key & 3); }
-
-// half element i (0..7) of a 16-byte chunk
-__device__ __forceinline__ unsigned sah_elem(const uint4& c, int i) {
-    const unsigned w = (i >> 1) == 0 ? c.x : (i >> 1) == 1 ? c.y : (i >> 1) == 2 ? c.z : c.w;
-    return (i & 1) ? (w >> 16) : (w & 0xffffu);
-}
-
-template <typename T, int ND, int NW>
+// LSE (cs_attention_half_fwd_lse, the forward of the differentiable half attention): besides `out`, the log-sum-exp of every
+// query's scaled scores goes to lse [(c s b h)][n] as float32, in log2 units like sc2, from the float32 running maximum and sum:
+// p(i, j) = exp2(sc2 * s(i, j) - lse(i)).  Nothing else differs.
+template <typename T, int ND, int NW, bool LSE = false>
 __global__ void __launch_bounds__(NW * 64) k_stereo_attention_half(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v,
                                                                    T* __restrict__ out, int S, int B, int H, int n, int n_k, int d,
-                                                                   float scale, int mode, int qtiles) {
+                                                                   float scale, int mode, int qtiles, float* __restrict__ lse = nullptr) {
     typedef typename sah_frag<T>::type frag;
     constexpr int SK = ND * 32 + 8, NT = NW * 64;
     constexpr int KI = (SAH_KT * ND * 4 + NT - 1) / NT;         // 16-byte K chunks of a tile per thread
@@ -209,6 +186,7 @@ __global__ void __launch_bounds__(NW * 64) k_stereo_attention_half(const T* __re
 
     const float l_all = l_run + __shfl_xor(l_run, 32);
     if (!q_ok) return;
+    if (LSE && hi == 0) lse[(size_t)bh * n + qi] = m_run + __builtin_amdgcn_logf(l_all);   // (v_log_f32 is log2; l_all >= 1)
     // out [(c s b)][n][(h d)]: lane (query, hi) holds columns 32 blk + 8 g + 4 hi .. + 3 in registers 4 g .. 4 g + 3
     T* orow = out + ((size_t)sb * n + qi) * ((size_t)H * d) + (size_t)hh * d;
 #pragma unroll
@@ -236,6 +214,18 @@ static hipError_t sah_launch(int nw, int blocks, const T* q, const T* k, const T
         hipLaunchKernelGGL((k_stereo_attention_half<T, ND, 2>), dim3(blocks), dim3(128), 0, stream, q, k, v, out, S, B, H, n, n_k, d, scale, mode, qtiles);
     else
         hipLaunchKernelGGL((k_stereo_attention_half<T, ND, 1>), dim3(blocks), dim3(64), 0, stream, q, k, v, out, S, B, H, n, n_k, d, scale, mode, qtiles);
+    return hipGetLastError();
+}
+
+template <typename T, int ND>
+static hipError_t sah_launch_lse(int nw, int blocks, const T* q, const T* k, const T* v, T* out, float* lse, int B, int H, int n, int n_k,
+                                 int d, float scale, int qtiles, hipStream_t stream) {
+    if (nw == 4)
+        hipLaunchKernelGGL((k_stereo_attention_half<T, ND, 4, true>), dim3(blocks), dim3(256), 0, stream, q, k, v, out, 1, B, H, n, n_k, d, scale, (int)CS_ATTN_SELF, qtiles, lse);
+    else if (nw == 2)
+        hipLaunchKernelGGL((k_stereo_attention_half<T, ND, 2, true>), dim3(blocks), dim3(128), 0, stream, q, k, v, out, 1, B, H, n, n_k, d, scale, (int)CS_ATTN_SELF, qtiles, lse);
+    else
+        hipLaunchKernelGGL((k_stereo_attention_half<T, ND, 1, true>), dim3(blocks), dim3(64), 0, stream, q, k, v, out, 1, B, H, n, n_k, d, scale, (int)CS_ATTN_SELF, qtiles, lse);
     return hipGetLastError();
 }
 
@@ -270,6 +260,33 @@ hipError_t launch_stereo_attention_half(const void* q, const void* k, const void
                                         int n, int n_k, int d, float scale, int mode, hipStream_t stream) {
     if (dtype == CS_ATTN_F16) return sah_dispatch<_Float16>(q, k, v, out, c, s, b, h, n, n_k, d, scale, mode, stream);
     if (dtype == CS_ATTN_BF16) return sah_dispatch<__bf16>(q, k, v, out, c, s, b, h, n, n_k, d, scale, mode, stream);
+    return hipErrorInvalidValue;
+}
+
+// the same launch as launch_stereo_attention_half(..., CS_ATTN_SELF) with c = s = 1: `out` is bit for bit that call's
+template <typename T>
+static hipError_t sah_dispatch_lse(const void* q, const void* k, const void* v, void* out, float* lse, int b, int h, int n, int n_k, int d,
+                                   float scale, hipStream_t stream) {
+    const long long bhn = (long long)b * h;
+    const int nw = stereo_attention_half_waves(bhn, n);
+    const int qtiles = (n + 32 * nw - 1) / (32 * nw);
+    const int blocks = (int)(bhn * qtiles);
+    const T *tq = (const T*)q, *tk = (const T*)k, *tv = (const T*)v;
+    T* to = (T*)out;
+    switch ((d + 31) / 32) {
+    case 1: return sah_launch_lse<T, 1>(nw, blocks, tq, tk, tv, to, lse, b, h, n, n_k, d, scale, qtiles, stream);
+    case 2: return sah_launch_lse<T, 2>(nw, blocks, tq, tk, tv, to, lse, b, h, n, n_k, d, scale, qtiles, stream);
+    case 3: return sah_launch_lse<T, 3>(nw, blocks, tq, tk, tv, to, lse, b, h, n, n_k, d, scale, qtiles, stream);
+    case 4: return sah_launch_lse<T, 4>(nw, blocks, tq, tk, tv, to, lse, b, h, n, n_k, d, scale, qtiles, stream);
+    case 5: return sah_launch_lse<T, 5>(nw, blocks, tq, tk, tv, to, lse, b, h, n, n_k, d, scale, qtiles, stream);
+    }
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_attention_half_fwd_lse(const void* q, const void* k, const void* v, void* out, float* lse, int dtype, int b, int h, int n,
+                                         int n_k, int d, float scale, hipStream_t stream) {
+    if (dtype == CS_ATTN_F16) return sah_dispatch_lse<_Float16>(q, k, v, out, lse, b, h, n, n_k, d, scale, stream);
+    if (dtype == CS_ATTN_BF16) return sah_dispatch_lse<__bf16>(q, k, v, out, lse, b, h, n, n_k, d, scale, stream);
     return hipErrorInvalidValue;
 }
 

@@ -205,6 +205,14 @@ hipError_t launch_attention_bwd(const float* q, const float* k, const float* v, 
 int stereo_attention_half_waves(long long batch_heads, int n);
 hipError_t launch_stereo_attention_half(const void* q, const void* k, const void* v, void* out, int dtype, int c, int s, int b, int h,
                                         int n, int n_k, int d, float scale, int mode, hipStream_t stream);
+// the SELF-mode half forward that also stores every query's log-sum-exp (float32, log2 units): cs_attention_half_fwd_lse
+hipError_t launch_attention_half_fwd_lse(const void* q, const void* k, const void* v, void* out, float* lse, int dtype, int b, int h, int n,
+                                         int n_k, int d, float scale, hipStream_t stream);
+// cs_attention_half_bwd.hip (dq, dk, dv of that forward in the half dtype: cs_attention_half_bwd)
+size_t attention_half_bwd_workspace_bytes(int b, int h, int n, int n_k, int d);
+hipError_t launch_attention_half_bwd(const void* q, const void* k, const void* v, const void* out, const float* lse, const void* d_out,
+                                     void* dq, void* dk, void* dv, int dtype, int b, int h, int n, int n_k, int d, float scale,
+                                     void* workspace, hipStream_t stream);
 // lazy depth-blur tiles in k_gpuwarp (tilemap != nullptr): rows of at most this many columns, not the mesh-quality warp
 int gpuwarp_lazy_max_width();
 

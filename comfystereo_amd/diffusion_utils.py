@@ -7,6 +7,13 @@ linear layers and runs the attention in the fused HIP kernels: under autograd (n
 every layer, inversion.py:184-212) through engine.differentiable_attention, whose backward recomputes the probabilities from one
 saved float per query instead of keeping [(b h), n, n_k] of them; without autograd through engine.stereo_attention.
 
+float16 / bfloat16 q, k, v (null-text optimisation on a half model: the reference casts latents and context to the model's dtype,
+model_wrappers.py:306-347): by default they are upcast to float32, run through the float32 kernels and cast back, forward and
+backward.  stereo_utils.HALF_ATTENTION = True -- the one switch BNAttention reads too -- sends q, k, v of one half dtype (head
+dimension a multiple of 8) to the half kernels instead: under autograd cs_attention_half_fwd_lse / cs_attention_half_bwd
+(engine.differentiable_attention(..., native_half=True): no conversion pass, the half tensors and a float32 lse saved for the
+backward), without autograd cs_stereo_attention_half.  Anything else keeps the upcast.
+
 The reference hands a controller the [(b h), n, n_k] probabilities, which the fused kernels never form: a controller other than
 None is refused with TypeError, an attention mask with ValueError (Stable Diffusion's UNet passes neither).
 
@@ -24,8 +31,13 @@ def _attend(q, k, v, heads, scale):
     """q [(b h), n, d], k and v [(b h), n_k, d] -> [(b), n, h * d] in q's dtype, on the fused kernels."""
     stereo_utils._need_gpu()
     dev = q.device if q.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    native_half = bool(stereo_utils.HALF_ATTENTION)
     if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
-        out = engine.differentiable_attention(q.to(dev), k.to(dev), v.to(dev), heads, scale)
+        out = engine.differentiable_attention(q.to(dev), k.to(dev), v.to(dev), heads, scale, native_half=native_half)
+    elif (native_half and q.dtype in (torch.float16, torch.bfloat16) and k.dtype == q.dtype and v.dtype == q.dtype
+          and q.shape[-1] % 8 == 0):
+        qh, kh, vh = (t.detach().to(dev).contiguous() for t in (q, k, v))
+        out = engine.stereo_attention(qh, kh, vh, heads, scale, "self")
     else:
         q32, k32, v32 = (t.detach().to(dev, torch.float32).contiguous() for t in (q, k, v))
         out = engine.stereo_attention(q32, k32, v32, heads, scale, "self").to(q.dtype)

@@ -544,18 +544,25 @@ def stereo_attention(q, k, v, heads, scale, mode, chunks=1, out=None):
     return out
 
 
-# ---- the differentiable fused attention (cs_attention_fwd_lse / cs_attention_bwd) -------------------
+# ---- the differentiable fused attention (cs_attention_fwd_lse / cs_attention_bwd and their _half forms) -------------------
 def _attention_grad_args(heads, scale, **tensors):
-    """The checks of stereo_attention for the float32 'self' form: q [(b h), n, d], k and v [(b h), n_k, d] and, where given,
-    out / d_out [(b), n, h * d] and lse [(b h), n].  ValueError before anything is launched.  -> (b, h, n, n_k, d)"""
+    """The checks of stereo_attention for the 'self' form: q [(b h), n, d], k and v [(b h), n_k, d] and, where given,
+    out / d_out [(b), n, h * d] and lse [(b h), n].  q, k, v, out and d_out are all float32, all float16 or all bfloat16; lse is
+    float32 whatever they are.  ValueError before anything is launched.  -> (b, h, n, n_k, d)"""
     for name, t in tensors.items():
         if not isinstance(t, torch.Tensor):
             raise ValueError(f"{name} must be a torch.Tensor")
-        if t.dtype != torch.float32:
-            raise ValueError(f"{name} must be float32, got {t.dtype}")
+    q, k, v = tensors["q"], tensors["k"], tensors["v"]
+    if q.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise ValueError(f"q must be float32, float16 or bfloat16, got {q.dtype}")
+    for name, t in tensors.items():
+        want = torch.float32 if name == "lse" else q.dtype
+        if t.dtype != want:
+            raise ValueError(f"{name} must be {want}" + ("" if name == "lse" else " like q (one dtype for q, k, v, out and d_out)")
+                             + f", got {t.dtype}")
         if not t.is_contiguous():
             raise ValueError(f"{name} must be contiguous")
-    q, k, v = tensors["q"], tensors["k"], tensors["v"]
+    half = q.dtype != torch.float32
     for name in ("q", "k", "v"):
         if tensors[name].dim() != 3:
             raise ValueError(f"{name} must be [(b h), tokens, d], got shape {tuple(tensors[name].shape)}")
@@ -569,8 +576,8 @@ def _attention_grad_args(heads, scale, **tensors):
     if heads <= 0 or bh % heads:
         raise ValueError(f"batch {bh} is not samples * heads = b * {heads}")
     d_max = _native.lib().cs_stereo_attention_max_head_dim()   # (host only: no device work)
-    if d % 4 or d > d_max:
-        raise ValueError(f"head dimension {d}: the fused attention takes multiples of 4 up to {d_max}")
+    if d % (8 if half else 4) or d > d_max:
+        raise ValueError(f"head dimension {d}: the fused attention takes multiples of 4 (float16 / bfloat16: of 8) up to {d_max}")
     if not math.isfinite(float(scale)):
         raise ValueError(f"scale must be finite, got {scale}")
     for name, shape in (("out", (bh // heads, n, heads * d)), ("d_out", (bh // heads, n, heads * d)), ("lse", (bh, n))):
@@ -582,36 +589,52 @@ def _attention_grad_args(heads, scale, **tensors):
     return bh // heads, heads, n, n_k, d
 
 
+def _attn_dtype(t):
+    return _native.ATTN_DTYPE["float16" if t.dtype == torch.float16 else "bfloat16"]
+
+
 def attention_lse(q, k, v, heads, scale):
     """cs_attention_fwd_lse: stereo_attention(q, k, v, heads, scale, "self") -- the same kernel, `out` bit for bit the same -- that
     also returns lse [(b h), n], the log-sum-exp of every query's scaled scores in log2 units: what attention_backward needs
-    instead of the [(b h), n, n_k] probabilities.  float32 only; argument checks as in stereo_attention.  -> (out, lse)"""
+    instead of the [(b h), n, n_k] probabilities.  q, k, v all float16 or all bfloat16 go to cs_attention_half_fwd_lse (d a multiple
+    of 8): `out` has their dtype, lse stays float32.  Argument checks as in stereo_attention.  -> (out, lse)"""
     b, h, n, n_k, d = _attention_grad_args(heads, scale, q=q, k=k, v=v)
-    out = torch.empty((b, n, h * d), dtype=torch.float32, device=q.device)
+    out = torch.empty((b, n, h * d), dtype=q.dtype, device=q.device)
     lse = torch.empty((b * h, n), dtype=torch.float32, device=q.device)
+    L = _native.lib()
     with torch.cuda.device(q.device):
-        _native.check(_native.lib().cs_attention_fwd_lse(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), b, h, n, n_k, d,
-                                                         float(scale), _stream()))
+        if q.dtype != torch.float32:
+            _native.check(L.cs_attention_half_fwd_lse(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _attn_dtype(q), b, h, n, n_k, d,
+                                                      float(scale), _stream()))
+        else:
+            _native.check(L.cs_attention_fwd_lse(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), b, h, n, n_k, d, float(scale), _stream()))
     return out, lse
 
 
 def attention_backward(q, k, v, out, lse, d_out, heads, scale):
     """cs_attention_bwd: the gradients of sum(out * d_out) with respect to q, k and v, from attention_lse's out and lse.  The
     probabilities are recomputed tile by tile; the only scratch is one float per query.  No atomics: two calls on the same inputs
-    return bit-identical tensors.  -> (dq, dk, dv), shaped like q, k, v"""
+    return bit-identical tensors.  float16 / bfloat16 q, k, v, out, d_out (one dtype, lse float32) go to cs_attention_half_bwd and
+    the gradients have that dtype.  -> (dq, dk, dv), shaped like q, k, v"""
     b, h, n, n_k, d = _attention_grad_args(heads, scale, q=q, k=k, v=v, out=out, lse=lse, d_out=d_out)
     L = _native.lib()
+    half = q.dtype != torch.float32
     dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-    nb = L.cs_attention_bwd_workspace_bytes(b, h, n, n_k, d)
+    nb = (L.cs_attention_half_bwd_workspace_bytes if half else L.cs_attention_bwd_workspace_bytes)(b, h, n, n_k, d)
     ws = torch.empty((nb,), dtype=torch.uint8, device=q.device)
     with torch.cuda.device(q.device):
-        _native.check(L.cs_attention_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(d_out), _ptr(dq), _ptr(dk), _ptr(dv),
-                                         b, h, n, n_k, d, float(scale), _ptr(ws), nb, _stream()))
+        if half:
+            _native.check(L.cs_attention_half_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(d_out), _ptr(dq), _ptr(dk),
+                                                  _ptr(dv), _attn_dtype(q), b, h, n, n_k, d, float(scale), _ptr(ws), nb, _stream()))
+        else:
+            _native.check(L.cs_attention_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(d_out), _ptr(dq), _ptr(dk), _ptr(dv),
+                                             b, h, n, n_k, d, float(scale), _ptr(ws), nb, _stream()))
     return dq, dk, dv
 
 
 class _DifferentiableAttention(torch.autograd.Function):
-    """Saves q, k, v, out and lse -- O(n d), never the O(n n_k) probabilities autograd keeps for einsum / softmax / einsum."""
+    """Saves q, k, v, out and lse -- O(n d), never the O(n n_k) probabilities autograd keeps for einsum / softmax / einsum.  The
+    tensors keep the dtype they come in (float32, or one half dtype: attention_lse / attention_backward dispatch on it)."""
 
     @staticmethod
     def forward(ctx, q, k, v, heads, scale):
@@ -628,14 +651,20 @@ class _DifferentiableAttention(torch.autograd.Function):
         return dq, dk, dv, None, None
 
 
-def differentiable_attention(q, k, v, heads, scale):
+def differentiable_attention(q, k, v, heads, scale, native_half=False):
     """stereo_attention(q, k, v, heads, scale, "self") that autograd can differentiate: q [(b h), n, d], k and v [(b h), n_k, d] ->
     [(b), n, h * d].  float16 / bfloat16 q, k, v are upcast to float32 before the fused kernels and the result is cast back to q's
-    dtype, as BNAttention's default path does (autograd differentiates the casts).  Gradients of gradients are not supported."""
+    dtype, as BNAttention's default path does (autograd differentiates the casts).  native_half=True: q, k, v of ONE half dtype with
+    d a multiple of 8 run the half kernels instead (cs_attention_half_fwd_lse / cs_attention_half_bwd): no conversion pass, and what
+    is saved for the backward is the half q, k, v, out plus the float32 lse; any other input keeps the upcast.  Gradients of
+    gradients are not supported."""
     for name, t in (("q", q), ("k", k), ("v", v)):
         if not isinstance(t, torch.Tensor):
             raise ValueError(f"{name} must be a torch.Tensor")
         if t.dtype not in (torch.float32, torch.float16, torch.bfloat16):
             raise ValueError(f"{name} must be float32, float16 or bfloat16, got {t.dtype}")
+    if (native_half and q.dtype != torch.float32 and k.dtype == q.dtype and v.dtype == q.dtype and q.dim() == 3
+            and q.shape[-1] % 8 == 0):
+        return _DifferentiableAttention.apply(q.contiguous(), k.contiguous(), v.contiguous(), int(heads), float(scale))
     out = _DifferentiableAttention.apply(q.float().contiguous(), k.float().contiguous(), v.float().contiguous(), int(heads), float(scale))
     return out.to(q.dtype)

@@ -13,7 +13,8 @@ float16 / bfloat16 q, k, v: by default they are upcast to float32, run through t
 engine.MESH_WARP / engine.DIALECT) sends them to cs_stereo_attention_half instead, with no conversion pass: the matrix
 operands (q, k, v, and the probabilities after the exponential) stay half on the half-input MFMA, the scores, the softmax and
 the accumulators are float32 -- the reference's own arithmetic in that dtype rounds more, not less.  float32 inputs take the
-float32 kernel either way.
+float32 kernel either way.  diffusion_utils.register_attention_control reads the same switch: with it set, half q, k, v take
+cs_stereo_attention_half without autograd and the half forward-with-lse / backward pair under autograd.
 
 No CPU fallback anywhere: without a GPU the calls raise RuntimeError."""
 import torch
@@ -39,7 +40,8 @@ def stereo_shift_torch(input_images: torch.Tensor, depthmaps: torch.Tensor, scal
     return out if input_images.is_cuda else out.to(input_images.device)
 
 
-# float16 / bfloat16 q, k, v of BNAttention: False = upcast, float32 kernel, cast back; True = cs_stereo_attention_half
+# float16 / bfloat16 q, k, v of BNAttention and of diffusion_utils' hook: False = upcast, float32 kernels, cast back; True = the half
+# kernels (cs_stereo_attention_half; under autograd cs_attention_half_fwd_lse / cs_attention_half_bwd)
 HALF_ATTENTION = False
 
 

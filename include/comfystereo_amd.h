@@ -423,6 +423,27 @@ CS_API int cs_attention_bwd(const float *q, const float *k, const float *v, cons
                      size_t workspace_bytes, void *stream);
 
 /*
+ * The same pair on float16 or bfloat16 tensors (the dtype null-text optimisation runs in on a half model), on the half-input
+ * MFMA and with no conversion pass: q, k, v, out, d_out, dq, dk, dv are all `dtype` (enum cs_attn_dtype) in the layouts of
+ * cs_attention_fwd_lse / cs_attention_bwd; lse and the workspace are float32.
+ *   cs_attention_half_fwd_lse  cs_stereo_attention_half(..., c = 1, s = 1, CS_ATTN_SELF) -- `out` is bit for bit that call's -- which
+ *     also stores lse(i) = log2 sum_j exp2(scale * log2(e) * q_i . k_j) as float32, from the kernel's float32 running maximum and sum.
+ *   cs_attention_half_bwd      dq, dk, dv of sum(out * d_out).  All five matrix products (S, dP, dV, dK, dQ) take half operands: q, k,
+ *     v, d_out as given, and the recomputed probabilities and dS rounded to `dtype` after the float32 arithmetic that forms them;
+ *     row sums, exponentials and every accumulator are float32.  Three kernels on the caller's stream, no atomics, each gradient
+ *     element accumulated by one lane in a fixed order and rounded to nearest-even once: bit-identical from run to run.
+ * No allocation.  Refusals are those of the float32 pair (sizes in bytes follow the dtype), and nothing is written on a refusal;
+ * in addition CS_EINVAL: unknown dtype; CS_ELIMIT: d not a multiple of 8.  CS_EWORKSPACE: workspace_bytes <
+ * cs_attention_half_bwd_workspace_bytes (which is 0 for non-positive sizes).
+ */
+CS_API int cs_attention_half_fwd_lse(const void *q, const void *k, const void *v, void *out, float *lse, int dtype, int b, int h,
+                              int n, int n_k, int d, double scale, void *stream);
+CS_API size_t cs_attention_half_bwd_workspace_bytes(int b, int h, int n, int n_k, int d);
+CS_API int cs_attention_half_bwd(const void *q, const void *k, const void *v, const void *out, const float *lse, const void *d_out,
+                          void *dq, void *dk, void *dv, int dtype, int b, int h, int n, int n_k, int d, double scale,
+                          void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Measurement hook for bench.py: while enabled, cs_generate brackets the launch of its dominant
  * kernel (the row warp + fill kernel of the selected technique) with HIP events on the caller's
  * stream.  cs_profile_read waits for the recorded events, returns the summed kernel time in
@@ -453,7 +474,7 @@ enum cs_debug_key {
     CS_DEBUG_HYBRID_UNFUSED = 9,    /* hybrid_edge: splat result -> node outputs in a streaming pass of its own (k_hybrid_out4) */
     CS_DEBUG_GPUWARP_FULL_MAPS = 10, /* gpu_warp with the depth blur: complete blurred maps (k_blur_copy_tiles) instead of the tile map */
     CS_DEBUG_HYBRID_FULL_MAPS = 11, /* hybrid_edge with the depth blur: complete blurred maps instead of the tile map */
-    CS_DEBUG_ATTN_WAVES = 12,       /* cs_stereo_attention, cs_stereo_attention_half, cs_attention_fwd_lse, cs_attention_bwd: 1, 2 or 4 waves per workgroup instead of the launcher's choice (tile-size sweeps) */
+    CS_DEBUG_ATTN_WAVES = 12,       /* cs_stereo_attention, cs_stereo_attention_half, cs_attention_fwd_lse, cs_attention_bwd, cs_attention_half_fwd_lse, cs_attention_half_bwd: 1, 2 or 4 waves per workgroup instead of the launcher's choice (tile-size sweeps) */
     CS_DEBUG_KEYS = 13
 };
 CS_API int cs_debug_set(int key, int value);

@@ -11,6 +11,10 @@ float32): self-attention at the four levels and cross-attention on 77 keys, engi
 stock-torch composition of the reference's arithmetic (einsum, softmax, einsum; diffusion_utils.py:192-203) under autograd and
 (b) F.scaled_dot_product_attention, all on the same GPU in one process, timed alternately.  Per row: median milliseconds of
 forward + backward and the peak of torch.cuda.max_memory_allocated above the inputs, for each of the three.
+--backward --dtype f16|bf16: the same rows on float16 / bfloat16 tensors for engine.differentiable_attention(..., native_half=True)
+(cs_attention_half_fwd_lse / cs_attention_half_bwd), next to (a) the upcast path for the same tensors (native_half=False: three
+casts, the float32 kernels, a cast back, and the same again in the backward), (b) the stock-torch composition in the dtype under
+autograd and (c) F.scaled_dot_product_attention in the dtype; time and peak memory above the inputs for each of the four.
 --sweep: the kernel alone with 1, 2 and 4 waves per workgroup forced (development switch attn_waves) next to the launcher's
 choice: the measurement behind stereo_attention_waves() in cs_attention.hip (with --dtype: stereo_attention_half_waves()).
 --dtype f16|bf16: cs_stereo_attention_half on random float16 / bfloat16 operands next to (a) the upcast path for the same
@@ -118,9 +122,10 @@ def half_rows(dtype, iters, warmup):
                                   speedup_vs_sdpa=round(t["sdpa"][0] / t["kernel"][0], 2), max_abs_diff_vs_upcast=err)), flush=True)
 
 
-def backward_rows(iters, warmup):
+def backward_rows(iters, warmup, dtype="f32"):
     heads, batch = 8, 2
     bh = batch * heads
+    dt = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}[dtype]
 
     def fold(o):   # '(b h) n d -> b n (h d)'
         return o.reshape(batch, heads, o.shape[1], o.shape[2]).permute(0, 2, 1, 3).reshape(batch, o.shape[1], heads * o.shape[2])
@@ -128,20 +133,22 @@ def backward_rows(iters, warmup):
     for level, n, d, _ in LEVELS:
         for kind, n_k in (("self", n), ("cross", 77)):
             scale = d ** -0.5
-            q = torch.randn(bh, n, d, device="cuda", requires_grad=True)
-            k, v = (torch.randn(bh, n_k, d, device="cuda", requires_grad=True) for _ in range(2))
-            d_out = torch.randn(batch, n, heads * d, device="cuda")
+            q = torch.randn(bh, n, d, device="cuda").to(dt).requires_grad_(True)
+            k, v = (torch.randn(bh, n_k, d, device="cuda").to(dt).requires_grad_(True) for _ in range(2))
+            d_out = torch.randn(batch, n, heads * d, device="cuda").to(dt)
 
             def run(fwd):
                 q.grad = k.grad = v.grad = None
                 fwd().backward(d_out)
 
             fns = {
-                "kernel": lambda: run(lambda: engine.differentiable_attention(q, k, v, heads, scale)),
+                "kernel": lambda: run(lambda: engine.differentiable_attention(q, k, v, heads, scale, native_half=True)),
                 "stock": lambda: run(lambda: fold(torch.einsum("b i j, b j d -> b i d",
                                                                (torch.einsum("b i d, b j d -> b i j", q, k) * scale).softmax(dim=-1), v))),
                 "sdpa": lambda: run(lambda: fold(F.scaled_dot_product_attention(q, k, v, scale=scale))),
             }
+            if dtype != "f32":   # what the same tensors cost without the half kernels
+                fns["upcast"] = lambda: run(lambda: engine.differentiable_attention(q, k, v, heads, scale))
             grads, peak = {}, {}
             for name, fn in fns.items():
                 fn()
@@ -153,11 +160,15 @@ def backward_rows(iters, warmup):
                 fn()
                 torch.cuda.synchronize()
                 peak[name] = torch.cuda.max_memory_allocated() - base
-            err = max(float((a - b).abs().max()) for a, b in zip(grads["kernel"], grads["stock"]))
+            err = max(float((a.float() - b.float()).abs().max()) for a, b in zip(grads["kernel"], grads["stock"]))
             del grads
             t = timed_alternately(fns, iters, warmup)
             flop = (4.0 + 10.0) * bh * n * n_k * d   # forward 2 products, backward 5 (S, dP, dV, dK, dQ), 2 flop per multiply-add
-            print(json.dumps(dict(backward=True, level=level, kind=kind, n=n, n_k=n_k, d=d, heads=heads, batch=batch,
+            extra = {}
+            if dtype != "f32":
+                extra = dict(dtype=dtype, upcast_ms=round(t["upcast"][0], 4), upcast_peak_mib=round(peak["upcast"] / 2 ** 20, 2),
+                             speedup_vs_upcast=round(t["upcast"][0] / t["kernel"][0], 2))
+            print(json.dumps(dict(extra, backward=True, level=level, kind=kind, n=n, n_k=n_k, d=d, heads=heads, batch=batch,
                                   kernel_ms=round(t["kernel"][0], 4), kernel_min_ms=round(t["kernel"][1], 4),
                                   stock_ms=round(t["stock"][0], 4), sdpa_ms=round(t["sdpa"][0], 4),
                                   kernel_peak_mib=round(peak["kernel"] / 2 ** 20, 2), stock_peak_mib=round(peak["stock"] / 2 ** 20, 2),
@@ -176,7 +187,7 @@ def main():
     args = ap.parse_args()
     torch.manual_seed(0)
     if args.backward:
-        backward_rows(args.iters, args.warmup)
+        backward_rows(args.iters, args.warmup, args.dtype)
         return
     if args.dtype != "f32" and not args.sweep:
         half_rows(args.dtype, args.iters, args.warmup)
