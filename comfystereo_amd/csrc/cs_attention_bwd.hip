@@ -10,8 +10,8 @@
 //   k_attention_bwd_dkdv   a wave owns 32 keys and walks the query tiles; the NW waves of a workgroup own NW consecutive key tiles
 //                          of one (b h) and share the 32-query Q / dO tiles (and their lse / delta) in LDS;
 //   k_attention_bwd_dq     a wave owns 32 queries and walks the key tiles, like the forward; the workgroup shares K / V in LDS.
-// Every gradient element is accumulated by ONE lane in a fixed order and stored once: no atomics, and the result is bit for
-// bit the same from run to run.
+// Every gradient element is accumulated by ONE lane in a fixed order (dK and dV: a sum per query tile, added tile after tile) and
+// stored once: no atomics, and the result is bit for bit the same from run to run.
 //
 // Layouts: q, dq [(b h)][n][d]; k, v, dk, dv [(b h)][n_k][d]; out, d_out [(b)][n][(h d)]; lse, delta [(b h)][n].
 //
@@ -281,19 +281,34 @@ __global__ void __launch_bounds__(NW * 64) k_attention_bwd_dkdv(const float* __r
                 if constexpr (DK) dp[r] = p * (dp[r] - ev[t]);
             }
         }
-        // dV^T += dO^T . P, dK^T += Q^T . dS
+        // dV^T += dO^T . P, dK^T += Q^T . dS.  A tile's product is summed on its own (a chain of 32 queries from zero) and then
+        // added to the running total, as tools/attention_grad_oracle.grads_tiled states it: one chain over all n queries lets the
+        // rounding error grow with n (a single key, P = 1, n = 161: four times the reference's own float32 error in dV).
 #pragma unroll
         for (int b = 0; b < ND; b++) {
+            if constexpr (DV) {
+                ab_f16 t;
 #pragma unroll
-            for (int r = 0; r < 16; r++) {
-                if constexpr (DV) {
+                for (int r = 0; r < 16; r++) t[r] = 0.0f;
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
                     const float da = Ds[ab_row(r, hi) * SK + b * 32 + col];
-                    av[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(da, st[r], av[b], 0, 0, 0);
+                    t = __builtin_amdgcn_mfma_f32_32x32x2f32(da, st[r], t, 0, 0, 0);
                 }
-                if constexpr (DK) {
+#pragma unroll
+                for (int r = 0; r < 16; r++) av[b][r] += t[r];
+            }
+            if constexpr (DK) {
+                ab_f16 t;
+#pragma unroll
+                for (int r = 0; r < 16; r++) t[r] = 0.0f;
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
                     const float qa = Qs[ab_row(r, hi) * SK + b * 32 + col];
-                    ak[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(qa, dp[r], ak[b], 0, 0, 0);
+                    t = __builtin_amdgcn_mfma_f32_32x32x2f32(qa, dp[r], t, 0, 0, 0);
                 }
+#pragma unroll
+                for (int r = 0; r < 16; r++) ak[b][r] += t[r];
             }
         }
     }

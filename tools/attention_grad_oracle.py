@@ -69,6 +69,26 @@ def chain_dot(a, b):
     return acc
 
 
+def chain_rowdot(a, b):
+    """a, b [(b h), n, d] float32 -> sum_c a[., i, c] b[., i, c] [(b h), n] float32: chain_dot(a[:, i:i + 1], b[:, i:i + 1])[:, 0, 0]
+    for every row i at once, the same fmaf chain in the same column order."""
+    d = a.shape[-1]
+    order = [c for g in range(0, d, 8) for t in range(4) for c in (g + t, g + 4 + t) if c < d]
+    a64, b64 = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    acc = np.zeros(a.shape[:-1], np.float32)
+    for c in order:
+        acc = (acc.astype(np.float64) + a64[..., c] * b64[..., c]).astype(np.float32)
+    return acc
+
+
+def lse2_plain32(q, k, scale):
+    """lse2 in plain float32 numpy (matmul, max, exp2, sum, log2; no tiling): what float32 arithmetic reaches without any care."""
+    f = np.float32
+    s = np.matmul(np.asarray(q, f), np.asarray(k, f).transpose(0, 2, 1)) * f(f(scale) * f(LOG2E))
+    m = s.max(-1)
+    return (m + np.log2(np.exp2(s - m[..., None]).sum(-1, dtype=f))).astype(f)
+
+
 def grads_tiled(q, k, v, d_out, heads, scale):
     """float32, the kernels' tile order -> (dq, dk, dv, out, lse)"""
     f = np.float32
@@ -93,9 +113,7 @@ def grads_tiled(q, k, v, d_out, heads, scale):
         m = m_new
     o = (acc / l[..., None]).astype(f)
     lse = (m + np.log2(l).astype(f)).astype(f)
-    delta = np.zeros((bh, n), f)
-    for i in range(n):   # (row by row: the same chain as dP)
-        delta[:, i] = chain_dot(do[:, i:i + 1], o[:, i:i + 1])[:, 0, 0]
+    delta = chain_rowdot(do, o)   # (row by row: the same chain as dP)
     p = np.exp2(s2 - lse[..., None]).astype(f)
     dp = chain_dot(do, v)
     ds = (p * (dp - delta[..., None])).astype(f)

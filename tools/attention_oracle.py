@@ -62,6 +62,8 @@ def case_inputs(case):
     bh = case["chunks"] * s * b * heads
     if case["kind"] == "routing":
         return routing_inputs(rs, case, bh)
+    if case["kind"] == "ramp":
+        return ramp_inputs(rs, case, bh)
     g = np.float32(case.get("gain", 1.0))
     q = rs.standard_normal((bh, n, d)).astype(np.float32) * g
     k = rs.standard_normal((bh, n_k, d)).astype(np.float32) * g
@@ -90,6 +92,26 @@ def routing_inputs(rs, case, bh):
                 keys = np.concatenate([k6[ci, 0, j], k6[ci, 1, j]]) if case["mode"] == "bi" else k6[ci, 0, j]
                 q6[ci, si, j] = np.float32(1024.0) * keys[t6[ci, si, j]]
     return q6.reshape(bh, n, d), k, v
+
+
+def ramp_inputs(rs, case, bh):
+    """Scores that climb (or fall) steadily along the keys instead of i.i.d. noise: with a fixed unit vector u,
+    k_j = g_j u + noise, g_j rising linearly from 0 to A, and q_i = c_i u + noise, c_i in [0.9 A, 1.1 A] for even i and in
+    [-1.1 A, -0.9 A] for odd i, A^2 = span * sqrt(d): a query's scaled scores span about case['span'] nats from the first key to the
+    last.  For an even query the running maximum of the online softmax rises on every key tile and ends on the last key (every
+    earlier tile's accumulator is rescaled by alpha < 1, the first tiles' probabilities vanish against the final maximum); for an
+    odd query the maximum sits in tile 0 and the later tiles underflow.  Neighbouring keys differ by span / n_k nats, so the
+    softmax is spread over several keys, not one-hot.  Returns q, k, v."""
+    n, n_k, d = case["n"], case["n_k"], case["d"]
+    u = rs.standard_normal(d)
+    u /= np.sqrt((u * u).sum())
+    amp = np.sqrt(case["span"] * np.sqrt(d))
+    g = amp * np.arange(n_k) / max(n_k - 1, 1)
+    c = amp * (0.9 + 0.2 * rs.random_sample((bh, n))) * np.where(np.arange(n) % 2 == 0, 1.0, -1.0)
+    k = g[None, :, None] * u + case["noise"] * rs.standard_normal((bh, n_k, d))
+    q = c[..., None] * u + case["noise"] * rs.standard_normal((bh, n, d))
+    v = rs.standard_normal((bh, n_k, d))
+    return q.astype(np.float32), k.astype(np.float32), v.astype(np.float32)
 
 
 def routing_targets(case):
