@@ -34,6 +34,9 @@ PIL_FLAG = {"in_f32": 1, "gray": 2, "out_planar": 4}
 ATTN_MODE = {"self": 0, "uni": 1, "bi": 2}
 # enum cs_attn_dtype (the element type of cs_stereo_attention_half, cs_attention_half_fwd_lse and cs_attention_half_bwd)
 ATTN_DTYPE = {"float16": 0, "bfloat16": 1}
+# enum cs_latent_dtype / cs_latent_op (StereoDiffusion Standard mode's latent shift: cs_latent_shift_apply, cs_decode_to_codes)
+LATENT_DTYPE = {"float32": 0, "float16": 1, "bfloat16": 2}
+LATENT_OP = {"first": 0, "reshift": 1}
 
 # the ABI version the ctypes signatures below were written for (include/comfystereo_amd.h CS_ABI_VERSION)
 ABI_VERSION = 4
@@ -50,6 +53,7 @@ EXPORTS = [
     "cs_stereo_attention_max_head_dim", "cs_stereo_attention", "cs_stereo_attention_half",
     "cs_attention_fwd_lse", "cs_attention_bwd_workspace_bytes", "cs_attention_bwd",
     "cs_attention_half_fwd_lse", "cs_attention_half_bwd_workspace_bytes", "cs_attention_half_bwd",
+    "cs_latent_shift_plan_workspace_bytes", "cs_latent_shift_plan", "cs_latent_shift_apply", "cs_decode_to_codes",
 ]
 
 # enum cs_debug_key (development switches; tests and profiling tools only)
@@ -241,6 +245,14 @@ def lib():
     L.cs_attention_half_bwd_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int]
     L.cs_attention_half_bwd.restype = c_int
     L.cs_attention_half_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, c_double, vp, c_size, vp]
+    L.cs_latent_shift_plan_workspace_bytes.restype = c_size
+    L.cs_latent_shift_plan_workspace_bytes.argtypes = []
+    L.cs_latent_shift_plan.restype = c_int
+    L.cs_latent_shift_plan.argtypes = [vp, c_int, c_int, c_int, c_double, c_double, vp, vp, c_size, vp]
+    L.cs_latent_shift_apply.restype = c_int
+    L.cs_latent_shift_apply.argtypes = [vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, vp]
+    L.cs_decode_to_codes.restype = c_int
+    L.cs_decode_to_codes.argtypes = [vp, c_int, c_int, c_int, c_int, c_int, vp, vp]
     _lib = L
     return L
 

@@ -228,19 +228,10 @@ __global__ void __launch_bounds__(256) k_stereo_shift(const float* __restrict__ 
     const bool flat = !(rng > 1.1920929e-07f);   // torch.finfo(float32).eps (:40)
     const float* drow = depth + ((size_t)b * h + row) * w;
     for (int col = tid; col < w; col += blockDim.x) {
-        const float nd = flat ? 0.0f : (1.0f * (drow[col] - mn)) / rng;
-        float dv;
-        if (pow_mode == 1) dv = nd;                      // torch.pow special-cases 1, 2 and 0.5
-        else if (pow_mode == 2) dv = nd * nd;
-        else if (pow_mode == 3) dv = sqrtf(nd);
-        else dv = csm::powf_exact(nd, e32, &T);          // (other exponents: libm powf; torch's scalar pow may differ in the last ulp)
-        const float prod = dv * scale_px32;
-        if (fabsf(prod) < 1.0e9f) {
-            const int cd = col + (int)prod;              // int() truncates toward zero (:64)
-            if (cd >= 0 && cd < w) {
-                if (asc) atomicMax(&win[cd], col);
-                else atomicMin(&win[cd], col);
-            }
+        int cd;
+        if (stereo_shift_dest(drow[col], mn, rng, flat, pow_mode, e32, scale_px32, col, w, &T, cd)) {
+            if (asc) atomicMax(&win[cd], col);
+            else atomicMin(&win[cd], col);
         }
     }
     __syncthreads();
@@ -1316,7 +1307,7 @@ int cs_stereo_shift(const float* input, const float* depth, int b, int c, int h,
     if (total >= (1ull << 31)) return fail(CS_ELIMIT, "depth tensor too large");
     hipLaunchKernelGGL(k_minmax, dim3(grid_for(total, 256), 1), dim3(256), 0, stream, depth, (int)total, stats, ST_L_MIN, ST_L_MAX);
     const double e = stereo_offset_exponent;
-    const int pow_mode = e == 1.0 ? 1 : (e == 2.0 ? 2 : (e == 0.5 ? 3 : 0));
+    const int pow_mode = stereo_shift_pow_mode(e);
     const size_t half = (size_t)b * c * h * w;
     const double balance = shift_both ? 0.5 : 0.0;
     for (int eye = 0; eye < 2; eye++) {
@@ -1333,6 +1324,61 @@ int cs_stereo_shift(const float* input, const float* depth, int b, int c, int h,
     }
     hipError_t er = hipGetLastError();
     return er == hipSuccess ? CS_OK : fail_hip(er, "cs_stereo_shift");
+}
+
+size_t cs_latent_shift_plan_workspace_bytes(void) { return al256(ST_WORDS * 4); }
+
+int cs_latent_shift_plan(const float* disp, int b, int h, int w, double scale_factor, double stereo_offset_exponent, int32_t* src_col,
+                         void* workspace, size_t workspace_bytes, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!disp || !src_col || !workspace) return fail(CS_EINVAL, "null pointer");
+    if (b <= 0 || h <= 0 || w <= 0) return fail(CS_EINVAL, "non-positive size");
+    if (!(scale_factor - scale_factor == 0.0) || !(stereo_offset_exponent - stereo_offset_exponent == 0.0))
+        return fail(CS_EINVAL, "cs_latent_shift_plan: scale_factor and stereo_offset_exponent must be finite");
+    // the destination table of a row stays within 32 KiB of LDS; the scan costs w * reach reads per row: made for latents
+    if (w > 8192) return fail(CS_ELIMIT, "cs_latent_shift_plan: rows of more than 8192 columns");
+    if (b > 65535) return fail(CS_ELIMIT, "cs_latent_shift_plan: more than 65 535 images in one call");
+    const size_t total = (size_t)b * h * w;
+    if (total >= (1ull << 31)) return fail(CS_ELIMIT, "depth tensor too large");
+    if (workspace_bytes < cs_latent_shift_plan_workspace_bytes()) return fail(CS_EWORKSPACE, "workspace too small");
+    // the stats pre-pass of cs_stereo_shift: one "frame" = the whole tensor (reference stereo_utils.py:36-45)
+    uint32_t* stats = (uint32_t*)workspace;
+    hipLaunchKernelGGL(k_stats_init, dim3(1), dim3(256), 0, stream, stats, 1);
+    hipLaunchKernelGGL(k_minmax, dim3(grid_for(total, 256), 1), dim3(256), 0, stream, disp, (int)total, stats, ST_L_MIN, ST_L_MAX);
+    const double scale_px = ((-1 * scale_factor) / 100.0) * (double)w;   // the right view with balance 0 (:54, :84-86)
+    hipError_t e = launch_latent_shift_plan(disp, b, h, w, stats, scale_px, stereo_offset_exponent, src_col, stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_latent_shift_plan");
+}
+
+static size_t latent_elem_bytes(int dtype) { return dtype == CS_LATENT_F32 ? 4 : 2; }
+
+int cs_latent_shift_apply(const void* left, void* right, const int32_t* src_col, uint8_t* mask, const void* noise, int dtype, int b,
+                          int c, int h, int w, int op, void* stream) {
+    if (!left || !right || !src_col) return fail(CS_EINVAL, "null pointer");
+    if (!mask) return fail(CS_EINVAL, op == CS_LATENT_RESHIFT ? "cs_latent_shift_apply: CS_LATENT_RESHIFT reads the mask CS_LATENT_FIRST stored"
+                                                               : "null pointer");
+    if (b <= 0 || c <= 0 || h <= 0 || w <= 0) return fail(CS_EINVAL, "non-positive size");
+    if (dtype < CS_LATENT_F32 || dtype > CS_LATENT_BF16) return fail(CS_EINVAL, "cs_latent_shift_apply: unknown dtype (CS_LATENT_F32 / F16 / BF16)");
+    if (op != CS_LATENT_FIRST && op != CS_LATENT_RESHIFT) return fail(CS_EINVAL, "cs_latent_shift_apply: unknown op (CS_LATENT_FIRST / RESHIFT)");
+    const size_t eb = latent_elem_bytes(dtype), bytes = (size_t)b * c * h * w * eb;
+    if (((uintptr_t)left | (uintptr_t)right | (uintptr_t)noise) & (eb - 1)) return fail(CS_EINVAL, "cs_latent_shift_apply: misaligned tensor");
+    if ((uintptr_t)src_col & 3) return fail(CS_EINVAL, "cs_latent_shift_apply: misaligned src_col");
+    if (overlaps(right, bytes, left, bytes) || overlaps(right, bytes, noise, bytes))
+        return fail(CS_EINVAL, "cs_latent_shift_apply: right must not overlap left or noise");
+    hipError_t e = launch_latent_shift_apply(left, right, src_col, mask, noise, dtype, b, c, h, w, op, (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_latent_shift_apply");
+}
+
+int cs_decode_to_codes(const void* image, int dtype, int n, int c, int h, int w, uint8_t* codes_nhwc, void* stream) {
+    if (!image || !codes_nhwc) return fail(CS_EINVAL, "null pointer");
+    if (n <= 0 || c <= 0 || h <= 0 || w <= 0) return fail(CS_EINVAL, "non-positive size");
+    if (dtype < CS_LATENT_F32 || dtype > CS_LATENT_BF16) return fail(CS_EINVAL, "cs_decode_to_codes: unknown dtype (CS_LATENT_F32 / F16 / BF16)");
+    const size_t count = (size_t)n * c * h * w;
+    if ((uintptr_t)image & (latent_elem_bytes(dtype) - 1)) return fail(CS_EINVAL, "cs_decode_to_codes: misaligned image");
+    if (overlaps(codes_nhwc, count, image, count * latent_elem_bytes(dtype)))
+        return fail(CS_EINVAL, "cs_decode_to_codes: codes must not overlap image");
+    hipError_t e = launch_decode_to_codes(image, dtype, n, c, h, w, codes_nhwc, (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_decode_to_codes");
 }
 
 int cs_stereo_attention_max_head_dim(void) { return stereo_attention_max_head_dim(); }

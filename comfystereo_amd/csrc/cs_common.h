@@ -169,6 +169,25 @@ __device__ __forceinline__ void block_minmax_update(float mn, float mx, uint32_t
     __syncthreads();
 }
 
+// ---- stereo_shift_torch's destination column (reference stereo_utils.py:36-45, :64-66), shared by k_stereo_shift and
+// k_latent_shift_plan: the depth normalised with the tensor's min / max (`flat`: the range is within eps, everything 0), raised
+// to the exponent (pow_mode 1 / 2 / 3: torch.pow's special cases 1, 2 and 0.5; 0: libm powf), times scale_px in float32 and
+// truncated toward zero.  False: the pixel leaves the row (or the product is no number).
+__device__ __forceinline__ bool stereo_shift_dest(float d, float mn, float rng, bool flat, int pow_mode, float e32, float scale_px32,
+                                                  int col, int w, const csm::PowfTables* T, int& cd) {
+    const float nd = flat ? 0.0f : (1.0f * (d - mn)) / rng;
+    float dv;
+    if (pow_mode == 1) dv = nd;                      // torch.pow special-cases 1, 2 and 0.5
+    else if (pow_mode == 2) dv = nd * nd;
+    else if (pow_mode == 3) dv = sqrtf(nd);
+    else dv = csm::powf_exact(nd, e32, T);           // (other exponents: libm powf; torch's scalar pow may differ in the last ulp)
+    const float prod = dv * scale_px32;
+    if (!(fabsf(prod) < 1.0e9f)) return false;
+    cd = col + (int)prod;                            // int() truncates toward zero (:64)
+    return cd >= 0 && cd < w;
+}
+__host__ __device__ __forceinline__ int stereo_shift_pow_mode(double e) { return e == 1.0 ? 1 : (e == 2.0 ? 2 : (e == 0.5 ? 3 : 0)); }
+
 // ---- grid of the tile kernels that give a workgroup to one (tile, row, EYE): k_polypoint, k_polytile, k_hybrid_splat_tile ----
 // blockIdx.x = tile * 8 + (row & 7): workgroup b runs on XCD b % 8 (observed dispatch order, MI355X_MICROARCH.md; speed only),
 // so all tiles of a row share one L2.  blockIdx.y (two-eye launches): the two eyes of a GROUP of 8 << CS_EYE_GROUP rows follow

@@ -213,6 +213,14 @@ size_t attention_half_bwd_workspace_bytes(int b, int h, int n, int n_k, int d);
 hipError_t launch_attention_half_bwd(const void* q, const void* k, const void* v, const void* out, const float* lse, const void* d_out,
                                      void* dq, void* dk, void* dv, int dtype, int b, int h, int n, int n_k, int d, float scale,
                                      void* workspace, hipStream_t stream);
+// cs_latentshift.hip (StereoDiffusion Standard mode's latent shift, mask and merge, and the decoded images' codes:
+// cs_latent_shift_plan, cs_latent_shift_apply, cs_decode_to_codes).  stats: ST_L_MIN / ST_L_MAX = the depth tensor's min / max;
+// dtype: enum cs_latent_dtype; op: enum cs_latent_op
+hipError_t launch_latent_shift_plan(const float* depth, int b, int h, int w, const uint32_t* stats, double scale_px, double exponent,
+                                    int32_t* src_col, hipStream_t stream);
+hipError_t launch_latent_shift_apply(const void* left, void* right, const int32_t* src_col, uint8_t* mask, const void* noise,
+                                     int dtype, int b, int c, int h, int w, int op, hipStream_t stream);
+hipError_t launch_decode_to_codes(const void* image, int dtype, int n, int c, int h, int w, uint8_t* codes, hipStream_t stream);
 // lazy depth-blur tiles in k_gpuwarp (tilemap != nullptr): rows of at most this many columns, not the mesh-quality warp
 int gpuwarp_lazy_max_width();
 

@@ -20,6 +20,10 @@ None is refused with TypeError, an attention mask with ValueError (Stable Diffus
 The replaced forwards are saved the way stereo_utils.register_attention_editor_diffusers saves them: stereo_utils.restore_attention
 undoes this hook too, and an editor registered later stacks on top of it.
 
+`diffusion_step`, `diffusion_step_no_cfg`, `init_latent` (reference :29-129): the reference's names, argument order and defaults.
+They are a few calls into the caller's UNet and scheduler and run on whatever device the tensors are on; stereodiffusion_nodes.
+text2stereoimage builds the Standard mode's loop from them.
+
 No CPU fallback: without a GPU the installed forward raises RuntimeError."""
 import torch
 import torch.nn as nn
@@ -100,3 +104,32 @@ def register_attention_control(model, controller):
         elif "mid" in name:
             total += walk(net, 0, "mid")
     return total
+
+
+def diffusion_step(model, controller, latents, context, t, guidance_scale, low_resource=False):
+    """One denoising step with classifier-free guidance (reference :29-66): context = [unconditional, conditional] embeddings;
+    low_resource runs the UNet once per half instead of once on the doubled batch."""
+    unet_in = model.scheduler.scale_model_input(latents, t)
+    if low_resource:
+        uncond = model.unet(unet_in, t, encoder_hidden_states=context[0])["sample"]
+        cond = model.unet(unet_in, t, encoder_hidden_states=context[1])["sample"]
+    else:
+        uncond, cond = model.unet(torch.cat([unet_in, unet_in]), t, encoder_hidden_states=context)["sample"].chunk(2)
+    guided = uncond + guidance_scale * (cond - uncond)
+    return controller.step_callback(model.scheduler.step(guided, t, latents)["prev_sample"])
+
+
+def diffusion_step_no_cfg(model, controller, latents, context, t):
+    """One denoising step without guidance (reference :69-98): one UNet call on the conditional embeddings alone."""
+    unet_in = model.scheduler.scale_model_input(latents, t)
+    noise_pred = model.unet(unet_in, t, encoder_hidden_states=context)["sample"]
+    return controller.step_callback(model.scheduler.step(noise_pred, t, latents)["prev_sample"])
+
+
+def init_latent(latent, model, height, width, generator, batch_size):
+    """-> (latent, latents): the starting latent [1,C,height/8,width/8] (drawn from `generator` when None is given) and its
+    view expanded to batch_size on the model's device (reference :101-129)."""
+    channels = model.unet.in_channels
+    if latent is None:
+        latent = torch.randn((1, channels, height // 8, width // 8), generator=generator)
+    return latent, latent.expand(batch_size, channels, height // 8, width // 8).to(model.device)

@@ -668,3 +668,114 @@ def differentiable_attention(q, k, v, heads, scale, native_half=False):
         return _DifferentiableAttention.apply(q.contiguous(), k.contiguous(), v.contiguous(), int(heads), float(scale))
     out = _DifferentiableAttention.apply(q.float().contiguous(), k.float().contiguous(), v.float().contiguous(), int(heads), float(scale))
     return out.to(q.dtype)
+
+
+# ---- StereoDiffusion Standard mode's latent shift, mask and merge (cs_latent_shift_*, cs_decode_to_codes) ----
+_LATENT_DTYPES = {torch.float32: "float32", torch.float16: "float16", torch.bfloat16: "bfloat16"}
+
+
+def _need_device(t):
+    """After the argument checks: the tensor must be on the GPU (the package's RuntimeError where there is none at all)."""
+    if not t.is_cuda:
+        if not torch.cuda.is_available():
+            raise RuntimeError("comfystereo_amd needs an MI355X (PyTorch-ROCm `cuda` device); there is no CPU fallback")
+        _dev(t)
+
+
+def latent_shift_plan(disp, scale_factor, stereo_offset_exponent=1.0):
+    """cs_latent_shift_plan on a device tensor: disp [B,H,W] float32, the disparity at the latents' size -> src_col int32
+    [B,H,W]: for every destination column of the right view of stereo_shift_torch(latents, disp, scale_factor) the source
+    column that ends up there, -1 in a hole.  Made once per image: the table does not depend on the latents."""
+    if not isinstance(disp, torch.Tensor):
+        raise ValueError("disp must be a torch.Tensor")
+    if disp.dtype != torch.float32:
+        raise ValueError(f"disp must be float32 (the reference's disparity dtype), got {disp.dtype}")
+    if disp.dim() != 3:
+        raise ValueError(f"disp must be [B,H,W], got shape {tuple(disp.shape)}")
+    if disp.numel() == 0:
+        raise ValueError(f"empty disp {tuple(disp.shape)}")
+    if not disp.is_contiguous():
+        raise ValueError("disp must be contiguous")
+    if not (math.isfinite(float(scale_factor)) and math.isfinite(float(stereo_offset_exponent))):
+        raise ValueError(f"scale_factor and stereo_offset_exponent must be finite, got {scale_factor} and {stereo_offset_exponent}")
+    b, h, w = disp.shape
+    if w > 8192:
+        raise ValueError(f"rows of {w} columns: cs_latent_shift_plan takes up to 8192 (it is made for latents)")
+    _need_device(disp)
+    L = _native.lib()
+    src_col = torch.empty((b, h, w), dtype=torch.int32, device=disp.device)
+    nb = L.cs_latent_shift_plan_workspace_bytes()
+    ws = torch.empty((max(nb, 256),), dtype=torch.uint8, device=disp.device)
+    with torch.cuda.device(disp.device):
+        _native.check(L.cs_latent_shift_plan(_ptr(disp), b, h, w, float(scale_factor), float(stereo_offset_exponent), _ptr(src_col),
+                                             _ptr(ws), max(nb, 256), _stream()))
+    return src_col
+
+
+def latent_shift_apply(left, right, src_col, mask, op, noise=None):
+    """cs_latent_shift_apply on device tensors, in place on `right` and `mask`: left, right (and noise) [B,C,H,W] of one dtype
+    (float32, float16, bfloat16), contiguous -- they may be the two halves of one [2B,C,H,W] tensor; src_col int32 [B,H,W] from
+    latent_shift_plan; mask uint8 [B,H,W].
+    op "first": right = left gathered through src_col (0 in a hole), mask = (channel 0 of that != 0), and with `noise` right =
+    noise wherever the mask is 0.  op "reshift": right = left gathered wherever the mask "first" stored is 1; the rest of right
+    stays.  Values are moved, never computed.  Returns right."""
+    if op not in _native.LATENT_OP:
+        raise ValueError(f"unknown op {op!r} (first, reshift)")
+    if noise is not None and op != "first":
+        raise ValueError("noise goes with op 'first' only")
+    tensors = [("left", left), ("right", right)] + ([("noise", noise)] if noise is not None else [])
+    for name, t in tensors:
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch.Tensor")
+        if t.dtype not in _LATENT_DTYPES:
+            raise ValueError(f"{name} must be float32, float16 or bfloat16, got {t.dtype}")
+        if t.dtype != left.dtype:
+            raise ValueError(f"left, right and noise must share one dtype, got {left.dtype} and {t.dtype} ({name})")
+        if t.dim() != 4 or tuple(t.shape) != tuple(left.shape):
+            raise ValueError(f"{name} must be [B,C,H,W] like left {tuple(left.shape)}, got shape {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+        if t.requires_grad:
+            raise ValueError(f"{name} requires grad: cs_latent_shift_apply works in place")
+    b, c, h, w = left.shape
+    if left.numel() == 0:
+        raise ValueError(f"empty latents {tuple(left.shape)}")
+    if not isinstance(src_col, torch.Tensor) or src_col.dtype != torch.int32 or tuple(src_col.shape) != (b, h, w) or not src_col.is_contiguous():
+        raise ValueError(f"src_col must be a contiguous int32 tensor {(b, h, w)} (latent_shift_plan's)")
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or tuple(mask.shape) != (b, h, w) or not mask.is_contiguous():
+        raise ValueError(f"mask must be a contiguous uint8 tensor {(b, h, w)}")
+    for name, t in tensors[1:] + [("src_col", src_col), ("mask", mask)]:
+        if t.device != left.device:
+            raise ValueError(f"left and {name} must be on the same device")
+    _need_device(left)
+    L = _native.lib()
+    with torch.cuda.device(left.device):
+        _native.check(L.cs_latent_shift_apply(_ptr(left), _ptr(right), _ptr(src_col), _ptr(mask),
+                                              _ptr(noise) if noise is not None else None,
+                                              _native.LATENT_DTYPE[_LATENT_DTYPES[left.dtype]], b, c, h, w, _native.LATENT_OP[op],
+                                              _stream()))
+    return right
+
+
+def decode_to_codes(image):
+    """cs_decode_to_codes on a device tensor: image [N,C,H,W] float32, float16 or bfloat16, the VAE's output -> uint8 [N,H,W,C]:
+    trunc(nan_to_num((image / 2 + 0.5).clamp(0, 1)).float() * 255), the quotient and the sum rounded to the tensor's dtype as
+    torch rounds them (reference stereodiffusion_nodes.py:673-677)."""
+    if not isinstance(image, torch.Tensor):
+        raise ValueError("image must be a torch.Tensor")
+    if image.dtype not in _LATENT_DTYPES:
+        raise ValueError(f"image must be float32, float16 or bfloat16, got {image.dtype}")
+    if image.dim() != 4:
+        raise ValueError(f"image must be [N,C,H,W], got shape {tuple(image.shape)}")
+    if image.numel() == 0:
+        raise ValueError(f"empty image {tuple(image.shape)}")
+    if not image.is_contiguous():
+        raise ValueError("image must be contiguous")
+    _need_device(image)
+    n, c, h, w = image.shape
+    L = _native.lib()
+    codes = torch.empty((n, h, w, c), dtype=torch.uint8, device=image.device)
+    with torch.cuda.device(image.device):
+        _native.check(L.cs_decode_to_codes(_ptr(image), _native.LATENT_DTYPE[_LATENT_DTYPES[image.dtype]], n, c, h, w, _ptr(codes),
+                                           _stream()))
+    return codes

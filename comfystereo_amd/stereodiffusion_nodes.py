@@ -1,24 +1,38 @@
-"""StereoDiffusion's Fast mode around its inpainting model (reference stereodiffusion_nodes.py,
-StereoDiffusionNode._generate_stereo_fast and _generate_stereo_fast_single):
+"""StereoDiffusion's two modes around their models (reference stereodiffusion_nodes.py).
+
+Fast mode, around its inpainting model (StereoDiffusionNode._generate_stereo_fast and _generate_stereo_fast_single):
 
     generate_stereo_fast  the whole per-frame work of the mode at any frame size, batched, with the model as a callback (:378-573)
     pil_resize            PIL.Image.resize(size) with Pillow's defaults (8-bit bicubic), byte for byte (:422-423, :481-482, :569-570)
     prepare_inpaint       the backward warp, the inpaint mask and the gap pre-fill handed to the model (:425-542)
     compose_stereo        the model's pixels pasted back under the mask and the side-by-side pair (:563-571)
 
-The arithmetic of pil_resize and prepare_inpaint runs in the HIP kernels behind cs_pil_resize and cs_inpaint_prepare (there is no
-CPU fallback: without a GPU they raise); compose_stereo is a `where` and a concatenation, plain torch plumbing on whatever device
-its tensors are on.
+Standard mode, around its UNet, VAE and scheduler (_generate_stereo_impl and _text2stereoimage):
+
+    generate_stereo_standard  the tensor work of the mode: codes, gray, the resizes to 512 x 512, the disparity, the loop, the
+                              resizes back into the side-by-side float frame (:249-307), with the inversion as a callback
+    text2stereoimage          the denoising loop with BNAttention installed, the latent shift at 20 % of the steps and its
+                              re-application every 20 %, the VAE decode and the uint8 codes (:576-682)
+
+The arithmetic of pil_resize and prepare_inpaint runs in the HIP kernels behind cs_pil_resize and cs_inpaint_prepare, the latent
+shift, its mask and merge and the codes of the decoded images in those behind cs_latent_shift_plan, cs_latent_shift_apply and
+cs_decode_to_codes (there is no CPU fallback: without a GPU they raise); compose_stereo is a `where` and a concatenation, plain
+torch plumbing on whatever device its tensors are on.  The Standard loop makes the shift table once, applies it with one launch
+per shift step and never indexes with a boolean mask, so it does not wait for the device and a step can be captured in a graph.
 
 A coloured depth is made gray as trunc((r * 0.2989 + g * 0.5870) + b * 0.1140) in float64, in this order.  That equals the
 reference on every depth with three equal channels; on a few hundred of the 2^24 colours the reference's BLAS product differs
 from it, and from itself between array shapes.
 
-Out of scope: loading and running the diffusion model itself -- generate_stereo_fast calls the `inpaint` it is given.
+Out of scope: loading and running the diffusion models themselves -- generate_stereo_fast calls the `inpaint` it is given,
+generate_stereo_standard the `invert` it is given (where the reference runs NullInversion.invert) and the UNet, VAE, text encoder
+and scheduler of the `model` it is given; null-text inversion itself and the ComfyUI and diffusers model wrappers are not here.
 """
 import torch
+import torch.nn.functional as F
 
-from . import engine
+from . import engine, stereo_utils
+from .diffusion_utils import diffusion_step, init_latent
 
 
 def prepare_inpaint(image, depth, scale_factor, threshold=0.05):
@@ -140,6 +154,185 @@ def generate_stereo_fast(image, depth_map, scale_factor, inpaint, threshold=0.05
     stereo = torch.empty((n, h, 2 * w, 3), dtype=torch.float32, device=dev)
     engine.pil_resize(left_u8, (w, h), f32="nhwc", codes=False, f32_out=stereo[:, :, :w])
     engine.pil_resize(right_u8, (w, h), f32="nhwc", codes=False, f32_out=stereo[:, :, w:])
+    if host:
+        stereo = stereo.cpu()
+    return stereo, stereo[:, :, :w], stereo[:, :, w:]
+
+
+# ---- Standard mode (reference :208-307, :576-682) ------------------------------------------------------------------------------
+class _EmptyControl:
+    """The controller the reference's loop passes to diffusion_step (inversion.py EmptyControl): it changes nothing."""
+
+    def step_callback(self, x_t):
+        return x_t
+
+
+def _shift_steps(num_inference_steps):
+    """(shift_step, reshift_interval): both 20 % of the steps, at least 1 (:626-628)."""
+    k = max(1, int(num_inference_steps * 0.2))
+    return k, k
+
+
+def _disparity_to_latent(disparity, size):
+    """The disparity [B,H,W] at the latents' size (:617-622)."""
+    return F.interpolate(disparity.unsqueeze(1), size=list(size), mode="bicubic", align_corners=False).squeeze(1).contiguous()
+
+
+class _StandardLoop:
+    """What the loop of _text2stereoimage carries from step to step (:624-667): the shift table, made once; the mask the
+    first shift stores; the noise of `deblur`.  step() is one iteration; it launches kernels and nothing else."""
+
+    def __init__(self, model, disp_latent, scale_factor, deblur, num_inference_steps, guidance_scale, noise):
+        self.model, self.guidance_scale, self.controller = model, guidance_scale, _EmptyControl()
+        self.shift_step, self.reshift_interval = _shift_steps(num_inference_steps)
+        self.src_col = engine.latent_shift_plan(disp_latent, scale_factor)
+        self.mask = torch.zeros(tuple(disp_latent.shape), dtype=torch.uint8, device=disp_latent.device)
+        self.noise = noise if deblur else None   # [1,C,h,w]: the right view's
+        self.shifted = False
+
+    def step(self, i, t, latents, context):
+        latents = diffusion_step(self.model, self.controller, latents, context, t, self.guidance_scale, low_resource=False)
+        if i == self.shift_step:
+            latents = latents.contiguous()
+            engine.latent_shift_apply(latents[:1], latents[1:], self.src_col, self.mask, "first", noise=self.noise)
+            self.shifted = True
+        elif self.shifted and i > self.shift_step and i % self.reshift_interval == 0:
+            latents = latents.contiguous()
+            engine.latent_shift_apply(latents[:1], latents[1:], self.src_col, self.mask, "reshift")
+        return latents
+
+
+@torch.no_grad()
+def _stereo_latents(model, prompt, uncond_embeddings, latent, disparity, scale_factor, direction, deblur, num_inference_steps,
+                    guidance_scale, noise=None, generator=None, on_step=None):
+    """The loop of text2stereoimage without the decode -> (latents [2,C,h,w], mask uint8 [1,h,w] or None when the loop never
+    reached the shift step).  on_step(i, latents) sees the latents after every iteration."""
+    if not (isinstance(prompt, (list, tuple)) and len(prompt) == 2 and all(isinstance(p, str) for p in prompt)):
+        raise ValueError("prompt must be a list of two strings (the left and the right view)")
+    if direction not in ("uni", "bi"):
+        raise ValueError(f"direction must be 'uni' or 'bi', got {direction!r}")
+    if not isinstance(num_inference_steps, int) or isinstance(num_inference_steps, bool) or num_inference_steps < 1:
+        raise ValueError(f"num_inference_steps must be a positive int, got {num_inference_steps!r}")
+    if latent is not None and not (isinstance(latent, torch.Tensor) and latent.dim() == 4 and latent.is_floating_point()):
+        raise ValueError("latent must be None or a float tensor [1 or 2,C,h,w]")
+    if not (isinstance(disparity, torch.Tensor) and disparity.dim() == 3 and disparity.shape[0] == 1 and disparity.dtype == torch.float32):
+        raise ValueError("disparity must be a float32 tensor [1,H,W]")
+    if noise is not None and not (isinstance(noise, torch.Tensor) and noise.dim() == 4 and noise.shape[0] == 2):
+        raise ValueError("noise must be None or a tensor [2,C,h,w] like the latents (the right view's half is used)")
+    stereo_utils._need_gpu()
+    steps = num_inference_steps
+    editor = stereo_utils.BNAttention(start_step=max(1, int(steps * 0.2)), total_steps=steps, direction=direction)
+    stereo_utils.register_attention_editor_diffusers(model, editor)
+    try:
+        batch_size = len(prompt)
+        height = width = WORK_SIZE
+        tok = model.tokenizer
+        text_input = tok(list(prompt), padding="max_length", max_length=tok.model_max_length, truncation=True, return_tensors="pt")
+        text_embeddings = model.text_encoder(text_input.input_ids.to(model.device))[0]
+        uncond_emb = None
+        if uncond_embeddings is None:
+            uncond_input = tok([""] * batch_size, padding="max_length", max_length=tok.model_max_length, return_tensors="pt")
+            uncond_emb = model.text_encoder(uncond_input.input_ids.to(model.device))[0]
+        _, latents = init_latent(latent, model, height, width, generator, batch_size)
+        if not latents.is_cuda:
+            raise ValueError(f"the model's device must be the GPU, got latents on {latents.device}")
+        if latents.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise ValueError(f"latents must be float32, float16 or bfloat16, got {latents.dtype}")
+        model.scheduler.set_timesteps(steps)
+        disp_latent = _disparity_to_latent(disparity.to(latents.device), latents.shape[-2:])
+        if deblur:
+            if noise is None:
+                # a generator draws on its own device (the reference's is a CPU one); the result goes to the latents'
+                where = generator.device if generator is not None else latents.device
+                noise = torch.randn(tuple(latents.shape), generator=generator, device=where, dtype=latents.dtype)
+            elif tuple(noise.shape) != tuple(latents.shape):
+                raise ValueError(f"noise {tuple(noise.shape)} must have the latents' shape {tuple(latents.shape)}")
+            noise = noise.to(latents.device, latents.dtype)[1:].contiguous()
+        loop = _StandardLoop(model, disp_latent, scale_factor, deblur, steps, guidance_scale, noise)
+        for i, t in enumerate(model.scheduler.timesteps[-steps:]):
+            if uncond_embeddings is not None:
+                context = torch.cat([uncond_embeddings[i].expand(*text_embeddings.shape), text_embeddings])
+            else:
+                context = torch.cat([uncond_emb, text_embeddings])
+            latents = loop.step(i, t, latents, context)
+            if on_step is not None:
+                on_step(i, latents)
+        return latents, (loop.mask if loop.shifted else None)
+    finally:
+        stereo_utils.restore_attention(model)   # (the reference leaves its hooks in place when the loop raises)
+
+
+@torch.no_grad()
+def text2stereoimage(model, prompt, uncond_embeddings, latent, disparity, scale_factor, direction, deblur, num_inference_steps,
+                     guidance_scale, noise=None, generator=None):
+    """StereoDiffusionNode._text2stereoimage (:576-682) on the device -> uint8 [2,512,512,3], the left and the right view.
+    model: the reference's `ldm_stable`, duck-typed: tokenizer, text_encoder, unet, vae, scheduler, device.  prompt: two strings;
+    uncond_embeddings: one embedding per step (null-text inversion's) or None (the empty prompt's); latent [2,C,64,64] (the
+    inverted x_t twice) or None; disparity float32 [1,512,512].  BNAttention is installed from step max(1, int(steps * 0.2)) on
+    and removed again whatever happens; at that step the right view becomes the shifted left view (deblur: with noise in the
+    holes), and every so many steps again under the mask of the first shift.  noise: the tensor [2,C,64,64] the deblur fill
+    draws from (its right-view half); None: torch.randn in the latents' dtype, from `generator` when given -- on the generator's
+    device (a CPU generator, the reference's kind, also serves init_latent when latent is None; a device generator needs a
+    latent), moved to the latents' --, on the latents' device otherwise.
+    Runs under torch.no_grad() like the reference (:575), the VAE decode included: a caller that has gradients enabled for the
+    inversion need not switch them off.  The loop does not wait for the device."""
+    latents, _ = _stereo_latents(model, prompt, uncond_embeddings, latent, disparity, scale_factor, direction, deblur,
+                                 num_inference_steps, guidance_scale, noise, generator)
+    image = model.vae.decode(1 / 0.18215 * latents)["sample"]
+    return engine.decode_to_codes(image.contiguous())
+
+
+def _norm_depth(depth):
+    """The reference's _norm_depth (:39-47) without reading the range back: (depth - min) / (max - min), zeros when the range is
+    within float32's eps."""
+    mn, mx = depth.min(), depth.max()
+    rng = mx - mn
+    return torch.where(rng > torch.finfo(torch.float32).eps, 1 * (depth - mn) / rng, torch.zeros_like(depth))
+
+
+def generate_stereo_standard(image, depth_map, scale_factor, direction, deblur, num_inference_steps, guidance_scale, model, invert,
+                             noise=None, generator=None):
+    """The tensor work of StereoDiffusionNode._generate_stereo_impl (:249-307) around its models.
+    image [N,H,W,3] float; depth_map [N,H,W,3], [N,H,W,1] or [N,H,W] float (three channels are made gray): only the first frame
+    is processed, as in the reference.  invert(image_u8 [512,512,3] uint8, on the device) -> (x_t [1,C,64,64], uncond_embeddings
+    or None): it stands where the reference calls NullInversion.invert.  model, direction, deblur, noise, generator: as for
+    text2stereoimage.  -> (stereo [1,H,2W,3], left [1,H,W,3], right [1,H,W,3]) float32, left and right being the two halves of
+    stereo.  Host tensors go to the device and the results come back to the host; device tensors stay where they are."""
+    if not (isinstance(image, torch.Tensor) and isinstance(depth_map, torch.Tensor)):
+        raise ValueError("image and depth_map must be torch tensors")
+    if not callable(invert):
+        raise ValueError("invert must be callable: invert(image_u8 [512,512,3]) -> (x_t, uncond_embeddings)")
+    if image.dim() != 4 or image.shape[-1] != 3 or not image.is_floating_point():
+        raise ValueError(f"image must be a float tensor [N,H,W,3], got {image.dtype} {tuple(image.shape)}")
+    if depth_map.dim() == 3:
+        depth_map = depth_map.unsqueeze(-1)
+    if (depth_map.dim() != 4 or depth_map.shape[-1] not in (1, 3) or not depth_map.is_floating_point()
+            or tuple(depth_map.shape[:3]) != tuple(image.shape[:3])):
+        raise ValueError(f"depth_map must be a float tensor [N,H,W,3], [N,H,W,1] or [N,H,W] matching image {tuple(image.shape)}, "
+                         f"got {depth_map.dtype} {tuple(depth_map.shape)}")
+    if image.numel() == 0:
+        raise ValueError(f"empty image {tuple(image.shape)}")
+    if direction not in ("uni", "bi"):
+        raise ValueError(f"direction must be 'uni' or 'bi', got {direction!r}")
+    if image.shape[0] > 1:
+        print("Warning: Standard (DDIM) mode processes only the first frame. "
+              "Use Fast (Warp + Inpaint) mode for batch/video processing.")
+    host = not image.is_cuda
+    dev = _device_for(image, depth_map)
+    image, depth_map = image[:1].to(dev, torch.float32), depth_map[:1].to(dev, torch.float32)
+    _, h, w, _ = image.shape
+    s = (WORK_SIZE, WORK_SIZE)
+    img_u8 = engine.pil_resize(image, s)
+    depth_u8 = engine.pil_resize(depth_map, s, gray=depth_map.shape[-1] == 3)
+    disp = _norm_depth(depth_u8[..., 0].float() / 255.0)
+    x_t, uncond_embeddings = invert(img_u8[0])
+    if not isinstance(x_t, torch.Tensor) or x_t.dim() != 4 or x_t.shape[0] != 1:
+        raise ValueError("invert must return (x_t [1,C,h,w], uncond_embeddings)")
+    codes = text2stereoimage(model, [""] * 2, uncond_embeddings, torch.cat([x_t, x_t], 0), disp, scale_factor, direction, deblur,
+                             num_inference_steps, guidance_scale, noise, generator)
+    stereo = torch.empty((1, h, 2 * w, 3), dtype=torch.float32, device=dev)
+    engine.pil_resize(codes[:1], (w, h), f32="nhwc", codes=False, f32_out=stereo[:, :, :w])
+    engine.pil_resize(codes[1:], (w, h), f32="nhwc", codes=False, f32_out=stereo[:, :, w:])
     if host:
         stereo = stereo.cpu()
     return stereo, stereo[:, :, :w], stereo[:, :, w:]

@@ -368,6 +368,36 @@ CS_API int cs_stereo_shift(const float *input, const float *depth, int b, int c,
                     void *stream);
 
 /*
+ * StereoDiffusion's Standard mode around its model (reference stereodiffusion_nodes.py:576-682): the latent shift as a plan
+ * made once per image and one launch per shift step, and the decoded images' way to uint8 codes.  Nothing here waits for the
+ * device or allocates, so a denoising step that uses them can be captured in a graph.
+ *   cs_latent_shift_plan  the right view of cs_stereo_shift(shift_both = 0) as a table: disp [b][h][w] float32 (normalised with
+ *     its global min / max, in cs_stereo_shift's arithmetic) -> src_col [b][h][w] int32, for every destination the source column
+ *     the reference's sweep leaves there (scale_px = -scale_factor / 100 * w: the highest for a positive scale_factor), -1 where
+ *     nothing lands.  workspace: cs_latent_shift_plan_workspace_bytes().  Made for latents (64 to a few hundred columns): a row's
+ *     table lives in LDS and a destination scans the sources within |trunc(scale_px)| columns of it (the whole row for an
+ *     exponent <= 0), w * reach LDS reads per row.  CS_ELIMIT: rows of more than 8 192 columns, more than 65 535 images.
+ *   cs_latent_shift_apply  left, right, noise [b][c][h][w] of `dtype` (enum cs_latent_dtype), mask [b][h][w] uint8; values are
+ *     moved, never computed.  CS_LATENT_FIRST (:650-660): right = left gathered through src_col, 0 in a hole; mask = (channel 0
+ *     of that != 0), so a landed +-0.0 counts as a hole; with noise != NULL (deblur) right = noise on every channel where the
+ *     mask is 0.  CS_LATENT_RESHIFT (:663-667): where the STORED mask is 1, right = left gathered; elsewhere right is left as it
+ *     is (noise is ignored).  left and right may be the two halves of one tensor; right must not overlap left or noise.
+ *   cs_decode_to_codes  image [n][c][h][w] of `dtype` -> codes [n][h][w][c] uint8 (:673-677): (x / 2 + 0.5) as torch computes
+ *     it in the tensor's dtype (quotient and sum each rounded to it once), clamped to [0, 1], NaN -> 0, times 255.0f in float32,
+ *     truncated.
+ * CS_EINVAL before any launch: null pointers (noise may be NULL; mask may not, for either op), non-positive sizes, unknown dtype
+ * or op, overlapping right.
+ */
+enum cs_latent_dtype { CS_LATENT_F32 = 0, CS_LATENT_F16 = 1, CS_LATENT_BF16 = 2 };
+enum cs_latent_op { CS_LATENT_FIRST = 0, CS_LATENT_RESHIFT = 1 };
+CS_API size_t cs_latent_shift_plan_workspace_bytes(void);
+CS_API int cs_latent_shift_plan(const float *disp, int b, int h, int w, double scale_factor, double stereo_offset_exponent,
+                         int32_t *src_col, void *workspace, size_t workspace_bytes, void *stream);
+CS_API int cs_latent_shift_apply(const void *left, void *right, const int32_t *src_col, uint8_t *mask, const void *noise,
+                          int dtype, int b, int c, int h, int w, int op, void *stream);
+CS_API int cs_decode_to_codes(const void *image, int dtype, int n, int c, int h, int w, uint8_t *codes_nhwc, void *stream);
+
+/*
  * Stereo attention (reference stereo_utils.py BNAttention :91-188, the hot path of StereoDiffusion's Standard mode): one fused
  * flash-style forward attention, float32 in and out, float32 accumulation on the f32-input MFMA; no score matrix is written,
  * there is no workspace, nothing is allocated, everything runs on the caller's stream.
