@@ -54,6 +54,7 @@ EXPORTS = [
     "cs_attention_fwd_lse", "cs_attention_bwd_workspace_bytes", "cs_attention_bwd",
     "cs_attention_half_fwd_lse", "cs_attention_half_bwd_workspace_bytes", "cs_attention_half_bwd",
     "cs_latent_shift_plan_workspace_bytes", "cs_latent_shift_plan", "cs_latent_shift_apply", "cs_decode_to_codes",
+    "cs_ddim_step", "cs_null_loss_workspace_bytes", "cs_null_loss_grad", "cs_adam_step",
 ]
 
 # enum cs_debug_key (development switches; tests and profiling tools only)
@@ -253,6 +254,16 @@ def lib():
     L.cs_latent_shift_apply.argtypes = [vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, vp]
     L.cs_decode_to_codes.restype = c_int
     L.cs_decode_to_codes.argtypes = [vp, c_int, c_int, c_int, c_int, c_int, vp, vp]
+    c_ll = ctypes.c_longlong
+    L.cs_ddim_step.restype = c_int
+    L.cs_ddim_step.argtypes = [vp, vp, vp, vp, c_int, c_ll, c_double, c_double, c_double, c_double, c_double, vp]
+    L.cs_null_loss_workspace_bytes.restype = c_size
+    L.cs_null_loss_workspace_bytes.argtypes = [c_ll]
+    L.cs_null_loss_grad.restype = c_int
+    L.cs_null_loss_grad.argtypes = [vp, vp, vp, vp, vp, vp, vp, c_int, c_ll, c_double, c_double, c_double, c_double, c_double, vp,
+                                    c_size, vp]
+    L.cs_adam_step.restype = c_int
+    L.cs_adam_step.argtypes = [vp, vp, vp, vp, c_int, c_ll, c_double, c_double, c_double, c_double, c_int, vp]
     _lib = L
     return L
 

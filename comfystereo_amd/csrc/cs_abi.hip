@@ -1381,6 +1381,81 @@ int cs_decode_to_codes(const void* image, int dtype, int n, int c, int h, int w,
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_decode_to_codes");
 }
 
+// ---- null-text inversion outside the UNet (cs_inversion.hip) ----
+static bool finite_d(double x) { return x - x == 0.0; }
+
+// the checks cs_ddim_step and cs_null_loss_grad share; c2 divides
+static const char* step_args_error(int dtype, long long count, double guidance, const double c[4]) {
+    if (count <= 0) return "non-positive count";
+    if (dtype < CS_LATENT_F32 || dtype > CS_LATENT_BF16) return "unknown dtype (CS_LATENT_F32 / F16 / BF16)";
+    if (!finite_d(guidance) || !finite_d(c[0]) || !finite_d(c[1]) || !finite_d(c[2]) || !finite_d(c[3]))
+        return "guidance and c1..c4 must be finite";
+    if ((float)c[1] == 0.0f) return "c2 (the square root of alpha_t) must not be 0";
+    return nullptr;
+}
+
+int cs_ddim_step(const void* sample, const void* eps_a, const void* eps_b, void* out, int dtype, long long count, double guidance,
+                 double c1, double c2, double c3, double c4, void* stream) {
+    if (!sample || !eps_a || !out) return fail(CS_EINVAL, "null pointer");
+    const double cd[4] = {c1, c2, c3, c4};
+    if (const char* msg = step_args_error(dtype, count, guidance, cd)) return fail(CS_EINVAL, msg);
+    const size_t eb = latent_elem_bytes(dtype), bytes = (size_t)count * eb;
+    if (((uintptr_t)sample | (uintptr_t)eps_a | (uintptr_t)eps_b | (uintptr_t)out) & (eb - 1)) return fail(CS_EINVAL, "cs_ddim_step: misaligned tensor");
+    if ((out != sample && overlaps(out, bytes, sample, bytes)) || overlaps(out, bytes, eps_a, bytes) || (eps_b && overlaps(out, bytes, eps_b, bytes)))
+        return fail(CS_EINVAL, "cs_ddim_step: out may be sample itself; it must not overlap anything else");
+    const float c[4] = {(float)c1, (float)c2, (float)c3, (float)c4};
+    hipError_t e = launch_ddim_step(sample, eps_a, eps_b, out, dtype, (size_t)count, (float)guidance, c, (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_ddim_step");
+}
+
+size_t cs_null_loss_workspace_bytes(long long count) { return count > 0 ? null_loss_workspace_bytes((size_t)count) : 0; }
+
+int cs_null_loss_grad(const void* eps_uncond, const void* eps_cond, const void* latent_cur, const void* latent_prev, void* rec,
+                      float* loss, void* grad, int dtype, long long count, double guidance, double c1, double c2, double c3, double c4,
+                      void* workspace, size_t workspace_bytes, void* stream) {
+    if (!eps_uncond || !eps_cond || !latent_cur || !latent_prev || !rec || !loss || !grad) return fail(CS_EINVAL, "null pointer");
+    const double cd[4] = {c1, c2, c3, c4};
+    if (const char* msg = step_args_error(dtype, count, guidance, cd)) return fail(CS_EINVAL, msg);
+    if ((unsigned long long)count > null_loss_max_count()) return fail(CS_ELIMIT, "cs_null_loss_grad: too many elements for a 32-bit grid");
+    const size_t eb = latent_elem_bytes(dtype), bytes = (size_t)count * eb, need = null_loss_workspace_bytes((size_t)count);
+    if (((uintptr_t)eps_uncond | (uintptr_t)eps_cond | (uintptr_t)latent_cur | (uintptr_t)latent_prev | (uintptr_t)rec | (uintptr_t)grad) & (eb - 1))
+        return fail(CS_EINVAL, "cs_null_loss_grad: misaligned tensor");
+    if (((uintptr_t)loss | (uintptr_t)workspace) & 3) return fail(CS_EINVAL, "cs_null_loss_grad: misaligned loss or workspace");
+    if (need && (!workspace || workspace_bytes < need)) return fail(CS_EWORKSPACE, "workspace too small");
+    const void* ins[4] = {eps_uncond, eps_cond, latent_cur, latent_prev};
+    for (const void* in : ins)
+        if (overlaps(rec, bytes, in, bytes) || overlaps(grad, bytes, in, bytes) || overlaps(loss, 4, in, bytes))
+            return fail(CS_EINVAL, "cs_null_loss_grad: outputs must not overlap inputs");
+    if (overlaps(rec, bytes, grad, bytes) || overlaps(loss, 4, rec, bytes) || overlaps(loss, 4, grad, bytes))
+        return fail(CS_EINVAL, "cs_null_loss_grad: outputs must not overlap each other");
+    const float c[4] = {(float)c1, (float)c2, (float)c3, (float)c4};
+    // d loss / d eps_uncond = (2 / n) * (rec - latent_prev) * d rec / d e * d e / d eps_uncond
+    const double grad_scale = 2.0 / (double)count * ((double)c[2] - (double)c[3] * (double)c[0] / (double)c[1]) * (1.0 - (double)(float)guidance);
+    hipError_t e = launch_null_loss_grad(eps_uncond, eps_cond, latent_cur, latent_prev, rec, loss, grad, dtype, (size_t)count,
+                                         (float)guidance, c, grad_scale, workspace, (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_null_loss_grad");
+}
+
+int cs_adam_step(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, int dtype, long long count, double lr, double beta1,
+                 double beta2, double eps, int step, void* stream) {
+    if (!param || !grad || !exp_avg || !exp_avg_sq) return fail(CS_EINVAL, "null pointer");
+    if (count <= 0) return fail(CS_EINVAL, "non-positive count");
+    if (dtype < CS_LATENT_F32 || dtype > CS_LATENT_BF16) return fail(CS_EINVAL, "cs_adam_step: unknown dtype (CS_LATENT_F32 / F16 / BF16)");
+    if (step < 1) return fail(CS_EINVAL, "cs_adam_step: the step number counts from 1");
+    if (!finite_d(lr) || !finite_d(eps) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0))
+        return fail(CS_EINVAL, "cs_adam_step: lr and eps must be finite, eps >= 0, betas in [0, 1)");
+    const size_t eb = latent_elem_bytes(dtype), bytes = (size_t)count * eb;
+    if (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & (eb - 1)) return fail(CS_EINVAL, "cs_adam_step: misaligned tensor");
+    if (overlaps(param, bytes, grad, bytes) || overlaps(param, bytes, exp_avg, bytes) || overlaps(param, bytes, exp_avg_sq, bytes) ||
+        overlaps(exp_avg, bytes, grad, bytes) || overlaps(exp_avg_sq, bytes, grad, bytes) || overlaps(exp_avg, bytes, exp_avg_sq, bytes))
+        return fail(CS_EINVAL, "cs_adam_step: param, grad, exp_avg and exp_avg_sq must not overlap");
+    // the bias corrections in double, as torch/optim/adam.py computes them from Python floats
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+    const float k[6] = {(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)sqrt(bc2), (float)eps, (float)(-(lr / bc1))};
+    hipError_t e = launch_adam_step(param, grad, exp_avg, exp_avg_sq, dtype, (size_t)count, k, (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_adam_step");
+}
+
 int cs_stereo_attention_max_head_dim(void) { return stereo_attention_max_head_dim(); }
 
 int cs_stereo_attention(const float* q, const float* k, const float* v, float* out, int c, int s, int b, int h, int n, int n_k,

@@ -221,6 +221,18 @@ hipError_t launch_latent_shift_plan(const float* depth, int b, int h, int w, con
 hipError_t launch_latent_shift_apply(const void* left, void* right, const int32_t* src_col, uint8_t* mask, const void* noise,
                                      int dtype, int b, int c, int h, int w, int op, hipStream_t stream);
 hipError_t launch_decode_to_codes(const void* image, int dtype, int n, int c, int h, int w, uint8_t* codes, hipStream_t stream);
+// cs_inversion.hip (null-text inversion outside the UNet: cs_ddim_step, cs_null_loss_grad, cs_adam_step).  dtype: enum
+// cs_latent_dtype; c: the step's four coefficients c1..c4; grad_scale: (2 / n) * (c3 - c4 * c1 / c2) * (1 - guidance);
+// adam: w1 = 1 - beta1, beta2, w2 = 1 - beta2, sqrt(bias correction 2), eps, -lr / bias correction 1
+hipError_t launch_ddim_step(const void* sample, const void* eps_a, const void* eps_b, void* out, int dtype, size_t n, float guidance,
+                            const float c[4], hipStream_t stream);
+size_t null_loss_max_count();
+size_t null_loss_workspace_bytes(size_t n);
+hipError_t launch_null_loss_grad(const void* eps_uncond, const void* eps_cond, const void* latent_cur, const void* latent_prev,
+                                 void* rec, float* loss, void* grad, int dtype, size_t n, float guidance, const float c[4],
+                                 double grad_scale, void* workspace, hipStream_t stream);
+hipError_t launch_adam_step(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, int dtype, size_t n, const float adam[6],
+                            hipStream_t stream);
 // lazy depth-blur tiles in k_gpuwarp (tilemap != nullptr): rows of at most this many columns, not the mesh-quality warp
 int gpuwarp_lazy_max_width();
 

@@ -779,3 +779,126 @@ def decode_to_codes(image):
         _native.check(L.cs_decode_to_codes(_ptr(image), _native.LATENT_DTYPE[_LATENT_DTYPES[image.dtype]], n, c, h, w, _ptr(codes),
                                            _stream()))
     return codes
+
+
+# ---- null-text inversion outside the UNet (cs_ddim_step, cs_null_loss_grad, cs_adam_step) ----
+def _flat_like(first, tensors, what):
+    """The shared checks of the three wrappers: tensors of first's shape, dtype and device, contiguous, not empty."""
+    name0, t0 = first
+    if not isinstance(t0, torch.Tensor):
+        raise ValueError(f"{name0} must be a torch.Tensor")
+    if t0.dtype not in _LATENT_DTYPES:
+        raise ValueError(f"{name0} must be float32, float16 or bfloat16, got {t0.dtype}")
+    if t0.numel() == 0:
+        raise ValueError(f"empty {name0} {tuple(t0.shape)}")
+    for name, t in [first] + list(tensors):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch.Tensor")
+        if t.dtype != t0.dtype:
+            raise ValueError(f"{what} must share one dtype, got {t0.dtype} ({name0}) and {t.dtype} ({name})")
+        if tuple(t.shape) != tuple(t0.shape):
+            raise ValueError(f"{name} must have {name0}'s shape {tuple(t0.shape)}, got {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+        if t.device != t0.device:
+            raise ValueError(f"{name0} and {name} must be on the same device")
+    return _native.LATENT_DTYPE[_LATENT_DTYPES[t0.dtype]], t0.numel()
+
+
+def _step_scalars(guidance, coeffs):
+    try:
+        vals = [float(guidance)] + [float(c) for c in coeffs]
+    except TypeError:
+        raise ValueError("coeffs must be four numbers (c1, c2, c3, c4)") from None
+    if len(vals) != 5:
+        raise ValueError(f"coeffs must be four numbers (c1, c2, c3, c4), got {len(vals) - 1}")
+    if not all(math.isfinite(v) for v in vals):
+        raise ValueError(f"guidance and coeffs must be finite, got {vals}")
+    if vals[2] == 0.0:
+        raise ValueError("coeffs[1] (the square root of alpha_t) must not be 0")
+    return vals
+
+
+def ddim_step(sample, eps_a, eps_b, guidance, coeffs, out=None):
+    """cs_ddim_step: guidance and one DDIM step in one launch.  e = eps_a + guidance * (eps_b - eps_a), or eps_a when eps_b is
+    None; out = c4 * ((sample - c1 * e) / c2) + c3 * e with coeffs = (c1, c2, c3, c4) = (sqrt(1 - a_t), sqrt(a_t),
+    sqrt(1 - a_other), sqrt(a_other)) as float32 values: NullInversion.prev_step and next_step (reference inversion.py:57-75) are
+    this formula with their two alphas.  Tensors of one shape and dtype (float32, float16, bfloat16), contiguous; every operation is
+    rounded to the dtype as torch rounds the reference's expression.  out: None (a new tensor) or a tensor to write, which may be
+    `sample` itself.  -> out"""
+    ins = [("eps_a", eps_a)] + ([("eps_b", eps_b)] if eps_b is not None else []) + ([("out", out)] if out is not None else [])
+    dtype, n = _flat_like(("sample", sample), ins, "sample, eps_a, eps_b and out")
+    g, c1, c2, c3, c4 = _step_scalars(guidance, coeffs)
+    for name, t in [("sample", sample)] + ins:
+        if t.requires_grad:
+            raise ValueError(f"{name} requires grad: cs_ddim_step is not differentiable (detach it, or run under no_grad on detached tensors)")
+    _need_device(sample)
+    if out is None:
+        out = torch.empty_like(sample)
+    with torch.cuda.device(sample.device):
+        _native.check(_native.lib().cs_ddim_step(_ptr(sample), _ptr(eps_a), _ptr(eps_b) if eps_b is not None else None, _ptr(out),
+                                                 dtype, n, g, c1, c2, c3, c4, _stream()))
+    return out
+
+
+def null_loss_grad(eps_uncond, eps_cond, latent_cur, latent_prev, guidance, coeffs):
+    """cs_null_loss_grad: the inner step of null-text optimisation outside the UNet (reference inversion.py:198-201) in one
+    launch -> (rec, loss, grad): rec = prev_step(eps_uncond + guidance * (eps_cond - eps_uncond), t, latent_cur) bit for bit,
+    loss = mean((rec - latent_prev)^2) as a float32 tensor [] (a fixed summation order: the same bits on every run), grad =
+    d loss / d eps_uncond in the tensors' dtype.  Nothing here waits for the device."""
+    dtype, n = _flat_like(("eps_uncond", eps_uncond), [("eps_cond", eps_cond), ("latent_cur", latent_cur), ("latent_prev", latent_prev)],
+                          "eps_uncond, eps_cond, latent_cur and latent_prev")
+    g, c1, c2, c3, c4 = _step_scalars(guidance, coeffs)
+    _need_device(eps_uncond)
+    L = _native.lib()
+    rec, grad = torch.empty_like(eps_uncond), torch.empty_like(eps_uncond)
+    loss = torch.empty((), dtype=torch.float32, device=eps_uncond.device)
+    nb = L.cs_null_loss_workspace_bytes(n)
+    ws = torch.empty((nb,), dtype=torch.uint8, device=eps_uncond.device) if nb else None
+    with torch.cuda.device(eps_uncond.device):
+        _native.check(L.cs_null_loss_grad(_ptr(eps_uncond), _ptr(eps_cond), _ptr(latent_cur), _ptr(latent_prev), _ptr(rec), _ptr(loss),
+                                          _ptr(grad), dtype, n, g, c1, c2, c3, c4, _ptr(ws) if nb else None, nb, _stream()))
+    return rec, loss, grad
+
+
+class NullTextLoss(torch.autograd.Function):
+    """loss = NullTextLoss.apply(eps_uncond, eps_cond, latent_cur, latent_prev, guidance, coeffs): mse_loss(prev_step(guided
+    prediction), latent_prev) of null-text optimisation (reference inversion.py:199-201) as one node of the graph.  The forward is
+    one cs_null_loss_grad launch and keeps the gradient with respect to eps_uncond; the backward scales it by grad_output.  Only
+    eps_uncond gets a gradient -- the reference computes eps_cond under no_grad and the latents are constants.  The loss is float32
+    whatever the dtype.  ctx.rec: the reconstructed latent, for callers that want it."""
+
+    @staticmethod
+    def forward(ctx, eps_uncond, eps_cond, latent_cur, latent_prev, guidance, coeffs):
+        rec, loss, grad = null_loss_grad(eps_uncond.detach(), eps_cond, latent_cur, latent_prev, guidance, coeffs)
+        ctx.save_for_backward(grad)
+        ctx.rec = rec
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        (grad,) = ctx.saved_tensors
+        return (grad * grad_output.to(grad.dtype)), None, None, None, None, None
+
+
+def adam_step(param, grad, exp_avg, exp_avg_sq, lr, step, beta1=0.9, beta2=0.999, eps=1e-8):
+    """cs_adam_step: one torch.optim.Adam step (no weight decay, no amsgrad) in place on param, exp_avg and exp_avg_sq, one launch.
+    Four tensors of one shape and dtype (float32, float16, bfloat16), contiguous; step: the 1-based number of this step (the bias
+    corrections are computed from it in double on the host).  A param that requires grad is updated through its data, as an
+    optimizer does.  -> param"""
+    dtype, n = _flat_like(("param", param), [("grad", grad), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)],
+                          "param, grad, exp_avg and exp_avg_sq")
+    if isinstance(step, bool) or not isinstance(step, int) or step < 1:
+        raise ValueError(f"step must be an int counting from 1, got {step!r}")
+    lr, beta1, beta2, eps = float(lr), float(beta1), float(beta2), float(eps)
+    if not (math.isfinite(lr) and math.isfinite(eps) and eps >= 0 and 0 <= beta1 < 1 and 0 <= beta2 < 1):
+        raise ValueError(f"lr and eps must be finite, eps >= 0 and the betas in [0, 1), got {lr}, {eps}, {beta1}, {beta2}")
+    for name, t in (("grad", grad), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
+        if t.requires_grad:
+            raise ValueError(f"{name} requires grad")
+    _need_device(param)
+    with torch.cuda.device(param.device):
+        _native.check(_native.lib().cs_adam_step(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), dtype, n, lr, beta1, beta2,
+                                                 eps, step, _stream()))
+    return param

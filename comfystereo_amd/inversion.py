@@ -1,0 +1,289 @@
+"""Drop-in for the reference's inversion.py: DDIM inversion with null-text optimisation.
+
+`NullInversion` and `EmptyControl` with the reference's names, argument order, defaults and return values (reference
+inversion.py:29-255).  The UNet, VAE, text encoder and scheduler are the caller's (`model`, the reference's `ldm_stable`,
+duck-typed); everything between two UNet calls runs in one HIP launch each:
+
+  ddim_loop           next_step (:67-75)                                        engine.ddim_step
+  null_optimization   guidance + prev_step + mse_loss + its gradient (:198-201)  engine.NullTextLoss (cs_null_loss_grad)
+                      Adam (:192, :202-204)                                      engine.adam_step
+                      the guided step to the next latent (:209-211)              engine.ddim_step
+  latent2image        (image / 2 + 0.5).clamp(0, 1) * 255 -> uint8 (:100-102)    engine.decode_to_codes
+  invert              register_attention_control(model, None) (:216)             diffusion_utils' fused attention hook
+
+The step's coefficients sqrt(1 - a_t), sqrt(a_t), sqrt(1 - a_other), sqrt(a_other) are the reference's own expressions on
+scheduler.alphas_cumprod, evaluated once per timestep on the host and cached.  The inner loop reads the loss once per inner step,
+for the early stop; nothing else waits for the device.
+
+float16 / bfloat16: CPU torch -- the run the fixtures record -- converts a 0-dim float32 tensor that is the FIRST operand of a
+product with a half tensor to the half dtype before it multiplies, and keeps the divisor's float32: c1, c3 and c4 are rounded to
+the tensors' dtype when the scheduler's alphas are tensors, c2 is not (`_operand`).  float32 needs none of this.
+
+No CPU fallback: without a GPU the first kernel raises RuntimeError, as the attention hook does.
+"""
+import math
+
+import numpy as np
+import torch
+
+from . import diffusion_utils, engine
+
+try:
+    from torch.func import functional_call
+except ImportError:   # the reference's condition for its ComfyUI gradient mode (:20-26)
+    functional_call = None
+
+
+class EmptyControl:
+    """Placeholder controller that passes attention through unchanged (reference :29-39)."""
+
+    def step_callback(self, x_t):
+        return x_t
+
+    def between_steps(self):
+        return
+
+    def __call__(self, attn, is_cross: bool, place_in_unet: str):
+        return attn
+
+
+def _sqrt(x):
+    """x ** 0.5 (:62-64, :72-74), correctly rounded.  torch evaluates the power -- and torch.sqrt -- of a 0-dim float32 tensor with
+    whatever its CPU dispatch picks on the host, and not every pick is correctly rounded (an ulp on some alphas).  The square root in
+    double, rounded to the tensor's dtype, is the correctly rounded result everywhere (a double holds more than twice a float32's
+    bits plus two), which is also what the reference's expression gives wherever it is right."""
+    if isinstance(x, torch.Tensor):
+        return torch.tensor(math.sqrt(float(x)), dtype=x.dtype if x.is_floating_point() else torch.float32)
+    return x ** 0.5
+
+
+def _operand(c, dtype, first):
+    """The float the kernels take for a coefficient `c` that multiplies (first=True) or divides a tensor of `dtype`."""
+    if first and isinstance(c, torch.Tensor) and dtype in (torch.float16, torch.bfloat16):
+        c = c.to(dtype)
+    return float(c)
+
+
+class NullInversion:
+    """DDIM inversion with null-text optimisation for image-to-latent conversion (reference :42-255)."""
+
+    def __init__(self, model, num_ddim_steps: int = 50, guidance_scale: float = 7.5):
+        self.model = model
+        self.num_ddim_steps = num_ddim_steps
+        self.guidance_scale = guidance_scale
+        self.model.scheduler.set_timesteps(num_ddim_steps)
+        self.prompt = None
+        self.context = None
+        self._is_comfyui = hasattr(model, 'comfy_model')
+        self._coeffs = {}
+        self.inner_steps_taken = []   # per outer step of the last null_optimization
+        self.losses = []              # per outer step, the loss of every inner step taken
+
+    # ---- the two steps: one formula, two choices of alphas ----
+    def _step_coeffs(self, kind, timestep, dtype):
+        sch = self.scheduler
+        # the scheduler is the model's and shared: another set_timesteps, or another schedule, must not meet this one's values
+        key = (kind, int(timestep), dtype, sch.num_inference_steps, id(sch.alphas_cumprod))
+        if key not in self._coeffs:
+            ratio = sch.config.num_train_timesteps // sch.num_inference_steps
+            if kind == "prev":   # (:58-63)
+                prev_timestep = timestep - ratio
+                alpha_prod_t = sch.alphas_cumprod[timestep]
+                alpha_other = sch.alphas_cumprod[prev_timestep] if prev_timestep >= 0 else sch.final_alpha_cumprod
+            else:                # (:68-73)
+                timestep, next_timestep = min(timestep - ratio, 999), timestep
+                alpha_prod_t = sch.alphas_cumprod[timestep] if timestep >= 0 else sch.final_alpha_cumprod
+                alpha_other = sch.alphas_cumprod[next_timestep]
+            beta_prod_t = 1 - alpha_prod_t
+            self._coeffs[key] = (_operand(_sqrt(beta_prod_t), dtype, True), _operand(_sqrt(alpha_prod_t), dtype, False),
+                                 _operand(_sqrt(1 - alpha_other), dtype, True), _operand(_sqrt(alpha_other), dtype, True))
+        return self._coeffs[key]
+
+    def _step(self, kind, eps_a, eps_b, guidance, timestep, sample):
+        sample = sample.detach().contiguous()
+        eps_a = eps_a.detach().contiguous()
+        eps_b = None if eps_b is None else eps_b.detach().contiguous()
+        return engine.ddim_step(sample, eps_a, eps_b, guidance, self._step_coeffs(kind, timestep, sample.dtype))
+
+    # prev_step / next_step: the values of the reference's; not differentiable (the inputs are detached): inside the optimisation
+    # the gradient goes through engine.NullTextLoss instead
+    def prev_step(self, model_output, timestep: int, sample):
+        return self._step("prev", model_output, None, 1.0, timestep, sample)
+
+    def next_step(self, model_output, timestep: int, sample):
+        return self._step("next", model_output, None, 1.0, timestep, sample)
+
+    def get_noise_pred_single(self, latents, t, context):
+        noise_pred = self.model.unet(latents, t, encoder_hidden_states=context)["sample"]
+        return noise_pred
+
+    def get_noise_pred(self, latents, t, is_forward=True, context=None):
+        latents_input = torch.cat([latents] * 2)
+        if context is None:
+            context = self.context
+        guidance_scale = 1 if is_forward else self.guidance_scale
+        noise_pred = self.model.unet(latents_input, t, encoder_hidden_states=context)["sample"]
+        noise_pred_uncond, noise_prediction_text = noise_pred.chunk(2)
+        # guidance (:88) and the step (:89-92) in one launch
+        return self._step("next" if is_forward else "prev", noise_pred_uncond, noise_prediction_text, guidance_scale, t, latents)
+
+    @torch.no_grad()
+    def latent2image(self, latents, return_type='np'):
+        latents = 1 / 0.18215 * latents.detach()
+        image = self.model.vae.decode(latents)['sample']
+        if return_type == 'np':
+            image = engine.decode_to_codes(image.contiguous())[0].cpu().numpy()
+        return image
+
+    def _get_device(self):
+        device = self.model.device
+        if isinstance(device, str):
+            device = torch.device(device)
+        return device
+
+    @torch.no_grad()
+    def image2latent(self, image):
+        device = self._get_device()
+        model_dtype = next(self.model.vae.parameters()).dtype
+        if hasattr(image, "convert") and hasattr(image, "size") and not isinstance(image, (np.ndarray, torch.Tensor)):
+            image = np.array(image)   # a PIL image
+        if isinstance(image, torch.Tensor) and image.dim() == 4:
+            latents = image.to(device=device, dtype=model_dtype)
+        else:
+            if isinstance(image, np.ndarray):
+                image = torch.from_numpy(image)
+            # on the host, as the reference: a device divides by a Python scalar through the reciprocal, which is not `/ 127.5`
+            image = image.cpu().float() / 127.5 - 1
+            image = image.permute(2, 0, 1).unsqueeze(0).to(device)
+            image = image.to(dtype=model_dtype)
+            latents = self.model.vae.encode(image)['latent_dist'].mean
+            latents = latents * 0.18215
+            latents = latents.to(device)
+        return latents
+
+    @torch.no_grad()
+    def init_prompt(self, prompt: str):
+        device = self._get_device()
+        tok = self.model.tokenizer
+        uncond_input = tok([""], padding="max_length", max_length=tok.model_max_length, return_tensors="pt")
+        uncond_embeddings = self.model.text_encoder(uncond_input.input_ids.to(device))[0].to(device)
+        text_input = tok([prompt], padding="max_length", max_length=tok.model_max_length, truncation=True, return_tensors="pt")
+        text_embeddings = self.model.text_encoder(text_input.input_ids.to(device))[0].to(device)
+        self.context = torch.cat([uncond_embeddings, text_embeddings])
+        self.prompt = prompt
+
+    @torch.no_grad()
+    def ddim_loop(self, latent):
+        uncond_embeddings, cond_embeddings = self.context.chunk(2)
+        all_latent = [latent]
+        latent = latent.clone().detach()
+        for i in range(self.num_ddim_steps):
+            t = self.model.scheduler.timesteps[len(self.model.scheduler.timesteps) - i - 1]
+            noise_pred = self.get_noise_pred_single(latent, t, cond_embeddings)
+            latent = self.next_step(noise_pred, t, latent)
+            all_latent.append(latent)
+        return all_latent
+
+    @property
+    def scheduler(self):
+        return self.model.scheduler
+
+    @torch.no_grad()
+    def ddim_inversion(self, image):
+        latent = self.image2latent(image)
+        image_rec = self.latent2image(latent)
+        ddim_latents = self.ddim_loop(latent)
+        return image_rec, ddim_latents
+
+    def null_optimization(self, latents, num_inner_steps, epsilon):
+        uncond_embeddings, cond_embeddings = self.context.chunk(2)
+        uncond_embeddings_list = []
+        latent_cur = latents[-1]
+        self.inner_steps_taken, self.losses = [], []
+        for i in range(self.num_ddim_steps):
+            uncond_embeddings = uncond_embeddings.clone().detach().contiguous()
+            uncond_embeddings.requires_grad = True
+            # a fresh Adam per outer step (:192): zero moments, step numbers from 1
+            lr = 1e-2 * (1. - i / 100.)
+            exp_avg, exp_avg_sq = torch.zeros_like(uncond_embeddings), torch.zeros_like(uncond_embeddings)
+            latent_prev = latents[len(latents) - i - 2].detach().contiguous()
+            latent_cur = latent_cur.detach().contiguous()
+            t = self.model.scheduler.timesteps[i]
+            coeffs = self._step_coeffs("prev", t, latent_cur.dtype)
+            with torch.no_grad():
+                noise_pred_cond = self.get_noise_pred_single(latent_cur, t, cond_embeddings).contiguous()
+            losses = []
+            for j in range(num_inner_steps):
+                noise_pred_uncond = self.get_noise_pred_single(latent_cur, t, uncond_embeddings).contiguous()
+                loss = engine.NullTextLoss.apply(noise_pred_uncond, noise_pred_cond, latent_cur, latent_prev, self.guidance_scale, coeffs)
+                (grad,) = torch.autograd.grad(loss, [uncond_embeddings])
+                engine.adam_step(uncond_embeddings, grad.contiguous(), exp_avg, exp_avg_sq, lr, j + 1)
+                loss_item = loss.item()   # the one wait per inner step: the early stop needs it
+                losses.append(loss_item)
+                if loss_item < epsilon + i * 2e-5:
+                    break
+            self.inner_steps_taken.append(len(losses))
+            self.losses.append(losses)
+            uncond_embeddings_list.append(uncond_embeddings[:1].detach())
+            with torch.no_grad():
+                context = torch.cat([uncond_embeddings, cond_embeddings])
+                latent_cur = self.get_noise_pred(latent_cur, t, False, context)
+        return uncond_embeddings_list
+
+    def invert(self, image, prompt: str, num_inner_steps=10, early_stop_epsilon=1e-5, null_text_optimization=True):
+        self.init_prompt(prompt)
+        diffusion_utils.register_attention_control(self.model, None)
+
+        # an array comes back as an array (the reference's return tuple); the work on it is the device's
+        as_array = isinstance(image, np.ndarray)
+        if as_array:
+            given = image
+            image = torch.from_numpy(image)
+        if isinstance(image, torch.Tensor) and image.dim() == 3:
+            if image.shape[0] != 512 or image.shape[1] != 512:
+                image = engine.pil_resize(image.to(self._get_device())[None], (512, 512))[0]
+            if image.max() <= 1:
+                image = (image * 255).to(torch.uint8)
+        if as_array:
+            given = given if image.data_ptr() == torch.from_numpy(given).data_ptr() else image.cpu().numpy()
+
+        image_rec, ddim_latents = self.ddim_inversion(image)
+
+        if null_text_optimization:
+            if self._is_comfyui:
+                if functional_call is not None:
+                    self.model.unet.enable_gradient_mode()
+                    try:
+                        uncond_embeddings = self.null_optimization(ddim_latents, num_inner_steps, early_stop_epsilon)
+                    finally:
+                        self.model.unet.disable_gradient_mode()
+                else:
+                    uncond_embeddings, _ = self.context.chunk(2)
+                    uncond_embeddings = [uncond_embeddings.clone().detach() for _ in range(self.num_ddim_steps)]
+            else:
+                uncond_embeddings = self.null_optimization(ddim_latents, num_inner_steps, early_stop_epsilon)
+        else:
+            uncond_embeddings, _ = self.context.chunk(2)
+            uncond_embeddings = [uncond_embeddings.clone().detach() for _ in range(self.num_ddim_steps)]
+
+        return (given if as_array else image, image_rec), ddim_latents[-1], uncond_embeddings
+
+
+def make_invert(model, num_ddim_steps, guidance_scale, null_text_optimization=True, num_inner_steps=10, early_stop_epsilon=1e-5):
+    """-> invert(image_u8 [512,512,3]) -> (x_t, uncond_embeddings): the callable stereodiffusion_nodes.generate_stereo_standard
+    takes where the reference runs NullInversion(ldm_stable, steps, guidance_scale).invert(image, "", ...)
+    (stereodiffusion_nodes.py:267-273).  The attention hook invert installs is removed again before it returns: the Standard
+    loop installs its own."""
+    from . import stereo_utils
+
+    def invert(image_u8):
+        inversion = NullInversion(model, num_ddim_steps, guidance_scale)
+        try:
+            _, x_t, uncond_embeddings = inversion.invert(image_u8, "", num_inner_steps=num_inner_steps,
+                                                         early_stop_epsilon=early_stop_epsilon,
+                                                         null_text_optimization=null_text_optimization)
+        finally:
+            stereo_utils.restore_attention(model)
+        return x_t, uncond_embeddings
+
+    return invert

@@ -26,7 +26,7 @@ from it, and from itself between array shapes.
 
 Out of scope: loading and running the diffusion models themselves -- generate_stereo_fast calls the `inpaint` it is given,
 generate_stereo_standard the `invert` it is given (where the reference runs NullInversion.invert) and the UNet, VAE, text encoder
-and scheduler of the `model` it is given; null-text inversion itself and the ComfyUI and diffusers model wrappers are not here.
+and scheduler of the `model` it is given; inversion.make_invert builds that callable; the ComfyUI and diffusers model wrappers are not here.
 """
 import torch
 import torch.nn.functional as F

@@ -398,6 +398,35 @@ CS_API int cs_latent_shift_apply(const void *left, void *right, const int32_t *s
 CS_API int cs_decode_to_codes(const void *image, int dtype, int n, int c, int h, int w, uint8_t *codes_nhwc, void *stream);
 
 /*
+ * Null-text inversion outside the UNet (reference inversion.py): what NullInversion.ddim_loop and NullInversion.null_optimization
+ * do between two UNet calls, one launch each.  Flat tensors of `count` elements of `dtype` (enum cs_latent_dtype).  Every operation
+ * of the reference's tensor expression is one operation here, rounded once to the dtype before the next (float32: plain IEEE;
+ * half types: the operation in float32, then the conversion): the results are the bits CPU torch gives.  The coefficients are
+ * float32 values passed as doubles:  c1 = sqrt(1 - a_t), c2 = sqrt(a_t), c3 = sqrt(1 - a_other), c4 = sqrt(a_other); prev_step
+ * (:57-65) and next_step (:67-75) differ only in which two alphas the host takes.
+ *   cs_ddim_step  e = eps_a + guidance * (eps_b - eps_a) (:88; eps_b NULL: e = eps_a);
+ *     out = c4 * ((sample - c1 * e) / c2) + c3 * e.  out may be sample itself.
+ *   cs_null_loss_grad  the inner step of null_optimization (:198-201): rec = that formula with eps_a = eps_uncond, eps_b =
+ *     eps_cond, sample = latent_cur; loss[0] = mean((rec - latent_prev)^2), one float32, every difference taken from the formula in
+ *     float64 before its roundings to the dtype, the squares summed in float32 in a fixed order without
+ *     atomics (two launches of it give the same bits); grad = d loss / d eps_uncond = (2 / count) * (rec - latent_prev) *
+ *     (c3 - c4 * c1 / c2) * (1 - guidance), in the dtype.  workspace: cs_null_loss_workspace_bytes(count), 0 (workspace may be
+ *     NULL) up to 32 768 elements, where one launch does everything.
+ *   cs_adam_step  one torch.optim.Adam step (no weight decay, no amsgrad, not maximising) in place on param, exp_avg and
+ *     exp_avg_sq; step counts from 1; the bias corrections are computed in double on the host, the moments are kept in the dtype.
+ * CS_EINVAL before any launch: null pointers (eps_b may be NULL), count <= 0, unknown dtype, non-finite coefficients, c2 = 0,
+ * step < 1, betas outside [0, 1), misaligned or overlapping tensors.
+ */
+CS_API int cs_ddim_step(const void *sample, const void *eps_a, const void *eps_b, void *out, int dtype, long long count,
+                        double guidance, double c1, double c2, double c3, double c4, void *stream);
+CS_API size_t cs_null_loss_workspace_bytes(long long count);
+CS_API int cs_null_loss_grad(const void *eps_uncond, const void *eps_cond, const void *latent_cur, const void *latent_prev,
+                             void *rec, float *loss, void *grad, int dtype, long long count, double guidance, double c1, double c2,
+                             double c3, double c4, void *workspace, size_t workspace_bytes, void *stream);
+CS_API int cs_adam_step(void *param, const void *grad, void *exp_avg, void *exp_avg_sq, int dtype, long long count, double lr,
+                        double beta1, double beta2, double eps, int step, void *stream);
+
+/*
  * Stereo attention (reference stereo_utils.py BNAttention :91-188, the hot path of StereoDiffusion's Standard mode): one fused
  * flash-style forward attention, float32 in and out, float32 accumulation on the f32-input MFMA; no score matrix is written,
  * there is no workspace, nothing is allocated, everything runs on the caller's stream.

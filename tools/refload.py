@@ -68,6 +68,15 @@ def load_sd_nodes():
     return importlib.import_module("refpkg.stereodiffusion_nodes")
 
 
+def load_inversion():
+    """inversion.py as a submodule of the same synthetic package (NullInversion; its own imports -- tqdm, and diffusion_utils with
+    einops -- are present, diffusers is not needed)."""
+    if "refpkg.inversion" in sys.modules:
+        return sys.modules["refpkg.inversion"]
+    load_node()
+    return importlib.import_module("refpkg.inversion")
+
+
 def quiet():
     """The D32 dialect (no numba, NumPy 2) emits an expected uint8-overflow warning per pixel sum."""
     warnings.filterwarnings("ignore", category=RuntimeWarning)
