@@ -1458,148 +1458,109 @@ int cs_adam_step(void* param, const void* grad, void* exp_avg, void* exp_avg_sq,
 
 int cs_stereo_attention_max_head_dim(void) { return stereo_attention_max_head_dim(); }
 
+// The argument checks of the six attention entry points, in one order: null pointers, dtype, sizes, mode, scale, head dimension,
+// then alignment and the index limits (the stereo forwards check alignment first, the differentiable family -- fwd_lse and bwd,
+// SELF mode with c = s = 1 -- the limits), the workspace, and last that no written region overlaps an earlier one.
+// elem: bytes per element, 4 (float32; dtype is not looked at) or 2 (dtype: enum cs_attn_dtype); a row of d elements is a whole
+// number of 16-byte chunks.  p[0 .. n_in) are read, p[n_in .. n_all) written; a region's size follows from the tensor it is shaped
+// like (ATTN_W: the backward's workspace, of which the caller holds workspace_bytes).
+enum attn_shape { ATTN_Q, ATTN_K, ATTN_LSE, ATTN_W };   // [(c s b h)][n][d], [(c s b h)][n_k][d], float32 [(b h)][n], workspace
+struct attn_ptr { const void* p; attn_shape shape; };
+
+static int attn_fail(int code, const char* fn, const char* msg) {
+    snprintf(g_err, sizeof(g_err), "%s: %s", fn, msg);
+    return code;
+}
+
+static int attn_check(const char* fn, int elem, int dtype, bool grad, int c, int s, int b, int h, int n, int n_k, int d, double scale,
+                      int mode, const attn_ptr* p, int n_in, int n_all, size_t workspace_bytes) {
+    for (int i = 0; i < n_all; i++)
+        if (!p[i].p) return fail(CS_EINVAL, "null pointer");
+    if (elem == 2 && dtype != CS_ATTN_F16 && dtype != CS_ATTN_BF16) return attn_fail(CS_EINVAL, fn, "unknown dtype (CS_ATTN_F16, CS_ATTN_BF16)");
+    if (c <= 0 || s <= 0 || b <= 0 || h <= 0 || n <= 0 || n_k <= 0 || d <= 0) return fail(CS_EINVAL, "non-positive size");
+    if (mode < CS_ATTN_SELF || mode > CS_ATTN_BI) return attn_fail(CS_EINVAL, fn, "unknown mode (CS_ATTN_*)");
+    if (mode != CS_ATTN_SELF && (s != 2 || n_k != n))
+        return attn_fail(CS_EINVAL, fn, "CS_ATTN_UNI / CS_ATTN_BI take two views (s = 2) with n_k = n");
+    if (!finite_d(scale)) return attn_fail(CS_EINVAL, fn, "scale must be finite");
+    if ((d & (16 / elem - 1)) || d > stereo_attention_max_head_dim())
+        return attn_fail(CS_ELIMIT, fn, elem == 2 ? "float16 / bfloat16 head dimension must be a multiple of 8 up to cs_stereo_attention_max_head_dim()"
+                                                  : "head dimension must be a multiple of 4 up to cs_stereo_attention_max_head_dim()");
+    // one workgroup per 32 * waves queries of a (c, s, b, h) (backward: or keys); token and key indices in 32-bit ints
+    const long long bhn = (long long)c * s * b * h;
+    const long long tiles = grad ? (n > n_k ? n : n_k) / 32 + 1 : (n + 31) / 32;
+    const bool limit = n > (1 << 24) || n_k > (1 << 24) || bhn >= (1ll << 31) || bhn * tiles >= (1ll << 31);
+    bool aligned = true;
+    for (int i = 0; i < n_all; i++) aligned = aligned && !((uintptr_t)p[i].p & 15);
+    if (!aligned && !grad) return attn_fail(CS_EINVAL, fn, "every pointer needs 16-byte alignment");
+    if (limit) return attn_fail(CS_ELIMIT, fn, "more than 2^24 tokens per view or 2^31 workgroups in one call");
+    if (!aligned) return attn_fail(CS_EINVAL, fn, "every pointer needs 16-byte alignment");
+    const size_t need = attention_bwd_workspace_bytes(b, h, n, n_k, d);
+    const size_t shape_bytes[4] = {(size_t)bhn * n * d * elem, (size_t)bhn * n_k * d * elem, (size_t)bhn * n * 4, need};
+    for (int i = 0; i < n_all; i++)
+        if (p[i].shape == ATTN_W && workspace_bytes < need) {
+            snprintf(g_err, sizeof(g_err), "%s: workspace too small (%s_workspace_bytes)", fn, fn);
+            return CS_EWORKSPACE;
+        }
+    for (int w = n_in; w < n_all; w++)
+        for (int i = 0; i < w; i++)
+            if (overlaps(p[w].p, shape_bytes[p[w].shape], p[i].p, shape_bytes[p[i].shape]))
+                return attn_fail(CS_EINVAL, fn, "a written tensor (or the workspace) must not overlap an input or another written one");
+    return CS_OK;
+}
+
 int cs_stereo_attention(const float* q, const float* k, const float* v, float* out, int c, int s, int b, int h, int n, int n_k,
                         int d, double scale, int mode, void* stream) {
-    if (!q || !k || !v || !out) return fail(CS_EINVAL, "null pointer");
-    if (c <= 0 || s <= 0 || b <= 0 || h <= 0 || n <= 0 || n_k <= 0 || d <= 0) return fail(CS_EINVAL, "non-positive size");
-    if (mode < CS_ATTN_SELF || mode > CS_ATTN_BI) return fail(CS_EINVAL, "cs_stereo_attention: unknown mode (CS_ATTN_*)");
-    if (mode != CS_ATTN_SELF && (s != 2 || n_k != n))
-        return fail(CS_EINVAL, "cs_stereo_attention: CS_ATTN_UNI / CS_ATTN_BI take two views (s = 2) with n_k = n");
-    if (!(scale == scale) || scale - scale != 0.0) return fail(CS_EINVAL, "cs_stereo_attention: scale must be finite");
-    if ((d & 3) || d > stereo_attention_max_head_dim())
-        return fail(CS_ELIMIT, "cs_stereo_attention: head dimension must be a multiple of 4 up to cs_stereo_attention_max_head_dim()");
-    if (((uintptr_t)q & 15) || ((uintptr_t)k & 15) || ((uintptr_t)v & 15) || ((uintptr_t)out & 15))
-        return fail(CS_EINVAL, "cs_stereo_attention: q, k, v and out need 16-byte alignment");
-    // one workgroup per 32 * waves queries of a (c, s, b, h); token and key indices in 32-bit ints
-    const long long bhn = (long long)c * s * b * h;
-    if (n > (1 << 24) || n_k > (1 << 24) || bhn >= (1ll << 31) || bhn * ((n + 31) / 32) >= (1ll << 31))
-        return fail(CS_ELIMIT, "cs_stereo_attention: more than 2^24 tokens per view or 2^31 workgroups in one call");
-    const size_t q_bytes = (size_t)bhn * n * d * 4, k_bytes = (size_t)bhn * n_k * d * 4;
-    if (overlaps(out, q_bytes, q, q_bytes) || overlaps(out, q_bytes, k, k_bytes) || overlaps(out, q_bytes, v, k_bytes))
-        return fail(CS_EINVAL, "cs_stereo_attention: out must not overlap q, k or v");
+    const attn_ptr p[4] = {{q, ATTN_Q}, {k, ATTN_K}, {v, ATTN_K}, {out, ATTN_Q}};
+    if (int rc = attn_check("cs_stereo_attention", 4, 0, false, c, s, b, h, n, n_k, d, scale, mode, p, 3, 4, 0)) return rc;
     hipError_t e = launch_stereo_attention(q, k, v, out, c, s, b, h, n, n_k, d, (float)scale, mode, (hipStream_t)stream);
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_stereo_attention");
 }
 
 int cs_stereo_attention_half(const void* q, const void* k, const void* v, void* out, int dtype, int c, int s, int b, int h, int n,
                              int n_k, int d, double scale, int mode, void* stream) {
-    if (!q || !k || !v || !out) return fail(CS_EINVAL, "null pointer");
-    if (dtype != CS_ATTN_F16 && dtype != CS_ATTN_BF16) return fail(CS_EINVAL, "cs_stereo_attention_half: unknown dtype (CS_ATTN_F16, CS_ATTN_BF16)");
-    if (c <= 0 || s <= 0 || b <= 0 || h <= 0 || n <= 0 || n_k <= 0 || d <= 0) return fail(CS_EINVAL, "non-positive size");
-    if (mode < CS_ATTN_SELF || mode > CS_ATTN_BI) return fail(CS_EINVAL, "cs_stereo_attention_half: unknown mode (CS_ATTN_*)");
-    if (mode != CS_ATTN_SELF && (s != 2 || n_k != n))
-        return fail(CS_EINVAL, "cs_stereo_attention_half: CS_ATTN_UNI / CS_ATTN_BI take two views (s = 2) with n_k = n");
-    if (!(scale == scale) || scale - scale != 0.0) return fail(CS_EINVAL, "cs_stereo_attention_half: scale must be finite");
-    if ((d & 7) || d > stereo_attention_max_head_dim())
-        return fail(CS_ELIMIT, "cs_stereo_attention_half: head dimension must be a multiple of 8 up to cs_stereo_attention_max_head_dim()");
-    if (((uintptr_t)q & 15) || ((uintptr_t)k & 15) || ((uintptr_t)v & 15) || ((uintptr_t)out & 15))
-        return fail(CS_EINVAL, "cs_stereo_attention_half: q, k, v and out need 16-byte alignment");
-    const long long bhn = (long long)c * s * b * h;
-    if (n > (1 << 24) || n_k > (1 << 24) || bhn >= (1ll << 31) || bhn * ((n + 31) / 32) >= (1ll << 31))
-        return fail(CS_ELIMIT, "cs_stereo_attention_half: more than 2^24 tokens per view or 2^31 workgroups in one call");
-    const size_t q_bytes = (size_t)bhn * n * d * 2, k_bytes = (size_t)bhn * n_k * d * 2;
-    if (overlaps(out, q_bytes, q, q_bytes) || overlaps(out, q_bytes, k, k_bytes) || overlaps(out, q_bytes, v, k_bytes))
-        return fail(CS_EINVAL, "cs_stereo_attention_half: out must not overlap q, k or v");
+    const attn_ptr p[4] = {{q, ATTN_Q}, {k, ATTN_K}, {v, ATTN_K}, {out, ATTN_Q}};
+    if (int rc = attn_check("cs_stereo_attention_half", 2, dtype, false, c, s, b, h, n, n_k, d, scale, mode, p, 3, 4, 0)) return rc;
     hipError_t e = launch_stereo_attention_half(q, k, v, out, dtype, c, s, b, h, n, n_k, d, (float)scale, mode, (hipStream_t)stream);
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_stereo_attention_half");
 }
 
-// the checks cs_attention_fwd_lse and cs_attention_bwd share with cs_stereo_attention (SELF mode, c = s = 1); half: the
-// float16 / bfloat16 pair, whose rows need d to be a multiple of 8
-static int attn_grad_args(int b, int h, int n, int n_k, int d, double scale, bool half = false) {
-    if (b <= 0 || h <= 0 || n <= 0 || n_k <= 0 || d <= 0) return fail(CS_EINVAL, "non-positive size");
-    if (!(scale == scale) || scale - scale != 0.0) return fail(CS_EINVAL, "attention: scale must be finite");
-    if (half && ((d & 7) || d > stereo_attention_max_head_dim()))
-        return fail(CS_ELIMIT, "attention: float16 / bfloat16 head dimension must be a multiple of 8 up to cs_stereo_attention_max_head_dim()");
-    if ((d & 3) || d > stereo_attention_max_head_dim())
-        return fail(CS_ELIMIT, "attention: head dimension must be a multiple of 4 up to cs_stereo_attention_max_head_dim()");
-    const long long bhn = (long long)b * h;
-    const long long tiles = (n > n_k ? n : n_k) / 32 + 1;
-    if (n > (1 << 24) || n_k > (1 << 24) || bhn >= (1ll << 31) || bhn * tiles >= (1ll << 31))
-        return fail(CS_ELIMIT, "attention: more than 2^24 tokens or 2^31 workgroups in one call");
-    return CS_OK;
-}
-
 int cs_attention_fwd_lse(const float* q, const float* k, const float* v, float* out, float* lse, int b, int h, int n, int n_k, int d,
                          double scale, void* stream) {
-    if (!q || !k || !v || !out || !lse) return fail(CS_EINVAL, "null pointer");
-    if (int rc = attn_grad_args(b, h, n, n_k, d, scale)) return rc;
-    if (((uintptr_t)q & 15) || ((uintptr_t)k & 15) || ((uintptr_t)v & 15) || ((uintptr_t)out & 15) || ((uintptr_t)lse & 15))
-        return fail(CS_EINVAL, "cs_attention_fwd_lse: q, k, v, out and lse need 16-byte alignment");
-    const size_t bhn = (size_t)b * h, q_bytes = bhn * n * d * 4, k_bytes = bhn * n_k * d * 4, l_bytes = bhn * n * 4;
-    const void* in[3] = {q, k, v};
-    const size_t in_bytes[3] = {q_bytes, k_bytes, k_bytes};
-    for (int i = 0; i < 3; i++)
-        if (overlaps(out, q_bytes, in[i], in_bytes[i]) || overlaps(lse, l_bytes, in[i], in_bytes[i]))
-            return fail(CS_EINVAL, "cs_attention_fwd_lse: out and lse must not overlap q, k or v");
-    if (overlaps(out, q_bytes, lse, l_bytes)) return fail(CS_EINVAL, "cs_attention_fwd_lse: out and lse must not overlap");
+    const attn_ptr p[5] = {{q, ATTN_Q}, {k, ATTN_K}, {v, ATTN_K}, {out, ATTN_Q}, {lse, ATTN_LSE}};
+    if (int rc = attn_check("cs_attention_fwd_lse", 4, 0, true, 1, 1, b, h, n, n_k, d, scale, CS_ATTN_SELF, p, 3, 5, 0)) return rc;
     hipError_t e = launch_attention_fwd_lse(q, k, v, out, lse, b, h, n, n_k, d, (float)scale, (hipStream_t)stream);
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_attention_fwd_lse");
 }
 
-size_t cs_attention_bwd_workspace_bytes(int b, int h, int n, int n_k, int d) { return attention_bwd_workspace_bytes(b, h, n, n_k, d); }
-
-int cs_attention_bwd(const float* q, const float* k, const float* v, const float* out, const float* lse, const float* d_out, float* dq,
-                     float* dk, float* dv, int b, int h, int n, int n_k, int d, double scale, void* workspace, size_t workspace_bytes,
-                     void* stream) {
-    if (!q || !k || !v || !out || !lse || !d_out || !dq || !dk || !dv || !workspace) return fail(CS_EINVAL, "null pointer");
-    if (int rc = attn_grad_args(b, h, n, n_k, d, scale)) return rc;
-    const size_t bhn = (size_t)b * h, q_bytes = bhn * n * d * 4, k_bytes = bhn * n_k * d * 4, l_bytes = bhn * n * 4;
-    const size_t need = attention_bwd_workspace_bytes(b, h, n, n_k, d);
-    // inputs 0..5, then the regions that are written: dq, dk, dv and the workspace
-    const void* p[10] = {q, k, v, out, lse, d_out, dq, dk, dv, workspace};
-    const size_t bytes[10] = {q_bytes, k_bytes, k_bytes, q_bytes, l_bytes, q_bytes, q_bytes, k_bytes, k_bytes, need};
-    for (int i = 0; i < 10; i++)
-        if ((uintptr_t)p[i] & 15) return fail(CS_EINVAL, "cs_attention_bwd: every pointer needs 16-byte alignment");
-    if (workspace_bytes < need) return fail(CS_EWORKSPACE, "cs_attention_bwd: workspace too small (cs_attention_bwd_workspace_bytes)");
-    for (int w = 6; w < 10; w++)
-        for (int i = 0; i < w; i++)
-            if (overlaps(p[w], bytes[w], p[i], bytes[i]))
-                return fail(CS_EINVAL, "cs_attention_bwd: dq, dk, dv and the workspace must not overlap an input or each other");
-    hipError_t e = launch_attention_bwd(q, k, v, out, lse, d_out, dq, dk, dv, b, h, n, n_k, d, (float)scale, workspace, (hipStream_t)stream);
-    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_attention_bwd");
-}
-
 int cs_attention_half_fwd_lse(const void* q, const void* k, const void* v, void* out, float* lse, int dtype, int b, int h, int n, int n_k,
                               int d, double scale, void* stream) {
-    if (!q || !k || !v || !out || !lse) return fail(CS_EINVAL, "null pointer");
-    if (dtype != CS_ATTN_F16 && dtype != CS_ATTN_BF16) return fail(CS_EINVAL, "cs_attention_half_fwd_lse: unknown dtype (CS_ATTN_F16, CS_ATTN_BF16)");
-    if (int rc = attn_grad_args(b, h, n, n_k, d, scale, true)) return rc;
-    if (((uintptr_t)q & 15) || ((uintptr_t)k & 15) || ((uintptr_t)v & 15) || ((uintptr_t)out & 15) || ((uintptr_t)lse & 15))
-        return fail(CS_EINVAL, "cs_attention_half_fwd_lse: q, k, v, out and lse need 16-byte alignment");
-    const size_t bhn = (size_t)b * h, q_bytes = bhn * n * d * 2, k_bytes = bhn * n_k * d * 2, l_bytes = bhn * n * 4;
-    const void* in[3] = {q, k, v};
-    const size_t in_bytes[3] = {q_bytes, k_bytes, k_bytes};
-    for (int i = 0; i < 3; i++)
-        if (overlaps(out, q_bytes, in[i], in_bytes[i]) || overlaps(lse, l_bytes, in[i], in_bytes[i]))
-            return fail(CS_EINVAL, "cs_attention_half_fwd_lse: out and lse must not overlap q, k or v");
-    if (overlaps(out, q_bytes, lse, l_bytes)) return fail(CS_EINVAL, "cs_attention_half_fwd_lse: out and lse must not overlap");
+    const attn_ptr p[5] = {{q, ATTN_Q}, {k, ATTN_K}, {v, ATTN_K}, {out, ATTN_Q}, {lse, ATTN_LSE}};
+    if (int rc = attn_check("cs_attention_half_fwd_lse", 2, dtype, true, 1, 1, b, h, n, n_k, d, scale, CS_ATTN_SELF, p, 3, 5, 0)) return rc;
     hipError_t e = launch_attention_half_fwd_lse(q, k, v, out, lse, dtype, b, h, n, n_k, d, (float)scale, (hipStream_t)stream);
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_attention_half_fwd_lse");
 }
 
-size_t cs_attention_half_bwd_workspace_bytes(int b, int h, int n, int n_k, int d) {
-    return attention_half_bwd_workspace_bytes(b, h, n, n_k, d);
+// one workspace rule for every dtype: delta, one float32 per query
+size_t cs_attention_bwd_workspace_bytes(int b, int h, int n, int n_k, int d) { return attention_bwd_workspace_bytes(b, h, n, n_k, d); }
+size_t cs_attention_half_bwd_workspace_bytes(int b, int h, int n, int n_k, int d) { return attention_bwd_workspace_bytes(b, h, n, n_k, d); }
+
+int cs_attention_bwd(const float* q, const float* k, const float* v, const float* out, const float* lse, const float* d_out, float* dq,
+                     float* dk, float* dv, int b, int h, int n, int n_k, int d, double scale, void* workspace, size_t workspace_bytes,
+                     void* stream) {
+    const attn_ptr p[10] = {{q, ATTN_Q}, {k, ATTN_K}, {v, ATTN_K}, {out, ATTN_Q}, {lse, ATTN_LSE}, {d_out, ATTN_Q},
+                            {dq, ATTN_Q}, {dk, ATTN_K}, {dv, ATTN_K}, {workspace, ATTN_W}};
+    if (int rc = attn_check("cs_attention_bwd", 4, 0, true, 1, 1, b, h, n, n_k, d, scale, CS_ATTN_SELF, p, 6, 10, workspace_bytes)) return rc;
+    hipError_t e = launch_attention_bwd(q, k, v, out, lse, d_out, dq, dk, dv, b, h, n, n_k, d, (float)scale, workspace, (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_attention_bwd");
 }
 
 int cs_attention_half_bwd(const void* q, const void* k, const void* v, const void* out, const float* lse, const void* d_out, void* dq,
                           void* dk, void* dv, int dtype, int b, int h, int n, int n_k, int d, double scale, void* workspace,
                           size_t workspace_bytes, void* stream) {
-    if (!q || !k || !v || !out || !lse || !d_out || !dq || !dk || !dv || !workspace) return fail(CS_EINVAL, "null pointer");
-    if (dtype != CS_ATTN_F16 && dtype != CS_ATTN_BF16) return fail(CS_EINVAL, "cs_attention_half_bwd: unknown dtype (CS_ATTN_F16, CS_ATTN_BF16)");
-    if (int rc = attn_grad_args(b, h, n, n_k, d, scale, true)) return rc;
-    const size_t bhn = (size_t)b * h, q_bytes = bhn * n * d * 2, k_bytes = bhn * n_k * d * 2, l_bytes = bhn * n * 4;
-    const size_t need = attention_half_bwd_workspace_bytes(b, h, n, n_k, d);
-    // inputs 0..5, then the regions that are written: dq, dk, dv and the workspace
-    const void* p[10] = {q, k, v, out, lse, d_out, dq, dk, dv, workspace};
-    const size_t bytes[10] = {q_bytes, k_bytes, k_bytes, q_bytes, l_bytes, q_bytes, q_bytes, k_bytes, k_bytes, need};
-    for (int i = 0; i < 10; i++)
-        if ((uintptr_t)p[i] & 15) return fail(CS_EINVAL, "cs_attention_half_bwd: every pointer needs 16-byte alignment");
-    if (workspace_bytes < need) return fail(CS_EWORKSPACE, "cs_attention_half_bwd: workspace too small (cs_attention_half_bwd_workspace_bytes)");
-    for (int w = 6; w < 10; w++)
-        for (int i = 0; i < w; i++)
-            if (overlaps(p[w], bytes[w], p[i], bytes[i]))
-                return fail(CS_EINVAL, "cs_attention_half_bwd: dq, dk, dv and the workspace must not overlap an input or each other");
+    const attn_ptr p[10] = {{q, ATTN_Q}, {k, ATTN_K}, {v, ATTN_K}, {out, ATTN_Q}, {lse, ATTN_LSE}, {d_out, ATTN_Q},
+                            {dq, ATTN_Q}, {dk, ATTN_K}, {dv, ATTN_K}, {workspace, ATTN_W}};
+    if (int rc = attn_check("cs_attention_half_bwd", 2, dtype, true, 1, 1, b, h, n, n_k, d, scale, CS_ATTN_SELF, p, 6, 10, workspace_bytes))
+        return rc;
     hipError_t e = launch_attention_half_bwd(q, k, v, out, lse, d_out, dq, dk, dv, dtype, b, h, n, n_k, d, (float)scale, workspace,
                                              (hipStream_t)stream);
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_attention_half_bwd");

@@ -10,7 +10,7 @@
 //
 // One wave owns 32 queries; a workgroup of NW waves shares the 32-key K / V tiles in LDS.  Per tile a wave computes
 //   S^T = K . Q^T   A = K (row: key, k: d), B = Q^T: the accumulator has the QUERY on the lane (column l & 31) and 16 keys in
-//                   its registers (row (r & 3) + 8 (r >> 2) + 4 (l >> 5)), so the softmax row reductions are in-lane plus
+//                   its registers (row at_row(r, l >> 5), cs_attention_tile.h), so the softmax row reductions are in-lane plus
 //                   one exchange with lane l ^ 32, and the rescale factor of a query is a per-lane scalar;
 //   O^T += V^T . P^T  register r of the S^T accumulator IS the B fragment of a k-step over the key pair
 //                   {a_r, a_r + 4}, a_r = (r & 3) + 8 (r >> 2): P never leaves the registers.  The A fragment is
@@ -18,19 +18,15 @@
 // The d-order inside the first product is free as long as both operands agree: k-step 4 g + j takes d = 8 g + 4 (l >> 5) + j,
 // so that a lane reads its four K operands of a group with one ds_read_b128 and keeps Q as float4s.  Rows of K are
 // ND * 32 + 4 floats apart: (stride / 4) is odd, the 16-byte slots of 8 consecutive keys fall on distinct bank quads.
+#include "cs_attention_tile.h"
 #include "cs_common.h"
 #include "cs_kernels.h"
 
 namespace cs {
 
-enum { SA_MAX_D = 160, SA_KT = 32 };   // largest head dimension (5 blocks of 32 output columns); keys per tile
+enum { SA_MAX_D = 160 };   // largest head dimension (5 blocks of 32 output columns)
 
 int stereo_attention_max_head_dim() { return SA_MAX_D; }
-
-typedef float sa_f16 __attribute__((ext_vector_type(16)));
-
-// accumulator register r of lane half hi <-> row of the 32 x 32 tile
-__device__ __forceinline__ int sa_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
 
 // LSE (cs_attention_fwd_lse, the forward of the differentiable attention): besides `out`, the log-sum-exp of every query's scaled
 // scores goes to lse [(c s b h)][n], in log2 units like sc2: p(i, j) = exp2(sc2 * s(i, j) - lse(i)).  Nothing else differs.
@@ -40,8 +36,8 @@ __global__ void __launch_bounds__(NW * 64) k_stereo_attention(const float* __res
                                                               int H, int n, int n_k, int d, float scale, int mode, int qtiles,
                                                               float* __restrict__ lse = nullptr) {
     constexpr int SK = ND * 32 + 4, SV = ND * 32, NT = NW * 64;
-    __shared__ __attribute__((aligned(16))) float Ks[SA_KT * SK];
-    __shared__ __attribute__((aligned(16))) float Vs[SA_KT * SV];
+    __shared__ __attribute__((aligned(16))) float Ks[AT_T * SK];
+    __shared__ __attribute__((aligned(16))) float Vs[AT_T * SV];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, hi = lane >> 5;
     const int bh = blockIdx.x / qtiles, qt = blockIdx.x - bh * qtiles;
     // (c s b h) -> the key set: view 0 of the same (c, b, h) for UNI / BI, followed by view 1 for BI
@@ -54,8 +50,8 @@ __global__ void __launch_bounds__(NW * 64) k_stereo_attention(const float* __res
     const int d4 = d >> 2;
 
     // the pad columns (d .. SK) are multiplied by Q's zero pad, rows past the key set by p = 0: both must be finite
-    for (int i = tid; i < SA_KT * SK; i += NT) Ks[i] = 0.0f;
-    for (int i = tid; i < SA_KT * SV; i += NT) Vs[i] = 0.0f;
+    for (int i = tid; i < AT_T * SK; i += NT) Ks[i] = 0.0f;
+    for (int i = tid; i < AT_T * SV; i += NT) Vs[i] = 0.0f;
 
     // Q fragment: query `col` of this wave, d = 8 g + 4 hi .. + 3 in qf[g]; zero past d and past n
     const int qi = (qt * NW + wave) * 32 + col;
@@ -68,7 +64,7 @@ __global__ void __launch_bounds__(NW * 64) k_stereo_attention(const float* __res
         qf[g] = (q_ok && c0 < d) ? *(const float4*)(qrow + c0) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     }
 
-    sa_f16 o[ND];
+    at_acc o[ND];
 #pragma unroll
     for (int b = 0; b < ND; b++)
 #pragma unroll
@@ -76,12 +72,12 @@ __global__ void __launch_bounds__(NW * 64) k_stereo_attention(const float* __res
     float m_run = -INFINITY, l_run = 0.0f;
     const float sc2 = scale * 1.44269504088896340736f;   // scores in units of log2: p = exp2(s - m)
 
-    const int ntiles = (nkeys + SA_KT - 1) / SA_KT;
+    const int ntiles = (nkeys + AT_T - 1) / AT_T;
     for (int kt = 0; kt < ntiles; kt++) {
         __syncthreads();   // the previous tile's readers (first pass: the zero fill) are done
-        for (int e = tid; e < SA_KT * d4; e += NT) {
+        for (int e = tid; e < AT_T * d4; e += NT) {
             const int row = e / d4, c4 = e - row * d4;
-            const int j = kt * SA_KT + row;
+            const int j = kt * AT_T + row;
             float4 kv = make_float4(0.0f, 0.0f, 0.0f, 0.0f), vv = kv;
             if (j < nkeys) {
                 const size_t off = ((size_t)j + (j >= n_k ? view_rows : 0)) * d + 4 * c4;
@@ -94,7 +90,7 @@ __global__ void __launch_bounds__(NW * 64) k_stereo_attention(const float* __res
         __syncthreads();
 
         // S^T = K . Q^T
-        sa_f16 st;
+        at_acc st;
 #pragma unroll
         for (int r = 0; r < 16; r++) st[r] = 0.0f;
 #pragma unroll
@@ -109,13 +105,13 @@ __global__ void __launch_bounds__(NW * 64) k_stereo_attention(const float* __res
         }
         // keys past the set: -inf BEFORE the running maximum is updated (tile 0 always holds key 0, so the maximum is
         // finite from the first tile on and exp2(-inf - m) = 0 is the only form -inf takes)
-        const int key0 = kt * SA_KT;
-        const bool tail = key0 + SA_KT > nkeys;
+        const int key0 = kt * AT_T;
+        const bool tail = key0 + AT_T > nkeys;
         float m_tile = -INFINITY;
 #pragma unroll
         for (int r = 0; r < 16; r++) {
             float sv = st[r] * sc2;
-            if (tail && key0 + sa_row(r, hi) >= nkeys) sv = -INFINITY;
+            if (tail && key0 + at_row(r, hi) >= nkeys) sv = -INFINITY;
             st[r] = sv;
             m_tile = fmaxf(m_tile, sv);
         }
@@ -140,7 +136,7 @@ __global__ void __launch_bounds__(NW * 64) k_stereo_attention(const float* __res
         for (int b = 0; b < ND; b++) {
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                const float vf = Vs[sa_row(r, hi) * SV + b * 32 + col];
+                const float vf = Vs[at_row(r, hi) * SV + b * 32 + col];
                 o[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(vf, st[r], o[b], 0, 0, 0);
             }
         }
@@ -163,70 +159,41 @@ __global__ void __launch_bounds__(NW * 64) k_stereo_attention(const float* __res
     }
 }
 
-template <int ND>
-static hipError_t sa_launch(int nw, int blocks, const float* q, const float* k, const float* v, float* out, int S, int B, int H, int n,
-                            int n_k, int d, float scale, int mode, int qtiles, hipStream_t stream) {
-    if (nw == 4)
-        hipLaunchKernelGGL((k_stereo_attention<ND, 4>), dim3(blocks), dim3(256), 0, stream, q, k, v, out, S, B, H, n, n_k, d, scale, mode, qtiles);
-    else if (nw == 2)
-        hipLaunchKernelGGL((k_stereo_attention<ND, 2>), dim3(blocks), dim3(128), 0, stream, q, k, v, out, S, B, H, n, n_k, d, scale, mode, qtiles);
-    else
-        hipLaunchKernelGGL((k_stereo_attention<ND, 1>), dim3(blocks), dim3(64), 0, stream, q, k, v, out, S, B, H, n, n_k, d, scale, mode, qtiles);
-    return hipGetLastError();
-}
-
-// Waves per workgroup, by measurement on the four SD 1.5 levels (tools/attention_bench.py --sweep): 4 everywhere.
-// A wave's share of the cooperative K / V tile load, not its MFMAs, bounds the tile loop, so four waves per tile win even where
-// they leave CUs idle (n = 256: 64 workgroups) or have no query of their own (n = 64).  1 and 2 stay selectable for sweeps.
-template <int ND>
-static hipError_t sa_launch_lse(int nw, int blocks, const float* q, const float* k, const float* v, float* out, float* lse, int B, int H,
-                                int n, int n_k, int d, float scale, int qtiles, hipStream_t stream) {
-    if (nw == 4)
-        hipLaunchKernelGGL((k_stereo_attention<ND, 4, true>), dim3(blocks), dim3(256), 0, stream, q, k, v, out, 1, B, H, n, n_k, d, scale, (int)CS_ATTN_SELF, qtiles, lse);
-    else if (nw == 2)
-        hipLaunchKernelGGL((k_stereo_attention<ND, 2, true>), dim3(blocks), dim3(128), 0, stream, q, k, v, out, 1, B, H, n, n_k, d, scale, (int)CS_ATTN_SELF, qtiles, lse);
-    else
-        hipLaunchKernelGGL((k_stereo_attention<ND, 1, true>), dim3(blocks), dim3(64), 0, stream, q, k, v, out, 1, B, H, n, n_k, d, scale, (int)CS_ATTN_SELF, qtiles, lse);
-    return hipGetLastError();
-}
-
-int stereo_attention_waves(long long batch_heads, int n) {
+// Waves per workgroup of every attention kernel, by measurement of the float32 forward on the four SD 1.5 levels
+// (tools/attention_bench.py --sweep): 4 everywhere.  A wave's share of the cooperative K / V tile load, not its
+// MFMAs, bounds the tile loop, so four waves per tile win even where they leave CUs idle (n = 256: 64 workgroups) or have no query
+// of their own (n = 64).  The half kernels and the backwards keep that 4 until tools/attention_bench.py --dtype ... --sweep says
+// otherwise; 1 and 2 stay selectable for sweeps with CS_DEBUG_ATTN_WAVES.
+int attention_waves(long long batch_heads, int n) {
     (void)batch_heads; (void)n;
     const int forced = dev_switch(CS_DEBUG_ATTN_WAVES);
     return (forced == 1 || forced == 2) ? forced : 4;
 }
 
-hipError_t launch_stereo_attention(const float* q, const float* k, const float* v, float* out, int c, int s, int b, int h, int n,
-                                   int n_k, int d, float scale, int mode, hipStream_t stream) {
+template <bool LSE>
+static hipError_t sa_launch(const float* q, const float* k, const float* v, float* out, float* lse, int c, int s, int b, int h, int n,
+                            int n_k, int d, float scale, int mode, hipStream_t stream) {
     const long long bhn = (long long)c * s * b * h;
-    const int nw = stereo_attention_waves(bhn, n);
+    const int nw = attention_waves(bhn, n);
     const int qtiles = (n + 32 * nw - 1) / (32 * nw);
     const int blocks = (int)(bhn * qtiles);
-    switch ((d + 31) / 32) {
-    case 1: return sa_launch<1>(nw, blocks, q, k, v, out, s, b, h, n, n_k, d, scale, mode, qtiles, stream);
-    case 2: return sa_launch<2>(nw, blocks, q, k, v, out, s, b, h, n, n_k, d, scale, mode, qtiles, stream);
-    case 3: return sa_launch<3>(nw, blocks, q, k, v, out, s, b, h, n, n_k, d, scale, mode, qtiles, stream);
-    case 4: return sa_launch<4>(nw, blocks, q, k, v, out, s, b, h, n, n_k, d, scale, mode, qtiles, stream);
-    case 5: return sa_launch<5>(nw, blocks, q, k, v, out, s, b, h, n, n_k, d, scale, mode, qtiles, stream);
-    }
-    return hipErrorInvalidValue;
+    return at_dispatch(d, nw, [&](auto nd, auto nwc) {
+        constexpr int ND = decltype(nd)::value, NW = decltype(nwc)::value;
+        hipLaunchKernelGGL((k_stereo_attention<ND, NW, LSE>), dim3(blocks), dim3(NW * 64), 0, stream, q, k, v, out, s, b, h, n, n_k, d,
+                           scale, mode, qtiles, lse);
+        return hipGetLastError();
+    });
+}
+
+hipError_t launch_stereo_attention(const float* q, const float* k, const float* v, float* out, int c, int s, int b, int h, int n,
+                                   int n_k, int d, float scale, int mode, hipStream_t stream) {
+    return sa_launch<false>(q, k, v, out, nullptr, c, s, b, h, n, n_k, d, scale, mode, stream);
 }
 
 // the same launch as launch_stereo_attention(..., CS_ATTN_SELF) with c = s = 1: `out` is bit for bit that call's
 hipError_t launch_attention_fwd_lse(const float* q, const float* k, const float* v, float* out, float* lse, int b, int h, int n, int n_k,
                                     int d, float scale, hipStream_t stream) {
-    const long long bhn = (long long)b * h;
-    const int nw = stereo_attention_waves(bhn, n);
-    const int qtiles = (n + 32 * nw - 1) / (32 * nw);
-    const int blocks = (int)(bhn * qtiles);
-    switch ((d + 31) / 32) {
-    case 1: return sa_launch_lse<1>(nw, blocks, q, k, v, out, lse, b, h, n, n_k, d, scale, qtiles, stream);
-    case 2: return sa_launch_lse<2>(nw, blocks, q, k, v, out, lse, b, h, n, n_k, d, scale, qtiles, stream);
-    case 3: return sa_launch_lse<3>(nw, blocks, q, k, v, out, lse, b, h, n, n_k, d, scale, qtiles, stream);
-    case 4: return sa_launch_lse<4>(nw, blocks, q, k, v, out, lse, b, h, n, n_k, d, scale, qtiles, stream);
-    case 5: return sa_launch_lse<5>(nw, blocks, q, k, v, out, lse, b, h, n, n_k, d, scale, qtiles, stream);
-    }
-    return hipErrorInvalidValue;
+    return sa_launch<true>(q, k, v, out, lse, 1, 1, b, h, n, n_k, d, scale, CS_ATTN_SELF, stream);
 }
 
 }  // namespace cs

@@ -15,8 +15,8 @@
 //
 // Layouts: q, dq [(b h)][n][d]; k, v, dk, dv [(b h)][n_k][d]; out, d_out [(b)][n][(h d)]; lse, delta [(b h)][n].
 //
-// MFMA arrangement (v_mfma_f32_32x32x2_f32; accumulator register r of lane half hi is row sa_row(r, hi), the lane's low five bits
-// the column; a k-ordered fmaf chain, so s(i, j) is bit for bit the forward's):
+// MFMA arrangement (v_mfma_f32_32x32x2_f32; accumulator register r of lane half hi is row at_row(r, hi) of cs_attention_tile.h, the
+// lane's low five bits the column; a k-ordered fmaf chain, so s(i, j) is bit for bit the forward's):
 //   dq kernel    S^T = K . Q^T and dP^T = V . dO^T: the QUERY on the lane, lse and delta per-lane scalars; Q and dO fragments in
 //                registers, K and V rows read from LDS with one ds_read_b128 per group of four k-steps; then
 //                dQ^T += K^T . dS^T with the dS^T accumulator registers as B fragments (k-step r = key pair {a_r, a_r + 4}).
@@ -30,16 +30,11 @@
 // rows are zero, so dS = 0 * finite = 0; in the dk/dv kernel such a key is a column nobody stores.  Queries past n: Q and dO rows are
 // zeros and lse = +inf, so P = exp2(0 - inf) = 0 and dS = 0 * (0 - 0) = 0: they add exact zeros to dK and dV; in the dq kernel such
 // a query is a column nobody stores (lse read as 0: finite arithmetic).
+#include "cs_attention_tile.h"
 #include "cs_common.h"
 #include "cs_kernels.h"
 
 namespace cs {
-
-enum { AB_T = 32 };   // keys / queries per tile
-
-typedef float ab_f16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ int ab_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
 
 // delta [(b h)][n]: one thread per row.  The chain is the one the MFMAs run for dP(i, j) = dO(i, :) . V(j, :) -- k-step 4 g + t
 // takes column 8 g + t, then column 8 g + 4 + t, each one fmaf -- so that where O(i, :) equals V(j, :) bit for bit (a single key:
@@ -71,8 +66,8 @@ __global__ void __launch_bounds__(NW * 64) k_attention_bwd_dq(const float* __res
                                                               float* __restrict__ dq, int H, int n, int n_k, int d, float scale,
                                                               int qtiles) {
     constexpr int SK = ND * 32 + 4, NT = NW * 64;
-    __shared__ __attribute__((aligned(16))) float Ks[AB_T * SK];
-    __shared__ __attribute__((aligned(16))) float Vs[AB_T * SK];
+    __shared__ __attribute__((aligned(16))) float Ks[AT_T * SK];
+    __shared__ __attribute__((aligned(16))) float Vs[AT_T * SK];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, hi = lane >> 5;
     const int bh = blockIdx.x / qtiles, qt = blockIdx.x - bh * qtiles;
     const float* kb = k + (size_t)bh * n_k * d;
@@ -80,7 +75,7 @@ __global__ void __launch_bounds__(NW * 64) k_attention_bwd_dq(const float* __res
     const int d4 = d >> 2;
 
     // the pad columns (d .. SK) meet zero Q / dO fragments, or end in dQ columns nobody stores: they must be finite
-    for (int i = tid; i < AB_T * SK; i += NT) { Ks[i] = 0.0f; Vs[i] = 0.0f; }
+    for (int i = tid; i < AT_T * SK; i += NT) { Ks[i] = 0.0f; Vs[i] = 0.0f; }
 
     // Q and dO fragments of query `col`: d = 8 g + 4 hi .. + 3 in qf[g] / dof[g]; zero past d and past n
     const int qi = (qt * NW + wave) * 32 + col;
@@ -99,19 +94,19 @@ __global__ void __launch_bounds__(NW * 64) k_attention_bwd_dq(const float* __res
     const float lse_i = q_ok ? lse[(size_t)bh * n + qi] : 0.0f;
     const float delta_i = q_ok ? delta[(size_t)bh * n + qi] : 0.0f;
 
-    ab_f16 acc[ND];
+    at_acc acc[ND];
 #pragma unroll
     for (int b = 0; b < ND; b++)
 #pragma unroll
         for (int r = 0; r < 16; r++) acc[b][r] = 0.0f;
     const float sc2 = scale * 1.44269504088896340736f;
 
-    const int ntiles = (n_k + AB_T - 1) / AB_T;
+    const int ntiles = (n_k + AT_T - 1) / AT_T;
     for (int kt = 0; kt < ntiles; kt++) {
         __syncthreads();   // the previous tile's readers (first pass: the zero fill) are done
-        for (int e = tid; e < AB_T * d4; e += NT) {
+        for (int e = tid; e < AT_T * d4; e += NT) {
             const int row = e / d4, c4 = e - row * d4;
-            const int j = kt * AB_T + row;
+            const int j = kt * AT_T + row;
             float4 kv = make_float4(0.0f, 0.0f, 0.0f, 0.0f), vv = kv;
             if (j < n_k) {
                 const size_t off = (size_t)j * d + 4 * c4;
@@ -124,7 +119,7 @@ __global__ void __launch_bounds__(NW * 64) k_attention_bwd_dq(const float* __res
         __syncthreads();
 
         // S^T = K . Q^T, dP^T = V . dO^T
-        ab_f16 st, dp;
+        at_acc st, dp;
 #pragma unroll
         for (int r = 0; r < 16; r++) { st[r] = 0.0f; dp[r] = 0.0f; }
 #pragma unroll
@@ -143,12 +138,12 @@ __global__ void __launch_bounds__(NW * 64) k_attention_bwd_dq(const float* __res
             }
         }
         // dS^T = P^T o (dP^T - delta); keys past the set: the score is -inf, P = 0
-        const int key0 = kt * AB_T;
-        const bool tail = key0 + AB_T > n_k;
+        const int key0 = kt * AT_T;
+        const bool tail = key0 + AT_T > n_k;
 #pragma unroll
         for (int r = 0; r < 16; r++) {
             float sv = st[r] * sc2;
-            if (tail && key0 + ab_row(r, hi) >= n_k) sv = -INFINITY;
+            if (tail && key0 + at_row(r, hi) >= n_k) sv = -INFINITY;
             const float p = __builtin_amdgcn_exp2f(sv - lse_i);
             st[r] = p * (dp[r] - delta_i);
         }
@@ -157,7 +152,7 @@ __global__ void __launch_bounds__(NW * 64) k_attention_bwd_dq(const float* __res
         for (int b = 0; b < ND; b++) {
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                const float kf = Ks[ab_row(r, hi) * SK + b * 32 + col];
+                const float kf = Ks[at_row(r, hi) * SK + b * 32 + col];
                 acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf, st[r], acc[b], 0, 0, 0);
             }
         }
@@ -189,10 +184,10 @@ __global__ void __launch_bounds__(NW * 64) k_attention_bwd_dkdv(const float* __r
                                                                 int n_k, int d, float scale, int kgroups) {
     constexpr int SK = ND * 32 + 4, NT = NW * 64;
     constexpr bool DK = PART != 1, DV = PART != 2;
-    __shared__ __attribute__((aligned(16))) float Qs[AB_T * SK];
-    __shared__ __attribute__((aligned(16))) float Ds[AB_T * SK];
-    __shared__ __attribute__((aligned(16))) float Ls[AB_T];
-    __shared__ __attribute__((aligned(16))) float Dl[AB_T];
+    __shared__ __attribute__((aligned(16))) float Qs[AT_T * SK];
+    __shared__ __attribute__((aligned(16))) float Ds[AT_T * SK];
+    __shared__ __attribute__((aligned(16))) float Ls[AT_T];
+    __shared__ __attribute__((aligned(16))) float Dl[AT_T];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, hi = lane >> 5;
     const int bh = blockIdx.x / kgroups, kg = blockIdx.x - bh * kgroups;
     const float* qb = q + (size_t)bh * n * d;
@@ -200,7 +195,7 @@ __global__ void __launch_bounds__(NW * 64) k_attention_bwd_dkdv(const float* __r
     const size_t dstride = (size_t)H * d;
     const int d4 = d >> 2;
 
-    for (int i = tid; i < AB_T * SK; i += NT) { Qs[i] = 0.0f; Ds[i] = 0.0f; }
+    for (int i = tid; i < AT_T * SK; i += NT) { Qs[i] = 0.0f; Ds[i] = 0.0f; }
 
     // K and V fragments of key `col` of this wave's tile: d = 8 g + 4 hi .. + 3 in kf[g] / vf[g]; zero past d and past n_k
     const int key0 = (kg * NW + wave) * 32;
@@ -218,19 +213,19 @@ __global__ void __launch_bounds__(NW * 64) k_attention_bwd_dkdv(const float* __r
         vf[g] = (DK && ok) ? *(const float4*)(vrow + c0) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     }
 
-    ab_f16 ak[ND], av[ND];
+    at_acc ak[ND], av[ND];
 #pragma unroll
     for (int b = 0; b < ND; b++)
 #pragma unroll
         for (int r = 0; r < 16; r++) { ak[b][r] = 0.0f; av[b][r] = 0.0f; }
     const float sc2 = scale * 1.44269504088896340736f;
 
-    const int ntiles = (n + AB_T - 1) / AB_T;
+    const int ntiles = (n + AT_T - 1) / AT_T;
     for (int qt = 0; qt < ntiles; qt++) {
         __syncthreads();   // the previous tile's readers (first pass: the zero fill) are done
-        for (int e = tid; e < AB_T * d4; e += NT) {
+        for (int e = tid; e < AT_T * d4; e += NT) {
             const int row = e / d4, c4 = e - row * d4;
-            const int i = qt * AB_T + row;
+            const int i = qt * AT_T + row;
             float4 qv = make_float4(0.0f, 0.0f, 0.0f, 0.0f), dv4 = qv;
             if (i < n) {
                 qv = *(const float4*)(qb + (size_t)i * d + 4 * c4);
@@ -239,8 +234,8 @@ __global__ void __launch_bounds__(NW * 64) k_attention_bwd_dkdv(const float* __r
             *(float4*)(Qs + row * SK + 4 * c4) = qv;
             *(float4*)(Ds + row * SK + 4 * c4) = dv4;
         }
-        if (tid < AB_T) {
-            const int i = qt * AB_T + tid;
+        if (tid < AT_T) {
+            const int i = qt * AT_T + tid;
             Ls[tid] = i < n ? lse[(size_t)bh * n + i] : INFINITY;   // a query past n: P = exp2(0 - inf) = 0
             Dl[tid] = i < n ? delta[(size_t)bh * n + i] : 0.0f;
         }
@@ -248,7 +243,7 @@ __global__ void __launch_bounds__(NW * 64) k_attention_bwd_dkdv(const float* __r
         if (!wave_on) continue;
 
         // S = Q . K^T, dP = dO . V^T: the key on the lane, 16 queries in the registers
-        ab_f16 st, dp;
+        at_acc st, dp;
 #pragma unroll
         for (int r = 0; r < 16; r++) { st[r] = 0.0f; dp[r] = 0.0f; }
 #pragma unroll
@@ -287,24 +282,24 @@ __global__ void __launch_bounds__(NW * 64) k_attention_bwd_dkdv(const float* __r
 #pragma unroll
         for (int b = 0; b < ND; b++) {
             if constexpr (DV) {
-                ab_f16 t;
+                at_acc t;
 #pragma unroll
                 for (int r = 0; r < 16; r++) t[r] = 0.0f;
 #pragma unroll
                 for (int r = 0; r < 16; r++) {
-                    const float da = Ds[ab_row(r, hi) * SK + b * 32 + col];
+                    const float da = Ds[at_row(r, hi) * SK + b * 32 + col];
                     t = __builtin_amdgcn_mfma_f32_32x32x2f32(da, st[r], t, 0, 0, 0);
                 }
 #pragma unroll
                 for (int r = 0; r < 16; r++) av[b][r] += t[r];
             }
             if constexpr (DK) {
-                ab_f16 t;
+                at_acc t;
 #pragma unroll
                 for (int r = 0; r < 16; r++) t[r] = 0.0f;
 #pragma unroll
                 for (int r = 0; r < 16; r++) {
-                    const float qa = Qs[ab_row(r, hi) * SK + b * 32 + col];
+                    const float qa = Qs[at_row(r, hi) * SK + b * 32 + col];
                     t = __builtin_amdgcn_mfma_f32_32x32x2f32(qa, dp[r], t, 0, 0, 0);
                 }
 #pragma unroll
@@ -333,58 +328,38 @@ __global__ void __launch_bounds__(NW * 64) k_attention_bwd_dkdv(const float* __r
     }
 }
 
-template <int ND, int NW>
-static hipError_t ab_launch_nw(const float* q, const float* k, const float* v, const float* d_out, const float* lse, const float* delta,
-                               float* dq, float* dk, float* dv, long long bhn, int H, int n, int n_k, int d, float scale,
-                               hipStream_t stream) {
-    const int kgroups = ((n_k + 31) / 32 + NW - 1) / NW, qtiles = (n + 32 * NW - 1) / (32 * NW);
-    if constexpr (ND < 5) {
-        hipLaunchKernelGGL((k_attention_bwd_dkdv<ND, NW, 0>), dim3((unsigned)(bhn * kgroups)), dim3(NW * 64), 0, stream, q, k, v, d_out,
-                           lse, delta, dk, dv, H, n, n_k, d, scale, kgroups);
-    } else {
-        hipLaunchKernelGGL((k_attention_bwd_dkdv<ND, NW, 1>), dim3((unsigned)(bhn * kgroups)), dim3(NW * 64), 0, stream, q, k, v, d_out,
-                           lse, delta, dk, dv, H, n, n_k, d, scale, kgroups);
-        hipLaunchKernelGGL((k_attention_bwd_dkdv<ND, NW, 2>), dim3((unsigned)(bhn * kgroups)), dim3(NW * 64), 0, stream, q, k, v, d_out,
-                           lse, delta, dk, dv, H, n, n_k, d, scale, kgroups);
-    }
-    hipLaunchKernelGGL((k_attention_bwd_dq<ND, NW>), dim3((unsigned)(bhn * qtiles)), dim3(NW * 64), 0, stream, q, k, v, d_out, lse,
-                       delta, dq, H, n, n_k, d, scale, qtiles);
-    return hipGetLastError();
-}
-
-template <int ND>
-static hipError_t ab_launch(int nw, const float* q, const float* k, const float* v, const float* d_out, const float* lse,
-                            const float* delta, float* dq, float* dk, float* dv, long long bhn, int H, int n, int n_k, int d, float scale,
-                            hipStream_t stream) {
-    if (nw == 4) return ab_launch_nw<ND, 4>(q, k, v, d_out, lse, delta, dq, dk, dv, bhn, H, n, n_k, d, scale, stream);
-    if (nw == 2) return ab_launch_nw<ND, 2>(q, k, v, d_out, lse, delta, dq, dk, dv, bhn, H, n, n_k, d, scale, stream);
-    return ab_launch_nw<ND, 1>(q, k, v, d_out, lse, delta, dq, dk, dv, bhn, H, n, n_k, d, scale, stream);
-}
-
 size_t attention_bwd_workspace_bytes(int b, int h, int n, int n_k, int d) {
     (void)n_k; (void)d;
     if (b <= 0 || h <= 0 || n <= 0 || n_k <= 0 || d <= 0) return 0;
     return ((size_t)b * h * n * 4 + 255) & ~(size_t)255;   // delta
 }
 
-// workgroup shapes: the forward's (stereo_attention_waves, with its development switch); a dk/dv workgroup of NW waves owns NW key
-// tiles and a dq workgroup NW query tiles
+// workgroup shapes: the forward's (attention_waves, with its development switch); a dk/dv workgroup of NW waves owns NW key tiles
+// and a dq workgroup NW query tiles
 hipError_t launch_attention_bwd(const float* q, const float* k, const float* v, const float* out, const float* lse, const float* d_out,
                                 float* dq, float* dk, float* dv, int b, int h, int n, int n_k, int d, float scale, void* workspace,
                                 hipStream_t stream) {
     const long long bhn = (long long)b * h;
-    const int nw = stereo_attention_waves(bhn, n);
+    const int nw = attention_waves(bhn, n);
     float* delta = (float*)workspace;
     const size_t rows = (size_t)bhn * n;
     hipLaunchKernelGGL(k_attention_delta, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, out, d_out, delta, h, n, d, rows);
-    switch ((d + 31) / 32) {
-    case 1: return ab_launch<1>(nw, q, k, v, d_out, lse, delta, dq, dk, dv, bhn, h, n, n_k, d, scale, stream);
-    case 2: return ab_launch<2>(nw, q, k, v, d_out, lse, delta, dq, dk, dv, bhn, h, n, n_k, d, scale, stream);
-    case 3: return ab_launch<3>(nw, q, k, v, d_out, lse, delta, dq, dk, dv, bhn, h, n, n_k, d, scale, stream);
-    case 4: return ab_launch<4>(nw, q, k, v, d_out, lse, delta, dq, dk, dv, bhn, h, n, n_k, d, scale, stream);
-    case 5: return ab_launch<5>(nw, q, k, v, d_out, lse, delta, dq, dk, dv, bhn, h, n, n_k, d, scale, stream);
-    }
-    return hipErrorInvalidValue;
+    return at_dispatch(d, nw, [&](auto nd, auto nwc) {
+        constexpr int ND = decltype(nd)::value, NW = decltype(nwc)::value;
+        const int kgroups = ((n_k + 31) / 32 + NW - 1) / NW, qtiles = (n + 32 * NW - 1) / (32 * NW);
+        if constexpr (ND < 5) {
+            hipLaunchKernelGGL((k_attention_bwd_dkdv<ND, NW, 0>), dim3((unsigned)(bhn * kgroups)), dim3(NW * 64), 0, stream, q, k, v, d_out,
+                               lse, delta, dk, dv, h, n, n_k, d, scale, kgroups);
+        } else {   // dv, then dk: see PART
+            hipLaunchKernelGGL((k_attention_bwd_dkdv<ND, NW, 1>), dim3((unsigned)(bhn * kgroups)), dim3(NW * 64), 0, stream, q, k, v, d_out,
+                               lse, delta, dk, dv, h, n, n_k, d, scale, kgroups);
+            hipLaunchKernelGGL((k_attention_bwd_dkdv<ND, NW, 2>), dim3((unsigned)(bhn * kgroups)), dim3(NW * 64), 0, stream, q, k, v, d_out,
+                               lse, delta, dk, dv, h, n, n_k, d, scale, kgroups);
+        }
+        hipLaunchKernelGGL((k_attention_bwd_dq<ND, NW>), dim3((unsigned)(bhn * qtiles)), dim3(NW * 64), 0, stream, q, k, v, d_out, lse,
+                           delta, dq, h, n, n_k, d, scale, qtiles);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace cs

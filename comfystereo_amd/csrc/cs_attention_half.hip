@@ -3,25 +3,17 @@
 // softmax (running maximum, sum, rescale) and both accumulators are float32, only the MFMA operands (Q, K, V, and P after the
 // exponential) are half.  No score matrix, no workspace.
 //
-// One wave owns 32 queries; a workgroup of NW waves shares the 32-key K / V tiles in LDS.  Per tile a wave computes
-//   S^T = K . Q^T   lane (r, h) (r = l & 31, h = l >> 5) holds K[key r][d = 16 g + 8 h + j], j = 0..7, of k-step g (one
-//                   ds_read_b128) and the matching eight Q elements of its query in registers; d is zero-padded to a multiple
-//                   of 16.  The accumulator has the query on the lane and key sa_row(reg, h) in register reg, as in the
-//                   float32 kernel: the softmax reductions are in-lane plus one exchange with lane l ^ 32.
-//   O^T += V^T . P^T  registers 8 s .. 8 s + 7 of the S^T accumulator, converted to half, ARE the B fragment of k-step s
-//                   (s = 0, 1): element j stands for key sa_row(8 s + j, h) = 16 s + 8 (j >> 2) + 4 h + (j & 3).  The A fragment
-//                   is V of those eight keys at output column 32 blk + r: V is staged TRANSPOSED and key-permuted,
-//                   Vt[column][slot 16 s + 8 h + j], so that the fragment is one ds_read_b128.
-// LDS banking (16-byte slots, 16 per 256-byte bank row; ds_read_b128 is served in 16-lane groups {0-3, 12-15, 20-27},
-// {4-11, 16-19, 28-31} of either wave half, i.e. one h and 16 rows that are pairwise distinct mod 16):
-//   K rows are 32 ND + 8 halves = (4 ND + 1) slots apart, Vt rows 40 halves = 5 slots: an odd slot stride times 16 rows distinct
-//   mod 16 gives 16 distinct slots, every fragment read is conflict-free.
-//   The transposing V store is a ds_write_b32 of the pair (key 2 m, key 2 m + 1) -- adjacent slots -- per column: a wave half is
-//   16 pairs x two 8-column chunks; the 16 pairs fill 16 consecutive dwords of a Vt row, rows are 20 dwords apart, 8 rows are
-//   160 = 0 (mod 32) dwords apart, so the lanes of the odd chunk take their columns in the order i ^ 4 (4 rows = 80 = 16 mod 32):
-//   the two chunks land on disjoint halves of the 32 write banks.
+// One wave owns 32 queries; a workgroup of NW waves shares the 32-key K / V tiles in LDS.  Fragments, the transposed LDS image and
+// the banking argument are cs_attention_tile.h's.  Per tile a wave computes
+//   S^T = K . Q^T   lane (r, h) holds K[key r][d = 16 g + 8 h + j], j = 0..7, of k-step g (one ds_read_b128 from the row-major
+//                   Ks, rows 32 ND + 8 halves apart) and the matching eight Q elements of its query in registers; d is zero-padded
+//                   to a multiple of 16.  The accumulator has the query on the lane and key at_row(reg, h) in register reg, as in
+//                   the float32 kernel.
+//   O^T += V^T . P^T  registers 8 s .. 8 s + 7 of the S^T accumulator, converted to half, are the B fragment of k-step s; the A
+//                   fragment is V of those eight keys at output column 32 blk + r, read from Vt[column][slot], V staged
+//                   transposed and key-permuted (stage(), the same store as sah_store_t).
 // The next tile's K / V are loaded into registers before this tile's products and stored to LDS after them.
-#include "cs_attention_half.h"
+#include "cs_attention_tile.h"
 #include "cs_common.h"
 #include "cs_kernels.h"
 
@@ -36,9 +28,9 @@ __global__ void __launch_bounds__(NW * 64) k_stereo_attention_half(const T* __re
                                                                    float scale, int mode, int qtiles, float* __restrict__ lse = nullptr) {
     typedef typename sah_frag<T>::type frag;
     constexpr int SK = ND * 32 + 8, NT = NW * 64;
-    constexpr int KI = (SAH_KT * ND * 4 + NT - 1) / NT;         // 16-byte K chunks of a tile per thread
-    constexpr int VI = (SAH_KT / 2 * ND * 4 + NT - 1) / NT;     // (key pair, 8-column chunk) tasks of a V tile per thread
-    __shared__ __attribute__((aligned(16))) T Ks[SAH_KT * SK];
+    constexpr int KI = (AT_T * ND * 4 + NT - 1) / NT;         // 16-byte K chunks of a tile per thread
+    constexpr int VI = (AT_T / 2 * ND * 4 + NT - 1) / NT;     // (key pair, 8-column chunk) tasks of a V tile per thread
+    __shared__ __attribute__((aligned(16))) T Ks[AT_T * SK];
     __shared__ __attribute__((aligned(16))) T Vt[ND * 32 * SAH_SVT];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, hi = lane >> 5;
     const int bh = blockIdx.x / qtiles, qt = blockIdx.x - bh * qtiles;
@@ -53,7 +45,7 @@ __global__ void __launch_bounds__(NW * 64) k_stereo_attention_half(const T* __re
 
     // K's pad columns (d .. SK) are multiplied by Q's zero pad, Vt's rows past d feed output columns nobody stores, keys past
     // the set are multiplied by p = 0: all of them must be finite
-    for (int i = tid; i < SAH_KT * SK / 2; i += NT) ((unsigned*)Ks)[i] = 0u;
+    for (int i = tid; i < AT_T * SK / 2; i += NT) ((unsigned*)Ks)[i] = 0u;
     for (int i = tid; i < ND * 32 * SAH_SVT / 2; i += NT) ((unsigned*)Vt)[i] = 0u;
 
     // Q fragment: query `col` of this wave, d = 16 g + 8 hi .. + 7 in qf[g]; zero past d and past n
@@ -69,7 +61,7 @@ __global__ void __launch_bounds__(NW * 64) k_stereo_attention_half(const T* __re
         qf[g] = __builtin_bit_cast(frag, raw);
     }
 
-    sah_acc o[ND];
+    at_acc o[ND];
 #pragma unroll
     for (int b = 0; b < ND; b++)
 #pragma unroll
@@ -84,14 +76,14 @@ __global__ void __launch_bounds__(NW * 64) k_stereo_attention_half(const T* __re
         for (int it = 0; it < KI; it++) {
             const int e = tid + it * NT;
             const int row = e / d8, c8 = e - row * d8;
-            const int j = kt * SAH_KT + row;
+            const int j = kt * AT_T + row;
             kr[it] = make_uint4(0u, 0u, 0u, 0u);
-            if (row < SAH_KT && j < nkeys) kr[it] = *(const uint4*)(kb + ((size_t)j + (j >= n_k ? view_rows : 0)) * d + 8 * c8);
+            if (row < AT_T && j < nkeys) kr[it] = *(const uint4*)(kb + ((size_t)j + (j >= n_k ? view_rows : 0)) * d + 8 * c8);
         }
 #pragma unroll
         for (int it = 0; it < VI; it++) {
             const int e = tid + it * NT;
-            const int c8 = e >> 4, j = kt * SAH_KT + 2 * (e & 15);
+            const int c8 = e >> 4, j = kt * AT_T + 2 * (e & 15);
             va[it] = vc[it] = make_uint4(0u, 0u, 0u, 0u);
             if (c8 < d8) {
                 if (j < nkeys) va[it] = *(const uint4*)(vb + ((size_t)j + (j >= n_k ? view_rows : 0)) * d + 8 * c8);
@@ -104,7 +96,7 @@ __global__ void __launch_bounds__(NW * 64) k_stereo_attention_half(const T* __re
         for (int it = 0; it < KI; it++) {
             const int e = tid + it * NT;
             const int row = e / d8, c8 = e - row * d8;
-            if (row < SAH_KT) *(uint4*)(Ks + row * SK + 8 * c8) = kr[it];
+            if (row < AT_T) *(uint4*)(Ks + row * SK + 8 * c8) = kr[it];
         }
 #pragma unroll
         for (int it = 0; it < VI; it++) {
@@ -123,7 +115,7 @@ __global__ void __launch_bounds__(NW * 64) k_stereo_attention_half(const T* __re
         }
     };
 
-    const int ntiles = (nkeys + SAH_KT - 1) / SAH_KT;
+    const int ntiles = (nkeys + AT_T - 1) / AT_T;
     fetch(0);
     for (int kt = 0; kt < ntiles; kt++) {
         __syncthreads();   // the previous tile's readers (first pass: the zero fill) are done
@@ -132,7 +124,7 @@ __global__ void __launch_bounds__(NW * 64) k_stereo_attention_half(const T* __re
         if (kt + 1 < ntiles) fetch(kt + 1);
 
         // S^T = K . Q^T
-        sah_acc st;
+        at_acc st;
 #pragma unroll
         for (int r = 0; r < 16; r++) st[r] = 0.0f;
 #pragma unroll
@@ -144,13 +136,13 @@ __global__ void __launch_bounds__(NW * 64) k_stereo_attention_half(const T* __re
         }
         // keys past the set: -inf BEFORE the running maximum is updated (tile 0 always holds key 0, so the maximum is
         // finite from the first tile on and exp2(-inf - m) = 0 is the only form -inf takes)
-        const int key0 = kt * SAH_KT;
-        const bool tail = key0 + SAH_KT > nkeys;
+        const int key0 = kt * AT_T;
+        const bool tail = key0 + AT_T > nkeys;
         float m_tile = -INFINITY;
 #pragma unroll
         for (int r = 0; r < 16; r++) {
             float sv = st[r] * sc2;
-            if (tail && key0 + sah_row(r, hi) >= nkeys) sv = -INFINITY;
+            if (tail && key0 + at_row(r, hi) >= nkeys) sv = -INFINITY;
             st[r] = sv;
             m_tile = fmaxf(m_tile, sv);
         }
@@ -205,89 +197,36 @@ __global__ void __launch_bounds__(NW * 64) k_stereo_attention_half(const T* __re
     }
 }
 
-template <typename T, int ND>
-static hipError_t sah_launch(int nw, int blocks, const T* q, const T* k, const T* v, T* out, int S, int B, int H, int n, int n_k, int d,
-                             float scale, int mode, int qtiles, hipStream_t stream) {
-    if (nw == 4)
-        hipLaunchKernelGGL((k_stereo_attention_half<T, ND, 4>), dim3(blocks), dim3(256), 0, stream, q, k, v, out, S, B, H, n, n_k, d, scale, mode, qtiles);
-    else if (nw == 2)
-        hipLaunchKernelGGL((k_stereo_attention_half<T, ND, 2>), dim3(blocks), dim3(128), 0, stream, q, k, v, out, S, B, H, n, n_k, d, scale, mode, qtiles);
-    else
-        hipLaunchKernelGGL((k_stereo_attention_half<T, ND, 1>), dim3(blocks), dim3(64), 0, stream, q, k, v, out, S, B, H, n, n_k, d, scale, mode, qtiles);
-    return hipGetLastError();
-}
-
-template <typename T, int ND>
-static hipError_t sah_launch_lse(int nw, int blocks, const T* q, const T* k, const T* v, T* out, float* lse, int B, int H, int n, int n_k,
-                                 int d, float scale, int qtiles, hipStream_t stream) {
-    if (nw == 4)
-        hipLaunchKernelGGL((k_stereo_attention_half<T, ND, 4, true>), dim3(blocks), dim3(256), 0, stream, q, k, v, out, 1, B, H, n, n_k, d, scale, (int)CS_ATTN_SELF, qtiles, lse);
-    else if (nw == 2)
-        hipLaunchKernelGGL((k_stereo_attention_half<T, ND, 2, true>), dim3(blocks), dim3(128), 0, stream, q, k, v, out, 1, B, H, n, n_k, d, scale, (int)CS_ATTN_SELF, qtiles, lse);
-    else
-        hipLaunchKernelGGL((k_stereo_attention_half<T, ND, 1, true>), dim3(blocks), dim3(64), 0, stream, q, k, v, out, 1, B, H, n, n_k, d, scale, (int)CS_ATTN_SELF, qtiles, lse);
-    return hipGetLastError();
-}
-
-// Waves per workgroup: 4, as in the float32 kernel, until tools/attention_bench.py --dtype ... --sweep says otherwise; 1 and 2
-// stay selectable with CS_DEBUG_ATTN_WAVES.
-int stereo_attention_half_waves(long long batch_heads, int n) {
-    (void)batch_heads; (void)n;
-    const int forced = dev_switch(CS_DEBUG_ATTN_WAVES);
-    return (forced == 1 || forced == 2) ? forced : 4;
-}
-
-template <typename T>
-static hipError_t sah_dispatch(const void* q, const void* k, const void* v, void* out, int c, int s, int b, int h, int n, int n_k, int d,
-                               float scale, int mode, hipStream_t stream) {
+// workgroup shapes: attention_waves (cs_attention.hip), with its development switch
+template <bool LSE>
+static hipError_t sah_launch(const void* q, const void* k, const void* v, void* out, float* lse, int dtype, int c, int s, int b, int h,
+                             int n, int n_k, int d, float scale, int mode, hipStream_t stream) {
     const long long bhn = (long long)c * s * b * h;
-    const int nw = stereo_attention_half_waves(bhn, n);
+    const int nw = attention_waves(bhn, n);
     const int qtiles = (n + 32 * nw - 1) / (32 * nw);
     const int blocks = (int)(bhn * qtiles);
-    const T *tq = (const T*)q, *tk = (const T*)k, *tv = (const T*)v;
-    T* to = (T*)out;
-    switch ((d + 31) / 32) {
-    case 1: return sah_launch<T, 1>(nw, blocks, tq, tk, tv, to, s, b, h, n, n_k, d, scale, mode, qtiles, stream);
-    case 2: return sah_launch<T, 2>(nw, blocks, tq, tk, tv, to, s, b, h, n, n_k, d, scale, mode, qtiles, stream);
-    case 3: return sah_launch<T, 3>(nw, blocks, tq, tk, tv, to, s, b, h, n, n_k, d, scale, mode, qtiles, stream);
-    case 4: return sah_launch<T, 4>(nw, blocks, tq, tk, tv, to, s, b, h, n, n_k, d, scale, mode, qtiles, stream);
-    case 5: return sah_launch<T, 5>(nw, blocks, tq, tk, tv, to, s, b, h, n, n_k, d, scale, mode, qtiles, stream);
-    }
-    return hipErrorInvalidValue;
+    return sah_dispatch(dtype, [&](auto* tag) {
+        typedef std::remove_pointer_t<decltype(tag)> T;
+        const T *tq = (const T*)q, *tk = (const T*)k, *tv = (const T*)v;
+        T* to = (T*)out;
+        return at_dispatch(d, nw, [&](auto nd, auto nwc) {
+            constexpr int ND = decltype(nd)::value, NW = decltype(nwc)::value;
+            hipLaunchKernelGGL((k_stereo_attention_half<T, ND, NW, LSE>), dim3(blocks), dim3(NW * 64), 0, stream, tq, tk, tv, to, s, b, h,
+                               n, n_k, d, scale, mode, qtiles, lse);
+            return hipGetLastError();
+        });
+    });
 }
 
 hipError_t launch_stereo_attention_half(const void* q, const void* k, const void* v, void* out, int dtype, int c, int s, int b, int h,
                                         int n, int n_k, int d, float scale, int mode, hipStream_t stream) {
-    if (dtype == CS_ATTN_F16) return sah_dispatch<_Float16>(q, k, v, out, c, s, b, h, n, n_k, d, scale, mode, stream);
-    if (dtype == CS_ATTN_BF16) return sah_dispatch<__bf16>(q, k, v, out, c, s, b, h, n, n_k, d, scale, mode, stream);
-    return hipErrorInvalidValue;
+    return sah_launch<false>(q, k, v, out, nullptr, dtype, c, s, b, h, n, n_k, d, scale, mode, stream);
 }
 
 // the same launch as launch_stereo_attention_half(..., CS_ATTN_SELF) with c = s = 1: `out` is bit for bit that call's
-template <typename T>
-static hipError_t sah_dispatch_lse(const void* q, const void* k, const void* v, void* out, float* lse, int b, int h, int n, int n_k, int d,
-                                   float scale, hipStream_t stream) {
-    const long long bhn = (long long)b * h;
-    const int nw = stereo_attention_half_waves(bhn, n);
-    const int qtiles = (n + 32 * nw - 1) / (32 * nw);
-    const int blocks = (int)(bhn * qtiles);
-    const T *tq = (const T*)q, *tk = (const T*)k, *tv = (const T*)v;
-    T* to = (T*)out;
-    switch ((d + 31) / 32) {
-    case 1: return sah_launch_lse<T, 1>(nw, blocks, tq, tk, tv, to, lse, b, h, n, n_k, d, scale, qtiles, stream);
-    case 2: return sah_launch_lse<T, 2>(nw, blocks, tq, tk, tv, to, lse, b, h, n, n_k, d, scale, qtiles, stream);
-    case 3: return sah_launch_lse<T, 3>(nw, blocks, tq, tk, tv, to, lse, b, h, n, n_k, d, scale, qtiles, stream);
-    case 4: return sah_launch_lse<T, 4>(nw, blocks, tq, tk, tv, to, lse, b, h, n, n_k, d, scale, qtiles, stream);
-    case 5: return sah_launch_lse<T, 5>(nw, blocks, tq, tk, tv, to, lse, b, h, n, n_k, d, scale, qtiles, stream);
-    }
-    return hipErrorInvalidValue;
-}
-
 hipError_t launch_attention_half_fwd_lse(const void* q, const void* k, const void* v, void* out, float* lse, int dtype, int b, int h, int n,
                                          int n_k, int d, float scale, hipStream_t stream) {
-    if (dtype == CS_ATTN_F16) return sah_dispatch_lse<_Float16>(q, k, v, out, lse, b, h, n, n_k, d, scale, stream);
-    if (dtype == CS_ATTN_BF16) return sah_dispatch_lse<__bf16>(q, k, v, out, lse, b, h, n, n_k, d, scale, stream);
-    return hipErrorInvalidValue;
+    return sah_launch<true>(q, k, v, out, lse, dtype, 1, 1, b, h, n, n_k, d, scale, CS_ATTN_SELF, stream);
 }
 
 }  // namespace cs

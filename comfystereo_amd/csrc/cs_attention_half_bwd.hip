@@ -16,22 +16,18 @@
 //
 // All five products run on the half-input MFMA.  Its operands are Q, K, V and dO as they arrive, and P and dS converted to half
 // (nearest-even) after the float32 arithmetic that forms them; scores, exponentials, dP - delta and all accumulators are float32.
-// Lane (r, h) (r = l & 31, h = l >> 5) of an A fragment holds row r, k = 8 h + j (j = 0..7); the accumulator has its column on
-// the lane and row sah_row(reg, h) in register reg.
+// Fragments, the accumulator's row map at_row and the transposed, row-permuted LDS images with their banking argument are
+// cs_attention_tile.h's.
 //   dq kernel    S^T = K . Q^T and dP^T = V . dO^T: the QUERY on the lane, lse and delta per-lane scalars; Q and dO fragments in
 //                registers, K and V rows read from the row-major images Ks / Vs [key][d] with one ds_read_b128 per k-step.  Then
 //                dQ^T += K^T . dS^T by the forward's operand trick: registers 8 s .. 8 s + 7 of the dS^T accumulator, converted to
-//                half, ARE the B fragment of k-step s (element j stands for key sah_row(8 s + j, h)); the A fragment comes from
-//                Kt[column][slot 16 s + 8 h + j], K staged TRANSPOSED and key-permuted (sah_slot) like the forward's Vt.
+//                half, are the B fragment of k-step s; the A fragment comes from Kt[column][slot], K staged transposed and
+//                key-permuted (sah_store_t) like the forward's Vt.
 //   dk/dv kernel S = Q . K^T and dP = dO . V^T: the KEY on the lane, K and V fragments in registers, Q and dO rows from the
 //                row-major images Qs / Ds [query][d]; lse and delta of a register's query from LDS (broadcast float4 reads).  Then
 //                dV^T += dO^T . P and dK^T += Q^T . dS with the P / dS registers as B fragments and the A fragments from the
 //                transposed, query-permuted images Dt / Qt [column][slot].
-// LDS banking (16-byte slots, 16 per 256-byte bank row; a ds_read_b128 is served in 16-lane groups of one h and 16 rows that are
-// pairwise distinct mod 16, see cs_attention_half.hip): rows of the row-major images are 32 ND + 8 halves = (4 ND + 1) slots
-// apart, rows of the transposed images SAH_SVT = 40 halves = 5 slots.  Both strides are odd, so 16 rows distinct mod 16 land on 16
-// distinct slots: every fragment read is conflict-free.  The transposing store is the forward's: a ds_write_b32 of the row pair
-// (2 m, 2 m + 1) -- adjacent slots -- per column, odd 8-column chunks taking their columns in the order i ^ 4.
+// Rows of the row-major images are 32 ND + 8 halves apart, rows of the transposed images SAH_SVT = 40 halves.
 // LDS per workgroup (independent of NW), ND = (d + 31) / 32 = 1 .. 5:
 //   dq     Ks + Vs + Kt = 2 * 32 * (32 ND + 8) * 2 + 32 ND * 40 * 2 bytes:  7 680, 14 336, 20 992, 27 648, 34 304 (33.5 KiB at d = 160)
 //   dk/dv  Qs + Ds + Qt + Dt + lse + delta = twice the K part of that + 256:  10 496, 19 712, 28 928, 38 144, 47 360 (46.25 KiB)
@@ -50,23 +46,11 @@
 // error of a converted dS is at most 2^-25, and the fixture's small-gradient case (d_out * 2^-12, float16) stays within the
 // project's accuracy condition in the kernels' arithmetic (tools/attention_half_grad_oracle.py, tile_ratio in the fixture) because
 // the reference rounds the same quantities to float16 too, twice.  bfloat16 has float32's range and needs no scaling.
-#include "cs_attention_half.h"
+#include "cs_attention_tile.h"
 #include "cs_common.h"
 #include "cs_kernels.h"
 
 namespace cs {
-
-// Stores columns 8 c8 .. 8 c8 + 7 of the row pair (2 m, 2 m + 1) -- lo and up -- into a transposed image at `slot` = sah_slot(2 m):
-// eight ds_write_b32, the odd chunks in the order i ^ 4 (cs_attention_half.hip's banking argument).
-template <typename T>
-__device__ __forceinline__ void ahb_store_t(T* img, const uint4& lo, const uint4& up, int c8, int slot) {
-    const bool odd = c8 & 1;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        const int ii = odd ? (i ^ 4) : i;
-        *(unsigned*)(img + (8 * c8 + ii) * SAH_SVT + slot) = sah_elem(lo, ii) | (sah_elem(up, ii) << 16);
-    }
-}
 
 template <typename T>
 __global__ void __launch_bounds__(256) k_attention_half_delta(const T* __restrict__ out, const T* __restrict__ d_out,
@@ -93,8 +77,8 @@ __global__ void __launch_bounds__(NW * 64) k_attention_half_bwd_dq(const T* __re
                                                                    int n_k, int d, float scale, int qtiles) {
     typedef typename sah_frag<T>::type frag;
     constexpr int SK = ND * 32 + 8, NT = NW * 64;
-    __shared__ __attribute__((aligned(16))) T Ks[SAH_KT * SK];
-    __shared__ __attribute__((aligned(16))) T Vs[SAH_KT * SK];
+    __shared__ __attribute__((aligned(16))) T Ks[AT_T * SK];
+    __shared__ __attribute__((aligned(16))) T Vs[AT_T * SK];
     __shared__ __attribute__((aligned(16))) T Kt[ND * 32 * SAH_SVT];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, hi = lane >> 5;
     const int bh = blockIdx.x / qtiles, qt = blockIdx.x - bh * qtiles;
@@ -102,7 +86,7 @@ __global__ void __launch_bounds__(NW * 64) k_attention_half_bwd_dq(const T* __re
     const T* vb = v + (size_t)bh * n_k * d;
     const int d8 = d >> 3;
 
-    for (int i = tid; i < SAH_KT * SK / 2; i += NT) { ((unsigned*)Ks)[i] = 0u; ((unsigned*)Vs)[i] = 0u; }
+    for (int i = tid; i < AT_T * SK / 2; i += NT) { ((unsigned*)Ks)[i] = 0u; ((unsigned*)Vs)[i] = 0u; }
     for (int i = tid; i < ND * 32 * SAH_SVT / 2; i += NT) ((unsigned*)Kt)[i] = 0u;
 
     // Q and dO fragments of query `col`: d = 16 g + 8 hi .. + 7 in qf[g] / dof[g]; zero past d and past n
@@ -123,7 +107,7 @@ __global__ void __launch_bounds__(NW * 64) k_attention_half_bwd_dq(const T* __re
     const float lse_i = q_ok ? lse[(size_t)bh * n + qi] : 0.0f;
     const float delta_i = q_ok ? delta[(size_t)bh * n + qi] : 0.0f;
 
-    sah_acc acc[ND];
+    at_acc acc[ND];
 #pragma unroll
     for (int b = 0; b < ND; b++)
 #pragma unroll
@@ -131,12 +115,12 @@ __global__ void __launch_bounds__(NW * 64) k_attention_half_bwd_dq(const T* __re
     const float sc2 = scale * 1.44269504088896340736f;
     const uint4 zero4 = make_uint4(0u, 0u, 0u, 0u);
 
-    const int ntiles = (n_k + SAH_KT - 1) / SAH_KT;
+    const int ntiles = (n_k + AT_T - 1) / AT_T;
     for (int kt = 0; kt < ntiles; kt++) {
         __syncthreads();   // the previous tile's readers (first pass: the zero fill) are done
         // task e = (key pair e & 15, 8 columns e >> 4): the pair's two chunks go to their rows of Ks / Vs and, transposed, to Kt
         for (int e = tid; e < 16 * d8; e += NT) {
-            const int c8 = e >> 4, m2 = 2 * (e & 15), j = kt * SAH_KT + m2;
+            const int c8 = e >> 4, m2 = 2 * (e & 15), j = kt * AT_T + m2;
             uint4 ka = zero4, kc = zero4, va = zero4, vc = zero4;
             if (j < n_k) { ka = *(const uint4*)(kb + (size_t)j * d + 8 * c8); va = *(const uint4*)(vb + (size_t)j * d + 8 * c8); }
             if (j + 1 < n_k) { kc = *(const uint4*)(kb + (size_t)(j + 1) * d + 8 * c8); vc = *(const uint4*)(vb + (size_t)(j + 1) * d + 8 * c8); }
@@ -144,12 +128,12 @@ __global__ void __launch_bounds__(NW * 64) k_attention_half_bwd_dq(const T* __re
             *(uint4*)(Ks + (m2 + 1) * SK + 8 * c8) = kc;
             *(uint4*)(Vs + m2 * SK + 8 * c8) = va;
             *(uint4*)(Vs + (m2 + 1) * SK + 8 * c8) = vc;
-            ahb_store_t(Kt, ka, kc, c8, sah_slot(m2));
+            sah_store_t(Kt, ka, kc, c8, sah_slot(m2));
         }
         __syncthreads();
 
         // S^T = K . Q^T, dP^T = V . dO^T
-        sah_acc st, dp;
+        at_acc st, dp;
 #pragma unroll
         for (int r = 0; r < 16; r++) { st[r] = 0.0f; dp[r] = 0.0f; }
 #pragma unroll
@@ -162,12 +146,12 @@ __global__ void __launch_bounds__(NW * 64) k_attention_half_bwd_dq(const T* __re
             }
         }
         // dS^T = P^T o (dP^T - delta); keys past the set: the score is -inf, P = 0
-        const int key0 = kt * SAH_KT;
-        const bool tail = key0 + SAH_KT > n_k;
+        const int key0 = kt * AT_T;
+        const bool tail = key0 + AT_T > n_k;
 #pragma unroll
         for (int r = 0; r < 16; r++) {
             float sv = st[r] * sc2;
-            if (tail && key0 + sah_row(r, hi) >= n_k) sv = -INFINITY;
+            if (tail && key0 + at_row(r, hi) >= n_k) sv = -INFINITY;
             const float p = __builtin_amdgcn_exp2f(sv - lse_i);
             st[r] = p * (dp[r] - delta_i);
         }
@@ -212,12 +196,12 @@ __global__ void __launch_bounds__(NW * 64) k_attention_half_bwd_dkdv(const T* __
                                                                      int kgroups) {
     typedef typename sah_frag<T>::type frag;
     constexpr int SK = ND * 32 + 8, NT = NW * 64;
-    __shared__ __attribute__((aligned(16))) T Qs[SAH_KT * SK];
-    __shared__ __attribute__((aligned(16))) T Ds[SAH_KT * SK];
+    __shared__ __attribute__((aligned(16))) T Qs[AT_T * SK];
+    __shared__ __attribute__((aligned(16))) T Ds[AT_T * SK];
     __shared__ __attribute__((aligned(16))) T Qt[ND * 32 * SAH_SVT];
     __shared__ __attribute__((aligned(16))) T Dt[ND * 32 * SAH_SVT];
-    __shared__ __attribute__((aligned(16))) float Ls[SAH_KT];
-    __shared__ __attribute__((aligned(16))) float Dl[SAH_KT];
+    __shared__ __attribute__((aligned(16))) float Ls[AT_T];
+    __shared__ __attribute__((aligned(16))) float Dl[AT_T];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, hi = lane >> 5;
     const int bh = blockIdx.x / kgroups, kg = blockIdx.x - bh * kgroups;
     const T* qb = q + (size_t)bh * n * d;
@@ -225,7 +209,7 @@ __global__ void __launch_bounds__(NW * 64) k_attention_half_bwd_dkdv(const T* __
     const size_t dstride = (size_t)H * d;
     const int d8 = d >> 3;
 
-    for (int i = tid; i < SAH_KT * SK / 2; i += NT) { ((unsigned*)Qs)[i] = 0u; ((unsigned*)Ds)[i] = 0u; }
+    for (int i = tid; i < AT_T * SK / 2; i += NT) { ((unsigned*)Qs)[i] = 0u; ((unsigned*)Ds)[i] = 0u; }
     for (int i = tid; i < ND * 32 * SAH_SVT / 2; i += NT) { ((unsigned*)Qt)[i] = 0u; ((unsigned*)Dt)[i] = 0u; }
 
     // K and V fragments of key `col` of this wave's tile: d = 16 g + 8 hi .. + 7 in kf[g] / vf[g]; zero past d and past n_k
@@ -245,7 +229,7 @@ __global__ void __launch_bounds__(NW * 64) k_attention_half_bwd_dkdv(const T* __
         vf[g] = __builtin_bit_cast(frag, rv);
     }
 
-    sah_acc ak[ND], av[ND];
+    at_acc ak[ND], av[ND];
 #pragma unroll
     for (int b = 0; b < ND; b++)
 #pragma unroll
@@ -253,12 +237,12 @@ __global__ void __launch_bounds__(NW * 64) k_attention_half_bwd_dkdv(const T* __
     const float sc2 = scale * 1.44269504088896340736f;
     const uint4 zero4 = make_uint4(0u, 0u, 0u, 0u);
 
-    const int ntiles = (n + SAH_KT - 1) / SAH_KT;
+    const int ntiles = (n + AT_T - 1) / AT_T;
     for (int qt = 0; qt < ntiles; qt++) {
         __syncthreads();   // the previous tile's readers (first pass: the zero fill) are done
         // task e = (query pair e & 15, 8 columns e >> 4): the pair's chunks go to their rows of Qs / Ds and, transposed, to Qt / Dt
         for (int e = tid; e < 16 * d8; e += NT) {
-            const int c8 = e >> 4, m2 = 2 * (e & 15), i = qt * SAH_KT + m2;
+            const int c8 = e >> 4, m2 = 2 * (e & 15), i = qt * AT_T + m2;
             uint4 qa = zero4, qc = zero4, da = zero4, dc = zero4;
             if (i < n) { qa = *(const uint4*)(qb + (size_t)i * d + 8 * c8); da = *(const uint4*)(db + (size_t)i * dstride + 8 * c8); }
             if (i + 1 < n) { qc = *(const uint4*)(qb + (size_t)(i + 1) * d + 8 * c8); dc = *(const uint4*)(db + (size_t)(i + 1) * dstride + 8 * c8); }
@@ -267,11 +251,11 @@ __global__ void __launch_bounds__(NW * 64) k_attention_half_bwd_dkdv(const T* __
             *(uint4*)(Ds + m2 * SK + 8 * c8) = da;
             *(uint4*)(Ds + (m2 + 1) * SK + 8 * c8) = dc;
             const int slot = sah_slot(m2);
-            ahb_store_t(Qt, qa, qc, c8, slot);
-            ahb_store_t(Dt, da, dc, c8, slot);
+            sah_store_t(Qt, qa, qc, c8, slot);
+            sah_store_t(Dt, da, dc, c8, slot);
         }
-        if (tid < SAH_KT) {
-            const int i = qt * SAH_KT + tid;
+        if (tid < AT_T) {
+            const int i = qt * AT_T + tid;
             Ls[tid] = i < n ? lse[(size_t)bh * n + i] : INFINITY;   // a query past n: P = exp2(0 - inf) = 0
             Dl[tid] = i < n ? delta[(size_t)bh * n + i] : 0.0f;
         }
@@ -279,7 +263,7 @@ __global__ void __launch_bounds__(NW * 64) k_attention_half_bwd_dkdv(const T* __
         if (!wave_on) continue;
 
         // S = Q . K^T, dP = dO . V^T: the key on the lane, 16 queries in the registers
-        sah_acc st, dp;
+        at_acc st, dp;
 #pragma unroll
         for (int r = 0; r < 16; r++) { st[r] = 0.0f; dp[r] = 0.0f; }
 #pragma unroll
@@ -341,59 +325,30 @@ __global__ void __launch_bounds__(NW * 64) k_attention_half_bwd_dkdv(const T* __
     }
 }
 
-template <typename T, int ND, int NW>
-static hipError_t ahb_launch_nw(const T* q, const T* k, const T* v, const T* d_out, const float* lse, const float* delta, T* dq, T* dk,
-                                T* dv, long long bhn, int H, int n, int n_k, int d, float scale, hipStream_t stream) {
-    const int kgroups = ((n_k + 31) / 32 + NW - 1) / NW, qtiles = (n + 32 * NW - 1) / (32 * NW);
-    hipLaunchKernelGGL((k_attention_half_bwd_dkdv<T, ND, NW>), dim3((unsigned)(bhn * kgroups)), dim3(NW * 64), 0, stream, q, k, v, d_out,
-                       lse, delta, dk, dv, H, n, n_k, d, scale, kgroups);
-    hipLaunchKernelGGL((k_attention_half_bwd_dq<T, ND, NW>), dim3((unsigned)(bhn * qtiles)), dim3(NW * 64), 0, stream, q, k, v, d_out, lse,
-                       delta, dq, H, n, n_k, d, scale, qtiles);
-    return hipGetLastError();
-}
-
-template <typename T, int ND>
-static hipError_t ahb_launch(int nw, const T* q, const T* k, const T* v, const T* d_out, const float* lse, const float* delta, T* dq,
-                             T* dk, T* dv, long long bhn, int H, int n, int n_k, int d, float scale, hipStream_t stream) {
-    if (nw == 4) return ahb_launch_nw<T, ND, 4>(q, k, v, d_out, lse, delta, dq, dk, dv, bhn, H, n, n_k, d, scale, stream);
-    if (nw == 2) return ahb_launch_nw<T, ND, 2>(q, k, v, d_out, lse, delta, dq, dk, dv, bhn, H, n, n_k, d, scale, stream);
-    return ahb_launch_nw<T, ND, 1>(q, k, v, d_out, lse, delta, dq, dk, dv, bhn, H, n, n_k, d, scale, stream);
-}
-
-size_t attention_half_bwd_workspace_bytes(int b, int h, int n, int n_k, int d) {
-    (void)n_k; (void)d;
-    if (b <= 0 || h <= 0 || n <= 0 || n_k <= 0 || d <= 0) return 0;
-    return ((size_t)b * h * n * 4 + 255) & ~(size_t)255;   // delta
-}
-
-// workgroup shapes: the half forward's (stereo_attention_half_waves, with its development switch); a dk/dv workgroup of NW waves
-// owns NW key tiles and a dq workgroup NW query tiles
-template <typename T>
-static hipError_t ahb_dispatch(const void* q, const void* k, const void* v, const void* out, const float* lse, const void* d_out, void* dq,
-                               void* dk, void* dv, int b, int h, int n, int n_k, int d, float scale, void* workspace, hipStream_t stream) {
-    const long long bhn = (long long)b * h;
-    const int nw = stereo_attention_half_waves(bhn, n);
-    float* delta = (float*)workspace;
-    const size_t rows = (size_t)bhn * n;
-    const T *tq = (const T*)q, *tk = (const T*)k, *tv = (const T*)v, *to = (const T*)out, *td = (const T*)d_out;
-    T *gq = (T*)dq, *gk = (T*)dk, *gv = (T*)dv;
-    hipLaunchKernelGGL((k_attention_half_delta<T>), dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, to, td, delta, h, n, d, rows);
-    switch ((d + 31) / 32) {
-    case 1: return ahb_launch<T, 1>(nw, tq, tk, tv, td, lse, delta, gq, gk, gv, bhn, h, n, n_k, d, scale, stream);
-    case 2: return ahb_launch<T, 2>(nw, tq, tk, tv, td, lse, delta, gq, gk, gv, bhn, h, n, n_k, d, scale, stream);
-    case 3: return ahb_launch<T, 3>(nw, tq, tk, tv, td, lse, delta, gq, gk, gv, bhn, h, n, n_k, d, scale, stream);
-    case 4: return ahb_launch<T, 4>(nw, tq, tk, tv, td, lse, delta, gq, gk, gv, bhn, h, n, n_k, d, scale, stream);
-    case 5: return ahb_launch<T, 5>(nw, tq, tk, tv, td, lse, delta, gq, gk, gv, bhn, h, n, n_k, d, scale, stream);
-    }
-    return hipErrorInvalidValue;
-}
-
+// workgroup shapes: the forward's (attention_waves, with its development switch); a dk/dv workgroup of NW waves owns NW key tiles
+// and a dq workgroup NW query tiles.  workspace: attention_bwd_workspace_bytes, delta as in the float32 backward
 hipError_t launch_attention_half_bwd(const void* q, const void* k, const void* v, const void* out, const float* lse, const void* d_out,
                                      void* dq, void* dk, void* dv, int dtype, int b, int h, int n, int n_k, int d, float scale,
                                      void* workspace, hipStream_t stream) {
-    if (dtype == CS_ATTN_F16) return ahb_dispatch<_Float16>(q, k, v, out, lse, d_out, dq, dk, dv, b, h, n, n_k, d, scale, workspace, stream);
-    if (dtype == CS_ATTN_BF16) return ahb_dispatch<__bf16>(q, k, v, out, lse, d_out, dq, dk, dv, b, h, n, n_k, d, scale, workspace, stream);
-    return hipErrorInvalidValue;
+    const long long bhn = (long long)b * h;
+    const int nw = attention_waves(bhn, n);
+    float* delta = (float*)workspace;
+    const size_t rows = (size_t)bhn * n;
+    return sah_dispatch(dtype, [&](auto* tag) {
+        typedef std::remove_pointer_t<decltype(tag)> T;
+        const T *tq = (const T*)q, *tk = (const T*)k, *tv = (const T*)v, *to = (const T*)out, *td = (const T*)d_out;
+        T *gq = (T*)dq, *gk = (T*)dk, *gv = (T*)dv;
+        hipLaunchKernelGGL((k_attention_half_delta<T>), dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, to, td, delta, h, n, d, rows);
+        return at_dispatch(d, nw, [&](auto nd, auto nwc) {
+            constexpr int ND = decltype(nd)::value, NW = decltype(nwc)::value;
+            const int kgroups = ((n_k + 31) / 32 + NW - 1) / NW, qtiles = (n + 32 * NW - 1) / (32 * NW);
+            hipLaunchKernelGGL((k_attention_half_bwd_dkdv<T, ND, NW>), dim3((unsigned)(bhn * kgroups)), dim3(NW * 64), 0, stream, tq, tk, tv,
+                               td, lse, delta, gk, gv, h, n, n_k, d, scale, kgroups);
+            hipLaunchKernelGGL((k_attention_half_bwd_dq<T, ND, NW>), dim3((unsigned)(bhn * qtiles)), dim3(NW * 64), 0, stream, tq, tk, tv, td,
+                               lse, delta, gq, h, n, n_k, d, scale, qtiles);
+            return hipGetLastError();
+        });
+    });
 }
 
 }  // namespace cs

@@ -190,26 +190,24 @@ hipError_t launch_pilresize(const void* in, int in_f32, int gray, int n, int h, 
                             float* out_f32, int planar, size_t pitch, void* workspace, hipStream_t stream);
 // cs_attention.hip (the reference's stereo attention, BNAttention: cs_stereo_attention).  mode: enum cs_attn_mode
 int stereo_attention_max_head_dim();
-int stereo_attention_waves(long long batch_heads, int n);   // waves per workgroup the launcher picks (32 queries each)
+int attention_waves(long long batch_heads, int n);   // waves per workgroup every attention launcher picks (32 rows each)
 hipError_t launch_stereo_attention(const float* q, const float* k, const float* v, float* out, int c, int s, int b, int h, int n,
                                    int n_k, int d, float scale, int mode, hipStream_t stream);
 // the SELF-mode forward that also stores every query's log-sum-exp (log2 units) to lse [(b h)][n]: cs_attention_fwd_lse
 hipError_t launch_attention_fwd_lse(const float* q, const float* k, const float* v, float* out, float* lse, int b, int h, int n, int n_k,
                                     int d, float scale, hipStream_t stream);
-// cs_attention_bwd.hip (dq, dk, dv of that forward: cs_attention_bwd).  workspace: attention_bwd_workspace_bytes
+// cs_attention_bwd.hip (dq, dk, dv of that forward: cs_attention_bwd).  workspace: attention_bwd_workspace_bytes, for any dtype
 size_t attention_bwd_workspace_bytes(int b, int h, int n, int n_k, int d);
 hipError_t launch_attention_bwd(const float* q, const float* k, const float* v, const float* out, const float* lse, const float* d_out,
                                 float* dq, float* dk, float* dv, int b, int h, int n, int n_k, int d, float scale, void* workspace,
                                 hipStream_t stream);
 // cs_attention_half.hip (the same attention on float16 / bfloat16 tensors: cs_stereo_attention_half).  dtype: enum cs_attn_dtype
-int stereo_attention_half_waves(long long batch_heads, int n);
 hipError_t launch_stereo_attention_half(const void* q, const void* k, const void* v, void* out, int dtype, int c, int s, int b, int h,
                                         int n, int n_k, int d, float scale, int mode, hipStream_t stream);
 // the SELF-mode half forward that also stores every query's log-sum-exp (float32, log2 units): cs_attention_half_fwd_lse
 hipError_t launch_attention_half_fwd_lse(const void* q, const void* k, const void* v, void* out, float* lse, int dtype, int b, int h, int n,
                                          int n_k, int d, float scale, hipStream_t stream);
 // cs_attention_half_bwd.hip (dq, dk, dv of that forward in the half dtype: cs_attention_half_bwd)
-size_t attention_half_bwd_workspace_bytes(int b, int h, int n, int n_k, int d);
 hipError_t launch_attention_half_bwd(const void* q, const void* k, const void* v, const void* out, const float* lse, const void* d_out,
                                      void* dq, void* dk, void* dv, int dtype, int b, int h, int n, int n_k, int d, float scale,
                                      void* workspace, hipStream_t stream);

@@ -16,7 +16,7 @@ forward + backward and the peak of torch.cuda.max_memory_allocated above the inp
 casts, the float32 kernels, a cast back, and the same again in the backward), (b) the stock-torch composition in the dtype under
 autograd and (c) F.scaled_dot_product_attention in the dtype; time and peak memory above the inputs for each of the four.
 --sweep: the kernel alone with 1, 2 and 4 waves per workgroup forced (development switch attn_waves) next to the launcher's
-choice: the measurement behind stereo_attention_waves() in cs_attention.hip (with --dtype: stereo_attention_half_waves()).
+choice: the measurement behind attention_waves() in cs_attention.hip (one rule for every dtype; --dtype sweeps the half kernels).
 --dtype f16|bf16: cs_stereo_attention_half on random float16 / bfloat16 operands next to (a) the upcast path for the same
 inputs (three casts to float32, the float32 kernel, one cast back: stereo_utils.HALF_ATTENTION = False) and (b)
 F.scaled_dot_product_attention in that dtype on the routed keys.  The three are timed alternately, round by round, in one
