@@ -351,26 +351,24 @@ static int poly_halo(double div_percent_a, double div_percent_b, double sep_perc
     return (int)ceil(s) + 2;
 }
 
-static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+// the per-frame statistics words every workspace starts with
+static size_t stats_bytes(size_t n) { return al256(n * ST_WORDS * 4); }
+// The stats pre-pass: the words of `frames` frames initialised and, with a depth map of `per_frame` values a frame, its min / max in
+// ST_L_MIN / ST_L_MAX (depth == nullptr: the caller's own kernels fill the words).  The reference's latent shifts normalise with
+// the min / max of the whole tensor: one frame of b * h * w values.
+static void stats_prepass(uint32_t* stats, int frames, const float* depth, size_t per_frame, hipStream_t stream) {
+    hipLaunchKernelGGL(k_stats_init, dim3((frames * ST_WORDS + 255) / 256), dim3(256), 0, stream, stats, frames);
+    if (depth)
+        hipLaunchKernelGGL(k_minmax, dim3(grid_for(per_frame, 256), frames), dim3(256), 0, stream, depth, (int)per_frame, stats, ST_L_MIN, ST_L_MAX);
+}
 // techniques with a D64 (numba typing) instantiation: the forward-map family, the z-buffered inverse map and -- through the
 // general row kernel only, the sweep of full D64 as a literal one-lane replay -- the polylines techniques
 // (round 5: also the three techniques no UI string reaches -- none_post / inverse_post: their mapping functions are @njit, the
 // float64 offset chain is all numba changes; hybrid_edge_plus = hybrid_edge + polylines_soft, both of which have the dialect)
 static bool dialect_d64_ok(int fill) { return fill >= 0 && fill <= CS_FILL_HYBRID_EDGE_PLUS && fill != CS_FILL_GPU_WARP; }
 static const char* const DIALECT_MSG = "dialect D64 (flags bits 3/4) exists for the CPU techniques, not for gpu_warp (torch arithmetic in both installs)";
-// flags of the rows the tiled polylines path hands to the row kernel + their compacted list (run_rows)
-// flagged-row block: [row flags, one byte per row][count / cursor pairs, 256 B][stretch-replay counters, 256 B][replay retry
-// flags, one byte per row] -- everything one memset clears -- then [row list, 4 B per row]
-// (round 5: + [tile hints, one 32-bit word per row and eye: bit t = tile t of that row-eye could not be finished by k_polypoint]
-// behind the retry flags, inside the cleared part)
-// (round 6: + [second-tier row flags, one byte per row][second-tier tile hints] behind the hints, inside the cleared part: what
-// k_polypoint_listed flags among the rows the first tier handed it)
-static size_t rowflag_hint_off(size_t rows) { return 2 * al256(rows) + 512; }
-static size_t rowflag_flag2_off(size_t rows) { return rowflag_hint_off(rows) + al256(rows * 8); }
-static size_t rowflag_hint2_off(size_t rows) { return rowflag_flag2_off(rows) + al256(rows); }
-static size_t rowflag_clear_bytes(size_t rows) { return rowflag_hint2_off(rows) + al256(rows * 8); }
-static size_t rowflag_bytes(size_t rows) { return rowflag_clear_bytes(rows) + al256(rows * 4); }
-static uint32_t* rowflag_list(uint8_t* rowflag, size_t rows) { return (uint32_t*)(rowflag + rowflag_clear_bytes(rows)); }
+// the flagged-row block of a call of `rows` rows (cs_kernels.h RowBlock: the one description of its layout)
+static size_t rowflag_bytes(size_t rows) { return row_block(nullptr, rows).bytes; }
 
 // polylines: tiled fast path + general row kernel over the rows it flagged; everything else: row kernel
 // anaglyph scratch of the tiled polylines path: both eyes as uint8 codes side by side
@@ -409,6 +407,8 @@ static bool poly_tile_takes(int d64, int w, int halo) {
 static int run_rows(int fill, RowArgs& A, int halo, uint8_t* rowflag, hipStream_t stream, uint8_t* ana_sbs = nullptr,
                     void* replay_scratch = nullptr, size_t replay_surplus = 0) {
     const bool poly = fill == CS_FILL_POLYLINES_SOFT || fill == CS_FILL_POLYLINES_SHARP;
+    const size_t rows = (size_t)A.n * A.h;
+    const RowBlock B = row_block(rowflag, rows);
     // anaglyph modes of the tiled polylines path (round 5): BOTH kernels -- the tile kernel and the row kernel over the rows it
     // flags -- write the two eyes as uint8 codes side by side into scratch (no mask), and k_anaglyph_compose makes the composite
     // of every row afterwards.  The row kernel then runs in its side-by-side form: no anaglyph stash in LDS (the width limit of
@@ -431,22 +431,17 @@ static int run_rows(int fill, RowArgs& A, int halo, uint8_t* rowflag, hipStream_
     const bool replay = poly && !A.d64 && replay_scratch && rowflag && !A.anaglyph && !dev_switch(CS_DEBUG_NO_REPLAY_KERNEL) &&
                         poly_replay_bytes(A.n, A.h, A.w, fill == CS_FILL_POLYLINES_SHARP) > 0;
     int hint_T = 0;         // tile width of k_polypoint when it took the call (its hint words are then valid)
-    bool cleared = false;   // the flagged-row block (row flags, counters, replay counters and retry flags) has been zeroed
-    if (replay)
-        (void)poly_replay_attach(A, fill == CS_FILL_POLYLINES_SHARP, replay_scratch, rowflag + al256((size_t)A.n * A.h) + 256, stream, replay_surplus);
+    bool cleared = false;   // the flagged-row block (everything in front of its list) has been zeroed
+    if (replay) poly_replay_attach(A, fill == CS_FILL_POLYLINES_SHARP, replay_scratch, B, replay_surplus);
     if (tiled && !A.anaglyph) {   // (anaglyph calls arrive here in their side-by-side form)
-        // workspace: [n*h flag bytes][count, padded to 256][n*h list entries]
-        const size_t rows = (size_t)A.n * A.h;
-        uint32_t* count = (uint32_t*)(rowflag + al256(rows));
-        uint32_t* list = rowflag_list(rowflag, rows);
-        hipError_t e = hipMemsetAsync(rowflag, 0, rowflag_clear_bytes(rows), stream);
+        hipError_t e = hipMemsetAsync(rowflag, 0, B.clear_bytes, stream);
         if (e != hipSuccess) return fail_hip(e, "rowflag memset");
         cleared = true;
         const RowArgs& T = A;
         if (polypoint_takes(halo))
-            e = launch_polypoint(T, halo, rowflag, stream, fill == CS_FILL_POLYLINES_SHARP, (uint32_t*)(rowflag + rowflag_hint_off(rows)), &hint_T);
+            e = launch_polypoint(T, halo, B.flags, stream, fill == CS_FILL_POLYLINES_SHARP, B.hints, &hint_T);
         else
-            e = launch_polytile(fill == CS_FILL_POLYLINES_SHARP, T, halo, rowflag, stream);
+            e = launch_polytile(fill == CS_FILL_POLYLINES_SHARP, T, halo, B.flags, stream);
         if (e != hipSuccess) return fail_hip(e, "tiled polylines launch");
         // single-eye modes (left-only / only-right): the tile kernels visit one eye, both depth maps are outputs all the same
         if (A.neyes == 2 && A.single >= 0 && !A.out_u8) {
@@ -457,13 +452,13 @@ static int run_rows(int fill, RowArgs& A, int halo, uint8_t* rowflag, hipStream_
                 if (e != hipSuccess) return fail_hip(e, "depth-map output launch");
             }
         }
-        e = launch_collect_rows(rowflag, (int)rows, count, list, stream);
+        e = launch_collect_rows(B.flags, (int)rows, B.first, B.list, stream);
         if (e != hipSuccess) return fail_hip(e, "flagged-row collection");
-        A.row_list = list; A.row_count = count;
-        const uint32_t* hints = (const uint32_t*)(rowflag + rowflag_hint_off(rows));
+        A.row_list = B.list; A.row_count = B.first;
+        const uint32_t* hints = B.hints;
         // (round 6) second tier: the flagged rows through the point kernel once more (k_polypoint_listed) with PP_DCAP2 = 192 instead
         // of 160 slots for pixels under reversed segments and longer per-pixel lists (8 points / 12 segments sharp, 6 / 9 soft); what
-        // THAT flags -- a second flag array and hint block, a third {count, cursor} pair -- is collected into the same list for the row kernel.  Depth maps with strong silhouettes
+        // THAT flags -- B.flags2 and B.hints2, counted in B.point2 -- is collected into the same list for the row kernel.  Depth maps with strong silhouettes
         // (tools/synth.scene8) overflowed the first tier's lists in 15 % (soft) / 48 % (sharp) of the rows at the metric's divergence
         // and sent them to the row kernel: 4 200 / 1 060 frames/s against 5 380 / 4 050 on stepped depth.  polylines_sharp only:
         // for soft the lean row kernel on the hinted tiles' columns is the cheaper second stop (0.96 against 1.16 ms per 16 frames,
@@ -471,15 +466,12 @@ static int run_rows(int fill, RowArgs& A, int halo, uint8_t* rowflag, hipStream_
         // (numba's sweep, d64 & 2: both techniques -- what the tier does not finish takes the dialect row kernel whole, there is no lean pass)
         if (hint_T > 0 && (fill == CS_FILL_POLYLINES_SHARP || (A.d64 & 2) || dev_switch(CS_DEBUG_PT_VARIANT) == PTV_SOFT_POINT_TIER2) &&
             dev_switch(CS_DEBUG_PT_VARIANT) != PTV_NO_POINT_TIER2) {
-            uint8_t* flag2 = rowflag + rowflag_flag2_off(rows);
-            uint32_t* hint2 = (uint32_t*)(rowflag + rowflag_hint2_off(rows));
-            uint32_t* count3 = count + 16;
-            e = launch_polypoint_tier2(T, halo, flag2, stream, fill == CS_FILL_POLYLINES_SHARP, hint2, hint_T, list, count);
+            e = launch_polypoint_tier2(T, halo, B.flags2, stream, fill == CS_FILL_POLYLINES_SHARP, B.hints2, hint_T, B.list, B.first);
             if (e == hipSuccess) {
-                e = launch_collect_rows(flag2, (int)rows, count3, list, stream);
+                e = launch_collect_rows(B.flags2, (int)rows, B.point2, B.list, stream);
                 if (e != hipSuccess) return fail_hip(e, "flagged-row collection (second tier)");
-                A.row_count = count3;
-                hints = hint2;
+                A.row_count = B.point2;
+                hints = B.hints2;
             } else if (e != hipErrorNotSupported) return fail_hip(e, "tiled polylines launch (second tier)");
         }
         // (the lean first pass works on the flagged tiles' column ranges; PTV_LEAN_WHOLE_ROWS: whole rows as in round 4)
@@ -491,30 +483,25 @@ static int run_rows(int fill, RowArgs& A, int halo, uint8_t* rowflag, hipStream_
         !dev_switch(CS_DEBUG_NO_TILE) && !ana_wide) {
         // the halo-tile kernel where it applies; 'naive' hands the rows it cannot decide to the row kernel
         const bool flagging = (fill == CS_FILL_NAIVE || fill == CS_FILL_NAIVE_INTERPOLATING) && rowflag;
-        const size_t rows = (size_t)A.n * A.h;
         if (flagging) {
-            hipError_t e = hipMemsetAsync(rowflag, 0, rowflag_clear_bytes(rows), stream);
+            hipError_t e = hipMemsetAsync(rowflag, 0, B.clear_bytes, stream);
             if (e != hipSuccess) return fail_hip(e, "rowflag memset");
         }
-        hipError_t e = launch_fwdtile(fill, A, halo, flagging ? rowflag : nullptr, stream);
+        hipError_t e = launch_fwdtile(fill, A, halo, flagging ? B.flags : nullptr, stream);
         if (e == hipSuccess) {
             if (!flagging) return CS_OK;
-            uint32_t* count = (uint32_t*)(rowflag + al256(rows));
-            uint32_t* list = rowflag_list(rowflag, rows);
-            e = launch_collect_rows(rowflag, (int)rows, count, list, stream);
+            e = launch_collect_rows(B.flags, (int)rows, B.first, B.list, stream);
             if (e != hipSuccess) return fail_hip(e, "flagged-row collection");
-            A.row_list = list; A.row_count = count;
+            A.row_list = B.list; A.row_count = B.first;
             // naive_interpolating, second tier (round 5): the flagged rows through the tile kernel once more with a window that holds every
-            // hole; what THAT flags (the retry-flag bytes of the block) is collected into the same list for the row kernel.  On depth
+            // hole; what THAT flags (B.naive_flags2(), the retry-flag bytes of the block) is collected into the same list for the row kernel.  On depth
             // saturated to 0 / 1 the holes between a near and a far plateau outgrow the first window in most rows (1 830 frames/s at 4K)
             if (fill == CS_FILL_NAIVE_INTERPOLATING && dev_switch(CS_DEBUG_PT_VARIANT) != PTV_NAIVE_NO_TIER2) {
-                uint8_t* flag2 = rowflag + al256(rows) + 512;
-                uint32_t* count2 = count + 8;
-                e = launch_fwdtile(fill, A, halo, flag2, stream, list, count);
+                e = launch_fwdtile(fill, A, halo, B.naive_flags2(), stream, B.list, B.first);
                 if (e == hipSuccess) {
-                    e = launch_collect_rows(flag2, (int)rows, count2, list, stream);
+                    e = launch_collect_rows(B.naive_flags2(), (int)rows, B.retry, B.list, stream);
                     if (e != hipSuccess) return fail_hip(e, "flagged-row collection (second tier)");
-                    A.row_count = count2;
+                    A.row_count = B.retry;
                 } else if (e != hipErrorNotSupported) return fail_hip(e, "forward tile kernel launch (second tier)");
             }
         } else if (e != hipErrorNotSupported) return fail_hip(e, "forward tile kernel launch");
@@ -527,7 +514,7 @@ static int run_rows(int fill, RowArgs& A, int halo, uint8_t* rowflag, hipStream_
         if (e != hipSuccess) return fail_hip(e, "lazy depth rows");
     }
     if (replay && !cleared) {   // (no tile kernel took the call: the block has not been cleared yet)
-        hipError_t e0 = hipMemsetAsync(rowflag, 0, rowflag_clear_bytes((size_t)A.n * A.h), stream);
+        hipError_t e0 = hipMemsetAsync(rowflag, 0, B.clear_bytes, stream);
         if (e0 != hipSuccess) return fail_hip(e0, "rowflag memset");
     }
     // (polylines with the replay kernel attached: the lean instantiation first -- evaluation, stretch list, export; the rows it
@@ -535,16 +522,13 @@ static int run_rows(int fill, RowArgs& A, int halo, uint8_t* rowflag, hipStream_
     hipError_t e = launch_rowwarp(fill, A, threads_for(fill, A.w), stream, 0, replay);
     if (e != hipSuccess) return fail_hip(e, "row kernel launch");
     if (replay) {
-        e = launch_poly_replay(fill == CS_FILL_POLYLINES_SHARP, A, halo, stream);
+        e = launch_poly_replay(fill == CS_FILL_POLYLINES_SHARP, A, B, halo, stream);
         if (e != hipSuccess) return fail_hip(e, "stretch replay launch");
         // rows with a stretch the replay kernel gave up on (usually none): once more through the row kernel, export off
-        const size_t rows = (size_t)A.n * A.h;
-        uint32_t* count2 = (uint32_t*)(rowflag + al256(rows)) + 8;   // (a second {count, cursor} pair in the cleared counter block)
-        uint32_t* list = rowflag_list(rowflag, rows);
-        e = launch_collect_rows(poly_replay_retry_flags(A), (int)rows, count2, list, stream);
+        e = launch_collect_rows(B.retry_flags, (int)rows, B.retry, B.list, stream);
         if (e != hipSuccess) return fail_hip(e, "replay retry collection");
         RowArgs R = A;
-        R.rp_dump = nullptr; R.row_list = list; R.row_count = count2; R.hint = nullptr;
+        R.rp_dump = nullptr; R.row_list = B.list; R.row_count = B.retry; R.hint = nullptr;
         // (one workgroup per CU: on saturated depth a few hundred rows per frame come back -- stretches whose list outgrows the
         // wave form's 64 entries --, 32 workgroups made them the tail of the call; an empty launch of 256 costs 0.03 ms)
         e = launch_rowwarp(fill, R, threads_for(fill, A.w), stream, 256);
@@ -647,8 +631,12 @@ int cs_output_shape(const cs_params* p, int* out_h, int* out_w, int* mask_h, int
 }
 
 
+// hyb / gpuwarp / ana_sbs / replay: the technique's scratch behind the depth maps (absent ones are empty) -- the splat result of
+// hybrid_edge, gpu_warp's scratch, both eyes as uint8 codes side by side (has_ana_sbs: run_rows composes this call's anaglyph from
+// them) and the stretch-replay scratch of the polylines techniques: the last item, so that a larger workspace extends its pool
 struct WsLayout {
-    size_t rowflag, gray_src, gray, L, R, wl, wr, tilemap, extra, total;
+    size_t rowflag, gray_src, gray, L, R, wl, wr, tilemap, hyb, gpuwarp, ana_sbs, replay, total;
+    bool has_ana_sbs;
 };
 // Scratch of one chunk of frames (everything but the per-frame statistics words, which stay one array for the whole call
 // at the start of the workspace so that callers find them at a fixed place).
@@ -666,16 +654,14 @@ static WsLayout ws_layout(const cs_params* p) {
     W.wl = o; if (blur) o += al256(n * hw * 4);
     W.wr = o; if (blur) o += al256(n * hw * 4);
     W.tilemap = o; if (blur) o += al256(blur_tilemap_bytes(p->n, p->h, p->w));
-    W.extra = o;
-    if (p->fill == CS_FILL_HYBRID_EDGE || p->fill == CS_FILL_HYBRID_EDGE_PLUS) o += al256(hybrid_workspace_bytes(p->n, p->h, p->w));
-    if (p->fill == CS_FILL_GPU_WARP) o += al256(gpuwarp_workspace_bytes(p->n, p->h, p->w, p->batch_size, p->flags & 4));
-    if ((p->fill == CS_FILL_POLYLINES_SOFT || p->fill == CS_FILL_POLYLINES_SHARP) &&
-        (p->mode == CS_MODE_RED_CYAN_ANAGLYPH || p->mode == CS_MODE_CYAN_RED_REVERSEANAGLYPH))
-        o += poly_anaglyph_bytes(p->n, p->h, p->w);   // (both eyes as uint8 codes side by side; the replay scratch behind it)
-    if (ana_wide_call(p->fill, p->mode == CS_MODE_RED_CYAN_ANAGLYPH || p->mode == CS_MODE_CYAN_RED_REVERSEANAGLYPH, p->w))
-        o += poly_anaglyph_bytes(p->n, p->h, p->w);   // (the same scratch for an anaglyph too wide for the row kernel's stash form)
-    if (p->fill == CS_FILL_POLYLINES_SOFT || p->fill == CS_FILL_POLYLINES_SHARP)   // scratch of the stretch replay kernel
-        o += al256(poly_replay_bytes(p->n, p->h, p->w, p->fill == CS_FILL_POLYLINES_SHARP));
+    const bool poly = p->fill == CS_FILL_POLYLINES_SOFT || p->fill == CS_FILL_POLYLINES_SHARP;
+    const bool ana = p->mode == CS_MODE_RED_CYAN_ANAGLYPH || p->mode == CS_MODE_CYAN_RED_REVERSEANAGLYPH;
+    W.hyb = o; if (p->fill == CS_FILL_HYBRID_EDGE || p->fill == CS_FILL_HYBRID_EDGE_PLUS) o += al256(hybrid_workspace_bytes(p->n, p->h, p->w));
+    W.gpuwarp = o; if (p->fill == CS_FILL_GPU_WARP) o += al256(gpuwarp_workspace_bytes(p->n, p->h, p->w, p->batch_size, p->flags & 4));
+    // (the anaglyphs of the polylines techniques, and those of the forward fills too wide for the row kernel's stash form)
+    W.has_ana_sbs = (poly && ana) || ana_wide_call(p->fill, ana, p->w);
+    W.ana_sbs = o; if (W.has_ana_sbs) o += poly_anaglyph_bytes(p->n, p->h, p->w);
+    W.replay = o; if (poly) o += al256(poly_replay_bytes(p->n, p->h, p->w, p->fill == CS_FILL_POLYLINES_SHARP));
     W.total = o;
     return W;
 }
@@ -709,7 +695,7 @@ static size_t ws_total(const cs_params* p) {
     const ChunkPlan C = plan_chunks(p);
     cs_params q = *p;
     q.n = C.cf;
-    return al256((size_t)p->n * ST_WORDS * 4) + (size_t)C.nch * ws_layout(&q).total;
+    return stats_bytes(p->n) + (size_t)C.nch * ws_layout(&q).total;
 }
 
 // the auxiliary stream (highest priority the device offers) and its fork / ready events: one set per device, created on
@@ -750,7 +736,7 @@ static int generate_chunk(const cs_params* p, const float* image, const float* d
     const bool gpu_warp = p->fill == CS_FILL_GPU_WARP;
     const bool blur = p->depth_map_blur && p->depth_blur_strength > 0;  // strength <= 0 == blur off (reference :1194, :1050)
 
-    hipLaunchKernelGGL(k_stats_init, dim3((n * ST_WORDS + 255) / 256), dim3(256), 0, sp, stats, n);
+    stats_prepass(stats, n, nullptr, 0, sp);   // (the gray conversion below fills the words)
     const bool resize = p->depth_h != h || p->depth_w != w;
     // RGB depth + blur: the gray conversion also builds the blur's edge bit rows (one pass over the depth input)
     const bool blur_map = !dev_switch(CS_DEBUG_BLUR_FULL_COPY);
@@ -832,7 +818,7 @@ static int generate_chunk(const cs_params* p, const float* image, const float* d
     ProfScope prof(stream);
     if (gpu_warp) {
         rc = launch_gpuwarp_node(p, image, dL, dR, scale_from_stats, stats, stereo, depth_l, depth_r, mask, out_h, out_w,
-                                 ws + W.extra, stream, lazy ? (const uint32_t*)(ws + W.tilemap) : nullptr, lazy ? gray : nullptr,
+                                 ws + W.gpuwarp, stream, lazy ? (const uint32_t*)(ws + W.tilemap) : nullptr, lazy ? gray : nullptr,
                                  lazy ? blur_tilemap_words(w) : 0);
         if (rc) return fail(rc, "gpu_warp launch failed");
         hipError_t e = hipGetLastError();
@@ -873,12 +859,11 @@ static int generate_chunk(const cs_params* p, const float* image, const float* d
     case CS_MODE_ONLY_RIGHT: A.single = 1; break;
     }
     if (p->fill == CS_FILL_HYBRID_EDGE || p->fill == CS_FILL_HYBRID_EDGE_PLUS) {
-        rc = launch_hybrid(A, ws + W.extra, stream, p->fill == CS_FILL_HYBRID_EDGE_PLUS, halo);
+        rc = launch_hybrid(A, ws + W.hyb, stream, p->fill == CS_FILL_HYBRID_EDGE_PLUS, halo);
         if (rc) return fail(rc, "hybrid_edge launch failed");
     } else {
-        const bool poly_ana = A.anaglyph && (p->fill == CS_FILL_POLYLINES_SOFT || p->fill == CS_FILL_POLYLINES_SHARP);
-        rc = run_rows(p->fill, A, halo, (uint8_t*)(ws + W.rowflag), stream, A.anaglyph ? (uint8_t*)(ws + W.extra) : nullptr,
-                      (void*)(ws + W.extra + (poly_ana ? poly_anaglyph_bytes(p->n, p->h, p->w) : 0)), surplus);
+        rc = run_rows(p->fill, A, halo, (uint8_t*)(ws + W.rowflag), stream, W.has_ana_sbs ? (uint8_t*)(ws + W.ana_sbs) : nullptr,
+                      ws + W.replay, surplus);
         if (rc) return rc;
     }
     hipError_t e = hipGetLastError();
@@ -902,7 +887,7 @@ int cs_generate(const cs_params* p, const float* image, const float* depth, floa
         return fail(CS_EINVAL, DIALECT_MSG);
     char* const ws = (char*)workspace;
     uint32_t* const stats = (uint32_t*)ws;
-    char* const scratch = ws + al256((size_t)p->n * ST_WORDS * 4);
+    char* const scratch = ws + stats_bytes(p->n);
     const ChunkPlan C = plan_chunks(p);
     // (one chunk: whatever the caller's workspace holds beyond cs_workspace_bytes extends the stretch-replay pool -- the last item
     // of the layout -- so that a caller who expects tie-heavy depth maps can give every flagged row room to export)
@@ -953,15 +938,18 @@ int cs_generate(const cs_params* p, const float* image, const float* depth, floa
     return rc;
 }
 
-// [statistics][flagged-row block][technique scratch: the splat result of hybrid_edge / the replay pool of polylines]
-static size_t asd_tech_bytes(int n, int h, int w, int fill) {
-    if (fill == CS_FILL_HYBRID_EDGE || fill == CS_FILL_HYBRID_EDGE_PLUS) return al256(hybrid_workspace_bytes(n, h, w));
-    if (fill == CS_FILL_POLYLINES_SOFT || fill == CS_FILL_POLYLINES_SHARP) return al256(poly_replay_bytes(n, h, w, fill == CS_FILL_POLYLINES_SHARP));
-    return 0;
+// [statistics][flagged-row block][technique scratch: the splat result of hybrid_edge / the replay scratch of polylines]
+struct AsdLayout { size_t rowflag, tech, total; };   // (the statistics at 0)
+static AsdLayout asd_layout(int n, int h, int w, int fill) {
+    AsdLayout W;
+    W.rowflag = stats_bytes(n);
+    W.tech = W.rowflag + rowflag_bytes((size_t)n * h);
+    W.total = W.tech;
+    if (fill == CS_FILL_HYBRID_EDGE || fill == CS_FILL_HYBRID_EDGE_PLUS) W.total += al256(hybrid_workspace_bytes(n, h, w));
+    if (fill == CS_FILL_POLYLINES_SOFT || fill == CS_FILL_POLYLINES_SHARP) W.total += al256(poly_replay_bytes(n, h, w, fill == CS_FILL_POLYLINES_SHARP));
+    return W;
 }
-size_t cs_asd_workspace_bytes_for(int n, int h, int w, int fill) {
-    return al256((size_t)n * ST_WORDS * 4) + rowflag_bytes((size_t)n * h) + asd_tech_bytes(n, h, w, fill);
-}
+size_t cs_asd_workspace_bytes_for(int n, int h, int w, int fill) { return asd_layout(n, h, w, fill).total; }
 size_t cs_asd_workspace_bytes(int n, int h, int w) {   // enough for any technique
     const size_t a = cs_asd_workspace_bytes_for(n, h, w, CS_FILL_HYBRID_EDGE), b = cs_asd_workspace_bytes_for(n, h, w, CS_FILL_POLYLINES_SHARP);
     return a > b ? a : b;
@@ -985,10 +973,11 @@ int cs_apply_stereo_divergence2(const uint8_t* image_u8, const float* depth, int
     if (n <= 0 || h <= 0 || w <= 0) return fail(CS_EINVAL, "non-positive size");
     if (fill < 0 || fill > CS_FILL_HYBRID_EDGE_PLUS || fill == CS_FILL_GPU_WARP) return fail(CS_EINVAL, "unknown fill technique");
     if (w > max_width_for(fill, 0) || !dialect_width_ok(fill, w, 0, dialect)) return fail(CS_ELIMIT, "frame too wide for the LDS-resident row kernel");
-    if (workspace_bytes < cs_asd_workspace_bytes_for(n, h, w, fill)) return fail(CS_EWORKSPACE, "workspace too small");
-    uint32_t* stats = (uint32_t*)workspace;
-    hipLaunchKernelGGL(k_stats_init, dim3((n * ST_WORDS + 255) / 256), dim3(256), 0, stream, stats, n);
-    hipLaunchKernelGGL(k_minmax, dim3(grid_for((size_t)h * w, 256), n), dim3(256), 0, stream, depth, h * w, stats, ST_L_MIN, ST_L_MAX);
+    const AsdLayout W = asd_layout(n, h, w, fill);
+    if (workspace_bytes < W.total) return fail(CS_EWORKSPACE, "workspace too small");
+    char* const ws = (char*)workspace;
+    uint32_t* stats = (uint32_t*)ws;
+    stats_prepass(stats, n, depth, (size_t)h * w, stream);
     RowArgs A;
     memset(&A, 0, sizeof(A));
     A.n = n; A.h = h; A.w = w;
@@ -1006,21 +995,19 @@ int cs_apply_stereo_divergence2(const uint8_t* image_u8, const float* depth, int
     A.single = -1;
     A.dbg = dev_switch(CS_DEBUG_DBG);
     if (fill == CS_FILL_HYBRID_EDGE || fill == CS_FILL_HYBRID_EDGE_PLUS) {
-        int rc = launch_hybrid(A, (char*)workspace + al256((size_t)n * ST_WORDS * 4) + rowflag_bytes((size_t)n * h), stream,
-                               fill == CS_FILL_HYBRID_EDGE_PLUS);
+        int rc = launch_hybrid(A, ws + W.tech, stream, fill == CS_FILL_HYBRID_EDGE_PLUS);
         if (rc) return fail(rc, "hybrid_edge launch failed");
     } else {
         int halo = poly_halo(divergence, divergence, separation, exponent, convergence, w);
         const bool poly = fill == CS_FILL_POLYLINES_SOFT || fill == CS_FILL_POLYLINES_SHARP;   // (the others have no replay scratch)
-        int rc = run_rows(fill, A, halo, (uint8_t*)workspace + al256((size_t)n * ST_WORDS * 4), stream, nullptr,
-                          poly ? (char*)workspace + al256((size_t)n * ST_WORDS * 4) + rowflag_bytes((size_t)n * h) : nullptr);
+        int rc = run_rows(fill, A, halo, (uint8_t*)(ws + W.rowflag), stream, nullptr, poly ? ws + W.tech : nullptr);
         if (rc) return rc;
     }
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_apply_stereo_divergence");
 }
 
-size_t cs_blur_workspace_bytes(int n, int h, int w) { return al256((size_t)n * ST_WORDS * 4) + 2 * al256((size_t)n * h * w * 4); }
+size_t cs_blur_workspace_bytes(int n, int h, int w) { return stats_bytes(n) + 2 * al256((size_t)n * h * w * 4); }
 
 int cs_directional_blur(const float* depth, int n, int h, int w, double blur_strength, double edge_threshold,
                         double blur_mask_width, double falloff_exponent, int vert_smooth_px, float* out_l, float* out_r, void* workspace,
@@ -1037,9 +1024,9 @@ int cs_directional_blur(const float* depth, int n, int h, int w, double blur_str
     }
     char* ws = (char*)workspace;
     uint32_t* stats = (uint32_t*)ws;
-    float* wl = (float*)(ws + al256((size_t)n * ST_WORDS * 4));
+    float* wl = (float*)(ws + stats_bytes(n));
     float* wr = wl + al256(n * hw * 4) / 4;
-    hipLaunchKernelGGL(k_stats_init, dim3((n * ST_WORDS + 255) / 256), dim3(256), 0, stream, stats, n);
+    stats_prepass(stats, n, nullptr, 0, stream);   // (launch_blur accumulates the outputs' min / max)
     int rc = launch_blur(depth, n, h, w, blur_strength, edge_threshold, blur_mask_width, falloff_exponent, vert_smooth_px, out_l, out_r, wl,
                          wr, stats, 0, stream);
     if (rc) return fail_blur(rc);
@@ -1063,8 +1050,8 @@ int cs_directional_blur_scipy(const float* depth, int n, int h, int w, double bl
     return rc ? fail(rc, "cs_directional_blur_scipy launch failed") : CS_OK;
 }
 
-size_t cs_warp_workspace_bytes(int n, int h, int w) { return al256((size_t)n * ST_WORDS * 4) + al256(gpuwarp_workspace_bytes(n, h, w, n, 0)); }
-size_t cs_warp_mesh_workspace_bytes(int n, int h, int w) { return al256((size_t)n * ST_WORDS * 4) + al256(gpuwarp_workspace_bytes(n, h, w, n, 1)); }
+size_t cs_warp_workspace_bytes(int n, int h, int w) { return stats_bytes(n) + al256(gpuwarp_workspace_bytes(n, h, w, n, 0)); }
+size_t cs_warp_mesh_workspace_bytes(int n, int h, int w) { return stats_bytes(n) + al256(gpuwarp_workspace_bytes(n, h, w, n, 1)); }
 
 static int forward_warp_common(const float* image, const float* depth, int n, int h, int w, double divergence_px,
                                double separation_px, double exponent, double convergence, int mesh, double grad_thr,
@@ -1078,10 +1065,9 @@ static int forward_warp_common(const float* image, const float* depth, int n, in
     if (workspace_bytes < (mesh ? cs_warp_mesh_workspace_bytes(n, h, w) : cs_warp_workspace_bytes(n, h, w)))
         return fail(CS_EWORKSPACE, "workspace too small");
     uint32_t* stats = (uint32_t*)workspace;
-    hipLaunchKernelGGL(k_stats_init, dim3((n * ST_WORDS + 255) / 256), dim3(256), 0, stream, stats, n);
-    hipLaunchKernelGGL(k_minmax, dim3(grid_for((size_t)h * w, 256), n), dim3(256), 0, stream, depth, h * w, stats, ST_L_MIN, ST_L_MAX);
+    stats_prepass(stats, n, depth, (size_t)h * w, stream);
     int rc = launch_gpuwarp_plain(image, depth, n, h, w, divergence_px, separation_px, exponent, convergence, warped,
-                                  gap_mask, stats, (char*)workspace + al256((size_t)n * ST_WORDS * 4), stream, mesh, grad_thr, max_stretch);
+                                  gap_mask, stats, (char*)workspace + stats_bytes(n), stream, mesh, grad_thr, max_stretch);
     if (rc == CS_ELIMIT) return fail(rc, "gpu_warp: gradient_threshold above 13 with max_stretch above 16 is not supported (more than 16 effective scatter rounds)");
     if (rc) return fail(rc, "gpu_warp launch failed");
     hipError_t e = hipGetLastError();
@@ -1111,7 +1097,7 @@ int cs_forward_warp_mesh(const float* image, const float* depth, int n, int h, i
 
 size_t cs_grid_warp_workspace_bytes(int n, int h, int w) {
     (void)h; (void)w;
-    return n <= 0 ? 0 : al256((size_t)n * ST_WORDS * 4) + al256((size_t)n * 16);
+    return n <= 0 ? 0 : stats_bytes(n) + al256((size_t)n * 16);
 }
 int cs_grid_warp_max_width(int op) {
     if (op == CS_GRID_MASK || op == CS_GRID_STRETCH) return gridwarp_max_width();
@@ -1136,9 +1122,8 @@ int cs_grid_warp(const float* image, const float* depth, int n, int c, int h, in
     if (workspace_bytes < cs_grid_warp_workspace_bytes(n, h, w)) return fail(CS_EWORKSPACE, "workspace too small");
     if (!warped && !mask) return CS_OK;
     uint32_t* stats = (uint32_t*)workspace;
-    float* fconst = (float*)((char*)workspace + al256((size_t)n * ST_WORDS * 4));
-    hipLaunchKernelGGL(k_stats_init, dim3((n * ST_WORDS + 255) / 256), dim3(256), 0, stream, stats, n);
-    hipLaunchKernelGGL(k_minmax, dim3(grid_for((size_t)h * w, 256), n), dim3(256), 0, stream, depth, h * w, stats, ST_L_MIN, ST_L_MAX);
+    float* fconst = (float*)((char*)workspace + stats_bytes(n));
+    stats_prepass(stats, n, depth, (size_t)h * w, stream);
     hipError_t e = launch_gridwarp(image, depth, n, c, h, w, divergence_px, separation_px, exponent, convergence, op, padding,
                                    warped, mask, stats, fconst, stream);
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_grid_warp");
@@ -1165,7 +1150,7 @@ int cs_detect_disocclusions(const float* depth, const float* grid, const float* 
 
 size_t cs_inpaint_prepare_workspace_bytes(int n, int h, int w) {
     if (n <= 0 || h <= 0 || w <= 0) return 0;
-    return al256((size_t)n * ST_WORDS * 4) + 2 * al256(inpaint_prep_bits_bytes(n, h, w));
+    return stats_bytes(n) + 2 * al256(inpaint_prep_bits_bytes(n, h, w));
 }
 int cs_inpaint_prepare_max_width(void) { return inpaint_prep_max_width(); }
 
@@ -1183,10 +1168,9 @@ int cs_inpaint_prepare(const float* image, const float* depth, int n, int h, int
     if (!warped && !filled && !mask && !warped_u8 && !filled_u8) return CS_OK;
     uint32_t* stats = (uint32_t*)workspace;
     const size_t bits = al256(inpaint_prep_bits_bytes(n, h, w));
-    uint32_t* nvb = (uint32_t*)((char*)workspace + al256((size_t)n * ST_WORDS * 4));
+    uint32_t* nvb = (uint32_t*)((char*)workspace + stats_bytes(n));
     uint32_t* disb = (uint32_t*)((char*)nvb + bits);
-    hipLaunchKernelGGL(k_stats_init, dim3((n * ST_WORDS + 255) / 256), dim3(256), 0, stream, stats, n);
-    hipLaunchKernelGGL(k_minmax, dim3(grid_for((size_t)h * w, 256), n), dim3(256), 0, stream, depth, h * w, stats, ST_L_MIN, ST_L_MAX);
+    stats_prepass(stats, n, depth, (size_t)h * w, stream);
     hipError_t e = launch_inpaint_prep(image, depth, n, h, w, divergence_px, threshold, warped, filled, mask, warped_u8, filled_u8,
                                        stats, nvb, disb, stream);
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_inpaint_prepare");
@@ -1291,7 +1275,7 @@ int cs_take_f32(const float* values, float* out, size_t count, int stride, void*
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_take_f32");
 }
 
-size_t cs_stereo_shift_workspace_bytes(void) { return al256(ST_WORDS * 4); }
+size_t cs_stereo_shift_workspace_bytes(void) { return stats_bytes(1); }
 
 int cs_stereo_shift(const float* input, const float* depth, int b, int c, int h, int w, double scale_factor, int shift_both,
                     double stereo_offset_exponent, float* out, void* workspace, size_t workspace_bytes, void* stream_) {
@@ -1301,11 +1285,10 @@ int cs_stereo_shift(const float* input, const float* depth, int b, int c, int h,
     if ((size_t)w * 4 > 64 * 1024) return fail(CS_ELIMIT, "row too wide for the LDS-resident winner table");
     if (workspace_bytes < cs_stereo_shift_workspace_bytes()) return fail(CS_EWORKSPACE, "workspace too small");
     uint32_t* stats = (uint32_t*)workspace;
-    hipLaunchKernelGGL(k_stats_init, dim3(1), dim3(256), 0, stream, stats, 1);
     // one "frame" = the whole depth tensor: the reference normalises with its global min / max (stereo_utils.py:36-45)
     const size_t total = (size_t)b * h * w;
     if (total >= (1ull << 31)) return fail(CS_ELIMIT, "depth tensor too large");
-    hipLaunchKernelGGL(k_minmax, dim3(grid_for(total, 256), 1), dim3(256), 0, stream, depth, (int)total, stats, ST_L_MIN, ST_L_MAX);
+    stats_prepass(stats, 1, depth, total, stream);
     const double e = stereo_offset_exponent;
     const int pow_mode = stereo_shift_pow_mode(e);
     const size_t half = (size_t)b * c * h * w;
@@ -1326,7 +1309,7 @@ int cs_stereo_shift(const float* input, const float* depth, int b, int c, int h,
     return er == hipSuccess ? CS_OK : fail_hip(er, "cs_stereo_shift");
 }
 
-size_t cs_latent_shift_plan_workspace_bytes(void) { return al256(ST_WORDS * 4); }
+size_t cs_latent_shift_plan_workspace_bytes(void) { return stats_bytes(1); }
 
 int cs_latent_shift_plan(const float* disp, int b, int h, int w, double scale_factor, double stereo_offset_exponent, int32_t* src_col,
                          void* workspace, size_t workspace_bytes, void* stream_) {
@@ -1343,8 +1326,7 @@ int cs_latent_shift_plan(const float* disp, int b, int h, int w, double scale_fa
     if (workspace_bytes < cs_latent_shift_plan_workspace_bytes()) return fail(CS_EWORKSPACE, "workspace too small");
     // the stats pre-pass of cs_stereo_shift: one "frame" = the whole tensor (reference stereo_utils.py:36-45)
     uint32_t* stats = (uint32_t*)workspace;
-    hipLaunchKernelGGL(k_stats_init, dim3(1), dim3(256), 0, stream, stats, 1);
-    hipLaunchKernelGGL(k_minmax, dim3(grid_for(total, 256), 1), dim3(256), 0, stream, disp, (int)total, stats, ST_L_MIN, ST_L_MAX);
+    stats_prepass(stats, 1, disp, total, stream);
     const double scale_px = ((-1 * scale_factor) / 100.0) * (double)w;   // the right view with balance 0 (:54, :84-86)
     hipError_t e = launch_latent_shift_plan(disp, b, h, w, stats, scale_px, stereo_offset_exponent, src_col, stream);
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_latent_shift_plan");

@@ -9,6 +9,7 @@
 namespace cs {
 
 __host__ __device__ inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }   // every block of a workspace starts on a 256-byte boundary
 __host__ __device__ inline int poly_npt(int w, int sharp) { return (sharp ? 2 * w : w) + 2; }
 
 struct EyeArgs {
@@ -81,16 +82,59 @@ struct RowArgs {
 int dev_switch(int key);
 
 
+// The flagged-row block: the scratch through which the tile kernels hand rows to the row kernel (cs_abi.hip run_rows), one view of it
+// per call.  Every part starts on a 256-byte boundary, in the order of the members; everything before `list` -- clear_bytes -- is
+// zeroed by ONE memset per call, so a part that kernels count or flag into has to be declared before it.
+enum { ROW_CTR_BYTES = 256, ROW_PAIR_WORDS = 8 };   // a counter part; the words from one {count, cursor} pair to the next
+struct RowBlock {
+    uint8_t* flags;         // [rows] bytes: rows the first tile pass (k_polypoint / k_polytile / k_fwdtile) leaves to the row kernel
+    uint32_t* first;        // {count, cursor} of the collection of `flags` -- the three pairs share one counter part
+    uint32_t* retry;        // {count, cursor} of the second collection of a call without point tier: naive_interpolating's second tier or
+                            // the replay retry (no technique has both)
+    uint32_t* point2;       // {count, cursor} of the point kernel's second tier (a polylines call may use it AND `retry`)
+    uint32_t* replay_ctr;   // RowArgs::rp_ctr, one counter part
+    uint8_t* retry_flags;   // [rows] bytes: rows with a stretch the replay kernel gave up on.  The polylines row kernel finds them
+                            // ROW_CTR_BYTES behind rp_ctr by itself: they directly follow the replay counters
+    uint32_t* hints;        // [rows][2 eyes] words: tile hints of the first point pass (RowArgs::hint)
+    uint8_t* flags2;        // [rows] bytes: rows the point kernel's second tier leaves to the row kernel
+    uint32_t* hints2;       // [rows][2 eyes] words: tile hints of that tier
+    uint32_t* list;         // [rows] words: the compacted rows of the latest collection (not cleared: written before it is read)
+    size_t clear_bytes, bytes;
+    // naive_interpolating has no replay kernel: its second tier flags rows in the bytes the polylines techniques retry through
+    uint8_t* naive_flags2() const { return retry_flags; }
+};
+// base == nullptr: the sizes alone (every pointer null)
+inline RowBlock row_block(uint8_t* base, size_t rows) {
+    static_assert(3 * ROW_PAIR_WORDS * 4 <= ROW_CTR_BYTES, "the three {count, cursor} pairs share one counter part");
+    static_assert(ROW_CTR_BYTES % 256 == 0, "no padding behind the replay counters: the row kernel finds the retry flags ROW_CTR_BYTES behind rp_ctr");
+    size_t o = 0;
+    auto take = [&](size_t bytes) { uint8_t* p = base ? base + o : nullptr; o += al256(bytes); return p; };
+    RowBlock B;
+    B.flags = take(rows);
+    B.first = (uint32_t*)take(ROW_CTR_BYTES);
+    B.retry = B.first ? B.first + ROW_PAIR_WORDS : nullptr;
+    B.point2 = B.first ? B.first + 2 * ROW_PAIR_WORDS : nullptr;
+    B.replay_ctr = (uint32_t*)take(ROW_CTR_BYTES);
+    B.retry_flags = take(rows);   // (directly behind the replay counters: see the static_assert)
+    B.hints = (uint32_t*)take(rows * 8);
+    B.flags2 = take(rows);
+    B.hints2 = (uint32_t*)take(rows * 8);
+    B.clear_bytes = o;
+    B.list = (uint32_t*)take(rows * 4);
+    B.bytes = o;
+    return B;
+}
+
 // cs_rowwarp.hip
 hipError_t launch_collect_rows(const uint8_t* flag, int total, uint32_t* count, uint32_t* list, hipStream_t stream);
 hipError_t launch_rowwarp(int fill, const RowArgs& A, int threads, hipStream_t stream, int max_groups = 0, int lean = 0);
 size_t rowwarp_lds_bytes(int fill, int w, int anaglyph = 1);   // anaglyph modes stash two channels of the first eye (2 B per pixel)
 // scratch of the stretch replay kernel for a call of n frames (0: the frame is too wide for its windows); poly_replay_attach
-// carves it into A.rp_* and zeroes the counters; launch_poly_replay runs the descriptors the row pass appended
+// carves it into A.rp_* and takes the replay counters of the call's flagged-row block (zeroed by the caller's memset of the block);
+// launch_poly_replay runs the descriptors the row pass appended and flags the rows it gives up on in B.retry_flags
 size_t poly_replay_bytes(int n, int h, int w, int sharp);
-hipError_t poly_replay_attach(RowArgs& A, int sharp, void* scratch, void* ctr_retry, hipStream_t stream, size_t surplus = 0);
-hipError_t launch_poly_replay(int sharp, const RowArgs& A, int halo, hipStream_t stream);
-uint8_t* poly_replay_retry_flags(const RowArgs& A);   // one byte per row: set by a stretch the replay kernel gave up on
+void poly_replay_attach(RowArgs& A, int sharp, void* scratch, const RowBlock& B, size_t surplus = 0);
+hipError_t launch_poly_replay(int sharp, const RowArgs& A, const RowBlock& B, int halo, hipStream_t stream);
 
 // cs_polytile.hip: tiled fast path of polylines; flags rows it cannot do for the general kernel
 hipError_t launch_polytile(int sharp, const RowArgs& A, int S, uint8_t* rowflag, hipStream_t stream);

@@ -30,7 +30,6 @@
 #include <stdlib.h>
 
 namespace cs {
-static inline size_t al256r(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // ---------------------------------------------------------------------------------------------
 // LDS carving
@@ -3140,28 +3139,24 @@ static size_t rp_pool_bytes(size_t rows, int w, int sharp) {
 size_t poly_replay_bytes(int n, int h, int w, int sharp) {
     if (w > 8192) return 0;
     const size_t rows = (size_t)n * h;   // descriptors: four stretches per image row
-    return al256r(rows * 4 * RP_DESC * 4) + rp_pool_bytes(rows, w, sharp) + 256;
+    return al256(rows * 4 * RP_DESC * 4) + rp_pool_bytes(rows, w, sharp) + 256;
 }
-// scratch: [descriptor list][dump pool]; `ctr_retry`: [counters 256 B][retry flags, one byte per row], zeroed by the caller
-// (it lies in the flagged-row block that run_rows clears with one memset)
-hipError_t poly_replay_attach(RowArgs& A, int sharp, void* scratch, void* ctr_retry, hipStream_t stream, size_t surplus) {
+// scratch: [descriptor list][dump pool]; the counters are those of the call's flagged-row block (zeroed by run_rows' one memset)
+void poly_replay_attach(RowArgs& A, int sharp, void* scratch, const RowBlock& B, size_t surplus) {
     const size_t rows = (size_t)A.n * A.h;
     char* b = (char*)scratch;
-    A.rp_ctr = (uint32_t*)ctr_retry;
+    A.rp_ctr = B.replay_ctr;
     A.rp_list = (uint32_t*)b;
-    A.rp_dump = (uint8_t*)(b + al256r(rows * 4 * RP_DESC * 4));
+    A.rp_dump = (uint8_t*)(b + al256(rows * 4 * RP_DESC * 4));
     const size_t pool16 = (rp_pool_bytes(rows, A.w, sharp) + surplus) >> 4;   // (surplus: workspace the caller gave beyond cs_workspace_bytes)
     A.rp_pool16 = (uint32_t)(pool16 < 0xffffffffu ? pool16 : 0xffffffffu); A.rp_cap = (uint32_t)(rows * 4);
-    (void)stream;
-    return hipSuccess;
 }
-uint8_t* poly_replay_retry_flags(const RowArgs& A) { return (uint8_t*)A.rp_ctr + 256; }
-hipError_t launch_poly_replay(int sharp, const RowArgs& A, int halo, hipStream_t stream) {
+hipError_t launch_poly_replay(int sharp, const RowArgs& A, const RowBlock& B, int halo, hipStream_t stream) {
     // the column window holds the columns of the 64 sorted points around the sweep (their span: 64 + 2 halo) and of the active
     // segments (2 halo + 1): 1024 columns up to a halo of 230, 4096 beyond (a stretch that outgrows them goes to the retry pass)
     const bool wide = 4 * (halo + 2) + 80 > RP_CWS;
     const dim3 grid(256 * (wide ? 5 : 19)), block(64);   // (resident waves per CU: 29 KB / 8.3 KB of LDS each)
-    uint8_t* retry = poly_replay_retry_flags(A);
+    uint8_t* retry = B.retry_flags;
     // first a lane per stretch (short lists: saturated depth), then a wave per stretch for what that kernel gave up
     // (PTV_REPLAY_WAVE_ONLY: the wave kernel alone, as in round 4.  A 64-entry lane instantiation for the long lists of noise
     // depth finished them all, bit-exact, and was 2.4 x SLOWER than the wave kernel: DESIGN section 10)

@@ -828,3 +828,78 @@ def test_naive_interpolating_second_tier_on_saturated_depth(engine, dev_switch):
         for g, r, w_, name in zip(got, one, want, NAMES):
             assert np.array_equal(g, r), (mode, blur, "two tiers vs one", name)
             assert np.array_equal(g, w_), (mode, blur, "vs oracle", name)
+
+
+def padded_block_depth(fill, n, h, w):
+    """Depth that sends rows of a 640-column frame through every stage behind the tile kernels.  Polylines: the lower half saturated to
+    0 / 1 with ties (synth.clipped: flagged by both tiers of the point kernel, and at this width the lean row pass has no scratch to
+    export stretches from, so they come back through the retry flags), the upper half silhouettes (synth.scene8: rows whose lists
+    overflow the first tier and that the second tier finishes).  naive_interpolating: a near plateau of varying place and width on
+    a far one -- with the parameters of the test the holes are up to 192 columns wide, the first window 106."""
+    if fill == "naive_interpolating":
+        d = np.zeros((n, h, w), np.float32)
+        for f in range(n):
+            for r in range(h):
+                a = 40 + (7 * r + 90 * f) % 200
+                d[f, r, a:a + 150 + r % 60] = 1.0
+    else:
+        d = np.stack([synth.scene8(h, w, seed=s) for s in range(n)]).astype(np.float32)
+        d[:, h // 2:] = np.stack([synth.clipped(1200, w, seed=s)[500:500 + h] for s in range(n)])[:, h // 2:]
+    return np.ascontiguousarray(d[..., None].repeat(3, -1))
+
+
+@pytest.mark.parametrize("fill,ui,mode", [("polylines_sharp", "Fill - Polylines Sharp", "left-right"),
+                                          ("polylines_sharp", "Fill - Polylines Sharp", "red-cyan-anaglyph"),
+                                          ("polylines_soft", "Fill - Polylines Soft", "left-right"),
+                                          ("polylines_soft", "Fill - Polylines Soft", "red-cyan-anaglyph"),
+                                          ("naive_interpolating", "Fill - Naive interpolating", "left-right")])
+def test_flagged_row_block_where_its_padding_matters(engine, dev_switch, fill, ui, mode):
+    """2 x 130 = 260 rows: al256(rows) = 512 differs from rows, so every member of the flagged-row block (cs_kernels.h RowBlock)
+    starts where no member would if one site took `rows` for al256(rows) or the reverse -- the other tests' row counts are large
+    or happen to be aligned.  Rows pass through every stage that addresses the block: the first collection, the second tier
+    (point kernel: polylines_sharp; forward tile kernel: naive_interpolating -- a row of 640 columns is one tile up to a halo of 92,
+    and a single tile sees every hole: divergence 30 at exponent 1 makes two) and the replay retry.  Bit-exact against the oracle.
+    That no stage is empty is read from Plan.stats() and the dbg = 14 counters; measured on the MI355X (rows to the row kernel with
+    two tiers / one tier): sharp 260 / 274, soft 269, naive_interpolating 4 / 179; 260 rows replayed, none of them by a replay kernel."""
+    n, h, w = 2, 130, 640
+    div, e = (30.0, 1.0) if fill == "naive_interpolating" else (12.0, 2.0)
+    img = synth.image_f32(n, h, w, seed=61)
+    if fill == "naive_interpolating":
+        img[:, 20:24, 100:400] = 0.0   # black pixels lengthen intervals beyond any window: the rows the second tier flags in its turn
+    depth = padded_block_depth(fill, n, h, w)
+    want = node_oracle.generate(img, depth, div, 0.0, mode, 0.0, 0.5, e, ui, 20.0, 20.0, False, batch_size=12)
+    p = engine.make_params(n, h, w, h, w, 3, fill, mode, div, 0.0, 0.0, 0.5, e, False, 20.0, 20.0, 1.0, 0, 12)
+
+    def run():
+        plan = engine.Plan(p, torch.device("cuda"))
+        got = [t.cpu().numpy() for t in plan.run(cuda(img), cuda(depth))]
+        return got, plan.stats().numpy().astype(np.int64)
+
+    got, st = run()
+    print(fill, mode, "stats words 9..15 summed over the frames:", st[:, 9:].sum(0).tolist())
+    assert st[:, 9].sum() == 0                                    # no kernel error flags
+    rows_default = int(st[:, 11].sum())
+    assert rows_default > 0                                       # rows reached the row kernel: flagged by every tier in front of it
+    tier_off = {"polylines_sharp": "no_point_tier2", "naive_interpolating": "naive_no_tier2"}.get(fill)
+    if tier_off:   # the second tier ran and finished rows of the first one's list (and flagged the rows counted above)
+        dev_switch("pt_variant", tier_off)
+        one, st1 = run()
+        dev_switch("pt_variant", "default")
+        print(fill, mode, "rows to the row kernel, one tier / two tiers:", int(st1[:, 11].sum()), rows_default)
+        assert int(st1[:, 11].sum()) > rows_default, (int(st1[:, 11].sum()), rows_default)
+        for g, r, name in zip(got, one, NAMES):
+            assert np.array_equal(g, r), (fill, mode, "two tiers vs one", name)
+    if fill != "naive_interpolating":
+        # dbg = 14: every stretch a replay kernel (or the stretch form inside the row kernel) gets is counted in words 12, 13 or 15.
+        # A row-eye that was replayed (word 10) is either exported -- at least one such stretch -- or comes back through the retry
+        # flags: the replayed row-eyes beyond the counted stretches took the retry pass.
+        dev_switch("dbg", 14)
+        counted, st14 = run()
+        dev_switch("dbg", 0)
+        print(fill, mode, "dbg = 14 words 9..15 summed over the frames:", st14[:, 9:].sum(0).tolist())
+        retried = int(st14[:, 10].sum()) - int(st14[:, 12].sum() + st14[:, 13].sum() + st14[:, 15].sum())
+        assert int(st[:, 10].sum()) > 0 and retried > 0, (st14[:, 9:].sum(0).tolist(),)
+        for g, r, name in zip(got, counted, NAMES):
+            assert np.array_equal(g, r), (fill, mode, "counters on vs off", name)
+    for g, w_, name in zip(got, want, NAMES):
+        assert np.array_equal(g, w_), (fill, mode, "vs oracle", name)
