@@ -41,22 +41,6 @@ LATENT_OP = {"first": 0, "reshift": 1}
 # the ABI version the ctypes signatures below were written for (include/comfystereo_amd.h CS_ABI_VERSION)
 ABI_VERSION = 4
 
-EXPORTS = [
-    "cs_version", "cs_last_error", "cs_max_width", "cs_max_width_mode", "cs_max_width_params", "cs_output_shape", "cs_workspace_bytes", "cs_generate",
-    "cs_asd_workspace_bytes", "cs_asd_workspace_bytes_for", "cs_apply_stereo_divergence", "cs_apply_stereo_divergence2", "cs_blur_workspace_bytes", "cs_directional_blur", "cs_blur_scipy_workspace_bytes", "cs_directional_blur_scipy",
-    "cs_warp_workspace_bytes", "cs_forward_warp", "cs_forward_warp2", "cs_warp_mesh_workspace_bytes", "cs_forward_warp_mesh", "cs_expand_u8", "cs_pack_u8", "cs_host_expand_u8", "cs_host_copy", "cs_take_f32", "cs_host_replicate_f32", "cs_stereo_shift_workspace_bytes", "cs_stereo_shift", "cs_profile", "cs_profile_read", "cs_profile_tiles", "cs_debug_set",
-    "cs_test_powf", "cs_test_exp", "cs_test_edge_threshold",
-    "cs_grid_warp_workspace_bytes", "cs_grid_warp_max_width", "cs_grid_warp", "cs_interpolate_fill", "cs_detect_disocclusions",
-    "cs_gaussian_blur_workspace_bytes", "cs_gaussian_blur_max_taps", "cs_gaussian_blur",
-    "cs_inpaint_prepare_workspace_bytes", "cs_inpaint_prepare_max_width", "cs_inpaint_prepare",
-    "cs_pil_resize_workspace_bytes", "cs_pil_resize_max_taps", "cs_pil_resize",
-    "cs_stereo_attention_max_head_dim", "cs_stereo_attention", "cs_stereo_attention_half",
-    "cs_attention_fwd_lse", "cs_attention_bwd_workspace_bytes", "cs_attention_bwd",
-    "cs_attention_half_fwd_lse", "cs_attention_half_bwd_workspace_bytes", "cs_attention_half_bwd",
-    "cs_latent_shift_plan_workspace_bytes", "cs_latent_shift_plan", "cs_latent_shift_apply", "cs_decode_to_codes",
-    "cs_ddim_step", "cs_null_loss_workspace_bytes", "cs_null_loss_grad", "cs_adam_step",
-]
-
 # enum cs_debug_key (development switches; tests and profiling tools only)
 DEBUG = {"dbg": 0, "no_tile": 1, "pt_variant": 2, "blur_two_pass": 3, "blur_edges_scalar": 4, "blur_full_copy": 5, "chunks": 6, "no_replay_kernel": 7,
          "blur_no_pre_edges": 8, "hybrid_unfused": 9, "gpuwarp_full_maps": 10,
@@ -106,7 +90,101 @@ class NativeError(RuntimeError):
         self.code = code
 
 
+_vp, _int, _dbl, _size, _ll, _flt = (ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_size_t, ctypes.c_longlong,
+                                      ctypes.c_float)
+_pp, _ip, _dp = ctypes.POINTER(Params), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)
+_nhw = [_int, _int, _int]
+_bhnnd = [_int, _int, _int, _int, _int]   # (b, h, n, n_k, d)
+
+# name -> (restype, argtypes) of every entry point, in the order of include/comfystereo_amd.h: lib() applies it, EXPORTS lists it
+SIGNATURES = {
+    # version, limits, the fused node (cs_generate)
+    "cs_version": (_int, []),
+    "cs_last_error": (ctypes.c_char_p, []),
+    "cs_max_width": (_int, [_int]),
+    "cs_max_width_mode": (_int, [_int, _int]),
+    "cs_max_width_params": (_int, [_pp]),
+    "cs_output_shape": (_int, [_pp, _ip, _ip, _ip, _ip]),
+    "cs_workspace_bytes": (_size, [_pp]),
+    "cs_generate": (_int, [_pp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _size, _vp]),
+    # apply_stereo_divergence
+    "cs_asd_workspace_bytes": (_size, _nhw),
+    "cs_asd_workspace_bytes_for": (_size, _nhw + [_int]),
+    "cs_apply_stereo_divergence": (_int, [_vp, _vp] + _nhw + [_dbl, _dbl, _dbl, _int, _dbl, _vp, _vp, _size, _vp]),
+    "cs_apply_stereo_divergence2": (_int, [_vp, _vp] + _nhw + [_dbl, _dbl, _dbl, _int, _dbl, _int, _vp, _vp, _size, _vp]),
+    # the directional depth blurs
+    "cs_blur_workspace_bytes": (_size, _nhw),
+    "cs_directional_blur": (_int, [_vp] + _nhw + [_dbl, _dbl, _dbl, _dbl, _int, _vp, _vp, _vp, _size, _vp]),
+    "cs_blur_scipy_workspace_bytes": (_size, _nhw),
+    "cs_directional_blur_scipy": (_int, [_vp] + _nhw + [_dbl, _dbl, _dbl, _dbl, _int, _vp, _vp, _vp, _size, _vp]),
+    # forward_warp_gpu
+    "cs_warp_workspace_bytes": (_size, _nhw),
+    "cs_forward_warp": (_int, [_vp, _vp] + _nhw + [_dbl, _dbl, _dbl, _dbl, _vp, _vp, _vp, _size, _vp]),
+    "cs_forward_warp2": (_int, [_vp, _vp] + _nhw + [_dbl, _dbl, _dbl, _dbl, _dbl, _int, _vp, _vp, _vp, _size, _vp]),
+    # the grid-sample warps
+    "cs_grid_warp_workspace_bytes": (_size, _nhw),
+    "cs_grid_warp_max_width": (_int, [_int]),
+    "cs_grid_warp": (_int, [_vp, _vp, _int] + _nhw + [_dbl, _dbl, _dbl, _dbl, _int, _int, _vp, _vp, _vp, _size, _vp]),
+    "cs_interpolate_fill": (_int, [_vp, _vp, _int] + _nhw + [_vp, _vp]),
+    "cs_detect_disocclusions": (_int, [_vp, _vp, _vp, _int, _int, _dbl, _vp, _vp]),
+    # Fast mode: inpaint preparation, Pillow's bicubic resize
+    "cs_inpaint_prepare_workspace_bytes": (_size, _nhw),
+    "cs_inpaint_prepare_max_width": (_int, []),
+    "cs_inpaint_prepare": (_int, [_vp, _vp] + _nhw + [_dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _size, _vp]),
+    "cs_pil_resize_workspace_bytes": (_size, [_int] * 6),
+    "cs_pil_resize_max_taps": (_int, []),
+    "cs_pil_resize": (_int, [_vp] + [_int] * 7 + [_vp, _vp, _size, _vp, _size, _vp]),
+    # the Gaussian depth blurs, the mesh warp
+    "cs_gaussian_blur_workspace_bytes": (_size, _nhw + [_int]),
+    "cs_gaussian_blur_max_taps": (_int, []),
+    "cs_gaussian_blur": (_int, [_int, _vp, _vp, _int, _dbl] + _nhw + [_vp, _vp, _size, _vp]),
+    "cs_warp_mesh_workspace_bytes": (_size, _nhw),
+    "cs_forward_warp_mesh": (_int, [_vp, _vp] + _nhw + [_dbl, _dbl, _dbl, _dbl, _dbl, _vp, _vp, _vp, _size, _vp]),
+    # codes and host staging
+    "cs_expand_u8": (_int, [_vp, _vp, _size, _vp]),
+    "cs_pack_u8": (_int, [_vp, _vp, _size, _int, _int, _vp]),
+    "cs_host_expand_u8": (_int, [_vp, _vp, _size, _int, _int, _int]),
+    "cs_host_copy": (_int, [_vp, _vp, _size, _int]),
+    "cs_take_f32": (_int, [_vp, _vp, _size, _int, _vp]),
+    "cs_host_replicate_f32": (_int, [_vp, _vp, _size, _int, _int]),
+    # StereoDiffusion: stereo_shift, Standard mode's latent shift, null-text inversion
+    "cs_stereo_shift_workspace_bytes": (_size, []),
+    "cs_stereo_shift": (_int, [_vp, _vp, _int] + _nhw + [_dbl, _int, _dbl, _vp, _vp, _size, _vp]),
+    "cs_latent_shift_plan_workspace_bytes": (_size, []),
+    "cs_latent_shift_plan": (_int, [_vp] + _nhw + [_dbl, _dbl, _vp, _vp, _size, _vp]),
+    "cs_latent_shift_apply": (_int, [_vp, _vp, _vp, _vp, _vp] + [_int] * 6 + [_vp]),
+    "cs_decode_to_codes": (_int, [_vp] + [_int] * 5 + [_vp, _vp]),
+    "cs_ddim_step": (_int, [_vp, _vp, _vp, _vp, _int, _ll] + [_dbl] * 5 + [_vp]),
+    "cs_null_loss_workspace_bytes": (_size, [_ll]),
+    "cs_null_loss_grad": (_int, [_vp] * 7 + [_int, _ll] + [_dbl] * 5 + [_vp, _size, _vp]),
+    "cs_adam_step": (_int, [_vp, _vp, _vp, _vp, _int, _ll, _dbl, _dbl, _dbl, _dbl, _int, _vp]),
+    # the stereo attention, its differentiable form, their float16 / bfloat16 forms
+    "cs_stereo_attention_max_head_dim": (_int, []),
+    "cs_stereo_attention": (_int, [_vp] * 4 + [_int] * 7 + [_dbl, _int, _vp]),
+    "cs_stereo_attention_half": (_int, [_vp] * 4 + [_int] * 8 + [_dbl, _int, _vp]),
+    "cs_attention_fwd_lse": (_int, [_vp] * 5 + _bhnnd + [_dbl, _vp]),
+    "cs_attention_bwd_workspace_bytes": (_size, _bhnnd),
+    "cs_attention_bwd": (_int, [_vp] * 9 + _bhnnd + [_dbl, _vp, _size, _vp]),
+    "cs_attention_half_fwd_lse": (_int, [_vp] * 5 + [_int] + _bhnnd + [_dbl, _vp]),
+    "cs_attention_half_bwd_workspace_bytes": (_size, _bhnnd),
+    "cs_attention_half_bwd": (_int, [_vp] * 9 + [_int] + _bhnnd + [_dbl, _vp, _size, _vp]),
+    # profiling, development switches, test hooks
+    "cs_profile": (_int, [_int]),
+    "cs_profile_read": (_int, [_dp, _ip]),
+    "cs_profile_tiles": (_int, [_dp]),
+    "cs_debug_set": (_int, [_int, _int]),
+    "cs_test_powf": (_int, [_vp, _flt, _vp, _size, _vp]),
+    "cs_test_exp": (_int, [_vp, _vp, _size, _vp]),
+    "cs_test_edge_threshold": (_flt, [_flt]),
+}
+EXPORTS = list(SIGNATURES)
+
 _lib = None
+
+
+def _declare(L, name):
+    f = getattr(L, name)
+    f.restype, f.argtypes = SIGNATURES[name]
 
 
 def lib():
@@ -118,152 +196,12 @@ def lib():
             f"{LIB_PATH} is missing: the HIP extension is not built (run `python __graft_entry__.py` or "
             "`make -C comfystereo_amd/csrc`).  comfystereo_amd has no CPU fallback.")
     L = ctypes.CDLL(LIB_PATH)
-    vp, c_int, c_double, c_size = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_size_t
-    pp = ctypes.POINTER(Params)
-    ip = ctypes.POINTER(ctypes.c_int)
-    L.cs_version.restype = c_int
-    L.cs_version.argtypes = []
+    _declare(L, "cs_version")
     if L.cs_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI version {L.cs_version()}, these bindings were written for {ABI_VERSION}: "
                           "rebuild it (`make -C comfystereo_amd/csrc`)")
-    L.cs_last_error.restype = ctypes.c_char_p
-    L.cs_last_error.argtypes = []
-    L.cs_max_width_mode.restype = c_int
-    L.cs_max_width_mode.argtypes = [c_int, c_int]
-    L.cs_max_width_params.restype = c_int
-    L.cs_max_width_params.argtypes = [ctypes.POINTER(Params)]
-    L.cs_max_width.restype = c_int
-    L.cs_max_width.argtypes = [c_int]
-    L.cs_output_shape.restype = c_int
-    L.cs_output_shape.argtypes = [pp, ip, ip, ip, ip]
-    L.cs_workspace_bytes.restype = c_size
-    L.cs_workspace_bytes.argtypes = [pp]
-    L.cs_generate.restype = c_int
-    L.cs_generate.argtypes = [pp, vp, vp, vp, vp, vp, vp, vp, c_size, vp]
-    L.cs_asd_workspace_bytes.restype = c_size
-    L.cs_asd_workspace_bytes.argtypes = [c_int, c_int, c_int]
-    L.cs_asd_workspace_bytes_for.restype = c_size
-    L.cs_asd_workspace_bytes_for.argtypes = [c_int, c_int, c_int, c_int]
-    L.cs_apply_stereo_divergence2.restype = c_int
-    L.cs_apply_stereo_divergence2.argtypes = [vp, vp, c_int, c_int, c_int, c_double, c_double, c_double, c_int, c_double, c_int,
-                                              vp, vp, c_size, vp]
-    L.cs_apply_stereo_divergence.restype = c_int
-    L.cs_apply_stereo_divergence.argtypes = [vp, vp, c_int, c_int, c_int, c_double, c_double, c_double, c_int, c_double,
-                                             vp, vp, c_size, vp]
-    L.cs_blur_workspace_bytes.restype = c_size
-    L.cs_blur_workspace_bytes.argtypes = [c_int, c_int, c_int]
-    L.cs_directional_blur.restype = c_int
-    L.cs_directional_blur.argtypes = [vp, c_int, c_int, c_int, c_double, c_double, c_double, c_double, c_int, vp, vp, vp,
-                                      c_size, vp]
-    L.cs_blur_scipy_workspace_bytes.restype = c_size
-    L.cs_blur_scipy_workspace_bytes.argtypes = [c_int, c_int, c_int]
-    L.cs_directional_blur_scipy.restype = c_int
-    L.cs_directional_blur_scipy.argtypes = [vp, c_int, c_int, c_int, c_double, c_double, c_double, c_double, c_int, vp, vp, vp, c_size, vp]
-    L.cs_warp_workspace_bytes.restype = c_size
-    L.cs_warp_workspace_bytes.argtypes = [c_int, c_int, c_int]
-    L.cs_warp_mesh_workspace_bytes.restype = c_size
-    L.cs_warp_mesh_workspace_bytes.argtypes = [c_int, c_int, c_int]
-    L.cs_forward_warp_mesh.restype = c_int
-    L.cs_forward_warp_mesh.argtypes = [vp, vp, c_int, c_int, c_int, c_double, c_double, c_double, c_double, c_double, vp, vp, vp, c_size, vp]
-    L.cs_forward_warp.restype = c_int
-    L.cs_forward_warp.argtypes = [vp, vp, c_int, c_int, c_int, c_double, c_double, c_double, c_double, vp, vp, vp, c_size, vp]
-    L.cs_forward_warp2.restype = c_int
-    L.cs_forward_warp2.argtypes = [vp, vp, c_int, c_int, c_int, c_double, c_double, c_double, c_double, c_double, c_int, vp, vp, vp, c_size, vp]
-    L.cs_pack_u8.restype = c_int
-    L.cs_pack_u8.argtypes = [vp, vp, c_size, c_int, c_int, vp]
-    L.cs_host_expand_u8.restype = c_int
-    L.cs_host_expand_u8.argtypes = [vp, vp, c_size, c_int, c_int, c_int]
-    L.cs_host_copy.restype = c_int
-    L.cs_host_copy.argtypes = [vp, vp, c_size, c_int]
-    L.cs_take_f32.restype = c_int
-    L.cs_take_f32.argtypes = [vp, vp, c_size, c_int, vp]
-    L.cs_host_replicate_f32.restype = c_int
-    L.cs_host_replicate_f32.argtypes = [vp, vp, c_size, c_int, c_int]
-    L.cs_stereo_shift_workspace_bytes.restype = c_size
-    L.cs_stereo_shift_workspace_bytes.argtypes = []
-    L.cs_stereo_shift.restype = c_int
-    L.cs_stereo_shift.argtypes = [vp, vp, c_int, c_int, c_int, c_int, c_double, c_int, c_double, vp, vp, c_size, vp]
-    L.cs_expand_u8.restype = c_int
-    L.cs_expand_u8.argtypes = [vp, vp, c_size, vp]
-    L.cs_profile.restype = c_int
-    L.cs_profile.argtypes = [c_int]
-    L.cs_profile_read.restype = c_int
-    L.cs_profile_read.argtypes = [ctypes.POINTER(c_double), ip]
-    L.cs_profile_tiles.restype = c_int
-    L.cs_profile_tiles.argtypes = [ctypes.POINTER(c_double)]
-    L.cs_debug_set.restype = c_int
-    L.cs_debug_set.argtypes = [c_int, c_int]
-    L.cs_test_powf.restype = c_int
-    L.cs_test_powf.argtypes = [vp, ctypes.c_float, vp, c_size, vp]
-    L.cs_test_exp.restype = c_int
-    L.cs_test_exp.argtypes = [vp, vp, c_size, vp]
-    L.cs_test_edge_threshold.restype = ctypes.c_float
-    L.cs_test_edge_threshold.argtypes = [ctypes.c_float]
-    L.cs_grid_warp_workspace_bytes.restype = c_size
-    L.cs_grid_warp_workspace_bytes.argtypes = [c_int, c_int, c_int]
-    L.cs_grid_warp_max_width.restype = c_int
-    L.cs_grid_warp_max_width.argtypes = [c_int]
-    L.cs_grid_warp.restype = c_int
-    L.cs_grid_warp.argtypes = [vp, vp, c_int, c_int, c_int, c_int, c_double, c_double, c_double, c_double, c_int, c_int, vp, vp, vp,
-                               c_size, vp]
-    L.cs_interpolate_fill.restype = c_int
-    L.cs_interpolate_fill.argtypes = [vp, vp, c_int, c_int, c_int, c_int, vp, vp]
-    L.cs_detect_disocclusions.restype = c_int
-    L.cs_detect_disocclusions.argtypes = [vp, vp, vp, c_int, c_int, c_double, vp, vp]
-    L.cs_gaussian_blur_workspace_bytes.restype = c_size
-    L.cs_gaussian_blur_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int]
-    L.cs_gaussian_blur_max_taps.restype = c_int
-    L.cs_gaussian_blur_max_taps.argtypes = []
-    L.cs_gaussian_blur.restype = c_int
-    L.cs_gaussian_blur.argtypes = [c_int, vp, vp, c_int, c_double, c_int, c_int, c_int, vp, vp, c_size, vp]
-    L.cs_inpaint_prepare_workspace_bytes.restype = c_size
-    L.cs_inpaint_prepare_workspace_bytes.argtypes = [c_int, c_int, c_int]
-    L.cs_inpaint_prepare_max_width.restype = c_int
-    L.cs_inpaint_prepare_max_width.argtypes = []
-    L.cs_inpaint_prepare.restype = c_int
-    L.cs_inpaint_prepare.argtypes = [vp, vp, c_int, c_int, c_int, c_double, c_double, vp, vp, vp, vp, vp, vp, c_size, vp]
-    L.cs_pil_resize_workspace_bytes.restype = c_size
-    L.cs_pil_resize_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int, c_int]
-    L.cs_pil_resize_max_taps.restype = c_int
-    L.cs_pil_resize_max_taps.argtypes = []
-    L.cs_pil_resize.restype = c_int
-    L.cs_pil_resize.argtypes = [vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, vp, vp, c_size, vp, c_size, vp]
-    L.cs_stereo_attention_max_head_dim.restype = c_int
-    L.cs_stereo_attention_max_head_dim.argtypes = []
-    L.cs_stereo_attention.restype = c_int
-    L.cs_stereo_attention.argtypes = [vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_int, vp]
-    L.cs_stereo_attention_half.restype = c_int
-    L.cs_stereo_attention_half.argtypes = [vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_int, vp]
-    L.cs_attention_fwd_lse.restype = c_int
-    L.cs_attention_fwd_lse.argtypes = [vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_double, vp]
-    L.cs_attention_bwd_workspace_bytes.restype = c_size
-    L.cs_attention_bwd_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int]
-    L.cs_attention_bwd.restype = c_int
-    L.cs_attention_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_double, vp, c_size, vp]
-    L.cs_attention_half_fwd_lse.restype = c_int
-    L.cs_attention_half_fwd_lse.argtypes = [vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, c_double, vp]
-    L.cs_attention_half_bwd_workspace_bytes.restype = c_size
-    L.cs_attention_half_bwd_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int]
-    L.cs_attention_half_bwd.restype = c_int
-    L.cs_attention_half_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, c_double, vp, c_size, vp]
-    L.cs_latent_shift_plan_workspace_bytes.restype = c_size
-    L.cs_latent_shift_plan_workspace_bytes.argtypes = []
-    L.cs_latent_shift_plan.restype = c_int
-    L.cs_latent_shift_plan.argtypes = [vp, c_int, c_int, c_int, c_double, c_double, vp, vp, c_size, vp]
-    L.cs_latent_shift_apply.restype = c_int
-    L.cs_latent_shift_apply.argtypes = [vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, vp]
-    L.cs_decode_to_codes.restype = c_int
-    L.cs_decode_to_codes.argtypes = [vp, c_int, c_int, c_int, c_int, c_int, vp, vp]
-    c_ll = ctypes.c_longlong
-    L.cs_ddim_step.restype = c_int
-    L.cs_ddim_step.argtypes = [vp, vp, vp, vp, c_int, c_ll, c_double, c_double, c_double, c_double, c_double, vp]
-    L.cs_null_loss_workspace_bytes.restype = c_size
-    L.cs_null_loss_workspace_bytes.argtypes = [c_ll]
-    L.cs_null_loss_grad.restype = c_int
-    L.cs_null_loss_grad.argtypes = [vp, vp, vp, vp, vp, vp, vp, c_int, c_ll, c_double, c_double, c_double, c_double, c_double, vp,
-                                    c_size, vp]
-    L.cs_adam_step.restype = c_int
-    L.cs_adam_step.argtypes = [vp, vp, vp, vp, c_int, c_ll, c_double, c_double, c_double, c_double, c_int, vp]
+    for name in SIGNATURES:
+        _declare(L, name)
     _lib = L
     return L
 

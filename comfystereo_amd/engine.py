@@ -21,10 +21,77 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
-def _dev(t):
+def _opt_ptr(t):
+    return None if t is None else _ptr(t)
+
+
+# ---- the wrappers' vocabulary: one refusal of a tensor, one device check, one workspace, one guarded launch ------------------------
+_DTYPE_NAMES = {torch.float32: "float32", torch.float16: "float16", torch.bfloat16: "bfloat16"}   # keys of _native's dtype enums
+_FLOATS = tuple(_DTYPE_NAMES)
+_FLOATS_TEXT = "float32, float16 or bfloat16"
+
+
+def _tensor(name, t, **checks):
+    """The one refusal of a tensor argument: ValueError unless `t` is a torch.Tensor that passes `checks`.  They run in the order
+    their keywords are written, which decides the fault reported for an argument that is bad in several ways:
+      dims=(counts, what), shape=(shape, what)   "<name> must <what> <t's shape>"
+      dtypes=(dtypes, what)                      "<name> must be <what>, got <t's dtype>"
+      like=(dtype, message)                      message, its {got} filled with t's dtype
+      not_empty=label                            "empty <label> <t's shape>"
+      contiguous=True                            "<name> must be contiguous"
+      no_grad=why                                "<name> requires grad: <why>" (why may be empty)"""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name} must be a torch.Tensor")
+    for check, want in checks.items():
+        if check == "dims" and t.dim() not in want[0] or check == "shape" and tuple(t.shape) != tuple(want[0]):
+            raise ValueError(f"{name} must {want[1]} {tuple(t.shape)}")
+        if check == "dtypes" and t.dtype not in want[0]:
+            raise ValueError(f"{name} must be {want[1]}, got {t.dtype}")
+        if check == "like" and t.dtype != want[0]:
+            raise ValueError(want[1].format(got=t.dtype))
+        if check == "not_empty" and t.numel() == 0:
+            raise ValueError(f"empty {want} {tuple(t.shape)}")
+        if check == "contiguous" and not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+        if check == "no_grad" and t.requires_grad:
+            raise ValueError(f"{name} requires grad" + (f": {want}" if want else ""))
+    return t
+
+
+def _on_gpu(t, no_gpu_error=False):
+    """`t` lives on the GPU, or ValueError.  no_gpu_error: where there is no GPU at all, the package's RuntimeError instead (the
+    wrappers that run this after their argument checks).  -> t"""
     if not t.is_cuda:
+        if no_gpu_error and not torch.cuda.is_available():
+            raise RuntimeError("comfystereo_amd needs an MI355X (PyTorch-ROCm `cuda` device); there is no CPU fallback")
         raise ValueError("comfystereo_amd engine calls need device-resident tensors (there is no CPU path)")
     return t
+
+
+def _same_device(first, *named, msg=None):
+    """Every (name, tensor) of `named` lives where the tensor of `first` does, or ValueError."""
+    for name, t in named:
+        if t.device != first[1].device:
+            raise ValueError(msg or f"{first[0]} and {name} must be on the same device")
+
+
+def _workspace(nbytes, device, pass_floor=False):
+    """The scratch of one call: at least 256 bytes -> (uint8 tensor, the byte count the native call is given: what the library
+    asked for, or with pass_floor what was allocated)."""
+    size = max(nbytes, 256)
+    return torch.empty((size,), dtype=torch.uint8, device=device), size if pass_floor else nbytes
+
+
+def _launch(device, fn, *args):
+    """fn(*args, stream) on `device` -- the device of the call's tensors, whichever device is current -- and on that device's
+    current stream; NativeError unless it returns CS_OK."""
+    with torch.cuda.device(device):
+        _native.check(fn(*args, _stream()))
+
+
+def _dtype_code(t, table):
+    """t's dtype in one of the library's dtype enums (_native.ATTN_DTYPE, _native.LATENT_DTYPE)."""
+    return table[_DTYPE_NAMES[t.dtype]]
 
 
 # The reference picks its gpu_warp implementation at import time: forward_warp_mesh when `moderngl` is importable,
@@ -36,6 +103,7 @@ MESH_WARP = False
 # source lines (float64 disparities, int64 sums), available for none / naive /
 # naive_interpolating / inverse.
 DIALECT = "D32"
+DIALECTS = {"D32": 0, "D64": 3, "f64-disparity": 1, "int64-sum": 2}
 
 
 def make_params(n, h, w, depth_h, depth_w, depth_c, fill, mode, divergence, separation, stereo_balance,
@@ -85,12 +153,11 @@ class Plan:
         self.depth_r = torch.empty((p.n, p.h, p.w, 3), **f32)
         self.mask = torch.empty((p.n, mh, mw), **f32)
         self.ws_bytes = L.cs_workspace_bytes(ctypes.byref(p)) + int(tie_pool_bytes)
-        self.ws = torch.empty((max(self.ws_bytes, 256),), dtype=torch.uint8, device=device)
+        self.ws, _ = _workspace(self.ws_bytes, device)
 
     def run(self, image, depth):
-        L = _native.lib()
-        _native.check(L.cs_generate(ctypes.byref(self.p), _ptr(image), _ptr(depth), _ptr(self.stereo), _ptr(self.depth_l),
-                                    _ptr(self.depth_r), _ptr(self.mask), _ptr(self.ws), self.ws_bytes, _stream()))
+        _launch(self.ws.device, _native.lib().cs_generate, ctypes.byref(self.p), _ptr(image), _ptr(depth), _ptr(self.stereo),
+                _ptr(self.depth_l), _ptr(self.depth_r), _ptr(self.mask), _ptr(self.ws), self.ws_bytes)
         return self.stereo, self.depth_l, self.depth_r, self.mask
 
     def stats(self):
@@ -102,11 +169,12 @@ class Plan:
 def expand_u8(codes, out=None):
     """uint8 codes -> float32 k/255 on the device (true division, like the reference's np2tensor)."""
     L = _native.lib()
-    codes = _dev(codes).contiguous()
-    assert codes.dtype == torch.uint8
+    codes = _on_gpu(codes).contiguous()
+    if codes.dtype != torch.uint8:
+        raise ValueError("codes must be uint8")
     if out is None:
         out = torch.empty(codes.shape, dtype=torch.float32, device=codes.device)
-    _native.check(L.cs_expand_u8(_ptr(codes), _ptr(out), codes.numel(), _stream()))
+    _launch(codes.device, L.cs_expand_u8, _ptr(codes), _ptr(out), codes.numel())
     return out
 
 
@@ -114,8 +182,8 @@ def generate(image, depth_map, divergence, separation, modes, stereo_balance, co
              stereo_offset_exponent, fill, depth_blur_edge_threshold, depth_blur_strength, depth_map_blur,
              depth_blur_falloff=1.0, depth_blur_vert_smooth=0, batch_size=4):
     """Fused batch path on device tensors: image [N,H,W,3], depth_map [N,H',W',C] float32 -> 4 device tensors."""
-    image = _dev(image).contiguous().float()
-    depth_map = _dev(depth_map).contiguous().float()
+    image = _on_gpu(image).contiguous().float()
+    depth_map = _on_gpu(depth_map).contiguous().float()
     n, h, w, c = image.shape
     if c != 3:
         raise ValueError("image must be [N,H,W,3]")
@@ -125,9 +193,6 @@ def generate(image, depth_map, divergence, separation, modes, stereo_balance, co
     return Plan(p, image.device).run(image, depth_map)
 
 
-DIALECTS = {"D32": 0, "D64": 3, "f64-disparity": 1, "int64-sum": 2}
-
-
 def apply_stereo_divergence(image_u8, depth, divergence, separation, stereo_offset_exponent, fill, convergence_point=0.5,
                             dialect="D32"):
     """reference stereoimage_generation.py:1576-1620 for [N,H,W,3] uint8 + [N,H,W] float32 device tensors.
@@ -135,136 +200,125 @@ def apply_stereo_divergence(image_u8, depth, divergence, separation, stereo_offs
     int64 pixel sums; for polylines_soft / polylines_sharp float64 point coordinates and the float64 sweep -- a literal
     one-lane replay per row, ~100x slower than D32); none / naive / naive_interpolating / inverse / polylines_* / hybrid_edge only."""
     L = _native.lib()
-    image_u8 = _dev(image_u8).contiguous()
-    depth = _dev(depth).contiguous().float()
-    assert image_u8.dtype == torch.uint8
+    image_u8 = _on_gpu(image_u8).contiguous()
+    depth = _on_gpu(depth).contiguous().float()
+    if image_u8.dtype != torch.uint8:
+        raise ValueError("image_u8 must be uint8")
     squeeze = image_u8.dim() == 3
     if squeeze:
         image_u8, depth = image_u8[None], depth[None]
     n, h, w, _ = image_u8.shape
     out = torch.empty_like(image_u8)
-    nb = L.cs_asd_workspace_bytes_for(n, h, w, FILL[fill])
-    ws = torch.empty((max(nb, 256),), dtype=torch.uint8, device=image_u8.device)
-    _native.check(L.cs_apply_stereo_divergence2(_ptr(image_u8), _ptr(depth), n, h, w, float(divergence), float(separation),
-                                                float(stereo_offset_exponent), FILL[fill], float(convergence_point),
-                                                DIALECTS[dialect], _ptr(out), _ptr(ws), nb, _stream()))
+    ws, nb = _workspace(L.cs_asd_workspace_bytes_for(n, h, w, FILL[fill]), image_u8.device)
+    _launch(image_u8.device, L.cs_apply_stereo_divergence2, _ptr(image_u8), _ptr(depth), n, h, w, float(divergence), float(separation),
+            float(stereo_offset_exponent), FILL[fill], float(convergence_point), DIALECTS[dialect], _ptr(out), _ptr(ws), nb)
     return out[0] if squeeze else out
+
+
+def _directional_blur(entry, workspace_bytes, depth, scalars):
+    """The two directional blurs on a device tensor [N,H,W] (or [H,W]).  scalars(): the call's five numbers, converted at the
+    point and in the order the wrapper always converted them (which of two bad numbers is reported).  -> (left, right)"""
+    L = _native.lib()
+    shp = depth.shape
+    d3 = depth.reshape((-1,) + tuple(shp[-2:]))
+    n, h, w = d3.shape
+    out_l, out_r = torch.empty_like(d3), torch.empty_like(d3)
+    ws, nb = _workspace(getattr(L, workspace_bytes)(n, h, w), depth.device)
+    _launch(depth.device, getattr(L, entry), _ptr(d3), n, h, w, *scalars(), _ptr(out_l), _ptr(out_r), _ptr(ws), nb)
+    return out_l.reshape(shp), out_r.reshape(shp)
 
 
 def directional_blur(depth, blur_strength, edge_threshold, falloff_exponent=1.0, vert_smooth_px=0, blur_mask_width=None):
     """reference stereoimage_generation.py:1171-1251 for a [N,H,W] (or [H,W]) float32 device tensor, 0..255 scale.
     blur_mask_width: reach of the blur weights from an edge (default: the blur strength, like the reference's callers)."""
-    L = _native.lib()
-    depth = _dev(depth).contiguous().float()
-    shp = depth.shape
-    d3 = depth.reshape((-1,) + tuple(shp[-2:]))
-    n, h, w = d3.shape
-    out_l, out_r = torch.empty_like(d3), torch.empty_like(d3)
-    nb = L.cs_blur_workspace_bytes(n, h, w)
-    ws = torch.empty((max(nb, 256),), dtype=torch.uint8, device=depth.device)
-    mw = float(blur_strength if blur_mask_width is None else blur_mask_width)
-    _native.check(L.cs_directional_blur(_ptr(d3), n, h, w, float(blur_strength), float(edge_threshold), mw,
-                                        float(falloff_exponent), int(vert_smooth_px), _ptr(out_l), _ptr(out_r), _ptr(ws),
-                                        nb, _stream()))
-    return out_l.reshape(shp), out_r.reshape(shp)
+    _native.lib()
+
+    def scalars():
+        mw = float(blur_strength if blur_mask_width is None else blur_mask_width)
+        return float(blur_strength), float(edge_threshold), mw, float(falloff_exponent), int(vert_smooth_px)
+    return _directional_blur("cs_directional_blur", "cs_blur_workspace_bytes", _on_gpu(depth).contiguous().float(), scalars)
 
 
 def directional_blur_scipy(depth, blur_strength, edge_threshold, blur_mask_width=5, falloff_exponent=1.0, vert_smooth_px=0):
     """reference stereoimage_generation.py:1346-1419 (`directional_motion_blur`, the scipy blur of the numpy / PIL input path)
     for a [N,H,W] (or [H,W]) float32 device tensor, used as given (no 0..255 rescaling) -> (left, right)."""
-    L = _native.lib()
-    depth = _dev(depth).contiguous().float()
+    _native.lib()
+    depth = _on_gpu(depth).contiguous().float()
     if blur_strength <= 0:   # (:1374)
         return depth, depth
-    shp = depth.shape
-    d3 = depth.reshape((-1,) + tuple(shp[-2:]))
-    n, h, w = d3.shape
-    out_l, out_r = torch.empty_like(d3), torch.empty_like(d3)
-    nb = L.cs_blur_scipy_workspace_bytes(n, h, w)
-    ws = torch.empty((max(nb, 256),), dtype=torch.uint8, device=depth.device)
-    _native.check(L.cs_directional_blur_scipy(_ptr(d3), n, h, w, float(blur_strength), float(edge_threshold), float(blur_mask_width),
-                                              float(falloff_exponent), int(vert_smooth_px), _ptr(out_l), _ptr(out_r), _ptr(ws), nb, _stream()))
-    return out_l.reshape(shp), out_r.reshape(shp)
+    return _directional_blur("cs_directional_blur_scipy", "cs_blur_scipy_workspace_bytes", depth, lambda: (
+        float(blur_strength), float(edge_threshold), float(blur_mask_width), float(falloff_exponent), int(vert_smooth_px)))
+
+
+def _forward_warp(entry, workspace_bytes, image, depth, floats, ints=()):
+    """The two forward warps: image [B,3,H,W], depth [B,H,W] on the device -> (warped, gap mask bool)."""
+    L = _native.lib()
+    image = _on_gpu(image).contiguous().float()
+    depth = _on_gpu(depth).contiguous().float()
+    b, c, h, w = image.shape
+    if c != 3:
+        raise ValueError("image must have 3 channels ([B,3,H,W])")
+    warped = torch.empty_like(image)
+    mask = torch.empty((b, h, w), dtype=torch.uint8, device=image.device)
+    ws, nb = _workspace(getattr(L, workspace_bytes)(b, h, w), image.device)
+    _launch(image.device, getattr(L, entry), _ptr(image), _ptr(depth), b, h, w, *[float(v) for v in floats], *[int(v) for v in ints],
+            _ptr(warped), _ptr(mask), _ptr(ws), nb)
+    return warped, mask.bool()
 
 
 def forward_warp(image, depth, divergence_px, separation_px, stereo_offset_exponent, convergence_point=0.5,
                  gradient_threshold=1.5, max_stretch=8):
     """reference stereoimage_generation.py:277-450: image [B,3,H,W], depth [B,H,W] -> (warped, gap mask bool)."""
-    L = _native.lib()
-    image = _dev(image).contiguous().float()
-    depth = _dev(depth).contiguous().float()
-    b, c, h, w = image.shape
-    assert c == 3
-    warped = torch.empty_like(image)
-    mask = torch.empty((b, h, w), dtype=torch.uint8, device=image.device)
-    nb = L.cs_warp_workspace_bytes(b, h, w)
-    ws = torch.empty((max(nb, 256),), dtype=torch.uint8, device=image.device)
-    _native.check(L.cs_forward_warp2(_ptr(image), _ptr(depth), b, h, w, float(divergence_px), float(separation_px),
-                                     float(stereo_offset_exponent), float(convergence_point), float(gradient_threshold),
-                                     int(max_stretch), _ptr(warped), _ptr(mask), _ptr(ws), nb, _stream()))
-    return warped, mask.bool()
+    return _forward_warp("cs_forward_warp2", "cs_warp_workspace_bytes", image, depth, (divergence_px, separation_px,
+                         stereo_offset_exponent, convergence_point, gradient_threshold), (max_stretch,))
 
 
 def forward_warp_mesh(image, depth, divergence_px, separation_px, stereo_offset_exponent, convergence_point=0.5,
                       gradient_threshold=1.5):
     """reference stereoimage_generation.py:453-689 (the mesh-quality warp): image [B,3,H,W], depth [B,H,W] ->
     (warped, gap mask bool)."""
-    L = _native.lib()
-    image = _dev(image).contiguous().float()
-    depth = _dev(depth).contiguous().float()
-    b, c, h, w = image.shape
-    assert c == 3
-    warped = torch.empty_like(image)
-    mask = torch.empty((b, h, w), dtype=torch.uint8, device=image.device)
-    nb = L.cs_warp_mesh_workspace_bytes(b, h, w)
-    ws = torch.empty((max(nb, 256),), dtype=torch.uint8, device=image.device)
-    _native.check(L.cs_forward_warp_mesh(_ptr(image), _ptr(depth), b, h, w, float(divergence_px), float(separation_px),
-                                         float(stereo_offset_exponent), float(convergence_point), float(gradient_threshold),
-                                         _ptr(warped), _ptr(mask), _ptr(ws), nb, _stream()))
-    return warped, mask.bool()
+    return _forward_warp("cs_forward_warp_mesh", "cs_warp_mesh_workspace_bytes", image, depth, (divergence_px, separation_px,
+                         stereo_offset_exponent, convergence_point, gradient_threshold))
 
 
 def stereo_shift(input_images, depthmaps, scale_factor=8.0, shift_both=False, stereo_offset_exponent=1.0):
     """reference stereo_utils.py:15-88 for device tensors: input [B,C,H,W], depth [B,H,W] float32 -> [2B,C,H,W]."""
     L = _native.lib()
-    x = _dev(input_images).contiguous().float()
-    d = _dev(depthmaps).contiguous().float()
+    x = _on_gpu(input_images).contiguous().float()
+    d = _on_gpu(depthmaps).contiguous().float()
     b, c, h, w = x.shape
-    assert tuple(d.shape) == (b, h, w)
+    if tuple(d.shape) != (b, h, w):
+        raise ValueError("depthmaps must be [B,H,W] like input_images [B,C,H,W]")
     out = torch.empty((2 * b, c, h, w), dtype=torch.float32, device=x.device)
-    nb = L.cs_stereo_shift_workspace_bytes()
-    ws = torch.empty((max(nb, 256),), dtype=torch.uint8, device=x.device)
-    _native.check(L.cs_stereo_shift(_ptr(x), _ptr(d), b, c, h, w, float(scale_factor), int(bool(shift_both)),
-                                    float(stereo_offset_exponent), _ptr(out), _ptr(ws), nb, _stream()))
+    ws, nb = _workspace(L.cs_stereo_shift_workspace_bytes(), x.device)
+    _launch(x.device, L.cs_stereo_shift, _ptr(x), _ptr(d), b, c, h, w, float(scale_factor), int(bool(shift_both)),
+            float(stereo_offset_exponent), _ptr(out), _ptr(ws), nb)
     return out
 
 
 def test_powf(x, y):
     L = _native.lib()
-    x = _dev(x).contiguous().float()
+    x = _on_gpu(x).contiguous().float()
     out = torch.empty_like(x)
-    _native.check(L.cs_test_powf(_ptr(x), float(y), _ptr(out), x.numel(), _stream()))
+    _launch(x.device, L.cs_test_powf, _ptr(x), float(y), _ptr(out), x.numel())
     return out
 
 
 def test_exp(x):
     L = _native.lib()
-    x = _dev(x).contiguous().double()
+    x = _on_gpu(x).contiguous().double()
     out = torch.empty_like(x)
-    _native.check(L.cs_test_exp(_ptr(x), _ptr(out), x.numel(), _stream()))
+    _launch(x.device, L.cs_test_exp, _ptr(x), _ptr(out), x.numel())
     return out
 
 
 # ---- the reference's grid-sample warps (cs_grid_warp, cs_interpolate_fill, cs_detect_disocclusions) -------------------------
 def _grid_input(t, name, dims):
     """A float32, contiguous, device-resident tensor of `dims` dimensions, or ValueError."""
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"{name} must be a torch.Tensor")
-    if t.dim() != dims:
-        raise ValueError(f"{name} must have {dims} dimensions, got shape {tuple(t.shape)}")
+    _tensor(name, t, dims=((dims,), f"have {dims} dimensions, got shape"))
     if not (t.is_floating_point() or t.dtype in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)):
         raise ValueError(f"{name}: unsupported dtype {t.dtype}")
-    return _dev(t).to(torch.float32).contiguous()
+    return _on_gpu(t).to(torch.float32).contiguous()
 
 
 def grid_warp(image, depth, divergence_px, separation_px, stereo_offset_exponent, convergence_point, op, padding="border"):
@@ -279,8 +333,7 @@ def grid_warp(image, depth, divergence_px, separation_px, stereo_offset_exponent
     c = 0
     if op != "mask":
         image = _grid_input(image, "image", 4)
-        if image.device != depth.device:
-            raise ValueError("image and depth must be on the same device")
+        _same_device(("image", image), ("depth", depth))
         if image.shape[0] != b or tuple(image.shape[2:]) != (h, w):
             raise ValueError(f"image {tuple(image.shape)} and depth {tuple(depth.shape)} do not match ([B,C,H,W] / [B,H,W])")
         c = image.shape[1]
@@ -291,13 +344,10 @@ def grid_warp(image, depth, divergence_px, separation_px, stereo_offset_exponent
     # (a frame wider than cs_grid_warp_max_width: the native call refuses it, NativeError CS_ELIMIT)
     warped = torch.empty((b, c, h, w), dtype=torch.float32, device=depth.device) if op != "mask" else None
     mask = torch.empty((b, h, w), dtype=torch.uint8, device=depth.device) if op != "warp" else None
-    nb = L.cs_grid_warp_workspace_bytes(b, h, w)
-    ws = torch.empty((max(nb, 256),), dtype=torch.uint8, device=depth.device)
-    _native.check(L.cs_grid_warp(_ptr(image) if warped is not None else None, _ptr(depth), b, c, h, w, float(divergence_px),
-                                 float(separation_px), float(stereo_offset_exponent), float(convergence_point),
-                                 _native.GRID_OP[op], _native.GRID_PADDING[padding],
-                                 _ptr(warped) if warped is not None else None, _ptr(mask) if mask is not None else None,
-                                 _ptr(ws), nb, _stream()))
+    ws, nb = _workspace(L.cs_grid_warp_workspace_bytes(b, h, w), depth.device)
+    _launch(depth.device, L.cs_grid_warp, _ptr(image) if warped is not None else None, _ptr(depth), b, c, h, w, float(divergence_px),
+            float(separation_px), float(stereo_offset_exponent), float(convergence_point), _native.GRID_OP[op],
+            _native.GRID_PADDING[padding], _opt_ptr(warped), _opt_ptr(mask), _ptr(ws), nb)
     return warped, (mask.bool() if mask is not None else None)
 
 
@@ -309,12 +359,12 @@ def interpolate_fill(image, mask):
         raise ValueError("mask must be a bool tensor")
     if mask.dim() != 3 or mask.shape[0] != image.shape[0] or tuple(mask.shape[1:]) != tuple(image.shape[2:]):
         raise ValueError(f"mask {tuple(mask.shape)} does not match image {tuple(image.shape)} ([B,H,W] / [B,C,H,W])")
-    mask = _dev(mask).to(image.device).contiguous().view(torch.uint8)
+    mask = _on_gpu(mask).to(image.device).contiguous().view(torch.uint8)
     b, c, h, w = image.shape
     if image.numel() == 0:
         raise ValueError(f"empty image {tuple(image.shape)}")
     out = torch.empty_like(image)
-    _native.check(L.cs_interpolate_fill(_ptr(image), _ptr(mask), b, c, h, w, _ptr(out), _stream()))
+    _launch(image.device, L.cs_interpolate_fill, _ptr(image), _ptr(mask), b, c, h, w, _ptr(out))
     return out
 
 
@@ -327,12 +377,11 @@ def detect_disocclusions(depth, grid, grid_x_warped, threshold=0.02):
     h, w = depth.shape
     if tuple(grid.shape) != (1, h, w, 2) or tuple(gxw.shape) != (h, w):
         raise ValueError(f"grid {tuple(grid.shape)} / grid_x_warped {tuple(gxw.shape)} do not match depth {(h, w)}")
-    if grid.device != depth.device or gxw.device != depth.device:
-        raise ValueError("depth, grid and grid_x_warped must be on the same device")
+    _same_device(("depth", depth), ("grid", grid), ("grid_x_warped", gxw), msg="depth, grid and grid_x_warped must be on the same device")
     if h == 0 or w < 2:
         raise ValueError(f"detect_disocclusions needs H >= 1 and W >= 2, got {(h, w)}")
     out = torch.empty((h, w), dtype=torch.uint8, device=depth.device)
-    _native.check(L.cs_detect_disocclusions(_ptr(depth), _ptr(grid), _ptr(gxw), h, w, float(threshold), _ptr(out), _stream()))
+    _launch(depth.device, L.cs_detect_disocclusions, _ptr(depth), _ptr(grid), _ptr(gxw), h, w, float(threshold), _ptr(out))
     return out.bool()
 
 
@@ -359,27 +408,19 @@ def gaussian_blur(depth, sigma, op="plain", edge_threshold=None):
     L = _native.lib()
     if op not in _native.GAUSS_OP:
         raise ValueError(f"unknown Gaussian blur operation {op!r}")
-    if not isinstance(depth, torch.Tensor):
-        raise ValueError("depth must be a torch.Tensor")
-    if depth.dim() not in (2, 3):
-        raise ValueError(f"depth must be [H,W] or [B,H,W], got shape {tuple(depth.shape)}")
-    if depth.dtype != torch.float32:
-        raise ValueError(f"depth must be float32, got {depth.dtype}")
-    if depth.numel() == 0:
-        raise ValueError(f"empty depth {tuple(depth.shape)}")
+    # (_tensor checks in the order written: the ladder this wrapper always had)
+    _tensor("depth", depth, dims=((2, 3), "be [H,W] or [B,H,W], got shape"), dtypes=((torch.float32,), "float32"), not_empty="depth")
     if op != "plain" and edge_threshold is None:
         raise ValueError(f"operation {op!r} needs an edge_threshold")
-    depth = _dev(depth).contiguous()
+    depth = _on_gpu(depth).contiguous()
     taps = gaussian_taps(sigma) if sigma > 0 else np.ones(1)
     d3 = depth.reshape((-1,) + tuple(depth.shape[-2:]))
     n, h, w = d3.shape
     taps_dev = torch.from_numpy(np.ascontiguousarray(taps, dtype=np.float64)).to(depth.device)
     out = torch.empty_like(d3)
-    nb = L.cs_gaussian_blur_workspace_bytes(n, h, w, taps.shape[0])
-    ws = torch.empty((max(nb, 256),), dtype=torch.uint8, device=depth.device)
-    _native.check(L.cs_gaussian_blur(_native.GAUSS_OP[op], _ptr(d3), _ptr(taps_dev), taps.shape[0],
-                                     float(edge_threshold) if edge_threshold is not None else 0.0, n, h, w, _ptr(out), _ptr(ws),
-                                     nb, _stream()))
+    ws, nb = _workspace(L.cs_gaussian_blur_workspace_bytes(n, h, w, taps.shape[0]), depth.device)
+    _launch(depth.device, L.cs_gaussian_blur, _native.GAUSS_OP[op], _ptr(d3), _ptr(taps_dev), taps.shape[0],
+            float(edge_threshold) if edge_threshold is not None else 0.0, n, h, w, _ptr(out), _ptr(ws), nb)
     return out.reshape(depth.shape)
 
 
@@ -393,8 +434,7 @@ def inpaint_prepare(image, depth, scale_factor, threshold=0.05, codes=False):
     L = _native.lib()
     image = _grid_input(image, "image", 4)
     depth = _grid_input(depth, "depth", 3)
-    if image.device != depth.device:
-        raise ValueError("image and depth must be on the same device")
+    _same_device(("image", image), ("depth", depth))
     b, h, w = depth.shape
     if image.shape[1] != 3 or image.shape[0] != b or tuple(image.shape[2:]) != (h, w):
         raise ValueError(f"image {tuple(image.shape)} and depth {tuple(depth.shape)} do not match ([B,3,H,W] / [B,H,W])")
@@ -406,12 +446,10 @@ def inpaint_prepare(image, depth, scale_factor, threshold=0.05, codes=False):
     mask = torch.empty((b, h, w), dtype=torch.uint8, device=dev)
     wu8 = torch.empty((b, h, w, 3), dtype=torch.uint8, device=dev) if codes else None
     fu8 = torch.empty((b, h, w, 3), dtype=torch.uint8, device=dev) if codes else None
-    nb = L.cs_inpaint_prepare_workspace_bytes(b, h, w)
-    ws = torch.empty((max(nb, 256),), dtype=torch.uint8, device=dev)
+    ws, nb = _workspace(L.cs_inpaint_prepare_workspace_bytes(b, h, w), dev)
     divergence_px = (float(scale_factor) / 100.0) * w
-    _native.check(L.cs_inpaint_prepare(_ptr(image), _ptr(depth), b, h, w, divergence_px, float(threshold), _ptr(warped),
-                                       _ptr(filled), _ptr(mask), _ptr(wu8) if codes else None, _ptr(fu8) if codes else None,
-                                       _ptr(ws), nb, _stream()))
+    _launch(dev, L.cs_inpaint_prepare, _ptr(image), _ptr(depth), b, h, w, divergence_px, float(threshold), _ptr(warped), _ptr(filled),
+            _ptr(mask), _opt_ptr(wu8), _opt_ptr(fu8), _ptr(ws), nb)
     out = (warped, filled, mask.bool())
     return out + (wu8, fu8) if codes else out
 
@@ -427,10 +465,7 @@ def pil_resize(x, size, gray=False, f32=None, codes=True, f32_out=None):
     a slice of wider rows (one eye of a side-by-side frame).
     A reduction by more than a factor of 64, or a side above 65 535: NativeError CS_ELIMIT."""
     L = _native.lib()
-    if not isinstance(x, torch.Tensor):
-        raise ValueError("x must be a torch.Tensor")
-    if x.dtype not in (torch.uint8, torch.float32):
-        raise ValueError(f"x must be uint8 or float32, got {x.dtype}")
+    _tensor("x", x, dtypes=((torch.uint8, torch.float32), "uint8 or float32"))
     if x.dim() == 3:
         x = x.unsqueeze(-1)
     if x.dim() != 4 or x.shape[-1] not in (1, 3):
@@ -446,7 +481,7 @@ def pil_resize(x, size, gray=False, f32=None, codes=True, f32_out=None):
     ow, oh = (int(v) for v in size)
     if ow <= 0 or oh <= 0 or x.numel() == 0:
         raise ValueError(f"empty image: {tuple(x.shape)} -> {(oh, ow)}")
-    x = _dev(x).contiguous()
+    x = _on_gpu(x).contiguous()
     n, h, w, c = x.shape
     co = 1 if gray else c
     dev = x.device
@@ -468,14 +503,32 @@ def pil_resize(x, size, gray=False, f32=None, codes=True, f32_out=None):
         flt = torch.empty((n, oh, ow, co), dtype=torch.float32, device=dev)
     flags = (_native.PIL_FLAG["in_f32"] if x.dtype == torch.float32 else 0) | (_native.PIL_FLAG["gray"] if gray else 0) | \
         (_native.PIL_FLAG["out_planar"] if f32 == "planar" else 0)
-    nb = L.cs_pil_resize_workspace_bytes(n, h, w, c, oh, ow)
-    ws = torch.empty((max(nb, 256),), dtype=torch.uint8, device=dev)
-    _native.check(L.cs_pil_resize(_ptr(x), n, h, w, c, oh, ow, flags, _ptr(out) if codes else None,
-                                  _ptr(flt) if flt is not None else None, pitch, _ptr(ws), max(nb, 256), _stream()))
+    ws, nb = _workspace(L.cs_pil_resize_workspace_bytes(n, h, w, c, oh, ow), dev, pass_floor=True)
+    _launch(dev, L.cs_pil_resize, _ptr(x), n, h, w, c, oh, ow, flags, _opt_ptr(out), _opt_ptr(flt), pitch, _ptr(ws), nb)
     return out if f32 is None else (out, flt)
 
 
 # ---- the reference's stereo attention (cs_stereo_attention) ---------------------------------------------
+def _qkv_shapes(q, k, v):
+    """q [B, n, d], k and v [B, n_k, d], none of them empty, or ValueError -> (B, n, n_k, d)"""
+    bh, n, d = q.shape
+    if k.shape != v.shape or k.shape[0] != bh or k.shape[2] != d:
+        raise ValueError(f"q {tuple(q.shape)}, k {tuple(k.shape)} and v {tuple(v.shape)} do not match")
+    n_k = k.shape[1]
+    if bh == 0 or n == 0 or n_k == 0 or d == 0:
+        raise ValueError(f"empty attention: q {tuple(q.shape)}, k {tuple(k.shape)}")
+    return bh, n, n_k, d
+
+
+def _head_dim_and_scale(d, half, scale, kernel):
+    """The head dimension the attention kernels take and a finite scale, or ValueError."""
+    d_max = _native.lib().cs_stereo_attention_max_head_dim()   # (host only: no device work)
+    if d % (8 if half else 4) or d > d_max:
+        raise ValueError(f"head dimension {d}: {kernel} takes multiples of 4 (float16 / bfloat16: of 8) up to {d_max}")
+    if not math.isfinite(float(scale)):
+        raise ValueError(f"scale must be finite, got {scale}")
+
+
 def stereo_attention(q, k, v, heads, scale, mode, chunks=1, out=None):
     """cs_stereo_attention on float32 device tensors: q [(c s b h), n, d], k and v [(c s b h), n_k, d] -> [(c s b), n, h * d],
     softmax(scale * q k^T) v over the keys `mode` selects, in one fused kernel (no score matrix is ever written).
@@ -487,27 +540,15 @@ def stereo_attention(q, k, v, heads, scale, mode, chunks=1, out=None):
     accumulators; the result has the inputs' dtype); there d must be a multiple of 8.  Mixed dtypes are a ValueError."""
     if mode not in _native.ATTN_MODE:
         raise ValueError(f"unknown attention mode {mode!r} (self, uni, bi)")
+    # (_tensor checks in the order written: the ladder this wrapper always had)
+    _tensor("q", q)
     for name, t in (("q", q), ("k", k), ("v", v)):
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"{name} must be a torch.Tensor")
-        if t.dim() != 3:
-            raise ValueError(f"{name} must be [(c s b h), tokens, d], got shape {tuple(t.shape)}")
-        if t.dtype not in (torch.float32, torch.float16, torch.bfloat16):
-            raise ValueError(f"{name} must be float32, float16 or bfloat16, got {t.dtype}")
-        if t.dtype != q.dtype:
-            raise ValueError(f"q, k and v must share one dtype, got {q.dtype} and {t.dtype} ({name})")
-        if not t.is_contiguous():
-            raise ValueError(f"{name} must be contiguous")
-        if t.requires_grad:
-            raise ValueError(f"{name} requires grad: cs_stereo_attention is forward only")
+        _tensor(name, t, dims=((3,), "be [(c s b h), tokens, d], got shape"), dtypes=(_FLOATS, _FLOATS_TEXT),
+                like=(q.dtype, f"q, k and v must share one dtype, got {q.dtype} and {{got}} ({name})"), contiguous=True,
+                no_grad="cs_stereo_attention is forward only")
     half = q.dtype != torch.float32
     heads, chunks = int(heads), int(chunks)
-    bh, n, d = q.shape
-    if k.shape != v.shape or k.shape[0] != bh or k.shape[2] != d:
-        raise ValueError(f"q {tuple(q.shape)}, k {tuple(k.shape)} and v {tuple(v.shape)} do not match")
-    n_k = k.shape[1]
-    if bh == 0 or n == 0 or n_k == 0 or d == 0:
-        raise ValueError(f"empty attention: q {tuple(q.shape)}, k {tuple(k.shape)}")
+    bh, n, n_k, d = _qkv_shapes(q, k, v)
     views = 1 if mode == "self" else 2
     if mode == "self":
         chunks = 1
@@ -515,32 +556,21 @@ def stereo_attention(q, k, v, heads, scale, mode, chunks=1, out=None):
         raise ValueError(f"batch {bh} is not chunks * views * samples * heads = {chunks} * {views} * b * {heads}")
     if mode != "self" and n_k != n:
         raise ValueError(f"mode {mode!r} needs as many keys as queries per view, got {n_k} and {n}")
-    d_max = _native.lib().cs_stereo_attention_max_head_dim()   # (host only: no device work)
-    if d % (8 if half else 4) or d > d_max:
-        raise ValueError(f"head dimension {d}: cs_stereo_attention takes multiples of 4 (float16 / bfloat16: of 8) up to {d_max}")
-    if not math.isfinite(float(scale)):
-        raise ValueError(f"scale must be finite, got {scale}")
+    _head_dim_and_scale(d, half, scale, "cs_stereo_attention")
     samples = bh // (heads * views * chunks)
     shape = (bh // heads, n, heads * d)
     if out is not None:
         if (not isinstance(out, torch.Tensor) or out.dtype != q.dtype or tuple(out.shape) != shape or not out.is_contiguous()
                 or out.device != q.device):
             raise ValueError(f"out must be a contiguous {q.dtype} tensor {shape} on {q.device}")
-    _dev(q)
-    if k.device != q.device or v.device != q.device:
-        raise ValueError("q, k and v must be on the same device")
+    _on_gpu(q)
+    _same_device(("q", q), ("k", k), ("v", v), msg="q, k and v must be on the same device")
     L = _native.lib()
     if out is None:
         out = torch.empty(shape, dtype=q.dtype, device=q.device)
-    with torch.cuda.device(q.device):
-        if half:
-            _native.check(L.cs_stereo_attention_half(_ptr(q), _ptr(k), _ptr(v), _ptr(out),
-                                                     _native.ATTN_DTYPE["float16" if q.dtype == torch.float16 else "bfloat16"],
-                                                     chunks, views, samples, heads, n, n_k, d, float(scale),
-                                                     _native.ATTN_MODE[mode], _stream()))
-            return out
-        _native.check(L.cs_stereo_attention(_ptr(q), _ptr(k), _ptr(v), _ptr(out), chunks, views, samples, heads, n, n_k, d,
-                                            float(scale), _native.ATTN_MODE[mode], _stream()))
+    _launch(q.device, L.cs_stereo_attention_half if half else L.cs_stereo_attention, _ptr(q), _ptr(k), _ptr(v), _ptr(out),
+            *([_dtype_code(q, _native.ATTN_DTYPE)] if half else []), chunks, views, samples, heads, n, n_k, d, float(scale),
+            _native.ATTN_MODE[mode])
     return out
 
 
@@ -549,48 +579,29 @@ def _attention_grad_args(heads, scale, **tensors):
     """The checks of stereo_attention for the 'self' form: q [(b h), n, d], k and v [(b h), n_k, d] and, where given,
     out / d_out [(b), n, h * d] and lse [(b h), n].  q, k, v, out and d_out are all float32, all float16 or all bfloat16; lse is
     float32 whatever they are.  ValueError before anything is launched.  -> (b, h, n, n_k, d)"""
+    # (_tensor checks in the order written: the ladder this wrapper always had)
     for name, t in tensors.items():
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"{name} must be a torch.Tensor")
+        _tensor(name, t)
     q, k, v = tensors["q"], tensors["k"], tensors["v"]
-    if q.dtype not in (torch.float32, torch.float16, torch.bfloat16):
-        raise ValueError(f"q must be float32, float16 or bfloat16, got {q.dtype}")
+    _tensor("q", q, dtypes=(_FLOATS, _FLOATS_TEXT))
     for name, t in tensors.items():
         want = torch.float32 if name == "lse" else q.dtype
-        if t.dtype != want:
-            raise ValueError(f"{name} must be {want}" + ("" if name == "lse" else " like q (one dtype for q, k, v, out and d_out)")
-                             + f", got {t.dtype}")
-        if not t.is_contiguous():
-            raise ValueError(f"{name} must be contiguous")
+        _tensor(name, t, like=(want, f"{name} must be {want}" + ("" if name == "lse" else " like q (one dtype for q, k, v, out and d_out)")
+                               + ", got {got}"), contiguous=True)
     half = q.dtype != torch.float32
     for name in ("q", "k", "v"):
-        if tensors[name].dim() != 3:
-            raise ValueError(f"{name} must be [(b h), tokens, d], got shape {tuple(tensors[name].shape)}")
+        _tensor(name, tensors[name], dims=((3,), "be [(b h), tokens, d], got shape"))
     heads = int(heads)
-    bh, n, d = q.shape
-    if k.shape != v.shape or k.shape[0] != bh or k.shape[2] != d:
-        raise ValueError(f"q {tuple(q.shape)}, k {tuple(k.shape)} and v {tuple(v.shape)} do not match")
-    n_k = k.shape[1]
-    if bh == 0 or n == 0 or n_k == 0 or d == 0:
-        raise ValueError(f"empty attention: q {tuple(q.shape)}, k {tuple(k.shape)}")
+    bh, n, n_k, d = _qkv_shapes(q, k, v)
     if heads <= 0 or bh % heads:
         raise ValueError(f"batch {bh} is not samples * heads = b * {heads}")
-    d_max = _native.lib().cs_stereo_attention_max_head_dim()   # (host only: no device work)
-    if d % (8 if half else 4) or d > d_max:
-        raise ValueError(f"head dimension {d}: the fused attention takes multiples of 4 (float16 / bfloat16: of 8) up to {d_max}")
-    if not math.isfinite(float(scale)):
-        raise ValueError(f"scale must be finite, got {scale}")
+    _head_dim_and_scale(d, half, scale, "the fused attention")
     for name, shape in (("out", (bh // heads, n, heads * d)), ("d_out", (bh // heads, n, heads * d)), ("lse", (bh, n))):
-        if name in tensors and tuple(tensors[name].shape) != shape:
-            raise ValueError(f"{name} must have shape {shape}, got {tuple(tensors[name].shape)}")
-    _dev(q)
-    if any(t.device != q.device for t in tensors.values()):
-        raise ValueError("all tensors must be on the same device")
+        if name in tensors:
+            _tensor(name, tensors[name], shape=(shape, f"have shape {shape}, got"))
+    _on_gpu(q)
+    _same_device(("q", q), *tensors.items(), msg="all tensors must be on the same device")
     return bh // heads, heads, n, n_k, d
-
-
-def _attn_dtype(t):
-    return _native.ATTN_DTYPE["float16" if t.dtype == torch.float16 else "bfloat16"]
 
 
 def attention_lse(q, k, v, heads, scale):
@@ -602,12 +613,9 @@ def attention_lse(q, k, v, heads, scale):
     out = torch.empty((b, n, h * d), dtype=q.dtype, device=q.device)
     lse = torch.empty((b * h, n), dtype=torch.float32, device=q.device)
     L = _native.lib()
-    with torch.cuda.device(q.device):
-        if q.dtype != torch.float32:
-            _native.check(L.cs_attention_half_fwd_lse(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _attn_dtype(q), b, h, n, n_k, d,
-                                                      float(scale), _stream()))
-        else:
-            _native.check(L.cs_attention_fwd_lse(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), b, h, n, n_k, d, float(scale), _stream()))
+    half = q.dtype != torch.float32
+    _launch(q.device, L.cs_attention_half_fwd_lse if half else L.cs_attention_fwd_lse, _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse),
+            *([_dtype_code(q, _native.ATTN_DTYPE)] if half else []), b, h, n, n_k, d, float(scale))
     return out, lse
 
 
@@ -620,15 +628,10 @@ def attention_backward(q, k, v, out, lse, d_out, heads, scale):
     L = _native.lib()
     half = q.dtype != torch.float32
     dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-    nb = (L.cs_attention_half_bwd_workspace_bytes if half else L.cs_attention_bwd_workspace_bytes)(b, h, n, n_k, d)
-    ws = torch.empty((nb,), dtype=torch.uint8, device=q.device)
-    with torch.cuda.device(q.device):
-        if half:
-            _native.check(L.cs_attention_half_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(d_out), _ptr(dq), _ptr(dk),
-                                                  _ptr(dv), _attn_dtype(q), b, h, n, n_k, d, float(scale), _ptr(ws), nb, _stream()))
-        else:
-            _native.check(L.cs_attention_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(d_out), _ptr(dq), _ptr(dk), _ptr(dv),
-                                             b, h, n, n_k, d, float(scale), _ptr(ws), nb, _stream()))
+    ws, nb = _workspace((L.cs_attention_half_bwd_workspace_bytes if half else L.cs_attention_bwd_workspace_bytes)(b, h, n, n_k, d), q.device)
+    _launch(q.device, L.cs_attention_half_bwd if half else L.cs_attention_bwd, _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse),
+            _ptr(d_out), _ptr(dq), _ptr(dk), _ptr(dv), *([_dtype_code(q, _native.ATTN_DTYPE)] if half else []), b, h, n, n_k, d,
+            float(scale), _ptr(ws), nb)
     return dq, dk, dv
 
 
@@ -659,10 +662,7 @@ def differentiable_attention(q, k, v, heads, scale, native_half=False):
     is saved for the backward is the half q, k, v, out plus the float32 lse; any other input keeps the upcast.  Gradients of
     gradients are not supported."""
     for name, t in (("q", q), ("k", k), ("v", v)):
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"{name} must be a torch.Tensor")
-        if t.dtype not in (torch.float32, torch.float16, torch.bfloat16):
-            raise ValueError(f"{name} must be float32, float16 or bfloat16, got {t.dtype}")
+        _tensor(name, t, dtypes=(_FLOATS, _FLOATS_TEXT))
     if (native_half and q.dtype != torch.float32 and k.dtype == q.dtype and v.dtype == q.dtype and q.dim() == 3
             and q.shape[-1] % 8 == 0):
         return _DifferentiableAttention.apply(q.contiguous(), k.contiguous(), v.contiguous(), int(heads), float(scale))
@@ -671,44 +671,24 @@ def differentiable_attention(q, k, v, heads, scale, native_half=False):
 
 
 # ---- StereoDiffusion Standard mode's latent shift, mask and merge (cs_latent_shift_*, cs_decode_to_codes) ----
-_LATENT_DTYPES = {torch.float32: "float32", torch.float16: "float16", torch.bfloat16: "bfloat16"}
-
-
-def _need_device(t):
-    """After the argument checks: the tensor must be on the GPU (the package's RuntimeError where there is none at all)."""
-    if not t.is_cuda:
-        if not torch.cuda.is_available():
-            raise RuntimeError("comfystereo_amd needs an MI355X (PyTorch-ROCm `cuda` device); there is no CPU fallback")
-        _dev(t)
-
-
 def latent_shift_plan(disp, scale_factor, stereo_offset_exponent=1.0):
     """cs_latent_shift_plan on a device tensor: disp [B,H,W] float32, the disparity at the latents' size -> src_col int32
     [B,H,W]: for every destination column of the right view of stereo_shift_torch(latents, disp, scale_factor) the source
     column that ends up there, -1 in a hole.  Made once per image: the table does not depend on the latents."""
-    if not isinstance(disp, torch.Tensor):
-        raise ValueError("disp must be a torch.Tensor")
-    if disp.dtype != torch.float32:
-        raise ValueError(f"disp must be float32 (the reference's disparity dtype), got {disp.dtype}")
-    if disp.dim() != 3:
-        raise ValueError(f"disp must be [B,H,W], got shape {tuple(disp.shape)}")
-    if disp.numel() == 0:
-        raise ValueError(f"empty disp {tuple(disp.shape)}")
-    if not disp.is_contiguous():
-        raise ValueError("disp must be contiguous")
+    # (_tensor checks in the order written: the ladder this wrapper always had)
+    _tensor("disp", disp, dtypes=((torch.float32,), "float32 (the reference's disparity dtype)"), dims=((3,), "be [B,H,W], got shape"),
+            not_empty="disp", contiguous=True)
     if not (math.isfinite(float(scale_factor)) and math.isfinite(float(stereo_offset_exponent))):
         raise ValueError(f"scale_factor and stereo_offset_exponent must be finite, got {scale_factor} and {stereo_offset_exponent}")
     b, h, w = disp.shape
     if w > 8192:
         raise ValueError(f"rows of {w} columns: cs_latent_shift_plan takes up to 8192 (it is made for latents)")
-    _need_device(disp)
+    _on_gpu(disp, no_gpu_error=True)
     L = _native.lib()
     src_col = torch.empty((b, h, w), dtype=torch.int32, device=disp.device)
-    nb = L.cs_latent_shift_plan_workspace_bytes()
-    ws = torch.empty((max(nb, 256),), dtype=torch.uint8, device=disp.device)
-    with torch.cuda.device(disp.device):
-        _native.check(L.cs_latent_shift_plan(_ptr(disp), b, h, w, float(scale_factor), float(stereo_offset_exponent), _ptr(src_col),
-                                             _ptr(ws), max(nb, 256), _stream()))
+    ws, nb = _workspace(L.cs_latent_shift_plan_workspace_bytes(), disp.device, pass_floor=True)
+    _launch(disp.device, L.cs_latent_shift_plan, _ptr(disp), b, h, w, float(scale_factor), float(stereo_offset_exponent), _ptr(src_col),
+            _ptr(ws), nb)
     return src_col
 
 
@@ -724,19 +704,12 @@ def latent_shift_apply(left, right, src_col, mask, op, noise=None):
     if noise is not None and op != "first":
         raise ValueError("noise goes with op 'first' only")
     tensors = [("left", left), ("right", right)] + ([("noise", noise)] if noise is not None else [])
+    # (_tensor checks in the order written: the ladder this wrapper always had)
+    like_left = f"be [B,C,H,W] like left {tuple(_tensor('left', left).shape)}, got shape"
     for name, t in tensors:
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"{name} must be a torch.Tensor")
-        if t.dtype not in _LATENT_DTYPES:
-            raise ValueError(f"{name} must be float32, float16 or bfloat16, got {t.dtype}")
-        if t.dtype != left.dtype:
-            raise ValueError(f"left, right and noise must share one dtype, got {left.dtype} and {t.dtype} ({name})")
-        if t.dim() != 4 or tuple(t.shape) != tuple(left.shape):
-            raise ValueError(f"{name} must be [B,C,H,W] like left {tuple(left.shape)}, got shape {tuple(t.shape)}")
-        if not t.is_contiguous():
-            raise ValueError(f"{name} must be contiguous")
-        if t.requires_grad:
-            raise ValueError(f"{name} requires grad: cs_latent_shift_apply works in place")
+        _tensor(name, t, dtypes=(_FLOATS, _FLOATS_TEXT),
+                like=(left.dtype, f"left, right and noise must share one dtype, got {left.dtype} and {{got}} ({name})"),
+                dims=((4,), like_left), shape=(left.shape, like_left), contiguous=True, no_grad="cs_latent_shift_apply works in place")
     b, c, h, w = left.shape
     if left.numel() == 0:
         raise ValueError(f"empty latents {tuple(left.shape)}")
@@ -744,16 +717,10 @@ def latent_shift_apply(left, right, src_col, mask, op, noise=None):
         raise ValueError(f"src_col must be a contiguous int32 tensor {(b, h, w)} (latent_shift_plan's)")
     if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or tuple(mask.shape) != (b, h, w) or not mask.is_contiguous():
         raise ValueError(f"mask must be a contiguous uint8 tensor {(b, h, w)}")
-    for name, t in tensors[1:] + [("src_col", src_col), ("mask", mask)]:
-        if t.device != left.device:
-            raise ValueError(f"left and {name} must be on the same device")
-    _need_device(left)
-    L = _native.lib()
-    with torch.cuda.device(left.device):
-        _native.check(L.cs_latent_shift_apply(_ptr(left), _ptr(right), _ptr(src_col), _ptr(mask),
-                                              _ptr(noise) if noise is not None else None,
-                                              _native.LATENT_DTYPE[_LATENT_DTYPES[left.dtype]], b, c, h, w, _native.LATENT_OP[op],
-                                              _stream()))
+    _same_device(("left", left), *tensors[1:], ("src_col", src_col), ("mask", mask))
+    _on_gpu(left, no_gpu_error=True)
+    _launch(left.device, _native.lib().cs_latent_shift_apply, _ptr(left), _ptr(right), _ptr(src_col), _ptr(mask), _opt_ptr(noise),
+            _dtype_code(left, _native.LATENT_DTYPE), b, c, h, w, _native.LATENT_OP[op])
     return right
 
 
@@ -761,23 +728,12 @@ def decode_to_codes(image):
     """cs_decode_to_codes on a device tensor: image [N,C,H,W] float32, float16 or bfloat16, the VAE's output -> uint8 [N,H,W,C]:
     trunc(nan_to_num((image / 2 + 0.5).clamp(0, 1)).float() * 255), the quotient and the sum rounded to the tensor's dtype as
     torch rounds them (reference stereodiffusion_nodes.py:673-677)."""
-    if not isinstance(image, torch.Tensor):
-        raise ValueError("image must be a torch.Tensor")
-    if image.dtype not in _LATENT_DTYPES:
-        raise ValueError(f"image must be float32, float16 or bfloat16, got {image.dtype}")
-    if image.dim() != 4:
-        raise ValueError(f"image must be [N,C,H,W], got shape {tuple(image.shape)}")
-    if image.numel() == 0:
-        raise ValueError(f"empty image {tuple(image.shape)}")
-    if not image.is_contiguous():
-        raise ValueError("image must be contiguous")
-    _need_device(image)
+    # (_tensor checks in the order written: the ladder this wrapper always had)
+    _tensor("image", image, dtypes=(_FLOATS, _FLOATS_TEXT), dims=((4,), "be [N,C,H,W], got shape"), not_empty="image", contiguous=True)
+    _on_gpu(image, no_gpu_error=True)
     n, c, h, w = image.shape
-    L = _native.lib()
     codes = torch.empty((n, h, w, c), dtype=torch.uint8, device=image.device)
-    with torch.cuda.device(image.device):
-        _native.check(L.cs_decode_to_codes(_ptr(image), _native.LATENT_DTYPE[_LATENT_DTYPES[image.dtype]], n, c, h, w, _ptr(codes),
-                                           _stream()))
+    _launch(image.device, _native.lib().cs_decode_to_codes, _ptr(image), _dtype_code(image, _native.LATENT_DTYPE), n, c, h, w, _ptr(codes))
     return codes
 
 
@@ -785,24 +741,13 @@ def decode_to_codes(image):
 def _flat_like(first, tensors, what):
     """The shared checks of the three wrappers: tensors of first's shape, dtype and device, contiguous, not empty."""
     name0, t0 = first
-    if not isinstance(t0, torch.Tensor):
-        raise ValueError(f"{name0} must be a torch.Tensor")
-    if t0.dtype not in _LATENT_DTYPES:
-        raise ValueError(f"{name0} must be float32, float16 or bfloat16, got {t0.dtype}")
-    if t0.numel() == 0:
-        raise ValueError(f"empty {name0} {tuple(t0.shape)}")
+    # (_tensor checks in the order written: the ladder this wrapper always had)
+    _tensor(name0, t0, dtypes=(_FLOATS, _FLOATS_TEXT), not_empty=name0)
     for name, t in [first] + list(tensors):
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"{name} must be a torch.Tensor")
-        if t.dtype != t0.dtype:
-            raise ValueError(f"{what} must share one dtype, got {t0.dtype} ({name0}) and {t.dtype} ({name})")
-        if tuple(t.shape) != tuple(t0.shape):
-            raise ValueError(f"{name} must have {name0}'s shape {tuple(t0.shape)}, got {tuple(t.shape)}")
-        if not t.is_contiguous():
-            raise ValueError(f"{name} must be contiguous")
-        if t.device != t0.device:
-            raise ValueError(f"{name0} and {name} must be on the same device")
-    return _native.LATENT_DTYPE[_LATENT_DTYPES[t0.dtype]], t0.numel()
+        _tensor(name, t, like=(t0.dtype, f"{what} must share one dtype, got {t0.dtype} ({name0}) and {{got}} ({name})"),
+                shape=(t0.shape, f"have {name0}'s shape {tuple(t0.shape)}, got"), contiguous=True)
+        _same_device(first, (name, t))
+    return _dtype_code(t0, _native.LATENT_DTYPE), t0.numel()
 
 
 def _step_scalars(guidance, coeffs):
@@ -830,14 +775,11 @@ def ddim_step(sample, eps_a, eps_b, guidance, coeffs, out=None):
     dtype, n = _flat_like(("sample", sample), ins, "sample, eps_a, eps_b and out")
     g, c1, c2, c3, c4 = _step_scalars(guidance, coeffs)
     for name, t in [("sample", sample)] + ins:
-        if t.requires_grad:
-            raise ValueError(f"{name} requires grad: cs_ddim_step is not differentiable (detach it, or run under no_grad on detached tensors)")
-    _need_device(sample)
+        _tensor(name, t, no_grad="cs_ddim_step is not differentiable (detach it, or run under no_grad on detached tensors)")
+    _on_gpu(sample, no_gpu_error=True)
     if out is None:
         out = torch.empty_like(sample)
-    with torch.cuda.device(sample.device):
-        _native.check(_native.lib().cs_ddim_step(_ptr(sample), _ptr(eps_a), _ptr(eps_b) if eps_b is not None else None, _ptr(out),
-                                                 dtype, n, g, c1, c2, c3, c4, _stream()))
+    _launch(sample.device, _native.lib().cs_ddim_step, _ptr(sample), _ptr(eps_a), _opt_ptr(eps_b), _ptr(out), dtype, n, g, c1, c2, c3, c4)
     return out
 
 
@@ -849,15 +791,13 @@ def null_loss_grad(eps_uncond, eps_cond, latent_cur, latent_prev, guidance, coef
     dtype, n = _flat_like(("eps_uncond", eps_uncond), [("eps_cond", eps_cond), ("latent_cur", latent_cur), ("latent_prev", latent_prev)],
                           "eps_uncond, eps_cond, latent_cur and latent_prev")
     g, c1, c2, c3, c4 = _step_scalars(guidance, coeffs)
-    _need_device(eps_uncond)
+    _on_gpu(eps_uncond, no_gpu_error=True)
     L = _native.lib()
     rec, grad = torch.empty_like(eps_uncond), torch.empty_like(eps_uncond)
     loss = torch.empty((), dtype=torch.float32, device=eps_uncond.device)
-    nb = L.cs_null_loss_workspace_bytes(n)
-    ws = torch.empty((nb,), dtype=torch.uint8, device=eps_uncond.device) if nb else None
-    with torch.cuda.device(eps_uncond.device):
-        _native.check(L.cs_null_loss_grad(_ptr(eps_uncond), _ptr(eps_cond), _ptr(latent_cur), _ptr(latent_prev), _ptr(rec), _ptr(loss),
-                                          _ptr(grad), dtype, n, g, c1, c2, c3, c4, _ptr(ws) if nb else None, nb, _stream()))
+    ws, nb = _workspace(L.cs_null_loss_workspace_bytes(n), eps_uncond.device)
+    _launch(eps_uncond.device, L.cs_null_loss_grad, _ptr(eps_uncond), _ptr(eps_cond), _ptr(latent_cur), _ptr(latent_prev), _ptr(rec),
+            _ptr(loss), _ptr(grad), dtype, n, g, c1, c2, c3, c4, _ptr(ws) if nb else None, nb)
     return rec, loss, grad
 
 
@@ -895,10 +835,8 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, lr, step, beta1=0.9, beta2=0.999
     if not (math.isfinite(lr) and math.isfinite(eps) and eps >= 0 and 0 <= beta1 < 1 and 0 <= beta2 < 1):
         raise ValueError(f"lr and eps must be finite, eps >= 0 and the betas in [0, 1), got {lr}, {eps}, {beta1}, {beta2}")
     for name, t in (("grad", grad), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
-        if t.requires_grad:
-            raise ValueError(f"{name} requires grad")
-    _need_device(param)
-    with torch.cuda.device(param.device):
-        _native.check(_native.lib().cs_adam_step(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), dtype, n, lr, beta1, beta2,
-                                                 eps, step, _stream()))
+        _tensor(name, t, no_grad="")
+    _on_gpu(param, no_gpu_error=True)
+    _launch(param.device, _native.lib().cs_adam_step, _ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), dtype, n, lr, beta1, beta2,
+            eps, step)
     return param
