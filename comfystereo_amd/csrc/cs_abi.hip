@@ -35,6 +35,14 @@ static int fail_blur(int rc) {
 static std::atomic<int> g_dev[CS_DEBUG_KEYS];
 int dev_switch(int key) { return (key >= 0 && key < CS_DEBUG_KEYS) ? g_dev[key].load(std::memory_order_relaxed) : 0; }
 
+// the classes of techniques, modes and parameters the host code below asks about
+static bool is_poly(int fill) { return fill == CS_FILL_POLYLINES_SOFT || fill == CS_FILL_POLYLINES_SHARP; }
+static bool is_hybrid(int fill) { return fill == CS_FILL_HYBRID_EDGE || fill == CS_FILL_HYBRID_EDGE_PLUS; }
+static bool is_anaglyph(int mode) { return mode == CS_MODE_RED_CYAN_ANAGLYPH || mode == CS_MODE_CYAN_RED_REVERSEANAGLYPH; }
+static bool blur_on(const cs_params* p) { return p->depth_map_blur && p->depth_blur_strength > 0; }   // (<= 0: the reference returns the depth as is, :1194, :1050)
+// gpu_warp: the frames of one reference sub-batch (they share the x255 decision, :1045)
+static int warp_group(const cs_params* p) { return p->batch_size > 0 ? (p->batch_size < p->n ? p->batch_size : p->n) : p->n; }
+
 // ---------------------------------------------------------------------------------------------
 // streaming kernels
 // ---------------------------------------------------------------------------------------------
@@ -351,6 +359,10 @@ static int poly_halo(double div_percent_a, double div_percent_b, double sep_perc
     return (int)ceil(s) + 2;
 }
 
+static int params_halo(const cs_params* p, int w) {   // ... of a cs_generate call on frames of `w` columns
+    return poly_halo(p->divergence * (1 + p->stereo_balance), p->divergence * (1 - p->stereo_balance), p->separation,
+                     p->stereo_offset_exponent, p->convergence_point, w);
+}
 // the per-frame statistics words every workspace starts with
 static size_t stats_bytes(size_t n) { return al256(n * ST_WORDS * 4); }
 // The stats pre-pass: the words of `frames` frames initialised and, with a depth map of `per_frame` values a frame, its min / max in
@@ -406,7 +418,7 @@ static bool poly_tile_takes(int d64, int w, int halo) {
 
 static int run_rows(int fill, RowArgs& A, int halo, uint8_t* rowflag, hipStream_t stream, uint8_t* ana_sbs = nullptr,
                     void* replay_scratch = nullptr, size_t replay_surplus = 0) {
-    const bool poly = fill == CS_FILL_POLYLINES_SOFT || fill == CS_FILL_POLYLINES_SHARP;
+    const bool poly = is_poly(fill);
     const size_t rows = (size_t)A.n * A.h;
     const RowBlock B = row_block(rowflag, rows);
     // anaglyph modes of the tiled polylines path (round 5): BOTH kernels -- the tile kernel and the row kernel over the rows it
@@ -568,7 +580,7 @@ static int max_width_for(int fill, int anaglyph) {
     // (polylines, round 5: the anaglyph modes run both kernels in their side-by-side form and compose afterwards, run_rows above:
     // no anaglyph stash in LDS, the limit of the side-by-side modes.  A call whose halo is too wide for the tile kernels still takes
     // the row kernel's anaglyph form: cs_generate checks that case against `row_form_max_width`)
-    if (fill == CS_FILL_POLYLINES_SOFT || fill == CS_FILL_POLYLINES_SHARP) anaglyph = 0;
+    if (is_poly(fill)) anaglyph = 0;
     if (ana_wide_fill(fill)) anaglyph = 0;   // (round 6: beyond the stash form's width the row kernel runs side by side + composition, run_rows)
     if (fill == CS_FILL_GPU_WARP) return gpuwarp_max_width();   // (the mesh-quality variant, cs_params.flags bit 2: cs_forward_warp_mesh's limit)
     if (fill == CS_FILL_HYBRID_EDGE) return hybrid_max_width();
@@ -577,22 +589,20 @@ static int max_width_for(int fill, int anaglyph) {
 }
 // polylines under the float64 disparity chain keep 8 more bytes per column in LDS (cs_rowwarp.hip Poly::xd)
 static bool dialect_width_ok(int fill, int w, int anaglyph, int d64) {
-    if (!(d64 & 1) || (fill != CS_FILL_POLYLINES_SOFT && fill != CS_FILL_POLYLINES_SHARP && fill != CS_FILL_HYBRID_EDGE && fill != CS_FILL_HYBRID_EDGE_PLUS)) return true;
+    if (!(d64 & 1) || !(is_poly(fill) || is_hybrid(fill))) return true;
     return rowwarp_lds_bytes(fill, w, fill == CS_FILL_HYBRID_EDGE ? 0 : anaglyph) + 8 * (size_t)w + 16 <= CS_LDS_BYTES;
 }
 // The ONE width predicate of cs_generate: nullptr when a frame of `w` columns with p's technique, mode, dialect flags
 // and disparity parameters is accepted, else the reason.  cs_max_width_params searches it, so a caller that pre-validates gets
 // exactly the answer the call itself would give.
 static const char* width_refusal(const cs_params* p, int w) {
-    const bool ana = p->mode == CS_MODE_RED_CYAN_ANAGLYPH || p->mode == CS_MODE_CYAN_RED_REVERSEANAGLYPH;
+    const bool ana = is_anaglyph(p->mode);
     if (w > max_width_for(p->fill, ana) || !dialect_width_ok(p->fill, w, ana, (p->flags >> 3) & 3))
         return "frame too wide for the LDS-resident row kernel";
-    if ((p->fill == CS_FILL_POLYLINES_SOFT || p->fill == CS_FILL_POLYLINES_SHARP) && ana && w > row_form_max_width(p->fill, 1)) {
+    if (is_poly(p->fill) && ana && w > row_form_max_width(p->fill, 1)) {
         // an anaglyph wider than the row kernel's anaglyph form: only through the tile kernels (run_rows' tiled anaglyph path;
         // cs_generate's images are float32)
-        const int halo = poly_halo(p->divergence * (1 + p->stereo_balance), p->divergence * (1 - p->stereo_balance), p->separation,
-                                   p->stereo_offset_exponent, p->convergence_point, w);
-        if (!poly_tile_takes((p->flags >> 3) & 3, w, halo))
+        if (!poly_tile_takes((p->flags >> 3) & 3, w, params_halo(p, w)))
             return "frame too wide for the LDS-resident row kernel (anaglyph form)";
     }
     return nullptr;
@@ -607,9 +617,7 @@ int cs_max_width_params(const cs_params* p) {
     return lo;
 }
 int cs_max_width(int fill) { return max_width_for(fill, 1); }
-int cs_max_width_mode(int fill, int mode) {
-    return max_width_for(fill, mode == CS_MODE_RED_CYAN_ANAGLYPH || mode == CS_MODE_CYAN_RED_REVERSEANAGLYPH);
-}
+int cs_max_width_mode(int fill, int mode) { return max_width_for(fill, is_anaglyph(mode)); }
 
 int cs_output_shape(const cs_params* p, int* out_h, int* out_w, int* mask_h, int* mask_w) {
     if (!p) return fail(CS_EINVAL, "null params");
@@ -646,7 +654,7 @@ static WsLayout ws_layout(const cs_params* p) {
     W.rowflag = o; o += rowflag_bytes(n * (size_t)p->h);
     bool resize = p->depth_h != p->h || p->depth_w != p->w;
     W.gray_src = o; if (resize) o += al256(n * (size_t)p->depth_h * p->depth_w * 4);
-    bool blur = p->depth_map_blur && p->depth_blur_strength > 0;  // strength <= 0: the reference returns the depth as is (:1194)
+    const bool blur = blur_on(p);
     // (the gray buffer sits BETWEEN the blurred maps: the lazy-tile readers address either of a pair with a 32-bit offset)
     W.L = o; if (blur) o += al256(n * hw * 4);
     W.gray = o; o += al256(n * hw * 4);
@@ -654,9 +662,8 @@ static WsLayout ws_layout(const cs_params* p) {
     W.wl = o; if (blur) o += al256(n * hw * 4);
     W.wr = o; if (blur) o += al256(n * hw * 4);
     W.tilemap = o; if (blur) o += al256(blur_tilemap_bytes(p->n, p->h, p->w));
-    const bool poly = p->fill == CS_FILL_POLYLINES_SOFT || p->fill == CS_FILL_POLYLINES_SHARP;
-    const bool ana = p->mode == CS_MODE_RED_CYAN_ANAGLYPH || p->mode == CS_MODE_CYAN_RED_REVERSEANAGLYPH;
-    W.hyb = o; if (p->fill == CS_FILL_HYBRID_EDGE || p->fill == CS_FILL_HYBRID_EDGE_PLUS) o += al256(hybrid_workspace_bytes(p->n, p->h, p->w));
+    const bool poly = is_poly(p->fill), ana = is_anaglyph(p->mode);
+    W.hyb = o; if (is_hybrid(p->fill)) o += al256(hybrid_workspace_bytes(p->n, p->h, p->w));
     W.gpuwarp = o; if (p->fill == CS_FILL_GPU_WARP) o += al256(gpuwarp_workspace_bytes(p->n, p->h, p->w, p->batch_size, p->flags & 4));
     // (the anaglyphs of the polylines techniques, and those of the forward fills too wide for the row kernel's stash form)
     W.has_ana_sbs = (poly && ana) || ana_wide_call(p->fill, ana, p->w);
@@ -683,7 +690,7 @@ struct ChunkPlan { int nch, cf; };
 static ChunkPlan plan_chunks(const cs_params* p) {
     const int n = p->n, forced = dev_switch(CS_DEBUG_CHUNKS) % 100;   // (+100: auxiliary stream at the default priority)
     int unit = 1;
-    if (p->fill == CS_FILL_GPU_WARP) unit = p->batch_size > 0 ? (p->batch_size < n ? p->batch_size : n) : n;
+    if (p->fill == CS_FILL_GPU_WARP) unit = warp_group(p);
     if (forced <= 1 || n < 2 * unit) return ChunkPlan{1, n};
     int cf = (n + forced - 1) / forced;
     cf = (cf + unit - 1) / unit * unit;
@@ -724,6 +731,32 @@ static AuxStream* aux_stream(int low) {
 
 size_t cs_workspace_bytes(const cs_params* p) { return (p && p->n > 0) ? ws_total(p) : 0; }
 
+// Lazy tiles: the tile kernels (cs_polypoint / cs_polytile / cs_fwdtile) read the edge-free tiles of the blurred depth -- a scaled
+// copy of the gray depth -- from the gray depth itself, so the blur leaves them unwritten and hands over the map of the tiles it
+// did write; run_rows completes the rows that still go to a row kernel.  (Round 2 measured the selector in k_gpuwarp and in the
+// hybrid splat as dearer than the copy; with both kernels restructured at the end of round 3 -- loads first, four workgroups per
+// CU -- it is cheaper.)  This call's warp reads the map:
+static bool lazy_tiles_wanted(const cs_params* p, int halo) {
+    const int fill = p->fill, w = p->w, d64 = (p->flags >> 3) & 3;
+    const bool tile_fill = is_poly(fill) || fill == CS_FILL_NONE || fill == CS_FILL_INVERSE || fill == CS_FILL_NAIVE || fill == CS_FILL_NAIVE_INTERPOLATING;
+    // gpu_warp (scatter-round warp, rows of at most 4096 columns) reads the map too since the end of round 3: the kernel is
+    // bound by its dependent chains, not by its instruction count -- the selector costs less than the copy of the tiles
+    const bool warp_lazy = fill == CS_FILL_GPU_WARP && !(p->flags & 4) && w <= gpuwarp_lazy_max_width() && !dev_switch(CS_DEBUG_GPUWARP_FULL_MAPS);
+    // hybrid_edge through the fused splat tile kernel (two-eye layouts): the same; the disabled-eye path and the unfused
+    // forms read complete maps, so the map is only used when both eyes run
+    const bool two_eyes = !(p->divergence * (1 + p->stereo_balance) < 0.001) && !(p->divergence * (1 - p->stereo_balance) < 0.001);
+    const bool hyb_lazy = fill == CS_FILL_HYBRID_EDGE && two_eyes && !dev_switch(CS_DEBUG_HYBRID_FULL_MAPS) &&
+                          hybrid_fused_ok(p->n, w, halo, is_anaglyph(p->mode), -1, d64, 0);
+    // (round 6: the polylines techniques under a dialect flag too -- the point kernel's dialect instantiations share the tile function,
+    // lazy loads included, and run_rows completes the rows of any call a row kernel ends up taking; the other techniques' dialect
+    // kernels keep complete maps: 0.94 of 17.1 ms per 64 frames under D64, profiles/r06_s39/)
+    const bool dialect_lazy = d64 == 0 || (is_poly(fill) && poly_tile_takes(d64, w, halo));
+    // (single-eye modes read complete maps; the readers address either blurred map from the gray depth between them with a
+    // 32-bit offset: ws_layout)
+    return (tile_fill || warp_lazy || hyb_lazy) && dialect_lazy && !dev_switch(CS_DEBUG_NO_TILE) && !dev_switch(CS_DEBUG_BLUR_FULL_COPY) &&
+           p->mode != CS_MODE_LEFT_ONLY && p->mode != CS_MODE_ONLY_RIGHT && al256((size_t)p->n * p->h * w * 4) < (1ull << 32) - (1u << 20);
+}
+
 // One chunk of frames: the pre-pass on `sp`, the warp on `stream` (the same stream, or `ready` recorded on sp and awaited
 // by stream in between).  `stats`: the chunk's slice of the call's statistics words; `ws`: the chunk's scratch (ws_layout).
 static int generate_chunk(const cs_params* p, const float* image, const float* depth, float* stereo, float* depth_l,
@@ -732,68 +765,39 @@ static int generate_chunk(const cs_params* p, const float* image, const float* d
     int rc;
     const WsLayout W = ws_layout(p);
     float* gray = (float*)(ws + W.gray);
+    uint32_t* const tilemap = (uint32_t*)(ws + W.tilemap);
     const int n = p->n, h = p->h, w = p->w, hw = h * w;
-    const bool gpu_warp = p->fill == CS_FILL_GPU_WARP;
-    const bool blur = p->depth_map_blur && p->depth_blur_strength > 0;  // strength <= 0 == blur off (reference :1194, :1050)
-
-    stats_prepass(stats, n, nullptr, 0, sp);   // (the gray conversion below fills the words)
+    const bool gpu_warp = p->fill == CS_FILL_GPU_WARP, blur = blur_on(p);
     const bool resize = p->depth_h != h || p->depth_w != w;
-    // RGB depth + blur: the gray conversion also builds the blur's edge bit rows (one pass over the depth input)
+    const int halo = params_halo(p, w);
+    // the blur's plan, made once.  The reference's callers pass the strength as the mask width too (:1051, :1479).  An RGB depth
+    // map at the frames' size: the gray conversion can build the blur's edge bit rows as well (one pass over the depth input)
+    const BlurParams prm = {p->depth_blur_strength, p->depth_blur_edge_threshold, p->depth_blur_strength, p->depth_blur_falloff,
+                            p->depth_blur_vert_smooth};
     const bool blur_map = !dev_switch(CS_DEBUG_BLUR_FULL_COPY);
-    const bool pre_edges = blur && !resize && p->depth_c == 3 &&
-                           blur_pre_edges_ok(n, h, w, p->depth_blur_strength, p->depth_blur_edge_threshold, p->depth_blur_strength,
-                                             p->depth_blur_vert_smooth, blur_map);
+    const BlurPlan B = blur ? blur_plan(prm, n, h, w, (float*)(ws + W.wl), (float*)(ws + W.wr), blur_map, true, !resize && p->depth_c == 3)
+                            : BlurPlan{};
+    // gray depth and its statistics
+    stats_prepass(stats, n, nullptr, 0, sp);   // (the gray conversion below fills the words)
     if (resize) {
         float* gs = (float*)(ws + W.gray_src);
         int shw = p->depth_h * p->depth_w;
         hipLaunchKernelGGL(k_gray, dim3(grid_for(shw / 32 + 1, 256), n), dim3(256), 0, sp, depth, gs, shw, p->depth_c, stats, 0);
         hipLaunchKernelGGL(k_resize_bilinear, dim3(grid_for(hw, 256), n), dim3(256), 0, sp, gs, p->depth_h, p->depth_w, gray, h, w, stats);
-    } else if (pre_edges) {
-        hipError_t e = launch_gray_edges(depth, gray, n, h, w, stats, p->depth_blur_strength, p->depth_blur_edge_threshold,
-                                         p->depth_blur_strength, p->depth_blur_vert_smooth, (float*)(ws + W.wl), (float*)(ws + W.wr), sp);
+    } else if (B.pre_edges) {
+        hipError_t e = launch_gray_edges(B, depth, gray, stats, sp);
         if (e != hipSuccess) return fail_hip(e, "gray + edge pass");
     } else {
         // (>= 8 float4 groups per thread: the per-workgroup min/max reduction is amortised -- 3x faster at 1080p)
         hipLaunchKernelGGL(k_gray, dim3(grid_for(hw / 32 + 1, 256), n), dim3(256), 0, sp, depth, gray, hw, p->depth_c, stats, 1);
     }
-    hipLaunchKernelGGL(k_finalize_stats, dim3((n + 63) / 64), dim3(64), 0, sp, stats, n,
-                       gpu_warp ? (p->batch_size > 0 ? (p->batch_size < n ? p->batch_size : n) : n) : 0, blur ? 1 : 0);
-    const float* dL = gray;
-    const float* dR = gray;
+    hipLaunchKernelGGL(k_finalize_stats, dim3((n + 63) / 64), dim3(64), 0, sp, stats, n, gpu_warp ? warp_group(p) : 0, blur ? 1 : 0);
+    // depth blur
+    const float *dL = gray, *dR = gray;
     int scale_from_stats = 1, lazy = 0;
-    const int halo = poly_halo(p->divergence * (1 + p->stereo_balance), p->divergence * (1 - p->stereo_balance), p->separation,
-                               p->stereo_offset_exponent, p->convergence_point, w);
     if (blur) {
-        float* L = (float*)(ws + W.L);
-        float* R = (float*)(ws + W.R);
-        // lazy tiles: the tile kernels (cs_polypoint / cs_polytile / cs_fwdtile) read the edge-free tiles of the blurred depth
-        // -- a scaled copy of the gray depth -- from the gray depth itself, so the blur leaves them unwritten and hands over
-        // the map of the tiles it did write; run_rows completes the rows that still go to a row kernel.  (Round 2 measured the
-        // selector in k_gpuwarp and in the hybrid splat as dearer than the copy; with both kernels restructured at the end of
-        // round 3 -- loads first, four workgroups per CU -- it is cheaper: see warp_lazy / hyb_lazy below.)
-        const bool tile_fill = p->fill == CS_FILL_POLYLINES_SOFT || p->fill == CS_FILL_POLYLINES_SHARP || p->fill == CS_FILL_NONE ||
-                               p->fill == CS_FILL_INVERSE || p->fill == CS_FILL_NAIVE || p->fill == CS_FILL_NAIVE_INTERPOLATING;
-        // gpu_warp (scatter-round warp, rows of at most 4096 columns) reads the map too since the end of round 3: the kernel is
-        // bound by its dependent chains, not by its instruction count -- the selector costs less than the copy of the tiles
-        const bool warp_lazy = gpu_warp && !(p->flags & 4) && w <= gpuwarp_lazy_max_width() && !dev_switch(CS_DEBUG_GPUWARP_FULL_MAPS);
-        // hybrid_edge through the fused splat tile kernel (two-eye layouts): the same; the disabled-eye path and the unfused
-        // forms read complete maps, so the map is only used when both eyes run
-        const bool two_eyes = !(p->divergence * (1 + p->stereo_balance) < 0.001) && !(p->divergence * (1 - p->stereo_balance) < 0.001);
-        const bool ana = p->mode == CS_MODE_RED_CYAN_ANAGLYPH || p->mode == CS_MODE_CYAN_RED_REVERSEANAGLYPH;
-        const bool hyb_lazy = p->fill == CS_FILL_HYBRID_EDGE && two_eyes && !dev_switch(CS_DEBUG_HYBRID_FULL_MAPS) &&
-                              hybrid_fused_ok(n, w, halo, ana, -1, (p->flags >> 3) & 3, 0);
-        // (round 6: the polylines techniques under a dialect flag too -- the point kernel's dialect instantiations share the tile function,
-        // lazy loads included, and run_rows completes the rows of any call a row kernel ends up taking; the other techniques' dialect
-        // kernels keep complete maps: 0.94 of 17.1 ms per 64 frames under D64, profiles/r06_s39/)
-        const int d64f = (p->flags >> 3) & 3;
-        const bool poly_fill = p->fill == CS_FILL_POLYLINES_SOFT || p->fill == CS_FILL_POLYLINES_SHARP;
-        const bool dialect_lazy = d64f == 0 || (poly_fill && poly_tile_takes(d64f, w, halo));
-        const bool want_lazy = (tile_fill || warp_lazy || hyb_lazy) && dialect_lazy && !dev_switch(CS_DEBUG_NO_TILE) && !dev_switch(CS_DEBUG_BLUR_FULL_COPY) &&
-                               p->mode != CS_MODE_LEFT_ONLY && p->mode != CS_MODE_ONLY_RIGHT &&
-                               al256((size_t)n * hw * 4) < (1ull << 32) - (1u << 20);
-        rc = launch_blur(gray, n, h, w, p->depth_blur_strength, p->depth_blur_edge_threshold, p->depth_blur_strength, p->depth_blur_falloff,
-                         p->depth_blur_vert_smooth, L, R, (float*)(ws + W.wl), (float*)(ws + W.wr), stats, 1, sp,
-                         blur_map ? (uint32_t*)(ws + W.tilemap) : nullptr, want_lazy ? &lazy : nullptr, pre_edges ? 1 : 0);
+        float *L = (float*)(ws + W.L), *R = (float*)(ws + W.R);
+        rc = launch_blur(B, gray, L, R, stats, sp, blur_map ? tilemap : nullptr, lazy_tiles_wanted(p, halo) ? &lazy : nullptr);
         if (rc) return fail_blur(rc);
         dL = L; dR = R;
         scale_from_stats = 0;  // the blur kernel already wrote scaled depth
@@ -801,25 +805,23 @@ static int generate_chunk(const cs_params* p, const float* image, const float* d
             std::lock_guard<std::mutex> lock(g_prof_mu);
             if (g_prof_tiles) {
                 const int words = blur_tilemap_words(w), rows = (int)(blur_tilemap_bytes(n, h, w) / ((size_t)words * 4));
-                hipLaunchKernelGGL(k_prof_count_tiles, dim3((rows * words + 255) / 256), dim3(256), 0, sp, (const uint32_t*)(ws + W.tilemap),
+                hipLaunchKernelGGL(k_prof_count_tiles, dim3((rows * words + 255) / 256), dim3(256), 0, sp, (const uint32_t*)tilemap,
                                    rows, words, (w + 63) / 64, g_prof_tiles);
                 g_prof_tiles_any = true; g_prof_tiles_stream = sp;
             }
         }
     }
-    const double left_div = p->divergence * (1 + p->stereo_balance);
-    const double right_div = p->divergence * (1 - p->stereo_balance);
-
+    // hand-over
     if (sp != stream) {   // the warp of this chunk waits for its pre-pass; the next chunk's pre-pass runs under it
         hipError_t e = hipEventRecord(ready, sp);
         if (e == hipSuccess) e = hipStreamWaitEvent(stream, ready, 0);
         if (e != hipSuccess) return fail_hip(e, "chunk hand-over");
     }
+    // warp
     ProfScope prof(stream);
     if (gpu_warp) {
         rc = launch_gpuwarp_node(p, image, dL, dR, scale_from_stats, stats, stereo, depth_l, depth_r, mask, out_h, out_w,
-                                 ws + W.gpuwarp, stream, lazy ? (const uint32_t*)(ws + W.tilemap) : nullptr, lazy ? gray : nullptr,
-                                 lazy ? blur_tilemap_words(w) : 0);
+                                 ws + W.gpuwarp, stream, lazy ? tilemap : nullptr, lazy ? gray : nullptr, lazy ? blur_tilemap_words(w) : 0);
         if (rc) return fail(rc, "gpu_warp launch failed");
         hipError_t e = hipGetLastError();
         return e == hipSuccess ? CS_OK : fail_hip(e, "cs_generate");
@@ -836,6 +838,7 @@ static int generate_chunk(const cs_params* p, const float* image, const float* d
     A.e64 = p->stereo_offset_exponent;
     A.d64 = (p->flags >> 3) & 3;
     A.neyes = 2;
+    const double left_div = p->divergence * (1 + p->stereo_balance), right_div = p->divergence * (1 - p->stereo_balance);
     eye_setup(A.eye[0], +1 * left_div, -1 * p->separation, w);
     eye_setup(A.eye[1], -1 * right_div, p->separation, w);
     A.eye[0].enabled = !(left_div < 0.001);
@@ -847,7 +850,7 @@ static int generate_chunk(const cs_params* p, const float* image, const float* d
     A.out_h = out_h; A.out_w = out_w;
     A.single = -1;
     A.dbg = dev_switch(CS_DEBUG_DBG);
-    if (lazy) { A.tilemap = (const uint32_t*)(ws + W.tilemap); A.lazy_gray = gray; A.tm_words = blur_tilemap_words(w); }
+    if (lazy) { A.tilemap = tilemap; A.lazy_gray = gray; A.tm_words = blur_tilemap_words(w); }
     switch (p->mode) {
     case CS_MODE_LEFT_RIGHT: A.eye[1].xoff = w; break;
     case CS_MODE_RIGHT_LEFT: A.eye[0].xoff = w; break;
@@ -858,7 +861,7 @@ static int generate_chunk(const cs_params* p, const float* image, const float* d
     case CS_MODE_LEFT_ONLY: A.single = 0; break;
     case CS_MODE_ONLY_RIGHT: A.single = 1; break;
     }
-    if (p->fill == CS_FILL_HYBRID_EDGE || p->fill == CS_FILL_HYBRID_EDGE_PLUS) {
+    if (is_hybrid(p->fill)) {
         rc = launch_hybrid(A, ws + W.hyb, stream, p->fill == CS_FILL_HYBRID_EDGE_PLUS, halo);
         if (rc) return fail(rc, "hybrid_edge launch failed");
     } else {
@@ -945,8 +948,8 @@ static AsdLayout asd_layout(int n, int h, int w, int fill) {
     W.rowflag = stats_bytes(n);
     W.tech = W.rowflag + rowflag_bytes((size_t)n * h);
     W.total = W.tech;
-    if (fill == CS_FILL_HYBRID_EDGE || fill == CS_FILL_HYBRID_EDGE_PLUS) W.total += al256(hybrid_workspace_bytes(n, h, w));
-    if (fill == CS_FILL_POLYLINES_SOFT || fill == CS_FILL_POLYLINES_SHARP) W.total += al256(poly_replay_bytes(n, h, w, fill == CS_FILL_POLYLINES_SHARP));
+    if (is_hybrid(fill)) W.total += al256(hybrid_workspace_bytes(n, h, w));
+    if (is_poly(fill)) W.total += al256(poly_replay_bytes(n, h, w, fill == CS_FILL_POLYLINES_SHARP));
     return W;
 }
 size_t cs_asd_workspace_bytes_for(int n, int h, int w, int fill) { return asd_layout(n, h, w, fill).total; }
@@ -994,13 +997,12 @@ int cs_apply_stereo_divergence2(const uint8_t* image_u8, const float* depth, int
     A.out_u8 = out_u8;
     A.single = -1;
     A.dbg = dev_switch(CS_DEBUG_DBG);
-    if (fill == CS_FILL_HYBRID_EDGE || fill == CS_FILL_HYBRID_EDGE_PLUS) {
+    if (is_hybrid(fill)) {
         int rc = launch_hybrid(A, ws + W.tech, stream, fill == CS_FILL_HYBRID_EDGE_PLUS);
         if (rc) return fail(rc, "hybrid_edge launch failed");
     } else {
         int halo = poly_halo(divergence, divergence, separation, exponent, convergence, w);
-        const bool poly = fill == CS_FILL_POLYLINES_SOFT || fill == CS_FILL_POLYLINES_SHARP;   // (the others have no replay scratch)
-        int rc = run_rows(fill, A, halo, (uint8_t*)(ws + W.rowflag), stream, nullptr, poly ? ws + W.tech : nullptr);
+        int rc = run_rows(fill, A, halo, (uint8_t*)(ws + W.rowflag), stream, nullptr, is_poly(fill) ? ws + W.tech : nullptr);   // (the others have no replay scratch)
         if (rc) return rc;
     }
     hipError_t e = hipGetLastError();
@@ -1027,8 +1029,8 @@ int cs_directional_blur(const float* depth, int n, int h, int w, double blur_str
     float* wl = (float*)(ws + stats_bytes(n));
     float* wr = wl + al256(n * hw * 4) / 4;
     stats_prepass(stats, n, nullptr, 0, stream);   // (launch_blur accumulates the outputs' min / max)
-    int rc = launch_blur(depth, n, h, w, blur_strength, edge_threshold, blur_mask_width, falloff_exponent, vert_smooth_px, out_l, out_r, wl,
-                         wr, stats, 0, stream);
+    const BlurParams prm = {blur_strength, edge_threshold, blur_mask_width, falloff_exponent, vert_smooth_px};
+    int rc = launch_blur(blur_plan(prm, n, h, w, wl, wr, false, false, false), depth, out_l, out_r, stats, stream);
     if (rc) return fail_blur(rc);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_directional_blur");

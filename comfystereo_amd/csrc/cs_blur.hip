@@ -122,8 +122,6 @@ __global__ void __launch_bounds__(1024) k_blur_weights(BlurArgs A) {
 #else
 #define BLUR_DEV_IS(n) false
 #endif
-#define BLUR_TW 64
-#define BLUR_TR 32
 __global__ void __launch_bounds__(256) k_blur_apply(BlurArgs A) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
@@ -246,7 +244,6 @@ __global__ void __launch_bounds__(256) k_blur_edges(BlurArgs A, unsigned long lo
 // row (8x fewer load instructions -- the scalar version is bound by the L1 request rate, not by HBM); the two missing
 // neighbours come from the adjacent lanes (shuffles; the first / last lane of a wave loads them).  A lane's four edge bits
 // form a nibble, eight lanes' nibbles a 32-bit half word (OR over xor-shuffles), two halves a word of the bit row.
-#define BLUR_ER4 4  // image rows per thread (8: 0.66 ms, 16: 0.85, 2: 0.71 -- the halo rows come from L2; fewer registers, more waves)
 // cross-lane moves as DPP modifiers (2-4 cycles each) instead of ds_bpermute round trips through the LDS crossbar (the
 // kernel was bound by those: 80 per thread).  Lanes without a source keep their own value.
 template <int CTRL>
@@ -831,7 +828,7 @@ __global__ void __launch_bounds__(256, 4) k_blur_fused(BlurArgs A, const unsigne
         auto load_q = [&](int q) -> float4 { return load_qf(d, scale, x0, y0, q); };
         const unsigned long long lastmask = (EW & 63) ? (~0ull >> (64 - (EW & 63))) : ~0ull;
         // (FAST) every global input of tile (fx0, fy0, fframe) into registers, RAW: nothing here consumes a loaded value, so no wait
-        // is placed before the phases that follow (NQ <= 32 and WR * NW <= 256: launch_blur checks).  Clamped, always valid addresses.
+        // is placed before the phases that follow (NQ <= 32 and WR * NW <= 256: blur_fast_ok).  Clamped, always valid addresses.
         auto fscale_of = [&](int fframe) -> float { return (scale_bits[fframe >> 5] >> (fframe & 31)) & 1u ? 255.0f : 1.0f; };
         auto fetch = [&](int fx0, int fy0, int fframe, BlurPre& Q) {
             const float* fd = A.depth + (size_t)fframe * h * w;
@@ -1260,42 +1257,13 @@ __global__ void __launch_bounds__(256) k_blur_copy_tiles(BlurArgs A, const uint3
 }
 
 static size_t blur_fused_lds(int v, int R, int bs) {
-    int WR = BLUR_TR + 2 * v, EW = BLUR_TW + 2 * R, NW = (EW + 63) >> 6;
-    (void)EW;
+    const int WR = BLUR_TR + 2 * v, NW = (BLUR_TW + 2 * R + 63) >> 6;
     return 32 + (size_t)(BLUR_TR * (((BLUR_TW + bs - 1 + 3) & ~3) + 4)) * 4 + 2 * (size_t)WR * BLUR_TW * 4 + 2 * (size_t)WR * NW * 8 +
            sizeof(csm::PowfTables) + 64 + 4 * (size_t)(R + 2);
 }
 
-// The geometry launch_blur and launch_gray_edges share: which path the parameters take and where the bit rows, the worklist
-// and the block summaries lie inside the two weight scratch buffers (each n * h * w floats).
-struct BlurPlan {
-    bool fused, listed, lazy;
-    int MW, HB, gx, gy;
-    size_t plane_bytes, mask_bytes, list_bytes, blk_bytes;
-};
-static BlurPlan blur_plan(int n, int h, int w, double strength, double mask_width, int vert, bool tilemap, bool node_path, int planes) {
-    BlurPlan P;
-    const int bs = (int)nearbyint(strength), radius = (int)mask_width, v = vert > 0 ? vert : 0;
-    P.fused = bs >= 1 && blur_fused_lds(v, radius, bs) <= 64 * 1024 && radius >= 1 && !dev_switch(CS_DEBUG_BLUR_TWO_PASS);
-    P.MW = (w + 63) / 64;
-    P.gy = (h + BLUR_TR - 1) / BLUR_TR; P.gx = (w + BLUR_TW - 1) / BLUR_TW; P.HB = (h + BLUR_ER4 - 1) / BLUR_ER4;
-    P.plane_bytes = ((size_t)n * h * P.MW * 8 + 255) & ~(size_t)255;
-    P.mask_bytes = P.plane_bytes * planes;
-    {   // counter, worklist (4 B per tile, the extremes behind it start on a 16-byte boundary: launch_blur), 4 x float4 of output
-        // extremes per entry
-        const size_t total = (size_t)n * P.gy * P.gx;
-        P.list_bytes = 256 + ((total * 4 + 15) & ~(size_t)15) + total * 64;
-    }
-    P.blk_bytes = (size_t)n * P.HB * P.MW * 16;
-    P.listed = P.fused && (w & 3) == 0 && P.gx < 1024 && P.gy < 1024 && n < 4096 && P.mask_bytes + P.list_bytes <= (size_t)n * h * w * 4;
-    // lazy mode: block summaries behind the second bit-row buffer
-    P.lazy = tilemap && node_path && P.listed && !dev_switch(CS_DEBUG_BLUR_EDGES_SCALAR) && BLUR_TR % BLUR_ER4 == 0 &&
-             P.mask_bytes + P.blk_bytes <= (size_t)n * h * w * 4;
-    return P;
-}
-
 // the largest float t >= 0 with fl(t / den) <= 0.5 (k_gray_edges); < 0: no such value (den not positive and finite)
-static float blur_edge_threshold(float den) {
+float blur_edge_threshold_host(float den) {   // (cs_test_edge_threshold)
     if (!(den > 0.0f) || !std::isfinite(den)) return -1.0f;
     volatile float d = den;
     float t = 0.5f * den;
@@ -1307,104 +1275,57 @@ static float blur_edge_threshold(float den) {
     return t;
 }
 
-float blur_edge_threshold_host(float den) { return blur_edge_threshold(den); }   // (cs_test_edge_threshold)
-
-bool blur_pre_edges_ok(int n, int h, int w, double strength, double edge_threshold, double mask_width, int vert, bool tilemap) {
-    if (dev_switch(CS_DEBUG_BLUR_NO_PRE_EDGES)) return false;
-    const BlurPlan P = blur_plan(n, h, w, strength, mask_width, vert, tilemap, true, 2);
-    return P.lazy && (w & 3) == 0 && blur_edge_threshold((float)(10.0 * edge_threshold)) >= 0.0f;
+BlurPlan blur_plan(const BlurParams& prm, int n, int h, int w, float* wl, float* wr, bool tilemap, bool node_path, bool rgb_depth) {
+    BlurPlan P;
+    P.prm = prm; P.n = n; P.h = h; P.w = w; P.node_path = node_path;
+    // the reference's integers: box width round(strength) (Python round(): half to even), mask_radius = int(blur_mask_width) (:1209)
+    P.bs = (int)nearbyint(prm.strength); P.radius = (int)prm.mask_width; P.vert = prm.vert > 0 ? prm.vert : 0;
+    P.edge_thr = blur_edge_threshold_host((float)(10.0 * prm.edge_threshold));
+    const bool lds_ok = P.bs >= 1 && P.radius >= 1 && blur_fused_lds(P.vert, P.radius, P.bs) <= 64 * 1024 && !dev_switch(CS_DEBUG_BLUR_TWO_PASS);
+    auto choose = [&](int planes) {
+        P.S = blur_scratch(wl, wr, n, h, w, planes);
+        const BlurScratch& S = P.S;
+        P.fused = lds_ok && S.fits_fused;
+        P.listed = P.fused && (w & 3) == 0 && S.fits_listed;
+        P.lazy = tilemap && node_path && P.listed && !dev_switch(CS_DEBUG_BLUR_EDGES_SCALAR) && BLUR_TR % BLUR_ER4 == 0 && S.fits_lazy;
+    };
+    // the two-plane bit rows of the one-pass gray conversion have one consumer, the lazy form (k_gray_edges: float4 columns,
+    // the edge test as a comparison with a host-side threshold)
+    choose(2);
+    P.pre_edges = rgb_depth && P.lazy && (w & 3) == 0 && !dev_switch(CS_DEBUG_BLUR_NO_PRE_EDGES) && P.edge_thr >= 0.0f;
+    if (!P.pre_edges) choose(1);
+    return P;
 }
 
-hipError_t launch_gray_edges(const float* rgb, float* gray, int n, int h, int w, uint32_t* stats, double strength,
-                             double edge_threshold, double mask_width, int vert, float* wl, float* wr, hipStream_t stream) {
-    const BlurPlan P = blur_plan(n, h, w, strength, mask_width, vert, true, true, 2);
-    hipLaunchKernelGGL(k_gray_edges, dim3((w + 255) / 256, (h + GE_RB - 1) / GE_RB, n), dim3(64), 0, stream, rgb, gray, h, w, stats,
-                       blur_edge_threshold((float)(10.0 * edge_threshold)), reinterpret_cast<unsigned long long*>(wl),
-                       reinterpret_cast<unsigned long long*>(wr), P.plane_bytes / 8, P.MW,
-                       reinterpret_cast<float4*>(reinterpret_cast<char*>(wr) + P.mask_bytes), P.HB);
+hipError_t launch_gray_edges(const BlurPlan& P, const float* rgb, float* gray, uint32_t* stats, hipStream_t stream) {
+    if (!P.pre_edges) return hipErrorInvalidValue;
+    const BlurScratch& S = P.S;
+    hipLaunchKernelGGL(k_gray_edges, dim3((P.w + 255) / 256, (P.h + GE_RB - 1) / GE_RB, P.n), dim3(64), 0, stream, rgb, gray, P.h, P.w, stats,
+                       P.edge_thr, S.bits_l, S.bits_r, S.plane_words, S.MW, S.block_summaries, S.HB);
     return hipGetLastError();
 }
 
-int launch_blur(const float* depth, int n, int h, int w, double strength, double edge_threshold, double mask_width,
-                double falloff, int vert, float* out_l, float* out_r, float* wl, float* wr, uint32_t* stats, int node_path,
-                hipStream_t stream, uint32_t* tilemap, int* lazy_used, int pre_edges) {
-    // (lazy_used == nullptr with a tile map: the caller wants COMPLETE maps; the map is then only the classification's output)
-    const bool want_lazy = lazy_used != nullptr;
-    if (lazy_used) *lazy_used = 0;
-    BlurArgs A;
-    A.depth = depth; A.n = n; A.h = h; A.w = w;
-    A.stats = node_path ? stats : nullptr;
-    A.stats_rw = node_path ? stats : nullptr;
-    A.den = (float)(10.0 * edge_threshold);
-    A.bs = (int)nearbyint(strength);  // Python round(): half to even
-    A.radius = (int)mask_width;  // mask_radius = int(blur_mask_width), reference :1209
-    A.vert = vert > 0 ? vert : 0;
-    if (A.bs < 1) return CS_EINVAL;  // torch raises on a zero-width kernel
-    A.fall32 = (float)falloff;
-    A.fall_mode = falloff == 1.0 ? 0 : falloff == 0.5 ? 1 : falloff == 2.0 ? 2 : falloff == 3.0 ? 3 : falloff == 0.0 ? 5 : 4;
-    A.wl = wl; A.wr = wr; A.out_l = out_l; A.out_r = out_r;
-    A.dbg = dev_switch(CS_DEBUG_DBG);
-    A.mask_plane = 0;
-    const BlurPlan P = blur_plan(n, h, w, strength, mask_width, A.vert, tilemap != nullptr, node_path != 0, pre_edges ? 2 : 1);
-    if (pre_edges && !P.lazy) return CS_EINVAL;   // (the caller asked blur_pre_edges_ok)
-    size_t ldsF = blur_fused_lds(A.vert, A.radius, A.bs);
-    if (P.fused) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_blur_fused<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsF);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_blur_fused<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsF);
-        if (e != hipSuccess) return CS_EHIP;
-        // the weight scratch buffers double as the frame-wide edge bit rows (2 x ceil(w/64) words per image row)
-        const int MW = P.MW;
-        unsigned long long* mask_l = reinterpret_cast<unsigned long long*>(wl);
-        unsigned long long* mask_r = reinterpret_cast<unsigned long long*>(wr);
-        // edge-free tiles are copied by k_blur_copy; the others reach k_blur_fused through a worklist behind the bit rows
-        const int gy = P.gy, gx = P.gx, HB = P.HB;
-        const size_t mask_bytes = P.mask_bytes;
-        const bool listed = P.listed, lazy = P.lazy;
-        float4* blk = lazy ? reinterpret_cast<float4*>(reinterpret_cast<char*>(wr) + mask_bytes) : nullptr;
-        if (pre_edges) A.mask_plane = P.plane_bytes / 8;   // (k_gray_edges wrote the bit rows and the summaries)
-        else if ((w & 3) == 0 && !dev_switch(CS_DEBUG_BLUR_EDGES_SCALAR))
-            hipLaunchKernelGGL(k_blur_edges4, dim3((w + 1023) / 1024, HB, n), dim3(256), 0, stream, A, mask_l, mask_r, MW, blk);
-        else
-            hipLaunchKernelGGL(k_blur_edges, dim3((w + 255) / 256, (h + BLUR_ER - 1) / BLUR_ER, n), dim3(256), 0, stream, A, mask_l, mask_r, MW);
-        if (listed) {
-            uint32_t* work_count = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(wl) + mask_bytes);
-            uint32_t* worklist = work_count + 64;
-            if (hipMemsetAsync(work_count, 0, 4, stream) != hipSuccess) return CS_EHIP;
-            if (lazy) {
-                if (hipMemsetAsync(tilemap, 0, blur_tilemap_bytes(n, h, w), stream) != hipSuccess) return CS_EHIP;
-                hipLaunchKernelGGL(k_blur_classify, dim3((gx * gy + 255) / 256, n), dim3(256), 0, stream, A,
-                                   (const unsigned long long*)mask_l, (const unsigned long long*)mask_r, MW, (const float4*)blk, HB,
-                                   work_count, worklist, tilemap, blur_tilemap_words(w));
-                if (want_lazy) *lazy_used = 1;
-                else hipLaunchKernelGGL(k_blur_copy_tiles, dim3((gx + BLUR_CW - 1) / BLUR_CW, gy, n), dim3(256), 0, stream, A,
-                                        (const uint32_t*)tilemap, blur_tilemap_words(w));
-            } else {
-                hipLaunchKernelGGL(k_blur_copy, dim3((gx + BLUR_CW - 1) / BLUR_CW, gy, n), dim3(256), 0, stream, A,
-                                   (const unsigned long long*)mask_l, (const unsigned long long*)mask_r, MW, work_count, worklist);
-            }
-            const size_t total = (size_t)n * gy * gx;
-            const int pg = (int)(total < 2048 ? total : 2048);
-            float4* tstat = A.stats_rw ? reinterpret_cast<float4*>(reinterpret_cast<char*>(worklist) + ((total * 4 + 15) & ~(size_t)15)) : nullptr;
-            // (one float4 chunk per lane: box widths up to 100 columns; one bit-row item per lane: vertical smoothing up to 48 rows)
-            const int pad4 = (A.bs / 2 + 3) & ~3;
-            const bool fast = (w & 3) == 0 && (reinterpret_cast<uintptr_t>(depth) & 15) == 0 && A.radius >= 1 && A.radius <= 31 &&
-                              ((pad4 + BLUR_TW + (A.bs - 1 - A.bs / 2) + 3) >> 2) <= 32 && (BLUR_TR + 2 * A.vert) * 2 <= 256 &&
-                              !dev_switch(CS_DEBUG_BLUR_EDGES_SCALAR);
-            if (fast)
-                hipLaunchKernelGGL(k_blur_fused<true>, dim3(pg), dim3(256), ldsF, stream, A, (const unsigned long long*)mask_l,
-                                   (const unsigned long long*)mask_r, MW, (const uint32_t*)work_count, (const uint32_t*)worklist, tstat);
-            else
-                hipLaunchKernelGGL(k_blur_fused<false>, dim3(pg), dim3(256), ldsF, stream, A, (const unsigned long long*)mask_l,
-                                   (const unsigned long long*)mask_r, MW, (const uint32_t*)work_count, (const uint32_t*)worklist, tstat);
-            if (tstat)
-                hipLaunchKernelGGL(k_blur_tile_stats, dim3(4, n), dim3(256), 0, stream, (const uint32_t*)work_count,
-                                   (const uint32_t*)worklist, (const float4*)tstat, A.stats_rw);
-        } else {
-            hipLaunchKernelGGL(k_blur_fused<false>, dim3(gx, gy, n), dim3(256), ldsF, stream, A, (const unsigned long long*)mask_l,
-                               (const unsigned long long*)mask_r, MW, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (float4*)nullptr);
-        }
-        return CS_OK;
-    }
+// k_blur_fused<true> fetches a tile's global inputs with one float4 chunk of the depth rows and one bit-row window item per
+// lane, from a worklist: NQ <= 32 chunks per tile row (box widths up to 100 columns), two words per bit-row window (mask radius
+// 1 .. 31) and WR * 2 <= 256 items (vertical smoothing up to 48 rows), float4 columns of a 16-byte aligned depth map
+static bool blur_fast_ok(const BlurArgs& A) {
+    const int pad4 = (A.bs / 2 + 3) & ~3;
+    return (A.w & 3) == 0 && (reinterpret_cast<uintptr_t>(A.depth) & 15) == 0 && A.radius >= 1 && A.radius <= 31 &&
+           ((pad4 + BLUR_TW + (A.bs - 1 - A.bs / 2) + 3) >> 2) <= 32 && (BLUR_TR + 2 * A.vert) * 2 <= 256 &&
+           !dev_switch(CS_DEBUG_BLUR_EDGES_SCALAR);
+}
+// k_blur_fused over the worklist (persistent workgroups; tstat: the tiles' output extremes, or null) or, list == nullptr, one
+// workgroup per tile of the frame
+template <bool FAST>
+static void launch_fused(const BlurArgs& A, const BlurScratch& S, size_t lds, const uint32_t* count, const uint32_t* list, float4* tstat,
+                         hipStream_t stream) {
+    const dim3 grid = list ? dim3((unsigned)(S.tiles < 2048 ? S.tiles : 2048)) : dim3(S.gx, S.gy, A.n);
+    hipLaunchKernelGGL(k_blur_fused<FAST>, grid, dim3(256), lds, stream, A, (const unsigned long long*)S.bits_l,
+                       (const unsigned long long*)S.bits_r, S.MW, count, list, tstat);
+}
+
+static int launch_blur_two_pass(const BlurArgs& A, hipStream_t stream) {
+    const int n = A.n, h = A.h, w = A.w;
     int threads = w <= 256 ? 256 : (w <= 1024 ? 512 : 1024);
     size_t ldsA = 4 * (size_t)w * 4 + 32 * 4 + sizeof(csm::PowfTables) + 64;
     size_t ldsB = ((size_t)(BLUR_TR + 2 * A.vert) * BLUR_TW * 2 + (size_t)BLUR_TR * (BLUR_TW + A.bs - 1)) * 4;
@@ -1415,6 +1336,68 @@ int launch_blur(const float* depth, int n, int h, int w, double strength, double
     if (e != hipSuccess) return CS_EHIP;
     hipLaunchKernelGGL(k_blur_weights, dim3(h, n), dim3(threads), ldsA, stream, A);
     hipLaunchKernelGGL(k_blur_apply, dim3((w + BLUR_TW - 1) / BLUR_TW, (h + BLUR_TR - 1) / BLUR_TR, n), dim3(256), ldsB, stream, A);
+    return CS_OK;
+}
+
+int launch_blur(const BlurPlan& P, const float* depth, float* out_l, float* out_r, uint32_t* stats, hipStream_t stream, uint32_t* tilemap,
+                int* lazy_used) {
+    // (lazy_used == nullptr with a tile map: the caller wants COMPLETE maps; the map is then only the classification's output)
+    if (lazy_used) *lazy_used = 0;
+    const BlurScratch& S = P.S;
+    const int n = P.n, h = P.h, w = P.w;
+    BlurArgs A;
+    A.depth = depth; A.n = n; A.h = h; A.w = w;
+    A.stats = P.node_path ? stats : nullptr;
+    A.stats_rw = P.node_path ? stats : nullptr;
+    A.den = (float)(10.0 * P.prm.edge_threshold);
+    A.bs = P.bs; A.radius = P.radius; A.vert = P.vert;
+    if (A.bs < 1) return CS_EINVAL;  // torch raises on a zero-width kernel
+    const double falloff = P.prm.falloff;
+    A.fall32 = (float)falloff;
+    A.fall_mode = falloff == 1.0 ? 0 : falloff == 0.5 ? 1 : falloff == 2.0 ? 2 : falloff == 3.0 ? 3 : falloff == 0.0 ? 5 : 4;
+    A.wl = S.wl; A.wr = S.wr;
+    A.out_l = out_l; A.out_r = out_r;
+    A.dbg = dev_switch(CS_DEBUG_DBG);
+    A.mask_plane = 0;
+    if (P.lazy && !tilemap) return CS_EINVAL;         // (the plan was made for a call with a tile map)
+    if (!P.fused) return launch_blur_two_pass(A, stream);
+
+    const size_t lds = blur_fused_lds(A.vert, A.radius, A.bs);
+    hipError_t e = hipFuncSetAttribute((const void*)k_blur_fused<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_blur_fused<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return CS_EHIP;
+    // edges: the frame's edge bit rows (and, lazy, the block summaries), unless k_gray_edges wrote them: both planes
+    if (P.pre_edges) A.mask_plane = S.plane_words;
+    else if ((w & 3) == 0 && !dev_switch(CS_DEBUG_BLUR_EDGES_SCALAR))
+        hipLaunchKernelGGL(k_blur_edges4, dim3((w + 1023) / 1024, S.HB, n), dim3(256), 0, stream, A, S.bits_l, S.bits_r, S.MW,
+                           P.lazy ? S.block_summaries : nullptr);
+    else
+        hipLaunchKernelGGL(k_blur_edges, dim3((w + 255) / 256, (h + BLUR_ER - 1) / BLUR_ER, n), dim3(256), 0, stream, A, S.bits_l, S.bits_r, S.MW);
+    if (!P.listed) {   // one workgroup per tile, edge in reach or not
+        launch_fused<false>(A, S, lds, nullptr, nullptr, nullptr, stream);
+        return CS_OK;
+    }
+    // classify or copy: edge-free tiles are a scaled copy of the input (lazy: left to the readers of the tile map, or to
+    // k_blur_copy_tiles); the others go onto the worklist
+    const unsigned long long *bits_l = S.bits_l, *bits_r = S.bits_r;
+    const dim3 copy_grid((S.gx + BLUR_CW - 1) / BLUR_CW, S.gy, n);
+    if (hipMemsetAsync(S.work_count, 0, 4, stream) != hipSuccess) return CS_EHIP;
+    if (P.lazy) {
+        if (hipMemsetAsync(tilemap, 0, blur_tilemap_bytes(n, h, w), stream) != hipSuccess) return CS_EHIP;
+        hipLaunchKernelGGL(k_blur_classify, dim3((S.gx * S.gy + 255) / 256, n), dim3(256), 0, stream, A, bits_l, bits_r, S.MW,
+                           (const float4*)S.block_summaries, S.HB, S.work_count, S.worklist, tilemap, blur_tilemap_words(w));
+        if (lazy_used) *lazy_used = 1;
+        else hipLaunchKernelGGL(k_blur_copy_tiles, copy_grid, dim3(256), 0, stream, A, (const uint32_t*)tilemap, blur_tilemap_words(w));
+    } else {
+        hipLaunchKernelGGL(k_blur_copy, copy_grid, dim3(256), 0, stream, A, bits_l, bits_r, S.MW, S.work_count, S.worklist);
+    }
+    // fused blur of the listed tiles, then (node path) the frames' output extremes from the tiles'
+    float4* const tstat = A.stats_rw ? S.tile_stats : nullptr;
+    if (blur_fast_ok(A)) launch_fused<true>(A, S, lds, S.work_count, S.worklist, tstat, stream);
+    else launch_fused<false>(A, S, lds, S.work_count, S.worklist, tstat, stream);
+    if (tstat)
+        hipLaunchKernelGGL(k_blur_tile_stats, dim3(4, n), dim3(256), 0, stream, (const uint32_t*)S.work_count, (const uint32_t*)S.worklist,
+                           (const float4*)tstat, A.stats_rw);
     return CS_OK;
 }
 

@@ -161,21 +161,86 @@ hipError_t launch_anaglyph_compose(const uint8_t* sbs, const uint8_t* rowflag, i
 hipError_t launch_depth_codes(const float* depth, int n, int h, int w, const uint32_t* stats, int scale_from_stats, float* out,
                               hipStream_t stream);
 
-// cs_blur.hip: directional depth blur; if `scale_from_stats`, the input is multiplied by 255 for frames
-// whose stats say so, and the per-frame min/max of both outputs are accumulated into stats.
-int launch_blur(const float* depth, int n, int h, int w, double strength, double edge_threshold, double mask_width,
-                double falloff, int vert, float* out_l, float* out_r, float* wl, float* wr, uint32_t* stats, int node_path,
-                hipStream_t stream, uint32_t* tilemap = nullptr, int* lazy_used = nullptr, int pre_edges = 0);
+// cs_blur.hip: directional depth blur (`directional_motion_blur_gpu`).  The reference's five parameters, as its callers pass them:
+struct BlurParams { double strength, edge_threshold, mask_width, falloff; int vert; };
+// the tile geometry the scratch view below shares with the kernels
+#define BLUR_TW 64   // columns of a blur tile (one word of a bit row)
+#define BLUR_TR 32   // rows of a blur tile
+#define BLUR_ER4 4   // image rows per thread of the float4 edge kernels = rows of a block summary
+                     // (8: 0.66 ms, 16: 0.85, 2: 0.71 -- the halo rows come from L2; fewer registers, more waves)
+// The blur's two weight scratch buffers wl / wr -- al256(n * h * w * 4) bytes each, float32 weights on the two-pass path -- as the
+// fused path uses them.  Each starts with its edge bit rows: `planes` planes (2: the x1 / x255 hypotheses of k_gray_edges) of
+// [n * h][MW] 64-bit words, `plane_words` words apart.  Behind them in wl: the worklist's counter part, the worklist (one word per
+// tile) and, on a 16-byte boundary, the tiles' output extremes; in wr: the 4-row block summaries.  base pointers null: the
+// geometry and the extents alone.
+enum { BLUR_CTR_BYTES = 256 };
+struct BlurScratch {
+    float *wl, *wr;                        // the buffers themselves (the two-pass path: [n][h][w] float32 weights)
+    unsigned long long *bits_l, *bits_r;   // [planes][n * h][MW]
+    size_t plane_words;
+    uint32_t* work_count;      // wl: one counter part (k_blur_copy / k_blur_classify count the listed tiles in its first word)
+    uint32_t* worklist;        // wl: [tiles] words
+    float4* tile_stats;        // wl: [tiles][4] {l min, l max, r min, r max} of the tiles k_blur_fused wrote (k_blur_tile_stats)
+    float4* block_summaries;   // wr: [n][HB][MW] {min, max, any edge bit per plane} (lazy mode: k_blur_classify)
+    int MW, HB, gx, gy;        // words per bit row, summary blocks per column, tiles per row and per column
+    size_t tiles;              // n * gy * gx
+    // what each form needs of a buffer: the bit rows to their last word; with the worklist and the extremes (wl); with the
+    // summaries (wr).  buf_bytes: what wl and wr each hold.  fits_*: the form's parts lie inside the buffers (the bit rows alone
+    // outgrow theirs for w == 1: 8 bytes of bits against 4 bytes of buffer per row) and, listed, a worklist entry holds the tile:
+    // 12 bits of frame, 10 + 10 of tile row and column.  listed and lazy compare with the unpadded size, as they always have.
+    size_t bits_bytes, listed_bytes, lazy_bytes, buf_bytes;
+    bool fits_fused, fits_listed, fits_lazy;
+};
+inline BlurScratch blur_scratch(float* wl, float* wr, int n, int h, int w, int planes) {
+    BlurScratch S;
+    S.MW = (w + 63) / 64; S.HB = (h + BLUR_ER4 - 1) / BLUR_ER4;
+    S.gx = (w + BLUR_TW - 1) / BLUR_TW; S.gy = (h + BLUR_TR - 1) / BLUR_TR;
+    S.tiles = (size_t)n * S.gy * S.gx;
+    const size_t row_words = (size_t)n * h * S.MW, plane_bytes = al256(row_words * 8), bits = plane_bytes * planes;
+    const size_t stats_off = bits + BLUR_CTR_BYTES + align16(S.tiles * 4);
+    auto at = [](float* base, size_t off) { return base ? reinterpret_cast<char*>(base) + off : nullptr; };
+    S.wl = wl; S.wr = wr;
+    S.plane_words = plane_bytes / 8;
+    S.bits_l = (unsigned long long*)at(wl, 0); S.bits_r = (unsigned long long*)at(wr, 0);
+    S.work_count = (uint32_t*)at(wl, bits);
+    S.worklist = (uint32_t*)at(wl, bits + BLUR_CTR_BYTES);
+    S.tile_stats = (float4*)at(wl, stats_off);
+    S.block_summaries = (float4*)at(wr, bits);
+    S.bits_bytes = bits - plane_bytes + row_words * 8;
+    S.listed_bytes = stats_off + S.tiles * 64;
+    S.lazy_bytes = bits + (size_t)n * S.HB * S.MW * 16;
+    S.buf_bytes = al256((size_t)n * h * w * 4);
+    const size_t room = (size_t)n * h * w * 4;
+    S.fits_fused = S.bits_bytes <= S.buf_bytes;
+    S.fits_listed = S.fits_fused && S.gx < 1024 && S.gy < 1024 && n < 4096 && S.listed_bytes <= room;
+    S.fits_lazy = S.fits_listed && S.lazy_bytes <= room;
+    return S;
+}
+// One call's choice of path -- fused: k_blur_fused, else the two-pass kernels, which need no bit rows; listed: edge-free tiles
+// are copied, the others reach k_blur_fused through the worklist; lazy: the tiles are classified from the block summaries into
+// the tile map; pre_edges: the gray conversion of an RGB depth map builds the two-plane bit rows and the summaries
+// (launch_gray_edges) -- and the view of wl / wr that goes with it.  generate_chunk makes ONE plan and hands it to both launches.
+struct BlurPlan {
+    BlurParams prm;
+    int n, h, w;
+    int bs, radius, vert;   // the reference's integers: box width, mask radius, rows of vertical smoothing each way
+    float edge_thr;         // blur_edge_threshold_host(10 * edge_threshold)
+    bool node_path;   // the input is multiplied by 255 for frames whose stats say so; the outputs' per-frame min / max go into stats
+    bool fused, listed, lazy, pre_edges;
+    BlurScratch S;
+};
+// tilemap: the caller has a tile map (blur_tilemap_bytes) for launch_blur; rgb_depth: it would convert the gray depth with
+// launch_gray_edges if the plan says pre_edges
+BlurPlan blur_plan(const BlurParams& prm, int n, int h, int w, float* wl, float* wr, bool tilemap, bool node_path, bool rgb_depth);
 // One pass over an RGB depth map instead of k_gray + k_blur_edges4: gray depth, its per-frame min / max and the edge bit rows
-// for both x255 hypotheses (cs_blur.hip k_gray_edges).  blur_pre_edges_ok: the parameters take launch_blur's lazy-tile path
-// (the only consumer of the two-plane bit rows); launch_blur is then called with pre_edges = 1 and the same wl / wr.
+// for both x255 hypotheses (cs_blur.hip k_gray_edges); P.pre_edges only
+hipError_t launch_gray_edges(const BlurPlan& P, const float* rgb, float* gray, uint32_t* stats, hipStream_t stream);
 float blur_edge_threshold_host(float den);   // the largest t with fl(t / den) <= 0.5, or < 0 (host arithmetic; no GPU)
-bool blur_pre_edges_ok(int n, int h, int w, double strength, double edge_threshold, double mask_width, int vert, bool tilemap);
-hipError_t launch_gray_edges(const float* rgb, float* gray, int n, int h, int w, uint32_t* stats, double strength,
-                             double edge_threshold, double mask_width, int vert, float* wl, float* wr, hipStream_t stream);
-// tilemap != nullptr (zeroed by launch_blur): the tiles are classified from the edge kernel's block summaries and the map names
-// the tiles with an edge in reach.  lazy_used != nullptr: edge-free tiles are left UNWRITTEN (RowArgs::tilemap; *lazy_used = 0
-// when the parameters took a path that writes everything); lazy_used == nullptr: a streaming copy completes the maps.
+// tilemap (P.lazy; zeroed here): names the tiles with an edge in reach.  lazy_used != nullptr: edge-free tiles are left UNWRITTEN
+// (RowArgs::tilemap; *lazy_used = 0 when the plan took a path that writes everything); lazy_used == nullptr: a streaming copy
+// completes the maps.
+int launch_blur(const BlurPlan& P, const float* depth, float* out_l, float* out_r, uint32_t* stats, hipStream_t stream,
+                uint32_t* tilemap = nullptr, int* lazy_used = nullptr);
 int blur_tilemap_words(int w);                 // 32-bit words per tile row, including the pad word the readers rely on
 size_t blur_tilemap_bytes(int n, int h, int w);
 // the rows of `list` (frame * h + row, *count of them; null: all `total` rows) complete in out_l / out_r: gray * scale for
