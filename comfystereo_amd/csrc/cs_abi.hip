@@ -95,17 +95,25 @@ __global__ void __launch_bounds__(256) k_gray(const float* __restrict__ depth, f
     if (do_minmax) block_minmax_commit(mn, mx, &stats[frame * ST_WORDS + ST_GRAY_MIN], &stats[frame * ST_WORDS + ST_GRAY_MAX]);
 }
 
-// per-frame min/max of a [n][hw] float array into the given stats words
+// per-frame min/max of a [n][hw] float array into the given stats words.  fminf / fmaxf drop a NaN.  NAN_POISONS (the latent
+// shifts only): a NaN anywhere makes the max word a NaN, as torch's min() / max() return one (reference stereo_utils.py:38-40) --
+// the key of a positive NaN lies above +inf's, so the atomic max keeps it; the range is then no number and the map counts as flat.
+template <bool NAN_POISONS>
 __global__ void __launch_bounds__(256) k_minmax(const float* __restrict__ a, int hw, uint32_t* stats, int wmin, int wmax) {
     const int frame = blockIdx.y;
     const float* src = a + (size_t)frame * hw;
     float mn = INFINITY, mx = -INFINITY;
+    int nan = 0;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < hw; i += gridDim.x * blockDim.x) {
         float g = src[i];
         mn = fminf(mn, g);
         mx = fmaxf(mx, g);
+        if (NAN_POISONS) nan |= g != g;
     }
     block_minmax_commit(mn, mx, &stats[frame * ST_WORDS + wmin], &stats[frame * ST_WORDS + wmax]);
+    if (NAN_POISONS) {
+        if (__syncthreads_or(nan) && threadIdx.x == 0) atomicMax(&stats[frame * ST_WORDS + wmax], csm::f2ord(csm::u2f(0x7fc00000u)));
+    }
 }
 
 // F.interpolate(mode='bilinear', align_corners=False) of the gray depth (GenerateStereo.py:141-148, 214-220) + min/max of the
@@ -368,10 +376,16 @@ static size_t stats_bytes(size_t n) { return al256(n * ST_WORDS * 4); }
 // The stats pre-pass: the words of `frames` frames initialised and, with a depth map of `per_frame` values a frame, its min / max in
 // ST_L_MIN / ST_L_MAX (depth == nullptr: the caller's own kernels fill the words).  The reference's latent shifts normalise with
 // the min / max of the whole tensor: one frame of b * h * w values.
-static void stats_prepass(uint32_t* stats, int frames, const float* depth, size_t per_frame, hipStream_t stream) {
+enum class NanInDepth { DROPPED, POISONS };   // POISONS: a NaN makes the max word a NaN (the latent shifts, torch's min / max)
+static void stats_prepass(uint32_t* stats, int frames, const float* depth, size_t per_frame, hipStream_t stream,
+                          NanInDepth nan = NanInDepth::DROPPED) {
     hipLaunchKernelGGL(k_stats_init, dim3((frames * ST_WORDS + 255) / 256), dim3(256), 0, stream, stats, frames);
-    if (depth)
-        hipLaunchKernelGGL(k_minmax, dim3(grid_for(per_frame, 256), frames), dim3(256), 0, stream, depth, (int)per_frame, stats, ST_L_MIN, ST_L_MAX);
+    if (!depth) return;
+    const dim3 grid(grid_for(per_frame, 256), frames);
+    if (nan == NanInDepth::POISONS)   // cs_stereo_shift and cs_latent_shift_plan: torch's min / max of the whole tensor
+        hipLaunchKernelGGL(k_minmax<true>, grid, dim3(256), 0, stream, depth, (int)per_frame, stats, ST_L_MIN, ST_L_MAX);
+    else
+        hipLaunchKernelGGL(k_minmax<false>, grid, dim3(256), 0, stream, depth, (int)per_frame, stats, ST_L_MIN, ST_L_MAX);
 }
 // techniques with a D64 (numba typing) instantiation: the forward-map family, the z-buffered inverse map and -- through the
 // general row kernel only, the sweep of full D64 as a literal one-lane replay -- the polylines techniques
@@ -1290,7 +1304,7 @@ int cs_stereo_shift(const float* input, const float* depth, int b, int c, int h,
     // one "frame" = the whole depth tensor: the reference normalises with its global min / max (stereo_utils.py:36-45)
     const size_t total = (size_t)b * h * w;
     if (total >= (1ull << 31)) return fail(CS_ELIMIT, "depth tensor too large");
-    stats_prepass(stats, 1, depth, total, stream);
+    stats_prepass(stats, 1, depth, total, stream, NanInDepth::POISONS);
     const double e = stereo_offset_exponent;
     const int pow_mode = stereo_shift_pow_mode(e);
     const size_t half = (size_t)b * c * h * w;
@@ -1328,7 +1342,7 @@ int cs_latent_shift_plan(const float* disp, int b, int h, int w, double scale_fa
     if (workspace_bytes < cs_latent_shift_plan_workspace_bytes()) return fail(CS_EWORKSPACE, "workspace too small");
     // the stats pre-pass of cs_stereo_shift: one "frame" = the whole tensor (reference stereo_utils.py:36-45)
     uint32_t* stats = (uint32_t*)workspace;
-    stats_prepass(stats, 1, disp, total, stream);
+    stats_prepass(stats, 1, disp, total, stream, NanInDepth::POISONS);
     const double scale_px = ((-1 * scale_factor) / 100.0) * (double)w;   // the right view with balance 0 (:54, :84-86)
     hipError_t e = launch_latent_shift_plan(disp, b, h, w, stats, scale_px, stereo_offset_exponent, src_col, stream);
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_latent_shift_plan");

@@ -15,14 +15,16 @@ def norm_depth(depth):
     """stereo_utils.py:36-45 / stereodiffusion_nodes.py:39-47 on a float32 array: its global min / max."""
     depth = np.asarray(depth, dtype=np.float32)
     mn, mx = depth.min(), depth.max()
-    if mx - mn > F32_EPS:
-        return (np.float32(1.0) * (depth - mn)) / (mx - mn)
+    with np.errstate(invalid="ignore"):   # (a NaN anywhere: the comparison fails and the map is flat; an infinity: NaN pixels)
+        if mx - mn > F32_EPS:
+            return (np.float32(1.0) * (depth - mn)) / (mx - mn)
     return np.zeros(depth.shape, dtype=np.float32)
 
 
 def shift_products(disp, scale_factor, exponent=1.0):
     """norm(disp) ** e * scale_px of the right view, float32 (stereo_utils.py:54, :63-64, :84-86); torch.pow takes the
-    exponents 1 and 0.5 as the identity and the square root."""
+    exponents 1, 2 and 0.5 as the identity, the square and the square root; any other exponent is glibc's powf (the checker's
+    oracle_powf, as in oracle/stereo_shift_oracle.py), which torch's own pow may leave by one unit in the last place."""
     disp = np.asarray(disp, dtype=np.float32)
     w = disp.shape[-1]
     scale_px = ((-1 * float(scale_factor)) / 100.0) * w
@@ -31,9 +33,22 @@ def shift_products(disp, scale_factor, exponent=1.0):
         dv = nd
     elif exponent == 0.5:
         dv = np.sqrt(nd)
+    elif exponent == 2.0:
+        dv = nd * nd
     else:
-        raise ValueError("the restatement covers the exponents 1 and 0.5")
-    return dv * np.float32(scale_px), scale_px
+        dv = _powf(nd, exponent)
+    with np.errstate(invalid="ignore", over="ignore"):
+        return dv * np.float32(scale_px), scale_px
+
+
+def _powf(nd, exponent):
+    """glibc powf(nd, (float)exponent) element by element, once per distinct value."""
+    from oracle import oracle
+    L = oracle.lib()
+    e32 = float(np.float32(exponent))
+    vals, inverse = np.unique(nd.ravel().view(np.uint32), return_inverse=True)
+    table = np.array([L.oracle_powf(float(v), e32) for v in vals.view(np.float32)], dtype=np.float32)
+    return table[inverse].reshape(nd.shape)
 
 
 def plan(disp, scale_factor, exponent=1.0):
@@ -41,7 +56,9 @@ def plan(disp, scale_factor, exponent=1.0):
     destination, -1 where nothing lands."""
     prod, scale_px = shift_products(disp, scale_factor, exponent)
     b, h, w = prod.shape
-    shift = np.trunc(prod.astype(np.float64)).astype(np.int64)   # int() truncates toward zero (:64)
+    p64 = prod.astype(np.float64)
+    # int() truncates toward zero (:64); of an infinite or NaN product it raises: here such a pixel leaves the row, as in the kernels
+    shift = np.trunc(np.where(np.isfinite(p64), p64, 2.0 * w)).astype(np.int64)
     src = np.full((b, h, w), -1, dtype=np.int32)
     bi, ri = np.meshgrid(np.arange(b), np.arange(h), indexing="ij")
     cols = range(w) if scale_px < 0 else range(w - 1, -1, -1)     # (:59-62): what is written last stays
@@ -128,7 +145,7 @@ def margin(disp, scale_factor, exponent=1.0):
     shift can change."""
     prod, _ = shift_products(disp, scale_factor, exponent)
     p = prod.astype(np.float64)
-    p = p[p != 0]
+    p = p[np.isfinite(p) & (p != 0)]
     if p.size == 0:
         return float("inf")
     return float(np.abs(p - np.rint(p)).min())
