@@ -1454,6 +1454,89 @@ int cs_adam_step(void* param, const void* grad, void* exp_avg, void* exp_avg_sq,
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_adam_step");
 }
 
+// ---- Fast mode's inpainting loop outside its models (cs_inpaintloop.hip) ----
+struct span { const void* p; size_t bytes; };
+
+// no written region overlaps another one or a read one
+static bool any_overlap(const span* outs, int n_out, const span* ins, int n_in) {
+    for (int i = 0; i < n_out; i++) {
+        for (int j = i + 1; j < n_out; j++)
+            if (overlaps(outs[i].p, outs[i].bytes, outs[j].p, outs[j].bytes)) return true;
+        for (int j = 0; j < n_in; j++)
+            if (overlaps(outs[i].p, outs[i].bytes, ins[j].p, ins[j].bytes)) return true;
+    }
+    return false;
+}
+
+static bool latent_dtype_ok(int dtype) { return dtype >= CS_LATENT_F32 && dtype <= CS_LATENT_BF16; }
+
+int cs_inpaint_image_prep(const uint8_t* filled, const uint8_t* mask, int n, int h, int w, int hl, int wl, int dtype, void* img,
+                          void* masked, void* x, void* stream) {
+    if (!filled || !mask || !img || !masked || !x) return fail(CS_EINVAL, "null pointer");
+    if (n <= 0 || h <= 0 || w <= 0 || hl <= 0 || wl <= 0) return fail(CS_EINVAL, "non-positive size");
+    if (!latent_dtype_ok(dtype)) return fail(CS_EINVAL, "cs_inpaint_image_prep: unknown dtype (CS_LATENT_F32 / F16 / BF16)");
+    const size_t eb = latent_elem_bytes(dtype), pixels = (size_t)n * h * w;
+    if (((uintptr_t)img | (uintptr_t)masked | (uintptr_t)x) & (eb - 1)) return fail(CS_EINVAL, "cs_inpaint_image_prep: misaligned tensor");
+    const span outs[3] = {{img, pixels * 3 * eb}, {masked, pixels * 3 * eb}, {x, (size_t)2 * n * 9 * hl * wl * eb}};
+    const span ins[2] = {{filled, pixels * 3}, {mask, pixels}};
+    if (any_overlap(outs, 3, ins, 2)) return fail(CS_EINVAL, "cs_inpaint_image_prep: img, masked and x must not overlap each other or an input");
+    hipError_t e = launch_inpaint_image_prep(filled, mask, n, h, w, hl, wl, dtype, img, masked, x, (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_inpaint_image_prep");
+}
+
+int cs_inpaint_latent_init(const void* mean_img, const void* mean_masked, int mean_dtype, const void* noise, int dtype, int n, int hl,
+                           int wl, double sa, double sb, void* x, void* img_latent, void* decode_in, void* stream) {
+    if (!mean_img || !mean_masked || !x || !img_latent) return fail(CS_EINVAL, "null pointer");
+    if (n <= 0 || hl <= 0 || wl <= 0) return fail(CS_EINVAL, "non-positive size");
+    if (!latent_dtype_ok(dtype) || !latent_dtype_ok(mean_dtype))
+        return fail(CS_EINVAL, "cs_inpaint_latent_init: unknown dtype or mean_dtype (CS_LATENT_F32 / F16 / BF16)");
+    if (!finite_d(sa) || !finite_d(sb)) return fail(CS_EINVAL, "cs_inpaint_latent_init: sa and sb must be finite");
+    const size_t eb = latent_elem_bytes(dtype), mb = latent_elem_bytes(mean_dtype), count = (size_t)n * 4 * hl * wl;
+    if ((((uintptr_t)noise | (uintptr_t)x | (uintptr_t)img_latent | (uintptr_t)decode_in) & (eb - 1)) || (((uintptr_t)mean_img | (uintptr_t)mean_masked) & (mb - 1)))
+        return fail(CS_EINVAL, "cs_inpaint_latent_init: misaligned tensor");
+    const span outs[3] = {{x, (size_t)2 * n * 9 * hl * wl * eb}, {img_latent, count * eb}, {decode_in, count * eb}};
+    const span ins[3] = {{mean_img, count * mb}, {mean_masked, count * mb}, {noise, count * eb}};
+    if (any_overlap(outs, 3, ins, 3)) return fail(CS_EINVAL, "cs_inpaint_latent_init: x, img_latent and decode_in must not overlap each other or an input");
+    hipError_t e = launch_inpaint_latent_init(mean_img, mean_masked, mean_dtype, noise, dtype, n, hl, wl, (float)sa, (float)sb, x, img_latent,
+                                              decode_in, (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_inpaint_latent_init");
+}
+
+int cs_inpaint_plms_step(const void* noise_pred, void* x, int dtype, int n, int hl, int wl, int kind, double guidance, double sc, double da,
+                         double denom, void* e_out, const void* e1, const void* e2, const void* e3, void* cur_sample, void* decode_in,
+                         void* stream) {
+    if (!noise_pred || !x) return fail(CS_EINVAL, "null pointer");
+    if (n <= 0 || hl <= 0 || wl <= 0) return fail(CS_EINVAL, "non-positive size");
+    if (!latent_dtype_ok(dtype)) return fail(CS_EINVAL, "cs_inpaint_plms_step: unknown dtype (CS_LATENT_F32 / F16 / BF16)");
+    if (kind < CS_PLMS_FIRST || kind > CS_PLMS_ORDER4) return fail(CS_EINVAL, "cs_inpaint_plms_step: unknown kind (CS_PLMS_*)");
+    // what the kind reads and writes
+    if (kind != CS_PLMS_SECOND && !e_out) return fail(CS_EINVAL, "cs_inpaint_plms_step: null e_out (every kind but CS_PLMS_SECOND keeps its prediction)");
+    if (kind <= CS_PLMS_SECOND && !cur_sample) return fail(CS_EINVAL, "cs_inpaint_plms_step: null cur_sample (CS_PLMS_FIRST writes it, CS_PLMS_SECOND reads it)");
+    if ((kind >= CS_PLMS_SECOND && !e1) || (kind >= CS_PLMS_ORDER3 && !e2) || (kind >= CS_PLMS_ORDER4 && !e3))
+        return fail(CS_EINVAL, "cs_inpaint_plms_step: null history (e1 from CS_PLMS_SECOND, e2 from ORDER3, e3 for ORDER4)");
+    if (!finite_d(guidance) || !finite_d(sc) || !finite_d(da) || !finite_d(denom))
+        return fail(CS_EINVAL, "cs_inpaint_plms_step: guidance, sc, da and denom must be finite");
+    if ((float)denom == 0.0f) return fail(CS_EINVAL, "cs_inpaint_plms_step: denom must not be 0");
+    // (a pointer the kind does not use is not passed on, whatever it holds)
+    if (kind == CS_PLMS_SECOND) e_out = nullptr;
+    if (kind > CS_PLMS_SECOND) cur_sample = nullptr;
+    if (kind < CS_PLMS_SECOND) e1 = nullptr;
+    if (kind < CS_PLMS_ORDER3) e2 = nullptr;
+    if (kind < CS_PLMS_ORDER4) e3 = nullptr;
+    const size_t eb = latent_elem_bytes(dtype), bytes = (size_t)n * 4 * hl * wl * eb;
+    if (((uintptr_t)noise_pred | (uintptr_t)x | (uintptr_t)e_out | (uintptr_t)e1 | (uintptr_t)e2 | (uintptr_t)e3 | (uintptr_t)cur_sample |
+         (uintptr_t)decode_in) & (eb - 1))
+        return fail(CS_EINVAL, "cs_inpaint_plms_step: misaligned tensor");
+    // cur_sample is written by CS_PLMS_FIRST and read by CS_PLMS_SECOND
+    const span outs[4] = {{x, (size_t)2 * n * 9 * hl * wl * eb}, {e_out, bytes}, {decode_in, bytes}, {kind == CS_PLMS_FIRST ? cur_sample : nullptr, bytes}};
+    const span ins[5] = {{noise_pred, 2 * bytes}, {e1, bytes}, {e2, bytes}, {e3, bytes}, {kind == CS_PLMS_SECOND ? cur_sample : nullptr, bytes}};
+    if (any_overlap(outs, 4, ins, 5))
+        return fail(CS_EINVAL, "cs_inpaint_plms_step: x, e_out, cur_sample and decode_in must not overlap each other or an input");
+    hipError_t e = launch_inpaint_plms_step(noise_pred, x, dtype, n, hl, wl, kind, (float)guidance, (float)sc, (float)da, (float)denom, e_out,
+                                            e1, e2, e3, cur_sample, decode_in, (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_inpaint_plms_step");
+}
+
 int cs_stereo_attention_max_head_dim(void) { return stereo_attention_max_head_dim(); }
 
 // The argument checks of the six attention entry points, in one order: null pointers, dtype, sizes, mode, scale, head dimension,

@@ -340,6 +340,16 @@ hipError_t launch_null_loss_grad(const void* eps_uncond, const void* eps_cond, c
                                  double grad_scale, void* workspace, hipStream_t stream);
 hipError_t launch_adam_step(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, int dtype, size_t n, const float adam[6],
                             hipStream_t stream);
+// cs_inpaintloop.hip (StereoDiffusion Fast mode's inpainting loop outside its models: cs_inpaint_image_prep,
+// cs_inpaint_latent_init, cs_inpaint_plms_step).  dtype, mean_dtype: enum cs_latent_dtype; kind: enum cs_plms_kind;
+// x [2n][9][hl][wl], the UNet's persistent input
+hipError_t launch_inpaint_image_prep(const uint8_t* filled, const uint8_t* mask, int n, int h, int w, int hl, int wl, int dtype, void* img,
+                                     void* masked, void* x, hipStream_t stream);
+hipError_t launch_inpaint_latent_init(const void* mean_img, const void* mean_masked, int mean_dtype, const void* noise, int dtype, int n,
+                                      int hl, int wl, float sa, float sb, void* x, void* img_latent, void* decode_in, hipStream_t stream);
+hipError_t launch_inpaint_plms_step(const void* noise_pred, void* x, int dtype, int n, int hl, int wl, int kind, float guidance, float sc,
+                                    float da, float denom, void* e_out, const void* e1, const void* e2, const void* e3, void* cur_sample,
+                                    void* decode_in, hipStream_t stream);
 // lazy depth-blur tiles in k_gpuwarp (tilemap != nullptr): rows of at most this many columns, not the mesh-quality warp
 int gpuwarp_lazy_max_width();
 

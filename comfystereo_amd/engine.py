@@ -840,3 +840,119 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, lr, step, beta1=0.9, beta2=0.999
     _launch(param.device, _native.lib().cs_adam_step, _ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), dtype, n, lr, beta1, beta2,
             eps, step)
     return param
+
+
+# ---- StereoDiffusion Fast mode's inpainting loop outside its models (cs_inpaint_*) ----
+def _unet_input(x, n, hl, wl, like=None):
+    """x: the persistent UNet input [2n, 9, hl, wl], contiguous, of a latent dtype (of `like`'s, when given)."""
+    _tensor("x", x, dtypes=(_FLOATS, _FLOATS_TEXT), shape=((2 * n, 9, hl, wl), f"be [2n,9,hl,wl] = {(2 * n, 9, hl, wl)}, got shape"),
+            contiguous=True, no_grad="the inpainting loop works in place")
+    if like is not None:
+        _tensor("x", x, like=(like[1].dtype, f"x and {like[0]} must share one dtype, got {{got}} and {like[1].dtype}"))
+
+
+def inpaint_image_prep(filled_u8, mask, x, latent_size):
+    """cs_inpaint_image_prep: what ComfyUIInpaintRunner.__call__ does to its image and mask before the VAE (reference
+    model_wrappers.py:562-572, :580).  filled_u8 uint8 [N,H,W,3]; mask uint8 or bool [N,H,W] (non-zero: inpaint); x [2N,9,hl,wl] of
+    the model's dtype, latent_size = (hl, wl).  -> (img, masked) [N,3,H,W] of x's dtype: codes / 255 * 2 - 1, and that times
+    (1 - mask); channel 4 of both halves of x receives F.interpolate(mask, (hl, wl), mode="nearest")."""
+    _tensor("filled_u8", filled_u8, dtypes=((torch.uint8,), "uint8"), dims=((4,), "be [N,H,W,3], got shape"), not_empty="filled_u8",
+            contiguous=True)
+    n, h, w, c = filled_u8.shape
+    if c != 3:
+        raise ValueError(f"filled_u8 must be [N,H,W,3], got shape {tuple(filled_u8.shape)}")
+    _tensor("mask", mask, dtypes=((torch.uint8, torch.bool), "uint8 or bool"), shape=((n, h, w), f"be [N,H,W] = {(n, h, w)}, got shape"),
+            contiguous=True)
+    hl, wl = (int(v) for v in latent_size)
+    if hl <= 0 or wl <= 0:
+        raise ValueError(f"latent_size must be positive, got {(hl, wl)}")
+    _unet_input(x, n, hl, wl)
+    _same_device(("filled_u8", filled_u8), ("mask", mask), ("x", x))
+    _on_gpu(filled_u8, no_gpu_error=True)
+    img = torch.empty((n, 3, h, w), dtype=x.dtype, device=x.device)
+    masked = torch.empty_like(img)
+    _launch(x.device, _native.lib().cs_inpaint_image_prep, _ptr(filled_u8), _ptr(mask), n, h, w, hl, wl, _dtype_code(x, _native.LATENT_DTYPE),
+            _ptr(img), _ptr(masked), _ptr(x))
+    return img, masked
+
+
+def inpaint_latent_init(mean_img, mean_masked, noise, coeffs, x, img_latent=None, decode_in=None):
+    """cs_inpaint_latent_init (reference model_wrappers.py:575-602): the VAE's two means [N,4,hl,wl] (one dtype, any of the three)
+    -> img_latent = (mean_img * 0.18215).to(x.dtype), returned; channels 0..3 of both halves of x = sa * img_latent + sb * noise
+    (scheduler.add_noise; coeffs = (sa, sb), noise [N,4,hl,wl] of x's dtype), or img_latent when noise is None (no timestep left);
+    channels 5..8 = (mean_masked * 0.18215).to(x.dtype); decode_in, when given, receives latents / 0.18215 (:628: a loop of no step)."""
+    _tensor("mean_img", mean_img, dtypes=(_FLOATS, _FLOATS_TEXT), dims=((4,), "be [N,4,hl,wl], got shape"), not_empty="mean_img", contiguous=True)
+    n, c, hl, wl = mean_img.shape
+    if c != 4:
+        raise ValueError(f"mean_img must be [N,4,hl,wl], got shape {tuple(mean_img.shape)}")
+    _tensor("mean_masked", mean_masked, like=(mean_img.dtype, f"mean_img and mean_masked must share one dtype, got {mean_img.dtype} and {{got}}"),
+            shape=(mean_img.shape, f"have mean_img's shape {tuple(mean_img.shape)}, got"), contiguous=True)
+    _unet_input(x, n, hl, wl)
+    named = [("mean_masked", mean_masked), ("x", x)]
+    for name, t in (("noise", noise), ("img_latent", img_latent), ("decode_in", decode_in)):
+        if t is not None:
+            _tensor(name, t, like=(x.dtype, f"x and {name} must share one dtype, got {x.dtype} and {{got}}"),
+                    shape=(mean_img.shape, f"have mean_img's shape {tuple(mean_img.shape)}, got"), contiguous=True, no_grad="")
+            named.append((name, t))
+    if noise is None:
+        sa, sb = 1.0, 0.0
+    else:
+        try:
+            sa, sb = (float(v) for v in coeffs)
+        except (TypeError, ValueError):
+            raise ValueError("coeffs must be two numbers (sa, sb)") from None
+        if not (math.isfinite(sa) and math.isfinite(sb)):
+            raise ValueError(f"coeffs must be finite, got {(sa, sb)}")
+    _same_device(("mean_img", mean_img), *named)
+    _on_gpu(mean_img, no_gpu_error=True)
+    if img_latent is None:
+        img_latent = torch.empty(mean_img.shape, dtype=x.dtype, device=x.device)
+    _launch(x.device, _native.lib().cs_inpaint_latent_init, _ptr(mean_img), _ptr(mean_masked), _dtype_code(mean_img, _native.LATENT_DTYPE),
+            _opt_ptr(noise), _dtype_code(x, _native.LATENT_DTYPE), n, hl, wl, sa, sb, _ptr(x), _ptr(img_latent), _opt_ptr(decode_in))
+    return img_latent
+
+
+def plms_step(noise_pred, x, kind, guidance, coeffs, e_out=None, history=(), cur_sample=None, decode_in=None):
+    """cs_inpaint_plms_step: classifier-free guidance and one PLMS step in one launch, in place on the UNet's input (reference
+    model_wrappers.py:621-625).  noise_pred [2N,4,hl,wl] (uncond, cond) and x [2N,9,hl,wl] of one dtype; kind: a key of
+    _native.PLMS_KIND; coeffs = (sc, da, denom): prev = sc * sample - da * m / denom with m the kind's combination of
+    e = u + guidance * (t - u) and `history` (the earlier predictions, the latest first; 0 to 3 of them as the kind asks).
+    prev goes into channels 0..3 of both halves of x, e into e_out (every kind but "second"), the sample into cur_sample ("first";
+    "second" reads it), prev / 0.18215 into decode_in when given.  All of these [N,4,hl,wl] of x's dtype.  -> x"""
+    if kind not in _native.PLMS_KIND:
+        raise ValueError(f"unknown kind {kind!r} ({', '.join(_native.PLMS_KIND)})")
+    k = _native.PLMS_KIND[kind]
+    _tensor("noise_pred", noise_pred, dtypes=(_FLOATS, _FLOATS_TEXT), dims=((4,), "be [2N,4,hl,wl], got shape"), not_empty="noise_pred",
+            contiguous=True, no_grad="cs_inpaint_plms_step is not differentiable")
+    n2, c, hl, wl = noise_pred.shape
+    if c != 4 or n2 % 2:
+        raise ValueError(f"noise_pred must be [2N,4,hl,wl], got shape {tuple(noise_pred.shape)}")
+    n = n2 // 2
+    _unet_input(x, n, hl, wl, like=("noise_pred", noise_pred))
+    history = tuple(history)
+    need = (0, 1, 1, 2, 3)[k]
+    if len(history) != need:
+        raise ValueError(f"kind {kind!r} takes {need} earlier prediction(s), got {len(history)}")
+    if (e_out is None) != (kind == "second"):
+        raise ValueError("e_out goes with every kind but 'second', whose prediction is not kept")
+    if (cur_sample is None) != (k > 1):
+        raise ValueError("cur_sample goes with the kinds 'first' (which writes it) and 'second' (which reads it) only")
+    named = [(f"history[{i}]", t) for i, t in enumerate(history)]
+    named += [(name, t) for name, t in (("e_out", e_out), ("cur_sample", cur_sample), ("decode_in", decode_in)) if t is not None]
+    for name, t in named:
+        _tensor(name, t, like=(x.dtype, f"x and {name} must share one dtype, got {x.dtype} and {{got}}"),
+                shape=((n, 4, hl, wl), f"be [N,4,hl,wl] = {(n, 4, hl, wl)}, got shape"), contiguous=True, no_grad="")
+    try:
+        g, sc, da, denom = [float(guidance)] + [float(v) for v in coeffs]
+    except (TypeError, ValueError):
+        raise ValueError("coeffs must be three numbers (sc, da, denom)") from None
+    if not all(math.isfinite(v) for v in (g, sc, da, denom)):
+        raise ValueError(f"guidance and coeffs must be finite, got {(g, sc, da, denom)}")
+    if denom == 0.0:
+        raise ValueError("coeffs[2] (denom) must not be 0")
+    _same_device(("noise_pred", noise_pred), ("x", x), *named)
+    _on_gpu(noise_pred, no_gpu_error=True)
+    h = [_ptr(t) for t in history] + [None] * (3 - len(history))
+    _launch(x.device, _native.lib().cs_inpaint_plms_step, _ptr(noise_pred), _ptr(x), _dtype_code(x, _native.LATENT_DTYPE), n, hl, wl, k, g, sc,
+            da, denom, _opt_ptr(e_out), h[0], h[1], h[2], _opt_ptr(cur_sample), _opt_ptr(decode_in))
+    return x

@@ -24,9 +24,11 @@ A coloured depth is made gray as trunc((r * 0.2989 + g * 0.5870) + b * 0.1140) i
 reference on every depth with three equal channels; on a few hundred of the 2^24 colours the reference's BLAS product differs
 from it, and from itself between array shapes.
 
-Out of scope: loading and running the diffusion models themselves -- generate_stereo_fast calls the `inpaint` it is given,
-generate_stereo_standard the `invert` it is given (where the reference runs NullInversion.invert) and the UNet, VAE, text encoder
-and scheduler of the `model` it is given; inversion.make_invert builds that callable; the ComfyUI and diffusers model wrappers are not here.
+Out of scope: loading the diffusion models -- generate_stereo_fast calls the `inpaint` it is given (inpaint_runner.make_inpaint
+builds it around the caller's inpainting UNet, VAE, text encoder and tokenizer, where the reference runs ComfyUIInpaintRunner),
+generate_stereo_standard the `invert` it is given (inversion.make_invert builds it, where the reference runs NullInversion.invert)
+and the UNet, VAE, text encoder and scheduler of the `model` it is given.  The ComfyUI VAE / text encoder / tokenizer wrappers, the
+model loaders and the diffusers StableDiffusionInpaintPipeline branch are not here.
 """
 import torch
 import torch.nn.functional as F

@@ -427,6 +427,46 @@ CS_API int cs_adam_step(void *param, const void *grad, void *exp_avg, void *exp_
                         double beta1, double beta2, double eps, int step, void *stream);
 
 /*
+ * StereoDiffusion's Fast mode outside its models (reference model_wrappers.py ComfyUIInpaintRunner.__call__, :522-641): the tensor
+ * work before and inside the inpainting loop, around ONE persistent UNet input
+ *   x [2n][9][hl][wl] of `dtype` (enum cs_latent_dtype): the uncond half (n frames), then the cond half -- the layout of
+ *   torch.cat([latent_model_input] * 2); per frame the latents (channels 0..3), the mask at the latents' size (4) and the masked
+ *   image's latents (5..8).  Channels 4..8 are written once, channels 0..3 by every step.
+ * Arithmetic as cs_ddim_step: every operation of the reference's tensor expression is one operation, rounded once to the dtype
+ * before the next; coefficients are passed as doubles and used as float32.  Nothing here waits for the device or allocates; one
+ * launch each; 16-byte accesses where the pointers and hl * wl (h * w) allow.
+ *   cs_inpaint_image_prep  (:562-572, :580) filled [n][h][w][3] uint8 codes, mask [n][h][w] uint8 (0 / non-zero) ->
+ *     img [n][3][h][w] = to_dtype((float32(code) / 255.0f) * 2.0f - 1.0f); masked = img * (1 - m) in the dtype (a negative pixel
+ *     under the mask is -0.0); channel 4 of both halves of x = the mask at torch's nearest source index, floor(dst * (in / out))
+ *     with the float32 scale.
+ *   cs_inpaint_latent_init  (:575-602) mean_img, mean_masked [n][4][hl][wl] of `mean_dtype` (what the VAE returned), noise of
+ *     `dtype` or NULL -> img_latent = to_dtype(mean_img * 0.18215) (the product in mean_dtype), to a tensor of its own;
+ *     channels 0..3 of both halves of x = sa * img_latent + sb * noise (scheduler.add_noise: product, product, sum), or
+ *     img_latent with noise NULL (an empty timestep list); channels 5..8 = to_dtype(mean_masked * 0.18215); with decode_in !=
+ *     NULL also decode_in [n][4][hl][wl] = latents / 0.18215 (:628), for a loop of no step.
+ *   cs_inpaint_plms_step  (:621-625) noise_pred [2n][4][hl][wl]: u (first half), t (second);  e = u + guidance * (t - u);
+ *     m by `kind` from e and the earlier predictions e1 (the latest), e2, e3:
+ *       CS_PLMS_FIRST   m = e; cur_sample = the sample             CS_PLMS_SECOND  m = (e + e1) / 2; the sample is cur_sample
+ *       CS_PLMS_ORDER2  m = (3 e - e1) / 2                         CS_PLMS_ORDER3  m = (23 e - 16 e1 + 5 e2) / 12
+ *       CS_PLMS_ORDER4  m = (1 / 24) * (55 e - 59 e1 + 37 e2 - 9 e3)
+ *     prev = sc * sample - da * m / denom, the sample being channels 0..3 of x's first half; prev goes into channels 0..3 of
+ *     both halves of x; e into e_out (every kind but SECOND, whose prediction is not kept; the slot of a ring of four the host
+ *     turns); with decode_in != NULL also decode_in = prev / 0.18215 (:628), for the last step.  e_out, e1..e3, cur_sample,
+ *     decode_in: [n][4][hl][wl].  Pointers the kind does not use may be NULL.
+ * CS_EINVAL before any launch: null pointers, non-positive sizes, unknown dtype or kind, misaligned tensors, outputs that overlap
+ * each other or an input, non-finite coefficients, denom == 0.
+ */
+enum cs_plms_kind { CS_PLMS_FIRST = 0, CS_PLMS_SECOND = 1, CS_PLMS_ORDER2 = 2, CS_PLMS_ORDER3 = 3, CS_PLMS_ORDER4 = 4 };
+CS_API int cs_inpaint_image_prep(const uint8_t *filled, const uint8_t *mask, int n, int h, int w, int hl, int wl, int dtype,
+                                 void *img, void *masked, void *x, void *stream);
+CS_API int cs_inpaint_latent_init(const void *mean_img, const void *mean_masked, int mean_dtype, const void *noise, int dtype,
+                                  int n, int hl, int wl, double sa, double sb, void *x, void *img_latent, void *decode_in,
+                                  void *stream);
+CS_API int cs_inpaint_plms_step(const void *noise_pred, void *x, int dtype, int n, int hl, int wl, int kind, double guidance,
+                                double sc, double da, double denom, void *e_out, const void *e1, const void *e2, const void *e3,
+                                void *cur_sample, void *decode_in, void *stream);
+
+/*
  * Stereo attention (reference stereo_utils.py BNAttention :91-188, the hot path of StereoDiffusion's Standard mode): one fused
  * flash-style forward attention, float32 in and out, float32 accumulation on the f32-input MFMA; no score matrix is written,
  * there is no workspace, nothing is allocated, everything runs on the caller's stream.
