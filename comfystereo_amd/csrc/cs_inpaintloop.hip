@@ -26,13 +26,17 @@ __device__ __forceinline__ float rnd(float x) { return (float)(T)x; }
 template <>
 __device__ __forceinline__ float rnd<float>(float x) { return x; }
 
-// a * b rounded to T.  For float16 the compiler folds the product and its conversion into v_fma_mixlo_f16 a, b, +0, and the sum
-// with +0 makes a product of -0.0 positive: the sign of a zero result is put back (the reference keeps it: a negative pixel under
-// the mask is -0.0 in the masked image and in its latents)
+// a * b rounded to T as CPU torch rounds it: the product rounded to float32, that rounded to T.  Left alone, the compiler folds a
+// float16 product and its conversion into v_fma_mixlo_f16 a, b, +0, which is wrong twice.  It rounds the exact product ONCE:
+// another float16 wherever the float32 product lands on a float16 tie, which a factor with a full float32 mantissa (a guidance
+// of 7.3, 1 / 24, 0.18215) does for every twentieth float16 subnormal.  And the sum with +0 makes a product of -0.0 positive (the
+// reference keeps it: a negative pixel under the mask is -0.0 in the masked image and in its latents).  The empty asm makes the
+// float32 product a value of its own: a v_mul_f32, then a v_cvt_f16_f32.
 template <class T>
 __device__ __forceinline__ float mul_rnd(float a, float b) {
-    const float r = rnd<T>(a * b);
-    return r == 0.0f ? csm::u2f((csm::f2u(a) ^ csm::f2u(b)) & 0x80000000u) : r;
+    float p = a * b;
+    asm("" : "+v"(p));
+    return rnd<T>(p);
 }
 
 // W consecutive elements of T moved as one access (W * sizeof(T) bytes, a power of two; 16 at the most per instruction)
