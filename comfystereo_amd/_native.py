@@ -37,6 +37,8 @@ ATTN_DTYPE = {"float16": 0, "bfloat16": 1}
 # enum cs_latent_dtype / cs_latent_op (StereoDiffusion Standard mode's latent shift: cs_latent_shift_apply, cs_decode_to_codes)
 LATENT_DTYPE = {"float32": 0, "float16": 1, "bfloat16": 2}
 LATENT_OP = {"first": 0, "reshift": 1}
+# enum cs_standard_op (the shift cs_standard_step applies after its DDIM step)
+STANDARD_OP = {"none": 0, "first": 1, "reshift": 2}
 # enum cs_plms_kind (the linear multistep combination of cs_inpaint_plms_step)
 PLMS_KIND = {"first": 0, "second": 1, "order2": 2, "order3": 3, "order4": 4}
 
@@ -164,6 +166,8 @@ SIGNATURES = {
     "cs_inpaint_image_prep": (_int, [_vp, _vp] + [_int] * 6 + [_vp, _vp, _vp, _vp]),
     "cs_inpaint_latent_init": (_int, [_vp, _vp, _int, _vp, _int] + _nhw + [_dbl, _dbl, _vp, _vp, _vp, _vp]),
     "cs_inpaint_plms_step": (_int, [_vp, _vp] + [_int] * 5 + [_dbl] * 4 + [_vp] * 6 + [_vp]),
+    # StereoDiffusion Standard mode between two UNet calls
+    "cs_standard_step": (_int, [_vp, _vp] + [_int] * 5 + [_dbl] * 5 + [_int, _vp, _vp, _vp, _vp]),
     # the stereo attention, its differentiable form, their float16 / bfloat16 forms
     "cs_stereo_attention_max_head_dim": (_int, []),
     "cs_stereo_attention": (_int, [_vp] * 4 + [_int] * 7 + [_dbl, _int, _vp]),

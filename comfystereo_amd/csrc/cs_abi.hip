@@ -1537,6 +1537,30 @@ int cs_inpaint_plms_step(const void* noise_pred, void* x, int dtype, int n, int 
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_inpaint_plms_step");
 }
 
+// ---- Standard mode between two UNet calls (cs_standardloop.hip) ----
+int cs_standard_step(void* x, const void* noise_pred, int dtype, int b, int c, int h, int w, double guidance, double c1, double c2,
+                     double c3, double c4, int op, const int32_t* src_col, uint8_t* mask, const void* noise, void* stream) {
+    if (!x || !noise_pred) return fail(CS_EINVAL, "null pointer");
+    if (b <= 0 || c <= 0 || h <= 0 || w <= 0) return fail(CS_EINVAL, "non-positive size");
+    if (op < CS_STANDARD_NONE || op > CS_STANDARD_RESHIFT) return fail(CS_EINVAL, "cs_standard_step: unknown op (CS_STANDARD_NONE / FIRST / RESHIFT)");
+    const double cd[4] = {c1, c2, c3, c4};
+    if (const char* msg = step_args_error(dtype, 1, guidance, cd)) return fail(CS_EINVAL, msg);
+    if (op != CS_STANDARD_NONE && (!src_col || !mask)) return fail(CS_EINVAL, "cs_standard_step: a shift op takes src_col and mask");
+    if (noise && op != CS_STANDARD_FIRST) return fail(CS_EINVAL, "cs_standard_step: noise goes with CS_STANDARD_FIRST only");
+    if (w > standard_step_max_width()) return fail(CS_ELIMIT, "cs_standard_step: rows of more than 8192 columns");
+    if ((size_t)b * h > 0x7fffffffull || (size_t)c * w > 0x7fffffffull) return fail(CS_ELIMIT, "cs_standard_step: b * h or c * w beyond 2^31 - 1");
+    if (op == CS_STANDARD_NONE) src_col = nullptr, mask = nullptr;   // (a pointer the op does not use is not passed on)
+    const size_t eb = latent_elem_bytes(dtype), pixels = (size_t)b * h * w, view_bytes = pixels * c * eb;
+    if (((uintptr_t)x | (uintptr_t)noise_pred | (uintptr_t)noise) & (eb - 1)) return fail(CS_EINVAL, "cs_standard_step: misaligned tensor");
+    if ((uintptr_t)src_col & 3) return fail(CS_EINVAL, "cs_standard_step: misaligned src_col");
+    const span outs[2] = {{x, 4 * view_bytes}, {mask, pixels}};
+    const span ins[3] = {{noise_pred, 4 * view_bytes}, {src_col, pixels * 4}, {noise, view_bytes}};
+    if (any_overlap(outs, 2, ins, 3)) return fail(CS_EINVAL, "cs_standard_step: x and mask must not overlap each other or an input");
+    const float cf[4] = {(float)c1, (float)c2, (float)c3, (float)c4};
+    hipError_t e = launch_standard_step(x, noise_pred, dtype, b, c, h, w, (float)guidance, cf, op, src_col, mask, noise, (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_standard_step");
+}
+
 int cs_stereo_attention_max_head_dim(void) { return stereo_attention_max_head_dim(); }
 
 // The argument checks of the six attention entry points, in one order: null pointers, dtype, sizes, mode, scale, head dimension,

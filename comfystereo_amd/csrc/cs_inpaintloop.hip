@@ -15,29 +15,16 @@
 #include <initializer_list>
 
 #include "cs_common.h"
+#include "cs_ddimstep.h"
 #include "cs_kernels.h"
 
 namespace cs {
 
 namespace {
 
-template <class T>
-__device__ __forceinline__ float rnd(float x) { return (float)(T)x; }
-template <>
-__device__ __forceinline__ float rnd<float>(float x) { return x; }
-
-// a * b rounded to T as CPU torch rounds it: the product rounded to float32, that rounded to T.  Left alone, the compiler folds a
-// float16 product and its conversion into v_fma_mixlo_f16 a, b, +0, which is wrong twice.  It rounds the exact product ONCE:
-// another float16 wherever the float32 product lands on a float16 tie, which a factor with a full float32 mantissa (a guidance
-// of 7.3, 1 / 24, 0.18215) does for every twentieth float16 subnormal.  And the sum with +0 makes a product of -0.0 positive (the
-// reference keeps it: a negative pixel under the mask is -0.0 in the masked image and in its latents).  The empty asm makes the
-// float32 product a value of its own: a v_mul_f32, then a v_cvt_f16_f32.
-template <class T>
-__device__ __forceinline__ float mul_rnd(float a, float b) {
-    float p = a * b;
-    asm("" : "+v"(p));
-    return rnd<T>(p);
-}
+// rnd<T>(x), x rounded to T as a float, and mul_rnd<T>(a, b), a product rounded to float32 and then to T as CPU torch rounds it
+// (the empty asm that keeps the compiler from folding it into v_fma_mixlo_f16): cs_ddimstep.h, the one
+// definition, shared with cs_inversion.hip and cs_standardloop.hip.
 
 // W consecutive elements of T moved as one access (W * sizeof(T) bytes, a power of two; 16 at the most per instruction)
 template <class T, int W>

@@ -11,8 +11,9 @@
 // Arithmetic: every operation of the reference's tensor expression is one operation here, rounded once to the tensors' dtype
 // before the next -- float32: plain IEEE (the library is built with -ffp-contract=off); float16 / bfloat16: the operation in
 // float32, then the conversion, which is what torch does with a half tensor and a scalar.  No atomics: the loss is summed in a
-// fixed order.
+// fixed order.  The guided prediction and the DDIM expression themselves are cs_ddimstep.h, shared with cs_standardloop.hip.
 #include "cs_common.h"
+#include "cs_ddimstep.h"
 #include "cs_kernels.h"
 
 namespace cs {
@@ -21,36 +22,6 @@ namespace {
 
 constexpr int INV_THREADS = 1024;            // the reduction's workgroup
 constexpr size_t INV_BLOCK_ELEMS = 32768;    // elements per workgroup of k_null_loss_grad: up to here one launch does it all
-
-// x rounded to T, as a float (float: x itself)
-template <class T>
-__device__ __forceinline__ float rnd(float x) { return (float)(T)x; }
-template <>
-__device__ __forceinline__ float rnd<float>(float x) { return x; }
-
-struct StepCoeffs {
-    float guidance, c1, c2, c3, c4;
-};
-
-// e = eps_a + guidance * (eps_b - eps_a) (:88), or eps_a
-template <class T>
-__device__ __forceinline__ float guided(float a, float b, bool has_b, float guidance) {
-    if (!has_b) return a;
-    const float d = rnd<T>(b - a);
-    const float gd = rnd<T>(guidance * d);
-    return rnd<T>(a + gd);
-}
-
-// c4 * ((sample - c1 * e) / c2) + c3 * e, in the reference's order (:62-64, :72-74)
-template <class T>
-__device__ __forceinline__ float ddim_value(float s, float e, const StepCoeffs& k) {
-    const float t = rnd<T>(k.c1 * e);
-    const float num = rnd<T>(s - t);
-    const float x0 = rnd<T>(num / k.c2);
-    const float dir = rnd<T>(k.c3 * e);
-    const float scaled = rnd<T>(k.c4 * x0);
-    return rnd<T>(scaled + dir);
-}
 
 // (hi, lo) += x without losing the rounding error of the sum (Knuth's two-sum; float32 throughout)
 __device__ __forceinline__ void two_sum_add(float& hi, float& lo, float x) {

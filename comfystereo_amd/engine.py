@@ -956,3 +956,48 @@ def plms_step(noise_pred, x, kind, guidance, coeffs, e_out=None, history=(), cur
     _launch(x.device, _native.lib().cs_inpaint_plms_step, _ptr(noise_pred), _ptr(x), _dtype_code(x, _native.LATENT_DTYPE), n, hl, wl, k, g, sc,
             da, denom, _opt_ptr(e_out), h[0], h[1], h[2], _opt_ptr(cur_sample), _opt_ptr(decode_in))
     return x
+
+
+# ---- StereoDiffusion Standard mode between two UNet calls (cs_standard_step) ----
+def standard_step(noise_pred, x, guidance, coeffs, op="none", src_col=None, mask=None, noise=None):
+    """cs_standard_step: classifier-free guidance, one DDIM step and the latent shift in one launch, in place on the UNet's
+    persistent input.  x [4B,C,h,w]: rows 0..B-1 the left views, B..2B-1 the right views, 2B..4B-1 their copy for the conditional
+    half; noise_pred [4B,C,h,w], the unconditional half first; both of one dtype (float32, float16, bfloat16), contiguous.
+    e = u + guidance * (c - u); new = c4 * ((x - c1 * e) / c2) + c3 * e with coeffs = (c1, c2, c3, c4) as for ddim_step; then by
+    `op` ("none", "first", "reshift") what latent_shift_apply does to (new left, new right) with src_col int32 [B,h,w], mask uint8
+    [B,h,w] and, for "first", an optional noise [B,C,h,w].  The result goes into both halves of x: bit for bit ddim_step on the
+    two halves, then latent_shift_apply, then the copy.  -> x"""
+    if op not in _native.STANDARD_OP:
+        raise ValueError(f"unknown op {op!r} (none, first, reshift)")
+    if noise is not None and op != "first":
+        raise ValueError("noise goes with op 'first' only")
+    if op != "none" and (src_col is None or mask is None):
+        raise ValueError(f"op {op!r} takes src_col and mask")
+    _tensor("x", x, dtypes=(_FLOATS, _FLOATS_TEXT), dims=((4,), "be [4B,C,h,w], got shape"), not_empty="x", contiguous=True,
+            no_grad="cs_standard_step works in place")
+    n4, c, h, w = x.shape
+    if n4 % 4:
+        raise ValueError(f"x must be [4B,C,h,w] (left views, right views, and their copy), got shape {tuple(x.shape)}")
+    b = n4 // 4
+    _tensor("noise_pred", noise_pred, like=(x.dtype, f"x and noise_pred must share one dtype, got {x.dtype} and {{got}}"),
+            shape=(x.shape, f"have x's shape {tuple(x.shape)}, got"), contiguous=True, no_grad="cs_standard_step is not differentiable")
+    named = [("noise_pred", noise_pred)]
+    if noise is not None:
+        _tensor("noise", noise, like=(x.dtype, f"x and noise must share one dtype, got {x.dtype} and {{got}}"),
+                shape=((b, c, h, w), f"be [B,C,h,w] = {(b, c, h, w)}, got shape"), contiguous=True, no_grad="")
+        named.append(("noise", noise))
+    if op != "none":
+        _tensor("src_col", src_col, dtypes=((torch.int32,), "int32 (latent_shift_plan's)"),
+                shape=((b, h, w), f"be [B,h,w] = {(b, h, w)}, got shape"), contiguous=True)
+        _tensor("mask", mask, dtypes=((torch.uint8,), "uint8"), shape=((b, h, w), f"be [B,h,w] = {(b, h, w)}, got shape"), contiguous=True)
+        named += [("src_col", src_col), ("mask", mask)]
+    else:
+        src_col = mask = None
+    if w > 8192:
+        raise ValueError(f"rows of {w} columns: cs_standard_step takes up to 8192 (latent_shift_plan's limit)")
+    g, c1, c2, c3, c4 = _step_scalars(guidance, coeffs)
+    _same_device(("x", x), *named)
+    _on_gpu(x, no_gpu_error=True)
+    _launch(x.device, _native.lib().cs_standard_step, _ptr(x), _ptr(noise_pred), _dtype_code(x, _native.LATENT_DTYPE), b, c, h, w, g, c1, c2,
+            c3, c4, _native.STANDARD_OP[op], _opt_ptr(src_col), _opt_ptr(mask), _opt_ptr(noise))
+    return x

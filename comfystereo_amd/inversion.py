@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from . import diffusion_utils, engine
+from .schedulers import _operand, _sqrt   # noqa: F401  (inpaint_runner imports them from here)
 
 try:
     from torch.func import functional_call
@@ -45,23 +46,6 @@ class EmptyControl:
 
     def __call__(self, attn, is_cross: bool, place_in_unet: str):
         return attn
-
-
-def _sqrt(x):
-    """x ** 0.5 (:62-64, :72-74), correctly rounded.  torch evaluates the power -- and torch.sqrt -- of a 0-dim float32 tensor with
-    whatever its CPU dispatch picks on the host, and not every pick is correctly rounded (an ulp on some alphas).  The square root in
-    double, rounded to the tensor's dtype, is the correctly rounded result everywhere (a double holds more than twice a float32's
-    bits plus two), which is also what the reference's expression gives wherever it is right."""
-    if isinstance(x, torch.Tensor):
-        return torch.tensor(math.sqrt(float(x)), dtype=x.dtype if x.is_floating_point() else torch.float32)
-    return x ** 0.5
-
-
-def _operand(c, dtype, first):
-    """The float the kernels take for a coefficient `c` that multiplies (first=True) or divides a tensor of `dtype`."""
-    if first and isinstance(c, torch.Tensor) and dtype in (torch.float16, torch.bfloat16):
-        c = c.to(dtype)
-    return float(c)
 
 
 class NullInversion:

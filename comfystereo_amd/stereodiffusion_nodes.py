@@ -27,14 +27,17 @@ from it, and from itself between array shapes.
 Out of scope: loading the diffusion models -- generate_stereo_fast calls the `inpaint` it is given (inpaint_runner.make_inpaint
 builds it around the caller's inpainting UNet, VAE, text encoder and tokenizer, where the reference runs ComfyUIInpaintRunner),
 generate_stereo_standard the `invert` it is given (inversion.make_invert builds it, where the reference runs NullInversion.invert)
-and the UNet, VAE, text encoder and scheduler of the `model` it is given.  The ComfyUI VAE / text encoder / tokenizer wrappers, the
-model loaders and the diffusers StableDiffusionInpaintPipeline branch are not here.
+and the UNet, VAE, text encoder and scheduler of the `model` it is given.  StereoDiffusionNode, the ComfyUI node (:64-206), builds
+all of these from MODEL, CLIP and VAE through model_wrappers.py; with its DDIMScheduler (schedulers.py) a step of the Standard loop
+is one UNet call on one persistent input and one engine.standard_step launch.  The model loaders and the diffusers
+StableDiffusionInpaintPipeline branch are not here: there is no download path.
 """
 import torch
 import torch.nn.functional as F
 
 from . import engine, stereo_utils
 from .diffusion_utils import diffusion_step, init_latent
+from .schedulers import DDIMScheduler
 
 
 def prepare_inpaint(image, depth, scale_factor, threshold=0.05):
@@ -191,6 +194,41 @@ class _StandardLoop:
         self.mask = torch.zeros(tuple(disp_latent.shape), dtype=torch.uint8, device=disp_latent.device)
         self.noise = noise if deblur else None   # [1,C,h,w]: the right view's
         self.shifted = False
+        # the fused path: our own DDIM scheduler, whose step the kernel restates; any other scheduler keeps diffusion_step
+        self.fused = isinstance(model.scheduler, DDIMScheduler)
+        self.x = None
+
+    def _op(self, i):
+        """The shift of iteration i (:650-667): "first" at the shift step, "reshift" every interval after it, else "none"."""
+        if i == self.shift_step:
+            return "first"
+        if self.shifted and i > self.shift_step and i % self.reshift_interval == 0:
+            return "reshift"
+        return "none"
+
+    def begin(self, latents, timesteps):
+        """The fused path's state: x [4,C,h,w], the UNet's one persistent input -- the latents twice --, every step's coefficients,
+        evaluated on the host, and the timesteps on the device, moved once: a step then copies nothing from the host.
+        -> the view of x that holds the latents"""
+        latents = latents.detach()
+        self.x = torch.cat([latents, latents]).contiguous()
+        self.coeffs = [self.model.scheduler.coeffs(t, latents.dtype) for t in timesteps]
+        self.timesteps = torch.as_tensor(timesteps).to(latents.device)
+        return self.x[:latents.shape[0]]
+
+    def fused_step(self, i, context):
+        """One UNet call on x and one launch: guidance, the DDIM step and the shift, written into both halves of x.  No cat, no
+        allocation of ours and no wait for the device."""
+        noise_pred = self.model.unet(self.x, self.timesteps[i], encoder_hidden_states=context)["sample"].detach()
+        if noise_pred.dtype != self.x.dtype:
+            raise ValueError(f"the UNet answers in {noise_pred.dtype}, the latents are {self.x.dtype}: the Standard loop needs a "
+                             "model whose dtype is the latents' (hand it latents in the model's dtype)")
+        if not noise_pred.is_contiguous():
+            noise_pred = noise_pred.contiguous()
+        op = self._op(i)
+        engine.standard_step(noise_pred, self.x, self.guidance_scale, self.coeffs[i], op, self.src_col, self.mask,
+                             self.noise if op == "first" else None)
+        self.shifted = self.shifted or op == "first"
 
     def step(self, i, t, latents, context):
         latents = diffusion_step(self.model, self.controller, latents, context, t, self.guidance_scale, low_resource=False)
@@ -251,6 +289,18 @@ def _stereo_latents(model, prompt, uncond_embeddings, latent, disparity, scale_f
                 raise ValueError(f"noise {tuple(noise.shape)} must have the latents' shape {tuple(latents.shape)}")
             noise = noise.to(latents.device, latents.dtype)[1:].contiguous()
         loop = _StandardLoop(model, disp_latent, scale_factor, deblur, steps, guidance_scale, noise)
+        if loop.fused:
+            timesteps = model.scheduler.timesteps[-steps:]
+            if uncond_embeddings is not None:
+                contexts = [torch.cat([uncond_embeddings[i].expand(*text_embeddings.shape), text_embeddings]) for i in range(len(timesteps))]
+            else:
+                contexts = [torch.cat([uncond_emb, text_embeddings])] * len(timesteps)
+            latents = loop.begin(latents, timesteps)
+            for i in range(len(timesteps)):
+                loop.fused_step(i, contexts[i])
+                if on_step is not None:
+                    on_step(i, latents)
+            return latents, (loop.mask if loop.shifted else None)
         for i, t in enumerate(model.scheduler.timesteps[-steps:]):
             if uncond_embeddings is not None:
                 context = torch.cat([uncond_embeddings[i].expand(*text_embeddings.shape), text_embeddings])
@@ -338,3 +388,95 @@ def generate_stereo_standard(image, depth_map, scale_factor, direction, deblur, 
     if host:
         stereo = stereo.cpu()
     return stereo, stereo[:, :, :w], stereo[:, :, w:]
+
+
+# ---- the ComfyUI node (reference :64-206, :685-692) -------------------------------------------------------------------------------
+FAST_MODE, STANDARD_MODE = "Fast (Warp + Inpaint)", "Standard (DDIM)"
+
+
+class StereoDiffusionNode:
+    """StereoDiffusion as a ComfyUI node: an image and its depth map -> the side-by-side pair, the left and the right image.
+    Connect MODEL, CLIP and VAE: an inpainting checkpoint (9-channel UNet) for Fast mode, any SD1 / SD2 checkpoint for Standard
+    mode.  There is no download path: without the three inputs the node raises."""
+
+    @classmethod
+    def INPUT_TYPES(cls):
+        return {
+            "required": {
+                "image": ("IMAGE",),
+                "depth_map": ("IMAGE",),
+                "scale_factor": ("FLOAT", {"default": 5.0, "min": 1.0, "max": 20.0, "step": 0.5,
+                                           "tooltip": "Controls the strength of the stereo effect (disparity)"}),
+                "direction": (["uni", "bi"], {"default": "uni",
+                                              "tooltip": "uni: unidirectional attention, bi: bidirectional attention"}),
+                "deblur": ("BOOLEAN", {"default": False, "tooltip": "Add noise to unfilled regions to avoid blurring"}),
+                "pipeline_mode": ([STANDARD_MODE, FAST_MODE], {
+                    "default": FAST_MODE,
+                    "tooltip": "Standard: DDIM inversion (high quality, slow). Fast: Warp image with depth, then AI-inpaint only the "
+                               "gap regions (fast, works with turbo/LCM models)"}),
+                "guidance_scale": ("FLOAT", {"default": 3.0, "min": 0.0, "max": 20.0, "step": 0.5,
+                                             "tooltip": "CFG scale. Standard mode: 3-10. Turbo models: 0.0. LCM: 1.0-2.0"}),
+                "num_inference_steps": ("INT", {
+                    "default": 20, "min": 1, "max": 100, "step": 1,
+                    "tooltip": "Number of inference steps. Standard DDIM: 30-100 (default 50). Fast inpainting: 20-30. Turbo/LCM: 1-8"}),
+                "seed": ("INT", {"default": 1337, "min": 0, "max": 0xffffffffffffffff, "control_after_generate": True,
+                                 "tooltip": "Random seed for reproducible results"}),
+            },
+            "optional": {
+                "null_text_optimization": ("BOOLEAN", {
+                    "default": True, "tooltip": "Enable null-text optimization for better reconstruction (Standard mode only)"}),
+                "denoise_strength": ("FLOAT", {
+                    "default": 0.6, "min": 0.1, "max": 1.0, "step": 0.05,
+                    "tooltip": "How much noise to add before denoising (Fast mode). Lower = preserve original more, Higher = more "
+                               "model creativity for filling gaps"}),
+                "model": ("MODEL", {"tooltip": "ComfyUI MODEL input. Fast mode: use inpainting model (9ch UNet). Standard mode: use "
+                                               "any SD1/SD2 model."}),
+                "clip": ("CLIP", {"tooltip": "CLIP from Load Checkpoint"}),
+                "vae": ("VAE", {"tooltip": "VAE from Load Checkpoint"}),
+                "model_id": ("STRING", {"default": "runwayml/stable-diffusion-v1-5",
+                                        "tooltip": "Fallback HuggingFace model ID (Standard mode, when no ComfyUI model connected)"}),
+                "inpaint_model_id": ("STRING", {"default": "runwayml/stable-diffusion-inpainting",
+                                                "tooltip": "Fallback inpainting model ID (Fast mode, when no ComfyUI model connected)"}),
+                "prompt": ("STRING", {"default": "", "multiline": True,
+                                      "tooltip": "Optional text prompt to guide inpainting (Fast mode). Describe the image content for "
+                                                 "better gap filling."}),
+            },
+        }
+
+    RETURN_TYPES = ("IMAGE", "IMAGE", "IMAGE")
+    RETURN_NAMES = ("stereo_pair", "left_image", "right_image")
+    FUNCTION = "generate_stereo"
+    CATEGORY = "image/stereo"
+
+    def generate_stereo(self, image, depth_map, scale_factor, direction, deblur, pipeline_mode=STANDARD_MODE, guidance_scale=7.5,
+                        num_inference_steps=50, seed=0, null_text_optimization=True, denoise_strength=0.5, model=None, clip=None,
+                        vae=None, model_id="", inpaint_model_id="runwayml/stable-diffusion-inpainting", prompt=""):
+        from . import inpaint_runner, inversion, model_wrappers
+        generator = torch.Generator(device="cpu")
+        generator.manual_seed(seed)
+        if model is None or clip is None or vae is None:
+            # (the reference downloads model_id / inpaint_model_id with diffusers here; this package has no network path)
+            raise ValueError("StereoDiffusion: connect MODEL, CLIP and VAE (Load Checkpoint); this node does not download "
+                             f"'{inpaint_model_id if pipeline_mode == FAST_MODE else model_id}'")
+        # outside inference mode for the whole call: null-text optimisation differentiates through the UNet (:193-194)
+        with torch.inference_mode(False):
+            if pipeline_mode == FAST_MODE:
+                # a model that is no inpainting model raises the 9-channel message (the reference falls back to a download)
+                runner = model_wrappers.make_inpaint_runner(model, clip, vae)
+                inpaint = inpaint_runner.make_inpaint(runner, prompt, int(num_inference_steps), guidance_scale, denoise_strength, seed)
+                return generate_stereo_fast(image, depth_map, scale_factor, inpaint)
+            ldm_stable = model_wrappers.ComfyUIModelWrapper(model, clip, vae)
+            if not ldm_stable.is_supported():
+                raise ValueError(ldm_stable.get_unsupported_message())
+            invert = inversion.make_invert(ldm_stable, int(num_inference_steps), guidance_scale, null_text_optimization)
+            return generate_stereo_standard(image, depth_map, scale_factor, direction, deblur, int(num_inference_steps), guidance_scale,
+                                            ldm_stable, invert, generator=generator)
+
+
+NODE_CLASS_MAPPINGS = {
+    "StereoDiffusion": StereoDiffusionNode,
+}
+
+NODE_DISPLAY_NAME_MAPPINGS = {
+    "StereoDiffusion": "StereoDiffusion",
+}

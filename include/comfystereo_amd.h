@@ -467,6 +467,33 @@ CS_API int cs_inpaint_plms_step(const void *noise_pred, void *x, int dtype, int 
                                 void *cur_sample, void *decode_in, void *stream);
 
 /*
+ * StereoDiffusion's Standard mode between two UNet calls (reference stereodiffusion_nodes.py:624-667 with diffusion_utils.py:29-66):
+ * classifier-free guidance, the DDIM step and the latent shift in ONE launch, around one persistent UNet input
+ *   x [4b][c][h][w] of `dtype` (enum cs_latent_dtype): rows 0..b-1 the left views, b..2b-1 the right views -- the current
+ *   latents --, rows 2b..4b-1 their copy for the conditional half, the layout of torch.cat([latents] * 2).
+ *   noise_pred [4b][c][h][w]: the UNet's answer, the unconditional half first.
+ * cs_standard_step: e = u + guidance * (c - u); new = c4 * ((x - c1 * e) / c2) + c3 * e, every operation rounded exactly as
+ * cs_ddim_step rounds it (one statement of the arithmetic serves both); then by `op` what cs_latent_shift_apply does to the
+ * pair (new left, new right):
+ *   CS_STANDARD_NONE     nothing.
+ *   CS_STANDARD_FIRST    right = new left gathered through src_col, 0 in a hole; mask = (channel 0 of that != 0); with noise !=
+ *                        NULL right = noise [b][c][h][w] on every channel where the mask is 0.
+ *   CS_STANDARD_RESHIFT  where the STORED mask is 1, right = new left gathered; elsewhere right keeps its own step.
+ * The result is written to both halves of x.  It is, bit for bit and for every value, cs_ddim_step on the two halves, then
+ * cs_latent_shift_apply, then the copy.  src_col int32 [b][h][w] (cs_latent_shift_plan's), mask uint8 [b][h][w]; both may be
+ * NULL for CS_STANDARD_NONE.  One workgroup owns a row of both views and gathers from its own copy of the new left row, so the
+ * result does not depend on the order in which anything runs.  Nothing here waits for the device or allocates; 16-byte
+ * accesses where w and the pointers allow.
+ * CS_EINVAL before any launch: null pointers, non-positive sizes, unknown dtype or op, noise without CS_STANDARD_FIRST,
+ * non-finite coefficients, c2 = 0, misaligned or overlapping tensors.  CS_ELIMIT: rows of more than 8 192 columns
+ * (cs_latent_shift_plan's limit), b * h or c * w beyond 2^31 - 1.
+ */
+enum cs_standard_op { CS_STANDARD_NONE = 0, CS_STANDARD_FIRST = 1, CS_STANDARD_RESHIFT = 2 };
+CS_API int cs_standard_step(void *x, const void *noise_pred, int dtype, int b, int c, int h, int w, double guidance, double c1,
+                            double c2, double c3, double c4, int op, const int32_t *src_col, uint8_t *mask, const void *noise,
+                            void *stream);
+
+/*
  * Stereo attention (reference stereo_utils.py BNAttention :91-188, the hot path of StereoDiffusion's Standard mode): one fused
  * flash-style forward attention, float32 in and out, float32 accumulation on the f32-input MFMA; no score matrix is written,
  * there is no workspace, nothing is allocated, everything runs on the caller's stream.

@@ -8,6 +8,14 @@ the same GPU, with HIP events:
   host, nan_to_num, * 255, uint8 there (:673-677) and the copy back for the same resize.
 
   python tools/standard_bench.py [--iters 200]
+  python tools/standard_bench.py --scheduler ddim [--steps 50] [--rounds 20]
+--scheduler ddim times the Standard loop's step outside the UNet instead (a UNet that returns a fixed tensor), three ways, in turn
+in one process, `rounds` times, the median per step reported:
+  fused    _StandardLoop.fused_step: one cs_standard_step launch on the persistent input
+  unfused  the loop without the fused step: diffusion_step (cat, chunk, torch's guidance) over the same DDIMScheduler.step
+           (cs_ddim_step), and cs_latent_shift_apply on the shift steps
+  stock    the same arithmetic in stock torch: cat, guidance, the DDIM expression on 0-dim coefficients, gather and boolean masks
+and counts the device kernels of one loop with torch.profiler, divided by its steps.  One JSON line per dtype.
 It prints a table and judges nothing: there is no threshold in it.  DESIGN.md section 2 holds the numbers of whoever ran it.
 """
 import argparse
@@ -55,11 +63,108 @@ def torch_reshift(latents, src_col, mask):
     return latents
 
 
+class FixedUNet(torch.nn.Module):
+    in_channels = 4
+
+    def __init__(self, pred):
+        super().__init__()
+        self.pred = pred
+
+    def forward(self, x, t, encoder_hidden_states=None):
+        return {"sample": self.pred}
+
+
+def loop_time(fn):
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    fn()
+    end.record()
+    torch.cuda.synchronize()
+    return start.elapsed_time(end) * 1e3   # microseconds
+
+
+def launches(fn):
+    from torch.profiler import ProfilerActivity, profile
+    fn()
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    return sum(1 for ev in prof.events() if ev.device_type == torch.autograd.DeviceType.CUDA and "memcpy" not in ev.name.lower())
+
+
+def ddim_main(args):
+    import json
+    import types
+
+    from comfystereo_amd import schedulers
+    from comfystereo_amd import stereodiffusion_nodes as sdn
+    steps, guidance = args.steps, 7.5
+    g = torch.Generator().manual_seed(0)
+    for dtype in (torch.float16, torch.float32):
+        pred = torch.randn((4, 4, 64, 64), generator=g).to(dtype).cuda()
+        start = torch.randn((2, 4, 64, 64), generator=g).to(dtype).cuda()
+        noise = torch.randn((1, 4, 64, 64), generator=g).to(dtype).cuda()
+        disp = torch.rand((1, 64, 64), generator=g).cuda()
+        context = torch.zeros((4, 77, 8), dtype=dtype, device="cuda")
+        sched = schedulers.DDIMScheduler()
+        sched.set_timesteps(steps)
+        model = types.SimpleNamespace(unet=FixedUNet(pred), scheduler=sched)
+        loop = sdn._StandardLoop(model, disp, 8.0, True, steps, guidance, noise)
+        ts = list(sched.timesteps)
+
+        def fused():
+            loop.shifted = False
+            loop.begin(start, sched.timesteps)
+            for i in range(steps):
+                loop.fused_step(i, context)
+
+        def unfused():   # what the loop ran before the fused step: loop.step over our scheduler's step
+            loop.shifted = False
+            lat = start
+            for i, t in enumerate(ts):
+                lat = loop.step(i, t, lat, context)
+
+        acp, final = sched.alphas_cumprod.cuda(), sched.final_alpha_cumprod.cuda()
+        src = loop.src_col
+
+        def stock():
+            lat, bmask = start, None
+            for i, t in enumerate(ts):
+                u, c = model.unet(torch.cat([lat, lat]), t)["sample"].chunk(2)
+                e = u + guidance * (c - u)
+                prev_t = int(t) - 1000 // steps
+                a_t, a_p = acp[int(t)], (acp[prev_t] if prev_t >= 0 else final)
+                lat = a_p ** 0.5 * ((lat - (1 - a_t) ** 0.5 * e) / a_t ** 0.5) + (1 - a_p) ** 0.5 * e
+                if i == loop.shift_step:
+                    lat, bmask = torch_first(lat, src, noise)
+                elif bmask is not None and i > loop.shift_step and i % loop.reshift_interval == 0:
+                    lat = torch_reshift(lat, src, bmask)
+
+        with torch.no_grad():
+            for fn in (fused, unfused, stock):
+                fn()
+            times = {"fused": [], "unfused": [], "stock": []}
+            for _ in range(args.rounds):   # alternating, so that drift falls on all three alike
+                for name, fn in (("fused", fused), ("unfused", unfused), ("stock", stock)):
+                    times[name].append(loop_time(fn) / steps)
+            out = dict(bench="standard_loop_ddim", dtype=str(dtype).split(".")[-1], latents=[2, 4, 64, 64], steps=steps, rounds=args.rounds)
+            for name, fn in (("fused", fused), ("unfused", unfused), ("stock", stock)):
+                out[f"{name}_us_per_step"] = round(float(np.median(times[name])), 2)
+                out[f"{name}_launches_per_step"] = round(launches(fn) / steps, 2)
+        print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--scheduler", choices=["ddim"], default=None)
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--rounds", type=int, default=20)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "standard_bench.py needs a GPU"
+    if args.scheduler == "ddim":
+        return ddim_main(args)
     rows = []
     g = torch.Generator().manual_seed(0)
     for side in (64, 128):
