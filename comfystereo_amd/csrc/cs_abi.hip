@@ -11,6 +11,7 @@
 
 #include "cs_common.h"
 #include "cs_kernels.h"
+#include "cs_latent.h"
 
 namespace cs {
 
@@ -1335,7 +1336,7 @@ int cs_latent_shift_plan(const float* disp, int b, int h, int w, double scale_fa
     if (!(scale_factor - scale_factor == 0.0) || !(stereo_offset_exponent - stereo_offset_exponent == 0.0))
         return fail(CS_EINVAL, "cs_latent_shift_plan: scale_factor and stereo_offset_exponent must be finite");
     // the destination table of a row stays within 32 KiB of LDS; the scan costs w * reach reads per row: made for latents
-    if (w > 8192) return fail(CS_ELIMIT, "cs_latent_shift_plan: rows of more than 8192 columns");
+    if (w > LATENT_MAX_WIDTH) return fail(CS_ELIMIT, "cs_latent_shift_plan: rows of more than 8192 columns");
     if (b > 65535) return fail(CS_ELIMIT, "cs_latent_shift_plan: more than 65 535 images in one call");
     const size_t total = (size_t)b * h * w;
     if (total >= (1ull << 31)) return fail(CS_ELIMIT, "depth tensor too large");
@@ -1348,7 +1349,35 @@ int cs_latent_shift_plan(const float* disp, int b, int h, int w, double scale_fa
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_latent_shift_plan");
 }
 
-static size_t latent_elem_bytes(int dtype) { return dtype == CS_LATENT_F32 ? 4 : 2; }
+// ---- the checks the latent loops' entry points share (element size and width limit: cs_latent.h) ----
+static bool latent_dtype_ok(int dtype) { return dtype >= CS_LATENT_F32 && dtype <= CS_LATENT_BF16; }
+
+// some pointer (null ones aside) is off the grid of `elem_bytes`, a power of two
+static bool misaligned(size_t elem_bytes, std::initializer_list<const void*> ptrs) {
+    uintptr_t bits = 0;
+    for (const void* p : ptrs) bits |= (uintptr_t)p;
+    return (bits & (elem_bytes - 1)) != 0;
+}
+
+struct span { const void* p; size_t bytes; };
+
+// some written region overlaps another one or a read one (a null region overlaps nothing)
+static bool any_overlap(const span* outs, int n_out, const span* ins, int n_in) {
+    for (int i = 0; i < n_out; i++) {
+        for (int j = i + 1; j < n_out; j++)
+            if (overlaps(outs[i].p, outs[i].bytes, outs[j].p, outs[j].bytes)) return true;
+        for (int j = 0; j < n_in; j++)
+            if (overlaps(outs[i].p, outs[i].bytes, ins[j].p, ins[j].bytes)) return true;
+    }
+    return false;
+}
+
+// c1..c4 as the kernels take them
+struct coeffs4 {
+    double d[4];
+    float f[4];
+    coeffs4(double c1, double c2, double c3, double c4) : d{c1, c2, c3, c4}, f{(float)c1, (float)c2, (float)c3, (float)c4} {}
+};
 
 int cs_latent_shift_apply(const void* left, void* right, const int32_t* src_col, uint8_t* mask, const void* noise, int dtype, int b,
                           int c, int h, int w, int op, void* stream) {
@@ -1356,13 +1385,13 @@ int cs_latent_shift_apply(const void* left, void* right, const int32_t* src_col,
     if (!mask) return fail(CS_EINVAL, op == CS_LATENT_RESHIFT ? "cs_latent_shift_apply: CS_LATENT_RESHIFT reads the mask CS_LATENT_FIRST stored"
                                                                : "null pointer");
     if (b <= 0 || c <= 0 || h <= 0 || w <= 0) return fail(CS_EINVAL, "non-positive size");
-    if (dtype < CS_LATENT_F32 || dtype > CS_LATENT_BF16) return fail(CS_EINVAL, "cs_latent_shift_apply: unknown dtype (CS_LATENT_F32 / F16 / BF16)");
+    if (!latent_dtype_ok(dtype)) return fail(CS_EINVAL, "cs_latent_shift_apply: unknown dtype (CS_LATENT_F32 / F16 / BF16)");
     if (op != CS_LATENT_FIRST && op != CS_LATENT_RESHIFT) return fail(CS_EINVAL, "cs_latent_shift_apply: unknown op (CS_LATENT_FIRST / RESHIFT)");
     const size_t eb = latent_elem_bytes(dtype), bytes = (size_t)b * c * h * w * eb;
-    if (((uintptr_t)left | (uintptr_t)right | (uintptr_t)noise) & (eb - 1)) return fail(CS_EINVAL, "cs_latent_shift_apply: misaligned tensor");
-    if ((uintptr_t)src_col & 3) return fail(CS_EINVAL, "cs_latent_shift_apply: misaligned src_col");
-    if (overlaps(right, bytes, left, bytes) || overlaps(right, bytes, noise, bytes))
-        return fail(CS_EINVAL, "cs_latent_shift_apply: right must not overlap left or noise");
+    if (misaligned(eb, {left, right, noise})) return fail(CS_EINVAL, "cs_latent_shift_apply: misaligned tensor");
+    if (misaligned(4, {src_col})) return fail(CS_EINVAL, "cs_latent_shift_apply: misaligned src_col");
+    const span out = {right, bytes}, ins[2] = {{left, bytes}, {noise, bytes}};
+    if (any_overlap(&out, 1, ins, 2)) return fail(CS_EINVAL, "cs_latent_shift_apply: right must not overlap left or noise");
     hipError_t e = launch_latent_shift_apply(left, right, src_col, mask, noise, dtype, b, c, h, w, op, (hipStream_t)stream);
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_latent_shift_apply");
 }
@@ -1370,11 +1399,11 @@ int cs_latent_shift_apply(const void* left, void* right, const int32_t* src_col,
 int cs_decode_to_codes(const void* image, int dtype, int n, int c, int h, int w, uint8_t* codes_nhwc, void* stream) {
     if (!image || !codes_nhwc) return fail(CS_EINVAL, "null pointer");
     if (n <= 0 || c <= 0 || h <= 0 || w <= 0) return fail(CS_EINVAL, "non-positive size");
-    if (dtype < CS_LATENT_F32 || dtype > CS_LATENT_BF16) return fail(CS_EINVAL, "cs_decode_to_codes: unknown dtype (CS_LATENT_F32 / F16 / BF16)");
-    const size_t count = (size_t)n * c * h * w;
-    if ((uintptr_t)image & (latent_elem_bytes(dtype) - 1)) return fail(CS_EINVAL, "cs_decode_to_codes: misaligned image");
-    if (overlaps(codes_nhwc, count, image, count * latent_elem_bytes(dtype)))
-        return fail(CS_EINVAL, "cs_decode_to_codes: codes must not overlap image");
+    if (!latent_dtype_ok(dtype)) return fail(CS_EINVAL, "cs_decode_to_codes: unknown dtype (CS_LATENT_F32 / F16 / BF16)");
+    const size_t eb = latent_elem_bytes(dtype), count = (size_t)n * c * h * w;
+    if (misaligned(eb, {image})) return fail(CS_EINVAL, "cs_decode_to_codes: misaligned image");
+    const span out = {codes_nhwc, count}, in = {image, count * eb};
+    if (any_overlap(&out, 1, &in, 1)) return fail(CS_EINVAL, "cs_decode_to_codes: codes must not overlap image");
     hipError_t e = launch_decode_to_codes(image, dtype, n, c, h, w, codes_nhwc, (hipStream_t)stream);
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_decode_to_codes");
 }
@@ -1385,7 +1414,7 @@ static bool finite_d(double x) { return x - x == 0.0; }
 // the checks cs_ddim_step and cs_null_loss_grad share; c2 divides
 static const char* step_args_error(int dtype, long long count, double guidance, const double c[4]) {
     if (count <= 0) return "non-positive count";
-    if (dtype < CS_LATENT_F32 || dtype > CS_LATENT_BF16) return "unknown dtype (CS_LATENT_F32 / F16 / BF16)";
+    if (!latent_dtype_ok(dtype)) return "unknown dtype (CS_LATENT_F32 / F16 / BF16)";
     if (!finite_d(guidance) || !finite_d(c[0]) || !finite_d(c[1]) || !finite_d(c[2]) || !finite_d(c[3]))
         return "guidance and c1..c4 must be finite";
     if ((float)c[1] == 0.0f) return "c2 (the square root of alpha_t) must not be 0";
@@ -1395,14 +1424,14 @@ static const char* step_args_error(int dtype, long long count, double guidance, 
 int cs_ddim_step(const void* sample, const void* eps_a, const void* eps_b, void* out, int dtype, long long count, double guidance,
                  double c1, double c2, double c3, double c4, void* stream) {
     if (!sample || !eps_a || !out) return fail(CS_EINVAL, "null pointer");
-    const double cd[4] = {c1, c2, c3, c4};
-    if (const char* msg = step_args_error(dtype, count, guidance, cd)) return fail(CS_EINVAL, msg);
+    const coeffs4 c(c1, c2, c3, c4);
+    if (const char* msg = step_args_error(dtype, count, guidance, c.d)) return fail(CS_EINVAL, msg);
     const size_t eb = latent_elem_bytes(dtype), bytes = (size_t)count * eb;
-    if (((uintptr_t)sample | (uintptr_t)eps_a | (uintptr_t)eps_b | (uintptr_t)out) & (eb - 1)) return fail(CS_EINVAL, "cs_ddim_step: misaligned tensor");
-    if ((out != sample && overlaps(out, bytes, sample, bytes)) || overlaps(out, bytes, eps_a, bytes) || (eps_b && overlaps(out, bytes, eps_b, bytes)))
-        return fail(CS_EINVAL, "cs_ddim_step: out may be sample itself; it must not overlap anything else");
-    const float c[4] = {(float)c1, (float)c2, (float)c3, (float)c4};
-    hipError_t e = launch_ddim_step(sample, eps_a, eps_b, out, dtype, (size_t)count, (float)guidance, c, (hipStream_t)stream);
+    if (misaligned(eb, {sample, eps_a, eps_b, out})) return fail(CS_EINVAL, "cs_ddim_step: misaligned tensor");
+    // out may be sample itself: then sample is no input to keep clear of
+    const span o = {out, bytes}, ins[3] = {{out == sample ? nullptr : sample, bytes}, {eps_a, bytes}, {eps_b, bytes}};
+    if (any_overlap(&o, 1, ins, 3)) return fail(CS_EINVAL, "cs_ddim_step: out may be sample itself; it must not overlap anything else");
+    hipError_t e = launch_ddim_step(sample, eps_a, eps_b, out, dtype, (size_t)count, (float)guidance, c.f, (hipStream_t)stream);
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_ddim_step");
 }
 
@@ -1412,21 +1441,19 @@ int cs_null_loss_grad(const void* eps_uncond, const void* eps_cond, const void* 
                       float* loss, void* grad, int dtype, long long count, double guidance, double c1, double c2, double c3, double c4,
                       void* workspace, size_t workspace_bytes, void* stream) {
     if (!eps_uncond || !eps_cond || !latent_cur || !latent_prev || !rec || !loss || !grad) return fail(CS_EINVAL, "null pointer");
-    const double cd[4] = {c1, c2, c3, c4};
-    if (const char* msg = step_args_error(dtype, count, guidance, cd)) return fail(CS_EINVAL, msg);
+    const coeffs4 cc(c1, c2, c3, c4);
+    const float* c = cc.f;
+    if (const char* msg = step_args_error(dtype, count, guidance, cc.d)) return fail(CS_EINVAL, msg);
     if ((unsigned long long)count > null_loss_max_count()) return fail(CS_ELIMIT, "cs_null_loss_grad: too many elements for a 32-bit grid");
     const size_t eb = latent_elem_bytes(dtype), bytes = (size_t)count * eb, need = null_loss_workspace_bytes((size_t)count);
-    if (((uintptr_t)eps_uncond | (uintptr_t)eps_cond | (uintptr_t)latent_cur | (uintptr_t)latent_prev | (uintptr_t)rec | (uintptr_t)grad) & (eb - 1))
-        return fail(CS_EINVAL, "cs_null_loss_grad: misaligned tensor");
-    if (((uintptr_t)loss | (uintptr_t)workspace) & 3) return fail(CS_EINVAL, "cs_null_loss_grad: misaligned loss or workspace");
+    if (misaligned(eb, {eps_uncond, eps_cond, latent_cur, latent_prev, rec, grad})) return fail(CS_EINVAL, "cs_null_loss_grad: misaligned tensor");
+    if (misaligned(4, {loss, workspace})) return fail(CS_EINVAL, "cs_null_loss_grad: misaligned loss or workspace");
     if (need && (!workspace || workspace_bytes < need)) return fail(CS_EWORKSPACE, "workspace too small");
-    const void* ins[4] = {eps_uncond, eps_cond, latent_cur, latent_prev};
-    for (const void* in : ins)
-        if (overlaps(rec, bytes, in, bytes) || overlaps(grad, bytes, in, bytes) || overlaps(loss, 4, in, bytes))
-            return fail(CS_EINVAL, "cs_null_loss_grad: outputs must not overlap inputs");
-    if (overlaps(rec, bytes, grad, bytes) || overlaps(loss, 4, rec, bytes) || overlaps(loss, 4, grad, bytes))
-        return fail(CS_EINVAL, "cs_null_loss_grad: outputs must not overlap each other");
-    const float c[4] = {(float)c1, (float)c2, (float)c3, (float)c4};
+    const span outs[3] = {{rec, bytes}, {grad, bytes}, {loss, 4}};
+    const span ins[4] = {{eps_uncond, bytes}, {eps_cond, bytes}, {latent_cur, bytes}, {latent_prev, bytes}};
+    for (const span& out : outs)
+        if (any_overlap(&out, 1, ins, 4)) return fail(CS_EINVAL, "cs_null_loss_grad: outputs must not overlap inputs");
+    if (any_overlap(outs, 3, nullptr, 0)) return fail(CS_EINVAL, "cs_null_loss_grad: outputs must not overlap each other");
     // d loss / d eps_uncond = (2 / n) * (rec - latent_prev) * d rec / d e * d e / d eps_uncond
     const double grad_scale = 2.0 / (double)count * ((double)c[2] - (double)c[3] * (double)c[0] / (double)c[1]) * (1.0 - (double)(float)guidance);
     hipError_t e = launch_null_loss_grad(eps_uncond, eps_cond, latent_cur, latent_prev, rec, loss, grad, dtype, (size_t)count,
@@ -1438,15 +1465,14 @@ int cs_adam_step(void* param, const void* grad, void* exp_avg, void* exp_avg_sq,
                  double beta2, double eps, int step, void* stream) {
     if (!param || !grad || !exp_avg || !exp_avg_sq) return fail(CS_EINVAL, "null pointer");
     if (count <= 0) return fail(CS_EINVAL, "non-positive count");
-    if (dtype < CS_LATENT_F32 || dtype > CS_LATENT_BF16) return fail(CS_EINVAL, "cs_adam_step: unknown dtype (CS_LATENT_F32 / F16 / BF16)");
+    if (!latent_dtype_ok(dtype)) return fail(CS_EINVAL, "cs_adam_step: unknown dtype (CS_LATENT_F32 / F16 / BF16)");
     if (step < 1) return fail(CS_EINVAL, "cs_adam_step: the step number counts from 1");
     if (!finite_d(lr) || !finite_d(eps) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0))
         return fail(CS_EINVAL, "cs_adam_step: lr and eps must be finite, eps >= 0, betas in [0, 1)");
     const size_t eb = latent_elem_bytes(dtype), bytes = (size_t)count * eb;
-    if (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & (eb - 1)) return fail(CS_EINVAL, "cs_adam_step: misaligned tensor");
-    if (overlaps(param, bytes, grad, bytes) || overlaps(param, bytes, exp_avg, bytes) || overlaps(param, bytes, exp_avg_sq, bytes) ||
-        overlaps(exp_avg, bytes, grad, bytes) || overlaps(exp_avg_sq, bytes, grad, bytes) || overlaps(exp_avg, bytes, exp_avg_sq, bytes))
-        return fail(CS_EINVAL, "cs_adam_step: param, grad, exp_avg and exp_avg_sq must not overlap");
+    if (misaligned(eb, {param, grad, exp_avg, exp_avg_sq})) return fail(CS_EINVAL, "cs_adam_step: misaligned tensor");
+    const span outs[3] = {{param, bytes}, {exp_avg, bytes}, {exp_avg_sq, bytes}}, in = {grad, bytes};
+    if (any_overlap(outs, 3, &in, 1)) return fail(CS_EINVAL, "cs_adam_step: param, grad, exp_avg and exp_avg_sq must not overlap");
     // the bias corrections in double, as torch/optim/adam.py computes them from Python floats
     const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
     const float k[6] = {(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)sqrt(bc2), (float)eps, (float)(-(lr / bc1))};
@@ -1455,28 +1481,13 @@ int cs_adam_step(void* param, const void* grad, void* exp_avg, void* exp_avg_sq,
 }
 
 // ---- Fast mode's inpainting loop outside its models (cs_inpaintloop.hip) ----
-struct span { const void* p; size_t bytes; };
-
-// no written region overlaps another one or a read one
-static bool any_overlap(const span* outs, int n_out, const span* ins, int n_in) {
-    for (int i = 0; i < n_out; i++) {
-        for (int j = i + 1; j < n_out; j++)
-            if (overlaps(outs[i].p, outs[i].bytes, outs[j].p, outs[j].bytes)) return true;
-        for (int j = 0; j < n_in; j++)
-            if (overlaps(outs[i].p, outs[i].bytes, ins[j].p, ins[j].bytes)) return true;
-    }
-    return false;
-}
-
-static bool latent_dtype_ok(int dtype) { return dtype >= CS_LATENT_F32 && dtype <= CS_LATENT_BF16; }
-
 int cs_inpaint_image_prep(const uint8_t* filled, const uint8_t* mask, int n, int h, int w, int hl, int wl, int dtype, void* img,
                           void* masked, void* x, void* stream) {
     if (!filled || !mask || !img || !masked || !x) return fail(CS_EINVAL, "null pointer");
     if (n <= 0 || h <= 0 || w <= 0 || hl <= 0 || wl <= 0) return fail(CS_EINVAL, "non-positive size");
     if (!latent_dtype_ok(dtype)) return fail(CS_EINVAL, "cs_inpaint_image_prep: unknown dtype (CS_LATENT_F32 / F16 / BF16)");
     const size_t eb = latent_elem_bytes(dtype), pixels = (size_t)n * h * w;
-    if (((uintptr_t)img | (uintptr_t)masked | (uintptr_t)x) & (eb - 1)) return fail(CS_EINVAL, "cs_inpaint_image_prep: misaligned tensor");
+    if (misaligned(eb, {img, masked, x})) return fail(CS_EINVAL, "cs_inpaint_image_prep: misaligned tensor");
     const span outs[3] = {{img, pixels * 3 * eb}, {masked, pixels * 3 * eb}, {x, (size_t)2 * n * 9 * hl * wl * eb}};
     const span ins[2] = {{filled, pixels * 3}, {mask, pixels}};
     if (any_overlap(outs, 3, ins, 2)) return fail(CS_EINVAL, "cs_inpaint_image_prep: img, masked and x must not overlap each other or an input");
@@ -1492,7 +1503,7 @@ int cs_inpaint_latent_init(const void* mean_img, const void* mean_masked, int me
         return fail(CS_EINVAL, "cs_inpaint_latent_init: unknown dtype or mean_dtype (CS_LATENT_F32 / F16 / BF16)");
     if (!finite_d(sa) || !finite_d(sb)) return fail(CS_EINVAL, "cs_inpaint_latent_init: sa and sb must be finite");
     const size_t eb = latent_elem_bytes(dtype), mb = latent_elem_bytes(mean_dtype), count = (size_t)n * 4 * hl * wl;
-    if ((((uintptr_t)noise | (uintptr_t)x | (uintptr_t)img_latent | (uintptr_t)decode_in) & (eb - 1)) || (((uintptr_t)mean_img | (uintptr_t)mean_masked) & (mb - 1)))
+    if (misaligned(eb, {noise, x, img_latent, decode_in}) || misaligned(mb, {mean_img, mean_masked}))
         return fail(CS_EINVAL, "cs_inpaint_latent_init: misaligned tensor");
     const span outs[3] = {{x, (size_t)2 * n * 9 * hl * wl * eb}, {img_latent, count * eb}, {decode_in, count * eb}};
     const span ins[3] = {{mean_img, count * mb}, {mean_masked, count * mb}, {noise, count * eb}};
@@ -1524,9 +1535,7 @@ int cs_inpaint_plms_step(const void* noise_pred, void* x, int dtype, int n, int 
     if (kind < CS_PLMS_ORDER3) e2 = nullptr;
     if (kind < CS_PLMS_ORDER4) e3 = nullptr;
     const size_t eb = latent_elem_bytes(dtype), bytes = (size_t)n * 4 * hl * wl * eb;
-    if (((uintptr_t)noise_pred | (uintptr_t)x | (uintptr_t)e_out | (uintptr_t)e1 | (uintptr_t)e2 | (uintptr_t)e3 | (uintptr_t)cur_sample |
-         (uintptr_t)decode_in) & (eb - 1))
-        return fail(CS_EINVAL, "cs_inpaint_plms_step: misaligned tensor");
+    if (misaligned(eb, {noise_pred, x, e_out, e1, e2, e3, cur_sample, decode_in})) return fail(CS_EINVAL, "cs_inpaint_plms_step: misaligned tensor");
     // cur_sample is written by CS_PLMS_FIRST and read by CS_PLMS_SECOND
     const span outs[4] = {{x, (size_t)2 * n * 9 * hl * wl * eb}, {e_out, bytes}, {decode_in, bytes}, {kind == CS_PLMS_FIRST ? cur_sample : nullptr, bytes}};
     const span ins[5] = {{noise_pred, 2 * bytes}, {e1, bytes}, {e2, bytes}, {e3, bytes}, {kind == CS_PLMS_SECOND ? cur_sample : nullptr, bytes}};
@@ -1543,21 +1552,20 @@ int cs_standard_step(void* x, const void* noise_pred, int dtype, int b, int c, i
     if (!x || !noise_pred) return fail(CS_EINVAL, "null pointer");
     if (b <= 0 || c <= 0 || h <= 0 || w <= 0) return fail(CS_EINVAL, "non-positive size");
     if (op < CS_STANDARD_NONE || op > CS_STANDARD_RESHIFT) return fail(CS_EINVAL, "cs_standard_step: unknown op (CS_STANDARD_NONE / FIRST / RESHIFT)");
-    const double cd[4] = {c1, c2, c3, c4};
-    if (const char* msg = step_args_error(dtype, 1, guidance, cd)) return fail(CS_EINVAL, msg);
+    const coeffs4 cc(c1, c2, c3, c4);
+    if (const char* msg = step_args_error(dtype, 1, guidance, cc.d)) return fail(CS_EINVAL, msg);
     if (op != CS_STANDARD_NONE && (!src_col || !mask)) return fail(CS_EINVAL, "cs_standard_step: a shift op takes src_col and mask");
     if (noise && op != CS_STANDARD_FIRST) return fail(CS_EINVAL, "cs_standard_step: noise goes with CS_STANDARD_FIRST only");
-    if (w > standard_step_max_width()) return fail(CS_ELIMIT, "cs_standard_step: rows of more than 8192 columns");
+    if (w > LATENT_MAX_WIDTH) return fail(CS_ELIMIT, "cs_standard_step: rows of more than 8192 columns");
     if ((size_t)b * h > 0x7fffffffull || (size_t)c * w > 0x7fffffffull) return fail(CS_ELIMIT, "cs_standard_step: b * h or c * w beyond 2^31 - 1");
     if (op == CS_STANDARD_NONE) src_col = nullptr, mask = nullptr;   // (a pointer the op does not use is not passed on)
     const size_t eb = latent_elem_bytes(dtype), pixels = (size_t)b * h * w, view_bytes = pixels * c * eb;
-    if (((uintptr_t)x | (uintptr_t)noise_pred | (uintptr_t)noise) & (eb - 1)) return fail(CS_EINVAL, "cs_standard_step: misaligned tensor");
-    if ((uintptr_t)src_col & 3) return fail(CS_EINVAL, "cs_standard_step: misaligned src_col");
+    if (misaligned(eb, {x, noise_pred, noise})) return fail(CS_EINVAL, "cs_standard_step: misaligned tensor");
+    if (misaligned(4, {src_col})) return fail(CS_EINVAL, "cs_standard_step: misaligned src_col");
     const span outs[2] = {{x, 4 * view_bytes}, {mask, pixels}};
     const span ins[3] = {{noise_pred, 4 * view_bytes}, {src_col, pixels * 4}, {noise, view_bytes}};
     if (any_overlap(outs, 2, ins, 3)) return fail(CS_EINVAL, "cs_standard_step: x and mask must not overlap each other or an input");
-    const float cf[4] = {(float)c1, (float)c2, (float)c3, (float)c4};
-    hipError_t e = launch_standard_step(x, noise_pred, dtype, b, c, h, w, (float)guidance, cf, op, src_col, mask, noise, (hipStream_t)stream);
+    hipError_t e = launch_standard_step(x, noise_pred, dtype, b, c, h, w, (float)guidance, cc.f, op, src_col, mask, noise, (hipStream_t)stream);
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_standard_step");
 }
 

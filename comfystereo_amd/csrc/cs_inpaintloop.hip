@@ -12,29 +12,19 @@
 // tensors' dtype before the next -- float32: plain IEEE (the library is built with -ffp-contract=off); float16 / bfloat16: the
 // operation in float32, then the conversion.  Every operand is elementwise: no LDS, no atomics.  16-byte accesses where the
 // pointers and hl * wl (h * w) allow, one element (pixel) per access otherwise.
-#include <initializer_list>
-
 #include "cs_common.h"
 #include "cs_ddimstep.h"
 #include "cs_kernels.h"
+#include "cs_latent.h"
 
 namespace cs {
 
 namespace {
 
-// rnd<T>(x), x rounded to T as a float, and mul_rnd<T>(a, b), a product rounded to float32 and then to T as CPU torch rounds it
-// (the empty asm that keeps the compiler from folding it into v_fma_mixlo_f16): cs_ddimstep.h, the one
-// definition, shared with cs_inversion.hip and cs_standardloop.hip.
-
-// W consecutive elements of T moved as one access (W * sizeof(T) bytes, a power of two; 16 at the most per instruction)
-template <class T, int W>
-struct alignas((W * sizeof(T) >= 16) ? 16 : W * sizeof(T)) Chunk {
-    T v[W];
-};
-template <class T, int W>
-__device__ __forceinline__ Chunk<T, W> load(const T* p) { return *reinterpret_cast<const Chunk<T, W>*>(p); }
-template <class T, int W>
-__device__ __forceinline__ void store(T* p, const Chunk<T, W>& c) { *reinterpret_cast<Chunk<T, W>*>(p) = c; }
+// rnd<T>(x), x rounded to T as a float, mul_rnd<T>(a, b), a product rounded to float32 and then to T as CPU torch rounds it
+// (the empty asm that keeps the compiler from folding it into v_fma_mixlo_f16), and guided<T>, the
+// guidance (:622): cs_ddimstep.h, the one definition, shared with cs_inversion.hip and cs_standardloop.hip.  Chunk, load and
+// store, the 16-byte access: cs_latent.h.
 
 constexpr float VAE_SCALE = 0.18215f;   // the Python scalar 0.18215 as torch hands it to a float32 operation
 
@@ -173,8 +163,7 @@ __global__ void __launch_bounds__(256) k_inpaint_plms_step(const T* __restrict__
         Chunk<T, W> e_c, prev_c, dec_c;
 #pragma unroll
         for (int q = 0; q < W; q++) {
-            const float uu = (float)u.v[q];
-            const float e = rnd<T>(uu + mul_rnd<T>(k.guidance, rnd<T>((float)t.v[q] - uu)));   // (:622)
+            const float e = guided<T>((float)u.v[q], (float)t.v[q], true, k.guidance);   // (:622)
             const float m = plms_combine<T>(k.kind, e, (float)h1.v[q], (float)h2.v[q], (float)h3.v[q]);
             // sc * sample - da * m / denom
             const float prev = rnd<T>(mul_rnd<T>(k.sc, (float)s.v[q]) - rnd<T>(mul_rnd<T>(k.da, m) / k.denom));
@@ -190,17 +179,6 @@ __global__ void __launch_bounds__(256) k_inpaint_plms_step(const T* __restrict__
     }
 }
 
-static int stream_grid(size_t items) {
-    const size_t blocks = (items + 255) / 256;
-    return (int)(blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks));
-}
-
-static bool aligned16(std::initializer_list<const void*> ptrs) {
-    uintptr_t bits = 0;
-    for (const void* p : ptrs) bits |= (uintptr_t)p;
-    return (bits & 15) == 0;
-}
-
 template <class T>
 static void image_prep(const uint8_t* filled, const uint8_t* mask, void* img, void* masked, void* x, int n, int h, int w, int hl, int wl,
                        hipStream_t stream) {
@@ -210,61 +188,36 @@ static void image_prep(const uint8_t* filled, const uint8_t* mask, void* img, vo
     // whole chunks per frame and per plane; the codes and the mask are read as 16-, 8- or 4-byte words
     const bool wide = hw % P == 0 && aligned16({filled, mask, img, masked});
     const size_t items = wide ? (pixels / P > cells ? pixels / P : cells) : (pixels > cells ? pixels : cells);
-    const dim3 grid(stream_grid(items)), block(256);
-    if (wide)
-        hipLaunchKernelGGL((k_inpaint_image_prep<T, P>), grid, block, 0, stream, filled, mask, (T*)img, (T*)masked, (T*)x, n, h, w, hl, wl,
-                           scale_h, scale_w);
-    else
-        hipLaunchKernelGGL((k_inpaint_image_prep<T, 1>), grid, block, 0, stream, filled, mask, (T*)img, (T*)masked, (T*)x, n, h, w, hl, wl,
-                           scale_h, scale_w);
+    launch_wide_or_narrow(wide, k_inpaint_image_prep<T, P>, k_inpaint_image_prep<T, 1>, dim3(stream_grid(items)), dim3(256), 0, stream,
+                          filled, mask, as<T>(img), as<T>(masked), as<T>(x), n, h, w, hl, wl, scale_h, scale_w);
 }
 
 hipError_t launch_inpaint_image_prep(const uint8_t* filled, const uint8_t* mask, int n, int h, int w, int hl, int wl, int dtype, void* img,
                                      void* masked, void* x, hipStream_t stream) {
-    if (dtype == CS_LATENT_F32)
-        image_prep<float>(filled, mask, img, masked, x, n, h, w, hl, wl, stream);
-    else if (dtype == CS_LATENT_F16)
-        image_prep<_Float16>(filled, mask, img, masked, x, n, h, w, hl, wl, stream);
-    else
-        image_prep<__bf16>(filled, mask, img, masked, x, n, h, w, hl, wl, stream);
+    with_latent_type(dtype, [&](auto tag) { image_prep<decltype(tag)>(filled, mask, img, masked, x, n, h, w, hl, wl, stream); });
     return hipGetLastError();
 }
 
+// M: the means' type, T: the model's
 template <class M, class T>
 static void latent_init(const void* mean_img, const void* mean_masked, const void* noise, void* x, void* img_latent, void* decode_in,
                         int n, size_t hwl, float sa, float sb, hipStream_t stream) {
     constexpr int W = 16 / sizeof(T);
     const size_t per = 4 * hwl, total = (size_t)n * per, half_stride = (size_t)n * 9 * hwl;
     const bool wide = hwl % W == 0 && aligned16({mean_img, mean_masked, noise, x, img_latent, decode_in});
-    const dim3 grid(stream_grid(wide ? total / W : total)), block(256);
-    if (wide)
-        hipLaunchKernelGGL((k_inpaint_latent_init<M, T, W>), grid, block, 0, stream, (const M*)mean_img, (const M*)mean_masked,
-                           (const T*)noise, (T*)x, (T*)img_latent, (T*)decode_in, per, total, half_stride, sa, sb);
-    else
-        hipLaunchKernelGGL((k_inpaint_latent_init<M, T, 1>), grid, block, 0, stream, (const M*)mean_img, (const M*)mean_masked,
-                           (const T*)noise, (T*)x, (T*)img_latent, (T*)decode_in, per, total, half_stride, sa, sb);
-}
-
-template <class M>
-static void latent_init_from(const void* mean_img, const void* mean_masked, const void* noise, int dtype, void* x, void* img_latent,
-                             void* decode_in, int n, size_t hwl, float sa, float sb, hipStream_t stream) {
-    if (dtype == CS_LATENT_F32)
-        latent_init<M, float>(mean_img, mean_masked, noise, x, img_latent, decode_in, n, hwl, sa, sb, stream);
-    else if (dtype == CS_LATENT_F16)
-        latent_init<M, _Float16>(mean_img, mean_masked, noise, x, img_latent, decode_in, n, hwl, sa, sb, stream);
-    else
-        latent_init<M, __bf16>(mean_img, mean_masked, noise, x, img_latent, decode_in, n, hwl, sa, sb, stream);
+    launch_wide_or_narrow(wide, k_inpaint_latent_init<M, T, W>, k_inpaint_latent_init<M, T, 1>, dim3(stream_grid(wide ? total / W : total)),
+                          dim3(256), 0, stream, as<M>(mean_img), as<M>(mean_masked), as<T>(noise), as<T>(x), as<T>(img_latent),
+                          as<T>(decode_in), per, total, half_stride, sa, sb);
 }
 
 hipError_t launch_inpaint_latent_init(const void* mean_img, const void* mean_masked, int mean_dtype, const void* noise, int dtype, int n,
                                       int hl, int wl, float sa, float sb, void* x, void* img_latent, void* decode_in, hipStream_t stream) {
     const size_t hwl = (size_t)hl * wl;
-    if (mean_dtype == CS_LATENT_F32)
-        latent_init_from<float>(mean_img, mean_masked, noise, dtype, x, img_latent, decode_in, n, hwl, sa, sb, stream);
-    else if (mean_dtype == CS_LATENT_F16)
-        latent_init_from<_Float16>(mean_img, mean_masked, noise, dtype, x, img_latent, decode_in, n, hwl, sa, sb, stream);
-    else
-        latent_init_from<__bf16>(mean_img, mean_masked, noise, dtype, x, img_latent, decode_in, n, hwl, sa, sb, stream);
+    with_latent_type(mean_dtype, [&](auto mean_tag) {
+        with_latent_type(dtype, [&](auto tag) {
+            latent_init<decltype(mean_tag), decltype(tag)>(mean_img, mean_masked, noise, x, img_latent, decode_in, n, hwl, sa, sb, stream);
+        });
+    });
     return hipGetLastError();
 }
 
@@ -274,13 +227,9 @@ static void plms_step(const void* noise_pred, void* x, void* e_out, const void* 
     constexpr int W = 16 / sizeof(T);
     const size_t per = 4 * hwl, total = (size_t)n * per, half_stride = (size_t)n * 9 * hwl;
     const bool wide = hwl % W == 0 && aligned16({noise_pred, x, e_out, e1, e2, e3, cur_sample, decode_in});
-    const dim3 grid(stream_grid(wide ? total / W : total)), block(256);
-    if (wide)
-        hipLaunchKernelGGL((k_inpaint_plms_step<T, W>), grid, block, 0, stream, (const T*)noise_pred, (T*)x, (T*)e_out, (const T*)e1,
-                           (const T*)e2, (const T*)e3, (T*)cur_sample, (T*)decode_in, per, total, half_stride, k);
-    else
-        hipLaunchKernelGGL((k_inpaint_plms_step<T, 1>), grid, block, 0, stream, (const T*)noise_pred, (T*)x, (T*)e_out, (const T*)e1,
-                           (const T*)e2, (const T*)e3, (T*)cur_sample, (T*)decode_in, per, total, half_stride, k);
+    launch_wide_or_narrow(wide, k_inpaint_plms_step<T, W>, k_inpaint_plms_step<T, 1>, dim3(stream_grid(wide ? total / W : total)), dim3(256),
+                          0, stream, as<T>(noise_pred), as<T>(x), as<T>(e_out), as<T>(e1), as<T>(e2), as<T>(e3), as<T>(cur_sample),
+                          as<T>(decode_in), per, total, half_stride, k);
 }
 
 hipError_t launch_inpaint_plms_step(const void* noise_pred, void* x, int dtype, int n, int hl, int wl, int kind, float guidance, float sc,
@@ -288,12 +237,7 @@ hipError_t launch_inpaint_plms_step(const void* noise_pred, void* x, int dtype, 
                                     void* decode_in, hipStream_t stream) {
     const PlmsCoeffs k{guidance, sc, da, denom, kind};
     const size_t hwl = (size_t)hl * wl;
-    if (dtype == CS_LATENT_F32)
-        plms_step<float>(noise_pred, x, e_out, e1, e2, e3, cur_sample, decode_in, n, hwl, k, stream);
-    else if (dtype == CS_LATENT_F16)
-        plms_step<_Float16>(noise_pred, x, e_out, e1, e2, e3, cur_sample, decode_in, n, hwl, k, stream);
-    else
-        plms_step<__bf16>(noise_pred, x, e_out, e1, e2, e3, cur_sample, decode_in, n, hwl, k, stream);
+    with_latent_type(dtype, [&](auto tag) { plms_step<decltype(tag)>(noise_pred, x, e_out, e1, e2, e3, cur_sample, decode_in, n, hwl, k, stream); });
     return hipGetLastError();
 }
 

@@ -15,6 +15,7 @@
 #include "cs_common.h"
 #include "cs_ddimstep.h"
 #include "cs_kernels.h"
+#include "cs_latent.h"
 
 namespace cs {
 
@@ -135,26 +136,16 @@ __global__ void __launch_bounds__(256) k_adam_step(T* __restrict__ param, const 
     }
 }
 
-static int stream_grid(size_t items) {
-    const size_t blocks = (items + 255) / 256;
-    return (int)(blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks));
-}
-
 static StepCoeffs step_coeffs(float guidance, const float c[4]) { return StepCoeffs{guidance, c[0], c[1], c[2], c[3]}; }
 
 hipError_t launch_ddim_step(const void* sample, const void* eps_a, const void* eps_b, void* out, int dtype, size_t n, float guidance,
                             const float c[4], hipStream_t stream) {
-    const dim3 grid(stream_grid(n)), block(256);
     const StepCoeffs k = step_coeffs(guidance, c);
-    if (dtype == CS_LATENT_F32)
-        hipLaunchKernelGGL(k_ddim_step<float>, grid, block, 0, stream, (const float*)sample, (const float*)eps_a, (const float*)eps_b,
-                           (float*)out, n, k);
-    else if (dtype == CS_LATENT_F16)
-        hipLaunchKernelGGL(k_ddim_step<_Float16>, grid, block, 0, stream, (const _Float16*)sample, (const _Float16*)eps_a,
-                           (const _Float16*)eps_b, (_Float16*)out, n, k);
-    else
-        hipLaunchKernelGGL(k_ddim_step<__bf16>, grid, block, 0, stream, (const __bf16*)sample, (const __bf16*)eps_a, (const __bf16*)eps_b,
-                           (__bf16*)out, n, k);
+    with_latent_type(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(k_ddim_step<T>, dim3(stream_grid(n)), dim3(256), 0, stream, as<T>(sample), as<T>(eps_a), as<T>(eps_b), as<T>(out),
+                           n, k);
+    });
     return hipGetLastError();
 }
 
@@ -175,35 +166,23 @@ hipError_t launch_null_loss_grad(const void* eps_uncond, const void* eps_cond, c
     const StepCoeffs k = step_coeffs(guidance, c);
     float* partial = (float*)workspace;
     const float count = (float)n;
-    if (dtype == CS_LATENT_F32)
-        hipLaunchKernelGGL(k_null_loss_grad<float>, grid, block, 0, stream, (const float*)eps_uncond, (const float*)eps_cond,
-                           (const float*)latent_cur, (const float*)latent_prev, (float*)rec, (float*)grad, loss, partial, n, k,
-                           grad_scale, count);
-    else if (dtype == CS_LATENT_F16)
-        hipLaunchKernelGGL(k_null_loss_grad<_Float16>, grid, block, 0, stream, (const _Float16*)eps_uncond, (const _Float16*)eps_cond,
-                           (const _Float16*)latent_cur, (const _Float16*)latent_prev, (_Float16*)rec, (_Float16*)grad, loss, partial,
-                           n, k, grad_scale, count);
-    else
-        hipLaunchKernelGGL(k_null_loss_grad<__bf16>, grid, block, 0, stream, (const __bf16*)eps_uncond, (const __bf16*)eps_cond,
-                           (const __bf16*)latent_cur, (const __bf16*)latent_prev, (__bf16*)rec, (__bf16*)grad, loss, partial, n, k,
-                           grad_scale, count);
+    with_latent_type(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(k_null_loss_grad<T>, grid, block, 0, stream, as<T>(eps_uncond), as<T>(eps_cond), as<T>(latent_cur),
+                           as<T>(latent_prev), as<T>(rec), as<T>(grad), loss, partial, n, k, grad_scale, count);
+    });
     if (blocks > 1) hipLaunchKernelGGL(k_null_loss_final, dim3(1), block, 0, stream, partial, blocks, loss, count);
     return hipGetLastError();
 }
 
 hipError_t launch_adam_step(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, int dtype, size_t n, const float k6[6],
                             hipStream_t stream) {
-    const dim3 grid(stream_grid(n)), block(256);
     const AdamCoeffs k{k6[0], k6[1], k6[2], k6[3], k6[4], k6[5]};
-    if (dtype == CS_LATENT_F32)
-        hipLaunchKernelGGL(k_adam_step<float>, grid, block, 0, stream, (float*)param, (const float*)grad, (float*)exp_avg,
-                           (float*)exp_avg_sq, n, k);
-    else if (dtype == CS_LATENT_F16)
-        hipLaunchKernelGGL(k_adam_step<_Float16>, grid, block, 0, stream, (_Float16*)param, (const _Float16*)grad, (_Float16*)exp_avg,
-                           (_Float16*)exp_avg_sq, n, k);
-    else
-        hipLaunchKernelGGL(k_adam_step<__bf16>, grid, block, 0, stream, (__bf16*)param, (const __bf16*)grad, (__bf16*)exp_avg,
-                           (__bf16*)exp_avg_sq, n, k);
+    with_latent_type(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(k_adam_step<T>, dim3(stream_grid(n)), dim3(256), 0, stream, as<T>(param), as<T>(grad), as<T>(exp_avg),
+                           as<T>(exp_avg_sq), n, k);
+    });
     return hipGetLastError();
 }
 

@@ -352,7 +352,6 @@ hipError_t launch_inpaint_plms_step(const void* noise_pred, void* x, int dtype, 
                                     void* decode_in, hipStream_t stream);
 // cs_standardloop.hip (StereoDiffusion Standard mode between two UNet calls: cs_standard_step).  dtype: enum cs_latent_dtype;
 // op: enum cs_standard_op; cf: the step's four coefficients c1..c4; x [4b][c][h][w], the UNet's persistent input
-int standard_step_max_width();
 hipError_t launch_standard_step(void* x, const void* noise_pred, int dtype, int b, int c, int h, int w, float guidance, const float cf[4],
                                 int op, const int32_t* src_col, uint8_t* mask, const void* noise, hipStream_t stream);
 // lazy depth-blur tiles in k_gpuwarp (tilemap != nullptr): rows of at most this many columns, not the mesh-quality warp

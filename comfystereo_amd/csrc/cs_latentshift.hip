@@ -13,6 +13,7 @@
 // lowest (positive shift) first.
 #include "cs_common.h"
 #include "cs_kernels.h"
+#include "cs_latent.h"
 
 namespace cs {
 
@@ -60,12 +61,11 @@ hipError_t launch_latent_shift_plan(const float* depth, int b, int h, int w, con
 }
 
 // U: the element as an unsigned integer of its size (values are moved, never computed).  One thread per pixel (b, row, x), all
-// channels.  `x != 0` of a float is `some bit but the sign is set`: +-0.0 is a hole, a NaN is not.
+// channels.  The gather and the mask `channel 0 != 0`: shift_gathered and shift_mask of cs_latent.h, which k_standard_step shares.
 template <class U>
 __global__ void __launch_bounds__(256) k_latent_shift_apply(const U* __restrict__ left, U* __restrict__ right,
                                                             const int32_t* __restrict__ src_col, uint8_t* __restrict__ mask,
                                                             const U* __restrict__ noise, int c, int h, int w, size_t pixels, int op) {
-    const U abs_bits = (U)~((U)1 << (8 * sizeof(U) - 1));
     const size_t plane = (size_t)h * w, step = (size_t)gridDim.x * blockDim.x;
     for (size_t pix = blockIdx.x * (size_t)blockDim.x + threadIdx.x; pix < pixels; pix += step) {
         const size_t br = pix / w;
@@ -73,37 +73,32 @@ __global__ void __launch_bounds__(256) k_latent_shift_apply(const U* __restrict_
         const size_t bb = br / h, r = br - bb * h;
         const size_t base = (bb * c * h + r) * w;   // (b, channel 0, row, column 0)
         const int src = src_col[pix];
-        const bool landed = (unsigned)src < (unsigned)w;
+        const bool landed = shift_landed(src, w);
+        const auto gathered = [&](int ch) { return shift_gathered(landed, left, base + ch * plane + src); };
         if (op == CS_LATENT_FIRST) {
-            const U v0 = landed ? left[base + src] : (U)0;
-            const bool m = (v0 & abs_bits) != 0;
+            const U v0 = gathered(0);
+            const bool m = shift_mask(v0);
             mask[pix] = m ? 1 : 0;
             if (noise && !m) {
                 for (int ch = 0; ch < c; ch++) right[base + ch * plane + x] = noise[base + ch * plane + x];
             } else {
                 right[base + x] = v0;
-                for (int ch = 1; ch < c; ch++) right[base + ch * plane + x] = landed ? left[base + ch * plane + src] : (U)0;
+                for (int ch = 1; ch < c; ch++) right[base + ch * plane + x] = gathered(ch);
             }
         } else if (mask[pix]) {
-            for (int ch = 0; ch < c; ch++) right[base + ch * plane + x] = landed ? left[base + ch * plane + src] : (U)0;
+            for (int ch = 0; ch < c; ch++) right[base + ch * plane + x] = gathered(ch);
         }
     }
-}
-
-static int stream_grid(size_t items) {
-    const size_t blocks = (items + 255) / 256;
-    return (int)(blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks));
 }
 
 hipError_t launch_latent_shift_apply(const void* left, void* right, const int32_t* src_col, uint8_t* mask, const void* noise,
                                      int dtype, int b, int c, int h, int w, int op, hipStream_t stream) {
     const size_t pixels = (size_t)b * h * w;
-    if (dtype == CS_LATENT_F32)
-        hipLaunchKernelGGL(k_latent_shift_apply<uint32_t>, dim3(stream_grid(pixels)), dim3(256), 0, stream, (const uint32_t*)left,
-                           (uint32_t*)right, src_col, mask, (const uint32_t*)noise, c, h, w, pixels, op);
-    else
-        hipLaunchKernelGGL(k_latent_shift_apply<uint16_t>, dim3(stream_grid(pixels)), dim3(256), 0, stream, (const uint16_t*)left,
-                           (uint16_t*)right, src_col, mask, (const uint16_t*)noise, c, h, w, pixels, op);
+    with_latent_type(dtype, [&](auto tag) {
+        using U = typename BitsOf<sizeof(tag)>::type;   // float16 and bfloat16: one instantiation
+        hipLaunchKernelGGL(k_latent_shift_apply<U>, dim3(stream_grid(pixels)), dim3(256), 0, stream, as<U>(left), as<U>(right), src_col,
+                           mask, as<U>(noise), c, h, w, pixels, op);
+    });
     return hipGetLastError();
 }
 
@@ -151,13 +146,10 @@ __global__ void __launch_bounds__(256) k_decode_to_codes(const T* __restrict__ i
 
 hipError_t launch_decode_to_codes(const void* image, int dtype, int n, int c, int h, int w, uint8_t* codes, hipStream_t stream) {
     const size_t hw = (size_t)h * w, pixels = (size_t)n * hw;
-    const dim3 grid(stream_grid(pixels)), block(256);
-    if (dtype == CS_LATENT_F32)
-        hipLaunchKernelGGL(k_decode_to_codes<float>, grid, block, 0, stream, (const float*)image, c, hw, pixels, codes);
-    else if (dtype == CS_LATENT_F16)
-        hipLaunchKernelGGL(k_decode_to_codes<_Float16>, grid, block, 0, stream, (const _Float16*)image, c, hw, pixels, codes);
-    else
-        hipLaunchKernelGGL(k_decode_to_codes<__bf16>, grid, block, 0, stream, (const __bf16*)image, c, hw, pixels, codes);
+    with_latent_type(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(k_decode_to_codes<T>, dim3(stream_grid(pixels)), dim3(256), 0, stream, as<T>(image), c, hw, pixels, codes);
+    });
     return hipGetLastError();
 }
 

@@ -16,33 +16,18 @@
 // workgroups or launches run.  A group is as many channels as fit the LDS budget (all of them at the latents' sizes); a later
 // group reads the mask the first one stored, from global memory, behind the barrier between the groups.
 // No atomics.  16-byte accesses where w and the pointers allow, one element per access otherwise.
-#include <initializer_list>
-
 #include "cs_common.h"
 #include "cs_ddimstep.h"
 #include "cs_kernels.h"
+#include "cs_latent.h"
 
 namespace cs {
 
 namespace {
 
 constexpr int SL_THREADS = 256;
-constexpr int SL_MAX_WIDTH = 8192;        // cs_latent_shift_plan's limit: the tables come from there
 constexpr size_t SL_LDS_BYTES = 49152;    // the LDS of one workgroup: at least one row of float32, all channels at the latents' sizes
-static_assert(SL_MAX_WIDTH * sizeof(float) <= SL_LDS_BYTES, "one row of the widest frame must fit");
-
-template <int BYTES> struct BitsOf;
-template <> struct BitsOf<4> { using type = uint32_t; };
-template <> struct BitsOf<2> { using type = uint16_t; };
-
-template <class T, int W>
-struct alignas((W * sizeof(T) >= 16) ? 16 : W * sizeof(T)) Chunk {
-    T v[W];
-};
-template <class T, int W>
-__device__ __forceinline__ Chunk<T, W> load(const T* p) { return *reinterpret_cast<const Chunk<T, W>*>(p); }
-template <class T, int W>
-__device__ __forceinline__ void store(T* p, const Chunk<T, W>& c) { *reinterpret_cast<Chunk<T, W>*>(p) = c; }
+static_assert(LATENT_MAX_WIDTH * sizeof(float) <= SL_LDS_BYTES, "one row of the widest frame must fit");
 
 // the step of W consecutive elements at offset `at` of x's and noise_pred's first halves
 template <class T, int W>
@@ -68,7 +53,6 @@ __global__ void __launch_bounds__(SL_THREADS) k_standard_step(T* x, const T* __r
     using U = typename BitsOf<sizeof(T)>::type;
     extern __shared__ __align__(16) unsigned char sl_lds[];
     T* row_left = reinterpret_cast<T*>(sl_lds);   // [group][w]: the new left values of this row
-    const U abs_bits = (U)~((U)1 << (8 * sizeof(U) - 1));
     const int b = blockIdx.x / h, r = blockIdx.x - b * h, tid = threadIdx.x;
     const size_t plane = (size_t)h * w, view = (size_t)c * plane, half = 2 * (size_t)nb * view;
     const size_t left0 = (size_t)b * view + (size_t)r * w;          // (left view b, channel 0, row r, column 0) of x and noise_pred
@@ -100,13 +84,13 @@ __global__ void __launch_bounds__(SL_THREADS) k_standard_step(T* x, const T* __r
                 for (int q = 0; q < W; q++) {
                     const size_t pix = pix0 + col + q;
                     const int src = src_col[pix];
-                    const bool landed = (unsigned)src < (unsigned)w;
-                    const T moved = landed ? row_left[(size_t)g * w + src] : (T)0.0f;
+                    // (the gather and the mask: cs_latent.h, the statement k_latent_shift_apply uses, here on the LDS row)
+                    const bool landed = shift_landed(src, w);
+                    const T moved = shift_gathered(landed, row_left, (size_t)g * w + src);
                     bool m;
                     if (op == CS_STANDARD_FIRST && g0 == 0) {
-                        // mask = (channel 0 of the gathered view != 0): +-0.0 is a hole, a NaN is not
-                        const T v0 = landed ? row_left[src] : (T)0.0f;
-                        m = (__builtin_bit_cast(U, v0) & abs_bits) != 0;
+                        const T v0 = shift_gathered(landed, row_left, src);
+                        m = shift_mask(__builtin_bit_cast(U, v0));
                         if (g == 0) mask[pix] = m ? 1 : 0;
                     } else {
                         m = mask[pix] != 0;   // RESHIFT: the stored mask; FIRST, a later group: what the first group stored
@@ -124,41 +108,24 @@ __global__ void __launch_bounds__(SL_THREADS) k_standard_step(T* x, const T* __r
     }
 }
 
-static bool aligned16(std::initializer_list<const void*> ptrs) {
-    uintptr_t bits = 0;
-    for (const void* p : ptrs) bits |= (uintptr_t)p;
-    return (bits & 15) == 0;
-}
-
 template <class T>
 static void standard_step(void* x, const void* noise_pred, const int32_t* src_col, uint8_t* mask, const void* noise, int b, int c, int h,
                           int w, int op, const StepCoeffs& k, hipStream_t stream) {
     constexpr int W = 16 / sizeof(T);
     const size_t row_bytes = (size_t)w * sizeof(T);
-    const size_t fit = SL_LDS_BYTES / row_bytes;   // >= 1: w <= SL_MAX_WIDTH
+    const size_t fit = SL_LDS_BYTES / row_bytes;   // >= 1: w <= LATENT_MAX_WIDTH
     const int group = op == CS_STANDARD_NONE ? c : (int)(fit < (size_t)c ? fit : (size_t)c);
     const size_t lds = op == CS_STANDARD_NONE ? 0 : (size_t)group * row_bytes;
-    const dim3 grid((unsigned)((size_t)b * h)), block(SL_THREADS);
     // whole chunks per row, and every row then starts on the 16-byte grid
-    if (w % W == 0 && aligned16({x, noise_pred, noise}))
-        hipLaunchKernelGGL((k_standard_step<T, W>), grid, block, lds, stream, (T*)x, (const T*)noise_pred, src_col, mask, (const T*)noise, b,
-                           c, h, w, group, op, k);
-    else
-        hipLaunchKernelGGL((k_standard_step<T, 1>), grid, block, lds, stream, (T*)x, (const T*)noise_pred, src_col, mask, (const T*)noise, b,
-                           c, h, w, group, op, k);
+    launch_wide_or_narrow(w % W == 0 && aligned16({x, noise_pred, noise}), k_standard_step<T, W>, k_standard_step<T, 1>,
+                          dim3((unsigned)((size_t)b * h)), dim3(SL_THREADS), lds, stream, as<T>(x), as<T>(noise_pred), src_col, mask,
+                          as<T>(noise), b, c, h, w, group, op, k);
 }
-
-int standard_step_max_width() { return SL_MAX_WIDTH; }
 
 hipError_t launch_standard_step(void* x, const void* noise_pred, int dtype, int b, int c, int h, int w, float guidance, const float cf[4],
                                 int op, const int32_t* src_col, uint8_t* mask, const void* noise, hipStream_t stream) {
     const StepCoeffs k{guidance, cf[0], cf[1], cf[2], cf[3]};
-    if (dtype == CS_LATENT_F32)
-        standard_step<float>(x, noise_pred, src_col, mask, noise, b, c, h, w, op, k, stream);
-    else if (dtype == CS_LATENT_F16)
-        standard_step<_Float16>(x, noise_pred, src_col, mask, noise, b, c, h, w, op, k, stream);
-    else
-        standard_step<__bf16>(x, noise_pred, src_col, mask, noise, b, c, h, w, op, k, stream);
+    with_latent_type(dtype, [&](auto tag) { standard_step<decltype(tag)>(x, noise_pred, src_col, mask, noise, b, c, h, w, op, k, stream); });
     return hipGetLastError();
 }
 

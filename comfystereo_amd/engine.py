@@ -89,6 +89,29 @@ def _launch(device, fn, *args):
         _native.check(fn(*args, _stream()))
 
 
+def _like_x(name, t, x, shape, what, no_grad=""):
+    """A tensor that goes with `x` in an in-place step: x's dtype, this shape ("<name> must <what> <t's shape>"), contiguous, no
+    grad."""
+    _tensor(name, t, like=(x.dtype, f"x and {name} must share one dtype, got {x.dtype} and {{got}}"), shape=(shape, what), contiguous=True,
+            no_grad=no_grad)
+
+
+def _numbers(lead, coeffs, names, counted=False):
+    """`lead` (guidance, or nothing) and `coeffs`, as many as `names`, as finite floats, or ValueError.  counted: the wording of
+    the DDIM wrappers, which name the count they got, show the values as a list and let float()'s own ValueError through."""
+    def wanted(got=""):
+        return f"coeffs must be {('two', 'three', 'four')[len(names) - 2]} numbers ({', '.join(names)}){got}"
+    try:
+        vals = [float(v) for v in lead] + [float(c) for c in coeffs]
+    except (TypeError,) if counted else (TypeError, ValueError):
+        raise ValueError(wanted()) from None
+    if len(vals) != len(lead) + len(names):
+        raise ValueError(wanted(f", got {len(vals) - len(lead)}" if counted else ""))
+    if not all(math.isfinite(v) for v in vals):
+        raise ValueError(f"{'guidance and ' if lead else ''}coeffs must be finite, got {vals if counted else tuple(vals)}")
+    return vals
+
+
 def _dtype_code(t, table):
     """t's dtype in one of the library's dtype enums (_native.ATTN_DTYPE, _native.LATENT_DTYPE)."""
     return table[_DTYPE_NAMES[t.dtype]]
@@ -671,6 +694,9 @@ def differentiable_attention(q, k, v, heads, scale, native_half=False):
 
 
 # ---- StereoDiffusion Standard mode's latent shift, mask and merge (cs_latent_shift_*, cs_decode_to_codes) ----
+LATENT_MAX_WIDTH = 8192   # the columns cs_latent_shift_plan takes, and cs_standard_step with its tables (cs_latent.h LATENT_MAX_WIDTH)
+
+
 def latent_shift_plan(disp, scale_factor, stereo_offset_exponent=1.0):
     """cs_latent_shift_plan on a device tensor: disp [B,H,W] float32, the disparity at the latents' size -> src_col int32
     [B,H,W]: for every destination column of the right view of stereo_shift_torch(latents, disp, scale_factor) the source
@@ -681,8 +707,8 @@ def latent_shift_plan(disp, scale_factor, stereo_offset_exponent=1.0):
     if not (math.isfinite(float(scale_factor)) and math.isfinite(float(stereo_offset_exponent))):
         raise ValueError(f"scale_factor and stereo_offset_exponent must be finite, got {scale_factor} and {stereo_offset_exponent}")
     b, h, w = disp.shape
-    if w > 8192:
-        raise ValueError(f"rows of {w} columns: cs_latent_shift_plan takes up to 8192 (it is made for latents)")
+    if w > LATENT_MAX_WIDTH:
+        raise ValueError(f"rows of {w} columns: cs_latent_shift_plan takes up to {LATENT_MAX_WIDTH} (it is made for latents)")
     _on_gpu(disp, no_gpu_error=True)
     L = _native.lib()
     src_col = torch.empty((b, h, w), dtype=torch.int32, device=disp.device)
@@ -751,14 +777,7 @@ def _flat_like(first, tensors, what):
 
 
 def _step_scalars(guidance, coeffs):
-    try:
-        vals = [float(guidance)] + [float(c) for c in coeffs]
-    except TypeError:
-        raise ValueError("coeffs must be four numbers (c1, c2, c3, c4)") from None
-    if len(vals) != 5:
-        raise ValueError(f"coeffs must be four numbers (c1, c2, c3, c4), got {len(vals) - 1}")
-    if not all(math.isfinite(v) for v in vals):
-        raise ValueError(f"guidance and coeffs must be finite, got {vals}")
+    vals = _numbers((guidance,), coeffs, ("c1", "c2", "c3", "c4"), counted=True)
     if vals[2] == 0.0:
         raise ValueError("coeffs[1] (the square root of alpha_t) must not be 0")
     return vals
@@ -885,24 +904,16 @@ def inpaint_latent_init(mean_img, mean_masked, noise, coeffs, x, img_latent=None
     n, c, hl, wl = mean_img.shape
     if c != 4:
         raise ValueError(f"mean_img must be [N,4,hl,wl], got shape {tuple(mean_img.shape)}")
+    what = f"have mean_img's shape {tuple(mean_img.shape)}, got"
     _tensor("mean_masked", mean_masked, like=(mean_img.dtype, f"mean_img and mean_masked must share one dtype, got {mean_img.dtype} and {{got}}"),
-            shape=(mean_img.shape, f"have mean_img's shape {tuple(mean_img.shape)}, got"), contiguous=True)
+            shape=(mean_img.shape, what), contiguous=True)
     _unet_input(x, n, hl, wl)
     named = [("mean_masked", mean_masked), ("x", x)]
     for name, t in (("noise", noise), ("img_latent", img_latent), ("decode_in", decode_in)):
         if t is not None:
-            _tensor(name, t, like=(x.dtype, f"x and {name} must share one dtype, got {x.dtype} and {{got}}"),
-                    shape=(mean_img.shape, f"have mean_img's shape {tuple(mean_img.shape)}, got"), contiguous=True, no_grad="")
+            _like_x(name, t, x, mean_img.shape, what)
             named.append((name, t))
-    if noise is None:
-        sa, sb = 1.0, 0.0
-    else:
-        try:
-            sa, sb = (float(v) for v in coeffs)
-        except (TypeError, ValueError):
-            raise ValueError("coeffs must be two numbers (sa, sb)") from None
-        if not (math.isfinite(sa) and math.isfinite(sb)):
-            raise ValueError(f"coeffs must be finite, got {(sa, sb)}")
+    sa, sb = (1.0, 0.0) if noise is None else _numbers((), coeffs, ("sa", "sb"))
     _same_device(("mean_img", mean_img), *named)
     _on_gpu(mean_img, no_gpu_error=True)
     if img_latent is None:
@@ -939,15 +950,11 @@ def plms_step(noise_pred, x, kind, guidance, coeffs, e_out=None, history=(), cur
         raise ValueError("cur_sample goes with the kinds 'first' (which writes it) and 'second' (which reads it) only")
     named = [(f"history[{i}]", t) for i, t in enumerate(history)]
     named += [(name, t) for name, t in (("e_out", e_out), ("cur_sample", cur_sample), ("decode_in", decode_in)) if t is not None]
+    shape = (n, 4, hl, wl)
+    what = f"be [N,4,hl,wl] = {shape}, got shape"
     for name, t in named:
-        _tensor(name, t, like=(x.dtype, f"x and {name} must share one dtype, got {x.dtype} and {{got}}"),
-                shape=((n, 4, hl, wl), f"be [N,4,hl,wl] = {(n, 4, hl, wl)}, got shape"), contiguous=True, no_grad="")
-    try:
-        g, sc, da, denom = [float(guidance)] + [float(v) for v in coeffs]
-    except (TypeError, ValueError):
-        raise ValueError("coeffs must be three numbers (sc, da, denom)") from None
-    if not all(math.isfinite(v) for v in (g, sc, da, denom)):
-        raise ValueError(f"guidance and coeffs must be finite, got {(g, sc, da, denom)}")
+        _like_x(name, t, x, shape, what)
+    g, sc, da, denom = _numbers((guidance,), coeffs, ("sc", "da", "denom"))
     if denom == 0.0:
         raise ValueError("coeffs[2] (denom) must not be 0")
     _same_device(("noise_pred", noise_pred), ("x", x), *named)
@@ -979,12 +986,10 @@ def standard_step(noise_pred, x, guidance, coeffs, op="none", src_col=None, mask
     if n4 % 4:
         raise ValueError(f"x must be [4B,C,h,w] (left views, right views, and their copy), got shape {tuple(x.shape)}")
     b = n4 // 4
-    _tensor("noise_pred", noise_pred, like=(x.dtype, f"x and noise_pred must share one dtype, got {x.dtype} and {{got}}"),
-            shape=(x.shape, f"have x's shape {tuple(x.shape)}, got"), contiguous=True, no_grad="cs_standard_step is not differentiable")
+    _like_x("noise_pred", noise_pred, x, x.shape, f"have x's shape {tuple(x.shape)}, got", no_grad="cs_standard_step is not differentiable")
     named = [("noise_pred", noise_pred)]
     if noise is not None:
-        _tensor("noise", noise, like=(x.dtype, f"x and noise must share one dtype, got {x.dtype} and {{got}}"),
-                shape=((b, c, h, w), f"be [B,C,h,w] = {(b, c, h, w)}, got shape"), contiguous=True, no_grad="")
+        _like_x("noise", noise, x, (b, c, h, w), f"be [B,C,h,w] = {(b, c, h, w)}, got shape")
         named.append(("noise", noise))
     if op != "none":
         _tensor("src_col", src_col, dtypes=((torch.int32,), "int32 (latent_shift_plan's)"),
@@ -993,8 +998,8 @@ def standard_step(noise_pred, x, guidance, coeffs, op="none", src_col=None, mask
         named += [("src_col", src_col), ("mask", mask)]
     else:
         src_col = mask = None
-    if w > 8192:
-        raise ValueError(f"rows of {w} columns: cs_standard_step takes up to 8192 (latent_shift_plan's limit)")
+    if w > LATENT_MAX_WIDTH:
+        raise ValueError(f"rows of {w} columns: cs_standard_step takes up to {LATENT_MAX_WIDTH} (latent_shift_plan's limit)")
     g, c1, c2, c3, c4 = _step_scalars(guidance, coeffs)
     _same_device(("x", x), *named)
     _on_gpu(x, no_gpu_error=True)

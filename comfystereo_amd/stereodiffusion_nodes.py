@@ -232,13 +232,11 @@ class _StandardLoop:
 
     def step(self, i, t, latents, context):
         latents = diffusion_step(self.model, self.controller, latents, context, t, self.guidance_scale, low_resource=False)
-        if i == self.shift_step:
+        op = self._op(i)
+        if op != "none":
             latents = latents.contiguous()
-            engine.latent_shift_apply(latents[:1], latents[1:], self.src_col, self.mask, "first", noise=self.noise)
-            self.shifted = True
-        elif self.shifted and i > self.shift_step and i % self.reshift_interval == 0:
-            latents = latents.contiguous()
-            engine.latent_shift_apply(latents[:1], latents[1:], self.src_col, self.mask, "reshift")
+            engine.latent_shift_apply(latents[:1], latents[1:], self.src_col, self.mask, op, noise=self.noise if op == "first" else None)
+            self.shifted = self.shifted or op == "first"
         return latents
 
 
@@ -289,24 +287,21 @@ def _stereo_latents(model, prompt, uncond_embeddings, latent, disparity, scale_f
                 raise ValueError(f"noise {tuple(noise.shape)} must have the latents' shape {tuple(latents.shape)}")
             noise = noise.to(latents.device, latents.dtype)[1:].contiguous()
         loop = _StandardLoop(model, disp_latent, scale_factor, deblur, steps, guidance_scale, noise)
+        timesteps = model.scheduler.timesteps[-steps:]
+
+        def context(i):
+            uncond = uncond_emb if uncond_embeddings is None else uncond_embeddings[i].expand(*text_embeddings.shape)
+            return torch.cat([uncond, text_embeddings])
+
         if loop.fused:
-            timesteps = model.scheduler.timesteps[-steps:]
-            if uncond_embeddings is not None:
-                contexts = [torch.cat([uncond_embeddings[i].expand(*text_embeddings.shape), text_embeddings]) for i in range(len(timesteps))]
-            else:
-                contexts = [torch.cat([uncond_emb, text_embeddings])] * len(timesteps)
+            # every step's context before the loop (one for all without null-text embeddings): a fused step allocates nothing
+            contexts = [context(0)] * len(timesteps) if uncond_embeddings is None else [context(i) for i in range(len(timesteps))]
             latents = loop.begin(latents, timesteps)
-            for i in range(len(timesteps)):
+        for i in range(len(timesteps)):
+            if loop.fused:
                 loop.fused_step(i, contexts[i])
-                if on_step is not None:
-                    on_step(i, latents)
-            return latents, (loop.mask if loop.shifted else None)
-        for i, t in enumerate(model.scheduler.timesteps[-steps:]):
-            if uncond_embeddings is not None:
-                context = torch.cat([uncond_embeddings[i].expand(*text_embeddings.shape), text_embeddings])
             else:
-                context = torch.cat([uncond_emb, text_embeddings])
-            latents = loop.step(i, t, latents, context)
+                latents = loop.step(i, timesteps[i], latents, context(i))
             if on_step is not None:
                 on_step(i, latents)
         return latents, (loop.mask if loop.shifted else None)

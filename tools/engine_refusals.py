@@ -14,6 +14,9 @@ Nothing is ever launched: while the cases run, the library is replaced by a guar
 limits, cs_output_shape) and raises `Accepted` from any other entry point.  A case that reaches one, or returns, was not refused:
 the tool fails.  The refusals engine.py raised as `assert` until its argument checks were single-sourced are stored as the
 ValueError they are now (FORMER_ASSERTS); a library from before that records AssertionError and --former-asserts rewrites the rows.
+
+The functions of LATER -- the wrappers of the loops between model calls, which came after that -- were recorded from the engine as
+it was before their own checks were single-sourced, and appended: the rows of the functions before them are the first recording's.
 """
 import argparse
 import json
@@ -40,6 +43,7 @@ FORMER_ASSERTS = {
     "forward_warp_mesh": "image must have 3 channels ([B,3,H,W])",
     "stereo_shift": "depthmaps must be [B,H,W] like input_images [B,C,H,W]",
 }
+LATER = ("inpaint_image_prep", "inpaint_latent_init", "plms_step", "standard_step")
 
 
 class CorpusError(Exception):
@@ -346,6 +350,93 @@ def _functions(dev):
                       + values("step", 0, -1, 1.0, True, "1", None) + values("lr", float("nan"), float("inf"), "abc", None)
                       + values("eps", -1e-8, float("nan"), "abc") + values("beta1", 1.0, -0.1, float("nan"), "abc")
                       + values("beta2", 1.0, 1.5, None) + [a for n in adam[1:] for a in grad(n)])
+    F.update(_loop_functions(dev))
+    return F
+
+
+def _each(names, *kinds):
+    return [a for n in names for kind in kinds for a in kind(n)]
+
+
+def twice(arg, first, second):
+    """One tensor spoilt in two ways: which fault is reported is the order of its checks."""
+    (ia, fa), (ib, fb) = first(arg)[0], second(arg)[0]
+    return [(f"{ia} & {ib.split(':', 1)[1]}", lambda kw: (fa(kw), fb(kw)))]
+
+
+def _orders(names, dtype="f16"):
+    """dtype before shape before stride, for every tensor of `names`"""
+    to, grow = (lambda n: cast(n, dtype)), (lambda n: resize(n, -1))
+    return [a for n in names for a in twice(n, to, grow) + twice(n, grow, strided) + twice(n, to, strided)]
+
+
+def _loop_functions(dev):
+    """The wrappers of the loops between model calls (LATER): Fast mode's three and Standard mode's fused step."""
+    F = {}
+    u8 = dict(dtype=torch.uint8)
+    few = lambda n, skip=(): junk(n, skip=("list", "tuple", "float", "dict") + skip)   # noqa: E731  (room for pairs of faults)
+    lat = lambda *lead: _z(dev, *lead, 2, 4)   # noqa: E731
+    sizes = values("latent_size", (0, 4), (2, -1), (3, 4), ("a", 4), (2,), (2, 4, 1), None, 3)
+    prep = ("filled_u8", "mask", "x")
+    F["inpaint_image_prep"] = (
+        engine.inpaint_image_prep,
+        lambda: dict(filled_u8=_z(dev, 1, 8, 16, 3, **u8), mask=_z(dev, 1, 8, 16, **u8), x=lat(2, 9), latent_size=(2, 4)),
+        _each(prep, few, fewer, more, strided) + cast("filled_u8", "f32", "i32", "bool", "f16") + cast("mask", "f32", "i32", "f16", "i64")
+        + cast("x", "f64", "i32", "u8") + resize("filled_u8", 3) + resize("filled_u8", 1, 0) + resize("mask", 1) + resize("x", 0)
+        + resize("x", 1) + resize("x", 3) + grad("x") + sizes + _orders(("x",), "f64") + host(dev, *prep))
+    opt = ("noise", "img_latent", "decode_in")
+    F["inpaint_latent_init"] = (
+        engine.inpaint_latent_init,
+        lambda: dict(mean_img=lat(1, 4), mean_masked=lat(1, 4), noise=lat(1, 4), coeffs=(0.8, 0.6), x=lat(2, 9), img_latent=lat(1, 4),
+                     decode_in=lat(1, 4)),
+        _each(("mean_img", "mean_masked", "x"), few, fewer, more, strided) + _each(opt, lambda n: few(n, ("None",)), fewer, more, strided, grad)
+        + cast("mean_img", "f64", "i32") + cast("mean_masked", "f64", "i32", "f16", "bf16") + cast("x", "f64", "i32", "f16")
+        + _each(opt, lambda n: cast(n, "f64", "f16", "bf16")) + resize("mean_img", 1) + resize("mean_img", 2, 0) + resize("mean_masked", 3)
+        + resize("x", 0) + resize("x", 3) + resize("noise", 2) + resize("img_latent", 0) + resize("decode_in", 3) + grad("x")
+        + _orders(opt) + _orders(("mean_masked",))
+        + values("coeffs", (0.8,), (0.8, 0.6, 0.1), (float("nan"), 0.6), (0.8, float("inf")), ("a", 0.6), (None, 0.6), None, 3.0)
+        + host(dev, "mean_img", "mean_masked", "x", *opt))
+    first = lambda f: lambda hist: (f(hist[0]),)   # noqa: E731
+    outs = ("e_out", "decode_in")
+    F["plms_step"] = (
+        engine.plms_step,
+        lambda: dict(noise_pred=lat(2, 4), x=lat(2, 9), kind="order2", guidance=3.0, coeffs=(1.0, 0.5, 0.9), e_out=lat(1, 4),
+                     history=(lat(1, 4),), cur_sample=None, decode_in=lat(1, 4)),
+        values("kind", "third", None, 0, "first", "second", "order4")
+        + _each(("noise_pred", "x") + outs, fewer, more, strided, grad) + _each(("noise_pred", "x", "e_out"), few)
+        + few("cur_sample", ("None",)) + few("decode_in", ("None",)) + [_set("cur_sample", "f16-tensor", lat(1, 4).half())]
+        + _each(("noise_pred", "x"), lambda n: cast(n, "f64", "i32", "f16", "bf16")) + _each(outs, lambda n: cast(n, "f64", "f16", "bf16"))
+        + resize("noise_pred", 0) + resize("noise_pred", 1) + resize("noise_pred", 2, 0) + resize("x", 1) + resize("x", 3)
+        + resize("e_out", 0) + resize("decode_in", 3) + _orders(outs)
+        + [_set("history", "none", ()), _set("history", "two", (lat(1, 4), lat(1, 4))), _set("history", "None", None),
+           _set("history", "int", 3), _set("history", "junk", ("a",)), _set("history", "[None]", (None,)),
+           _map("history", "f16", first(lambda t: t.half())), _map("history", "shape", first(lambda t: t[:, :3])),
+           _map("history", "strided", first(lambda t: t.new_zeros(1, 4, 2, 4, 2)[..., 0])),
+           _map("history", "requires-grad", first(lambda t: t.clone().requires_grad_(True)))]
+        + [("kind=first:history", lambda kw: kw.update(kind="first", history=())),
+           ("kind=second:no-e_out", lambda kw: kw.update(kind="second", e_out=None)),
+           ("kind=order4:history", lambda kw: kw.update(kind="order4", history=(lat(1, 4), lat(1, 4))))]
+        + values("guidance", float("nan"), float("inf"), "abc", None)
+        + values("coeffs", (1.0, 0.5), (1.0, 0.5, 0.9, 0.1), (1.0, 0.5, 0.0), (float("nan"), 0.5, 0.9), (1.0, 0.5, float("inf")),
+                 ("a", 0.5, 0.9), None, 3.0)
+        + host(dev, "noise_pred", "x", *outs) + ([_map("history", "host", first(lambda t: t.cpu()))] if dev != "cpu" else []))
+    big = ("x", "noise_pred", "noise")
+    wide = lambda *lead, **kw: _z(dev, *lead, 2, 8193, **kw)   # noqa: E731
+    F["standard_step"] = (
+        engine.standard_step,
+        lambda: dict(noise_pred=_z(dev, 4, 4, 2, 8), x=_z(dev, 4, 4, 2, 8), guidance=3.0, coeffs=COEFFS, op="first",
+                     src_col=_z(dev, 1, 2, 8, dtype=torch.int32), mask=_z(dev, 1, 2, 8, **u8), noise=_z(dev, 1, 4, 2, 8)),
+        values("op", "again", None, 0, "reshift", "none") + _each(("x", "noise_pred", "src_col", "mask"), few)
+        + few("noise", ("None",)) + _each(big + ("src_col", "mask"), fewer, more, strided) + _each(big, grad)
+        + _each(("x", "noise_pred"), lambda n: cast(n, "f64", "i32", "f16", "bf16")) + cast("noise", "f64", "f16", "bf16")
+        + cast("src_col", "i64", "f32", "i16", "bool") + cast("mask", "bool", "f32", "i32", "i64")
+        + resize("x", 0) + resize("x", 1, 0) + resize("noise_pred", 3) + resize("noise", 1) + resize("src_col", 2) + resize("mask", 1)
+        + _orders(("noise_pred", "noise")) + _orders(("src_col",), "i64") + _orders(("mask",), "bool")
+        + [("w=8193", lambda kw: kw.update(noise_pred=wide(4, 4), x=wide(4, 4), noise=wide(1, 4), src_col=wide(1, dtype=torch.int32),
+                                           mask=wide(1, **u8)))]
+        + values("guidance", float("nan"), "abc", None)
+        + values("coeffs", (0.6, 0.8, 0.5), (0.6, 0.0, 0.5, 0.9), (0.6, float("inf"), 0.5, 0.9), 3.0, None, (0.6, 0.8, 0.5, 0.9, 1.0))
+        + host(dev, *big, "src_col", "mask"))
     return F
 
 
@@ -420,6 +511,9 @@ def dump(rows, device, out):
     if any(kind == "ValueError" and msg == FORMER_ASSERTS.get(fn) for fn, _, kind, msg in rows):
         comment += ("  The rows of " + ", ".join(FORMER_ASSERTS) + " with the messages of tools/engine_refusals.py FORMER_ASSERTS"
                     " were AssertionError (no message) then: stored as ValueError.")
+    if any(fn in LATER for fn, _, _, _ in rows):
+        comment += ("  The rows of " + ", ".join(LATER) + " were appended later, recorded before the checks of the latent-loop"
+                    " wrappers were single-sourced.")
     enc = lambda v: json.dumps(v, separators=(",", ":"), ensure_ascii=True)   # noqa: E731
     out.write('{"comment":%s,\n"device":%s,\n"outcomes":%s,\n"cases":{\n' % (enc(comment), enc(device), enc(outcomes)))
     out.write(",\n".join(f"{enc(fn)}:{enc(cases_)}" for fn, cases_ in by_function.items()) + "\n}}\n")

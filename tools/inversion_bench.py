@@ -72,7 +72,7 @@ def main():
             e = emb_f.sum() * 0 + eps
             loss = engine.NullTextLoss.apply(e, eps_cond, cur, prev, GUIDANCE, COEFFS)
             (grad,) = torch.autograd.grad(loss, [emb_f])
-            engine.adam_step(emb_f, grad, m, v, 1e-2, state["k"])
+            engine.adam_step(emb_f, grad.contiguous(), m, v, 1e-2, state["k"])
 
         emb_s = emb_f.detach().clone().requires_grad_(True)
         opt = torch.optim.Adam([emb_s], lr=1e-2)
