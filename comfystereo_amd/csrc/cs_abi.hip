@@ -383,7 +383,7 @@ static void stats_prepass(uint32_t* stats, int frames, const float* depth, size_
     hipLaunchKernelGGL(k_stats_init, dim3((frames * ST_WORDS + 255) / 256), dim3(256), 0, stream, stats, frames);
     if (!depth) return;
     const dim3 grid(grid_for(per_frame, 256), frames);
-    if (nan == NanInDepth::POISONS)   // cs_stereo_shift and cs_latent_shift_plan: torch's min / max of the whole tensor
+    if (nan == NanInDepth::POISONS)   // the latent shifts, cs_grid_warp, cs_inpaint_prepare: torch's min / max return a NaN
         hipLaunchKernelGGL(k_minmax<true>, grid, dim3(256), 0, stream, depth, (int)per_frame, stats, ST_L_MIN, ST_L_MAX);
     else
         hipLaunchKernelGGL(k_minmax<false>, grid, dim3(256), 0, stream, depth, (int)per_frame, stats, ST_L_MIN, ST_L_MAX);
@@ -1140,7 +1140,7 @@ int cs_grid_warp(const float* image, const float* depth, int n, int c, int h, in
     if (!warped && !mask) return CS_OK;
     uint32_t* stats = (uint32_t*)workspace;
     float* fconst = (float*)((char*)workspace + stats_bytes(n));
-    stats_prepass(stats, n, depth, (size_t)h * w, stream);
+    stats_prepass(stats, n, depth, (size_t)h * w, stream, NanInDepth::POISONS);   // (amin / amax of a frame with a NaN are NaN: the frame is flat)
     hipError_t e = launch_gridwarp(image, depth, n, c, h, w, divergence_px, separation_px, exponent, convergence, op, padding,
                                    warped, mask, stats, fconst, stream);
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_grid_warp");
@@ -1187,7 +1187,7 @@ int cs_inpaint_prepare(const float* image, const float* depth, int n, int h, int
     const size_t bits = al256(inpaint_prep_bits_bytes(n, h, w));
     uint32_t* nvb = (uint32_t*)((char*)workspace + stats_bytes(n));
     uint32_t* disb = (uint32_t*)((char*)nvb + bits);
-    stats_prepass(stats, n, depth, (size_t)h * w, stream);
+    stats_prepass(stats, n, depth, (size_t)h * w, stream, NanInDepth::POISONS);   // (d.min() / d.max() of a frame with a NaN are NaN: the frame is flat)
     hipError_t e = launch_inpaint_prep(image, depth, n, h, w, divergence_px, threshold, warped, filled, mask, warped_u8, filled_u8,
                                        stats, nvb, disb, stream);
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_inpaint_prepare");

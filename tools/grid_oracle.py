@@ -14,6 +14,10 @@ import torch
 F32 = np.float32
 PADDINGS = ("border", "zeros", "reflection")
 STRETCH_PIXELS = 3
+# the two operations whose edge cases the designed inputs of tools/grid_edge_inputs.py sit on, as names, so that
+# tests/test_grid_edges_surface.py can put a wrong one in their place and see the designed cases notice
+rint = np.rint            # nearest sampling rounds half to even
+above = np.greater        # every threshold is a strict comparison
 
 
 def linspace(n):
@@ -30,18 +34,19 @@ def linspace(n):
 
 def fma32(a, b, c):
     """float32 fused multiply-add a * b + c (one rounding), exact: the product is exact in float64, the sum is an error-free
-    TwoSum, and a float64 sum that sits exactly on a float32 midpoint is resolved by the sign of its error term."""
+    TwoSum, and a float64 sum that sits exactly on a float32 midpoint is resolved by the sign of its error term.  An infinite or
+    NaN sum (an infinite operand, inf * 0, inf - inf) is the float64 result as it stands: there is no midpoint to resolve."""
     a, b, c = (np.asarray(v, dtype=np.float64) for v in (a, b, c))
-    p = a * b
-    s = p + c
-    bv = s - p
-    err = (p - (s - bv)) + (c - bv)
-    r = s.astype(F32)
     with np.errstate(invalid="ignore", over="ignore"):
+        p = a * b
+        s = p + c
+        bv = s - p
+        err = (p - (s - bv)) + (c - bv)
+        r = s.astype(F32)
         diff = s - r.astype(np.float64)
         nb = np.nextafter(r, np.where(diff > 0, F32(np.inf), F32(-np.inf))).astype(F32)
         mid = (r.astype(np.float64) + nb.astype(np.float64)) * 0.5
-        past = (s == mid) & (diff != 0) & (err != 0) & ((err > 0) == (diff > 0))
+        past = np.isfinite(diff) & (s == mid) & (diff != 0) & (err != 0) & ((err > 0) == (diff > 0))
     return np.where(past, nb, r).astype(F32)
 
 
@@ -67,13 +72,13 @@ def pixel_offset(depth, div, sep, e, conv):
     normalised by its own min / max (zero when the range is not above 1e-6), shifted by the convergence point and curved."""
     d = np.asarray(depth, dtype=F32)
     b = d.shape[0]
-    if (d.reshape(b, -1).max(1) > F32(1.0)).any():
+    if above(d.reshape(b, -1).max(1), F32(1.0)).any():
         d = d / F32(255.0)
     mn = d.reshape(b, -1).min(1)[:, None, None]
     mx = d.reshape(b, -1).max(1)[:, None, None]
     rng = mx - mn
     with np.errstate(divide="ignore", invalid="ignore"):
-        nd = np.where(rng > F32(1e-6), (d - mn) / np.maximum(rng, F32(1e-6)), F32(0.0)).astype(F32)
+        nd = np.where(above(rng, F32(1e-6)), (d - mn) / np.maximum(rng, F32(1e-6)), F32(0.0)).astype(F32)
     s = nd - F32(conv)
     od = np.sign(s) * _pow(np.abs(s), e)
     return od * F32(div) + F32(sep)
@@ -95,7 +100,7 @@ def forward_gap_mask(po):
     bi, yi, _ = np.nonzero(ok)
     hit[bi, yi, np.trunc(dest[ok]).astype(np.int64)] = True
     gap = ~hit
-    grad = np.abs(po[:, :, 1:] - po[:, :, :-1]) > F32(1.5)
+    grad = above(np.abs(po[:, :, 1:] - po[:, :, :-1]), F32(1.5))
     edge = np.zeros((b, h, w), dtype=bool)
     edge[:, :, :-1] = grad
     edge[:, :, 1:] |= grad
@@ -140,19 +145,21 @@ def stretch_grid(gx, gap):
 
 
 def source_coord(g, size, padding):
-    """grid_sample's unnormalisation (align_corners=True) and padding of one axis."""
-    x = (g + F32(1.0)) * (F32(size - 1) / F32(2.0))
-    if padding == "reflection":
-        if size <= 1:
-            x = np.zeros_like(x)
-        else:
-            span = F32(size - 1) * F32(2.0)
-            a = np.abs(x)
-            flips = np.trunc(a / span)
-            extra = fma32(-flips, span, a)
-            x = np.minimum(extra, span - extra)
-    if padding in ("border", "reflection"):
-        x = np.minimum(np.maximum(x, F32(0.0)), F32(size - 1))
+    """grid_sample's unnormalisation (align_corners=True) and padding of one axis.  The clip of border and reflection padding
+    takes a NaN coordinate to 0 (CPU torch orders its clamp so; an infinite grid value reflects to NaN: inf - inf * span)."""
+    with np.errstate(invalid="ignore"):
+        x = (np.asarray(g, dtype=F32) + F32(1.0)) * (F32(size - 1) / F32(2.0))
+        if padding == "reflection":
+            if size <= 1:
+                x = np.zeros_like(x)
+            else:
+                span = F32(size - 1) * F32(2.0)
+                a = np.abs(x)
+                flips = np.trunc(a / span)
+                extra = fma32(-flips, span, a)
+                x = np.minimum(extra, span - extra)
+        if padding in ("border", "reflection"):
+            x = np.minimum(np.fmax(x, F32(0.0)), F32(size - 1))
     return x.astype(F32)
 
 
@@ -183,8 +190,8 @@ def sample_bilinear(img, gx, gy, padding="border"):
 def sample_nearest(img, gx, gy, padding="border"):
     """F.grid_sample(..., mode='nearest', align_corners=True): coordinates rounded half to even."""
     b, c, h, w = img.shape
-    x = np.rint(source_coord(gx, w, padding))
-    y = np.rint(source_coord(gy, h, padding))
+    x = rint(source_coord(gx, w, padding))
+    y = rint(source_coord(gy, h, padding))
     inb = (x > F32(-1.0)) & (x < F32(w)) & (y > F32(-1.0)) & (y < F32(h))
     xs = np.where(inb, x, F32(0.0)).astype(np.int64)
     ys = np.where(inb, y, F32(0.0)).astype(np.int64)
@@ -221,11 +228,11 @@ def detect_disocclusions_gpu(depth, grid, gxw, threshold=0.02):
     if w < 2:
         raise IndexError("detect_disocclusions_gpu needs W >= 2 (the last column copies the one before it)")
     wd = sample_nearest(np.asarray(depth, F32)[None, None], grid[..., 0], grid[..., 1], "border")[0, 0]
-    deep = (wd - depth) > F32(threshold)
+    deep = above(wd - depth, F32(threshold))
     grad = np.empty((h, w), dtype=F32)
     grad[:, :-1] = np.abs(gxw[:, 1:] - gxw[:, :-1])
     grad[:, -1] = grad[:, -2]
-    return deep | (grad > F32(2.0 / w * 3.0))
+    return deep | above(grad, F32(2.0 / w * 3.0))
 
 
 def interpolate_fill_gpu(img, mask):

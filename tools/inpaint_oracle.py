@@ -20,11 +20,11 @@ def depth_chain(depth):
     """depth [H,W] -> d - 0.5: divided by 255 when the frame's maximum is above 1, normalised by the frame's own min / max when
     max - min is above 1e-6 (zeros otherwise)."""
     d = np.asarray(depth, dtype=F32)
-    if d.max() > F32(1.0):
+    if go.above(d.max(), F32(1.0)):
         d = d / F32(255.0)
     mn, mx = d.min(), d.max()
     rng = mx - mn
-    if rng > F32(1e-6):
+    if go.above(rng, F32(1e-6)):
         d = (d - mn) / rng
     else:
         d = np.zeros_like(d)
@@ -64,7 +64,7 @@ def frame(img, depth, divergence_px, threshold=0.05):
     valid = (gxw[0] >= F32(-1.0)) & (gxw[0] <= F32(1.0))
     d2 = d + F32(0.5)
     wd = go.sample_nearest(d2[None, None], gxw, gy, "border")[0, 0]
-    dis = dilate3((wd - d2) > F32(threshold))
+    dis = dilate3(go.above(wd - d2, F32(threshold)))
     mask0 = ~valid | dis
     mask = dilate3(mask0)   # (an empty mask0 stays empty: the reference's early return)
     left, right = nearest_borders(~mask)
