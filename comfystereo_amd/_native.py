@@ -162,6 +162,10 @@ SIGNATURES = {
     "cs_null_loss_workspace_bytes": (_size, [_ll]),
     "cs_null_loss_grad": (_int, [_vp] * 7 + [_int, _ll] + [_dbl] * 5 + [_vp, _size, _vp]),
     "cs_adam_step": (_int, [_vp, _vp, _vp, _vp, _int, _ll, _dbl, _dbl, _dbl, _dbl, _int, _vp]),
+    # null-text optimisation on F frames at once: per-frame losses, stop flags on the device, an Adam that skips stopped frames
+    "cs_null_loss_frames_workspace_bytes": (_size, [_ll, _ll]),
+    "cs_null_loss_grad_frames": (_int, [_vp] * 9 + [_int, _ll, _ll] + [_dbl] * 6 + [_vp, _size, _vp]),
+    "cs_adam_step_frames": (_int, [_vp] * 5 + [_int, _ll, _ll, _dbl, _dbl, _dbl, _dbl, _int, _vp]),
     # StereoDiffusion Fast mode's inpainting loop outside its models
     "cs_inpaint_image_prep": (_int, [_vp, _vp] + [_int] * 6 + [_vp, _vp, _vp, _vp]),
     "cs_inpaint_latent_init": (_int, [_vp, _vp, _int, _vp, _int] + _nhw + [_dbl, _dbl, _vp, _vp, _vp, _vp]),

@@ -1461,23 +1461,105 @@ int cs_null_loss_grad(const void* eps_uncond, const void* eps_cond, const void* 
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_null_loss_grad");
 }
 
+// the checks and the coefficients cs_adam_step and cs_adam_step_frames share
+static const char* adam_args_error(int dtype, double lr, double beta1, double beta2, double eps, int step) {
+    if (!latent_dtype_ok(dtype)) return "unknown dtype (CS_LATENT_F32 / F16 / BF16)";
+    if (step < 1) return "the step number counts from 1";
+    if (!finite_d(lr) || !finite_d(eps) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0))
+        return "lr and eps must be finite, eps >= 0, betas in [0, 1)";
+    return nullptr;
+}
+
+struct adam6 {
+    float k[6];
+    // the bias corrections in double, as torch/optim/adam.py computes them from Python floats
+    adam6(double lr, double beta1, double beta2, double eps, int step) {
+        const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+        const float v[6] = {(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)sqrt(bc2), (float)eps, (float)(-(lr / bc1))};
+        for (int i = 0; i < 6; ++i) k[i] = v[i];
+    }
+};
+
+static int fail_named(int code, const char* entry, const char* msg) {
+    snprintf(g_err, sizeof(g_err), "%s: %s", entry, msg);
+    return code;
+}
+
 int cs_adam_step(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, int dtype, long long count, double lr, double beta1,
                  double beta2, double eps, int step, void* stream) {
     if (!param || !grad || !exp_avg || !exp_avg_sq) return fail(CS_EINVAL, "null pointer");
     if (count <= 0) return fail(CS_EINVAL, "non-positive count");
-    if (!latent_dtype_ok(dtype)) return fail(CS_EINVAL, "cs_adam_step: unknown dtype (CS_LATENT_F32 / F16 / BF16)");
-    if (step < 1) return fail(CS_EINVAL, "cs_adam_step: the step number counts from 1");
-    if (!finite_d(lr) || !finite_d(eps) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0))
-        return fail(CS_EINVAL, "cs_adam_step: lr and eps must be finite, eps >= 0, betas in [0, 1)");
+    if (const char* msg = adam_args_error(dtype, lr, beta1, beta2, eps, step)) return fail_named(CS_EINVAL, "cs_adam_step", msg);
     const size_t eb = latent_elem_bytes(dtype), bytes = (size_t)count * eb;
     if (misaligned(eb, {param, grad, exp_avg, exp_avg_sq})) return fail(CS_EINVAL, "cs_adam_step: misaligned tensor");
     const span outs[3] = {{param, bytes}, {exp_avg, bytes}, {exp_avg_sq, bytes}}, in = {grad, bytes};
     if (any_overlap(outs, 3, &in, 1)) return fail(CS_EINVAL, "cs_adam_step: param, grad, exp_avg and exp_avg_sq must not overlap");
-    // the bias corrections in double, as torch/optim/adam.py computes them from Python floats
-    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-    const float k[6] = {(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)sqrt(bc2), (float)eps, (float)(-(lr / bc1))};
-    hipError_t e = launch_adam_step(param, grad, exp_avg, exp_avg_sq, dtype, (size_t)count, k, (hipStream_t)stream);
+    const adam6 a(lr, beta1, beta2, eps, step);
+    hipError_t e = launch_adam_step(param, grad, exp_avg, exp_avg_sq, dtype, (size_t)count, a.k, (hipStream_t)stream);
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_adam_step");
+}
+
+// ---- null-text optimisation on F frames at once (cs_inversion_frames.hip) ----
+size_t cs_null_loss_frames_workspace_bytes(long long frames, long long per) {
+    return frames > 0 && per > 0 ? null_loss_frames_workspace_bytes((size_t)frames, (size_t)per) : 0;
+}
+
+static const char* frames_error(long long frames, long long per, int* code) {
+    *code = CS_EINVAL;
+    if (frames <= 0 || per <= 0) return "non-positive count";
+    *code = CS_ELIMIT;
+    if ((unsigned long long)frames > null_loss_frames_max()) return "too many frames for the grid's second dimension (65535)";
+    return nullptr;
+}
+
+int cs_null_loss_grad_frames(const void* eps_uncond, const void* eps_cond, const void* latent_cur, const void* latent_prev, void* rec,
+                             float* loss, void* grad, const uint8_t* active_in, uint8_t* active_out, int dtype, long long frames,
+                             long long per, double guidance, double c1, double c2, double c3, double c4, double threshold,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+    if (!eps_uncond || !eps_cond || !latent_cur || !latent_prev || !rec || !loss || !grad || !active_in || !active_out)
+        return fail(CS_EINVAL, "null pointer");
+    const coeffs4 cc(c1, c2, c3, c4);
+    const float* c = cc.f;
+    int code;
+    if (const char* msg = frames_error(frames, per, &code)) return fail_named(code, "cs_null_loss_grad_frames", msg);
+    if (const char* msg = step_args_error(dtype, per, guidance, cc.d)) return fail(CS_EINVAL, msg);
+    if ((unsigned long long)per > null_loss_max_count())
+        return fail(CS_ELIMIT, "cs_null_loss_grad_frames: too many elements per frame for a 32-bit grid");
+    if (active_in == active_out) return fail(CS_EINVAL, "cs_null_loss_grad_frames: active_out must not be active_in");
+    if (threshold != threshold) return fail(CS_EINVAL, "cs_null_loss_grad_frames: threshold must not be a NaN");
+    const size_t eb = latent_elem_bytes(dtype), bytes = (size_t)frames * (size_t)per * eb;
+    const size_t need = null_loss_frames_workspace_bytes((size_t)frames, (size_t)per);
+    if (misaligned(eb, {eps_uncond, eps_cond, latent_cur, latent_prev, rec, grad}))
+        return fail(CS_EINVAL, "cs_null_loss_grad_frames: misaligned tensor");
+    if (misaligned(4, {loss, workspace})) return fail(CS_EINVAL, "cs_null_loss_grad_frames: misaligned loss or workspace");
+    if (need && (!workspace || workspace_bytes < need)) return fail(CS_EWORKSPACE, "workspace too small");
+    const span outs[4] = {{rec, bytes}, {grad, bytes}, {loss, 4 * (size_t)frames}, {active_out, (size_t)frames}};
+    const span ins[5] = {{eps_uncond, bytes}, {eps_cond, bytes}, {latent_cur, bytes}, {latent_prev, bytes}, {active_in, (size_t)frames}};
+    for (const span& out : outs)
+        if (any_overlap(&out, 1, ins, 5)) return fail(CS_EINVAL, "cs_null_loss_grad_frames: outputs must not overlap inputs");
+    if (any_overlap(outs, 4, nullptr, 0)) return fail(CS_EINVAL, "cs_null_loss_grad_frames: outputs must not overlap each other");
+    // per frame, as cs_null_loss_grad with count = per
+    const double grad_scale = 2.0 / (double)per * ((double)c[2] - (double)c[3] * (double)c[0] / (double)c[1]) * (1.0 - (double)(float)guidance);
+    hipError_t e = launch_null_loss_grad_frames(eps_uncond, eps_cond, latent_cur, latent_prev, rec, loss, grad, active_in, active_out, dtype,
+                                                (size_t)frames, (size_t)per, (float)guidance, c, grad_scale, threshold, workspace,
+                                                (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_null_loss_grad_frames");
+}
+
+int cs_adam_step_frames(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, const uint8_t* active, int dtype, long long frames,
+                        long long per, double lr, double beta1, double beta2, double eps, int step, void* stream) {
+    if (!param || !grad || !exp_avg || !exp_avg_sq || !active) return fail(CS_EINVAL, "null pointer");
+    int code;
+    if (const char* msg = frames_error(frames, per, &code)) return fail_named(code, "cs_adam_step_frames", msg);
+    if (const char* msg = adam_args_error(dtype, lr, beta1, beta2, eps, step)) return fail_named(CS_EINVAL, "cs_adam_step_frames", msg);
+    const size_t eb = latent_elem_bytes(dtype), bytes = (size_t)frames * (size_t)per * eb;
+    if (misaligned(eb, {param, grad, exp_avg, exp_avg_sq})) return fail(CS_EINVAL, "cs_adam_step_frames: misaligned tensor");
+    const span outs[3] = {{param, bytes}, {exp_avg, bytes}, {exp_avg_sq, bytes}}, ins[2] = {{grad, bytes}, {active, (size_t)frames}};
+    if (any_overlap(outs, 3, ins, 2)) return fail(CS_EINVAL, "cs_adam_step_frames: param, grad, exp_avg, exp_avg_sq and active must not overlap");
+    const adam6 a(lr, beta1, beta2, eps, step);
+    hipError_t e = launch_adam_step_frames(param, grad, exp_avg, exp_avg_sq, active, dtype, (size_t)frames, (size_t)per, a.k,
+                                           (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_adam_step_frames");
 }
 
 // ---- Fast mode's inpainting loop outside its models (cs_inpaintloop.hip) ----

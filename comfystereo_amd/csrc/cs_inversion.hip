@@ -16,44 +16,9 @@
 #include "cs_ddimstep.h"
 #include "cs_kernels.h"
 #include "cs_latent.h"
+#include "cs_nullloss.h"
 
 namespace cs {
-
-namespace {
-
-constexpr int INV_THREADS = 1024;            // the reduction's workgroup
-constexpr size_t INV_BLOCK_ELEMS = 32768;    // elements per workgroup of k_null_loss_grad: up to here one launch does it all
-
-// (hi, lo) += x without losing the rounding error of the sum (Knuth's two-sum; float32 throughout)
-__device__ __forceinline__ void two_sum_add(float& hi, float& lo, float x) {
-    const float s = hi + x;
-    const float bb = s - hi;
-    const float err = (hi - (s - bb)) + (x - bb);
-    hi = s;
-    lo += err;
-}
-
-// the workgroup's pairs -> thread 0's pair, a fixed tree
-__device__ __forceinline__ void block_reduce_pairs(float& hi, float& lo, float* sh_hi, float* sh_lo) {
-    const int tid = threadIdx.x;
-    sh_hi[tid] = hi;
-    sh_lo[tid] = lo;
-    __syncthreads();
-    for (int half = INV_THREADS / 2; half > 0; half >>= 1) {
-        if (tid < half) {
-            float h = sh_hi[tid], l = sh_lo[tid];
-            two_sum_add(h, l, sh_hi[tid + half]);
-            l += sh_lo[tid + half];
-            sh_hi[tid] = h;
-            sh_lo[tid] = l;
-        }
-        __syncthreads();
-    }
-    hi = sh_hi[0];
-    lo = sh_lo[0];
-}
-
-}  // namespace
 
 template <class T>
 __global__ void __launch_bounds__(256) k_ddim_step(const T* sample, const T* __restrict__ eps_a, const T* __restrict__ eps_b, T* out,
@@ -74,25 +39,12 @@ __global__ void __launch_bounds__(INV_THREADS) k_null_loss_grad(const T* __restr
                                                                 float* __restrict__ partial, size_t n, StepCoeffs k, double grad_scale,
                                                                 float count) {
     __shared__ float sh_hi[INV_THREADS], sh_lo[INV_THREADS];
-    const size_t begin = (size_t)blockIdx.x * INV_BLOCK_ELEMS;
-    const size_t end = begin + INV_BLOCK_ELEMS < n ? begin + INV_BLOCK_ELEMS : n;
     float hi = 0.0f, lo = 0.0f;
-    for (size_t i = begin + threadIdx.x; i < end; i += INV_THREADS) {
-        const float e = guided<T>((float)eps_uncond[i], (float)eps_cond[i], true, k.guidance);
-        rec[i] = (T)ddim_value<T>((float)latent_cur[i], e, k);
-        // loss and gradient: from the reconstruction before its roundings to T (float64 per element, which the bound against a
-        // float64 restatement asks for at small counts); each square enters the float32 sum rounded once
-        const double a = (double)(float)eps_uncond[i];
-        const double e64 = a + (double)k.guidance * ((double)(float)eps_cond[i] - a);
-        const double r64 = (double)k.c4 * (((double)(float)latent_cur[i] - (double)k.c1 * e64) / (double)k.c2) + (double)k.c3 * e64;
-        const double diff = r64 - (double)(float)latent_prev[i];
-        grad[i] = (T)(float)(grad_scale * diff);
-        two_sum_add(hi, lo, (float)(diff * diff));
-    }
+    null_loss_block<T>(eps_uncond, eps_cond, latent_cur, latent_prev, rec, grad, blockIdx.x, n, k, grad_scale, hi, lo);
     block_reduce_pairs(hi, lo, sh_hi, sh_lo);
     if (threadIdx.x == 0) {
         if (gridDim.x == 1) {
-            loss[0] = (hi + lo) / count;
+            loss[0] = null_loss_mean(hi, lo, count);
         } else {
             partial[2 * blockIdx.x] = hi;
             partial[2 * blockIdx.x + 1] = lo;
@@ -104,35 +56,17 @@ __global__ void __launch_bounds__(INV_THREADS) k_null_loss_final(const float* __
                                                                  float count) {
     __shared__ float sh_hi[INV_THREADS], sh_lo[INV_THREADS];
     float hi = 0.0f, lo = 0.0f;
-    for (int b = threadIdx.x; b < blocks; b += INV_THREADS) {
-        two_sum_add(hi, lo, partial[2 * b]);
-        lo += partial[2 * b + 1];
-    }
+    null_loss_final_share(partial, blocks, hi, lo);
     block_reduce_pairs(hi, lo, sh_hi, sh_lo);
-    if (threadIdx.x == 0) loss[0] = (hi + lo) / count;
+    if (threadIdx.x == 0) loss[0] = null_loss_mean(hi, lo, count);
 }
 
-struct AdamCoeffs {
-    float w1, beta2, w2, bc2_sqrt, eps, neg_step_size;
-};
-
-// torch/optim/adam.py _single_tensor_adam, operation by operation: lerp_, mul_, addcmul_, sqrt, div, add_, addcdiv_
 template <class T>
 __global__ void __launch_bounds__(256) k_adam_step(T* __restrict__ param, const T* __restrict__ grad, T* __restrict__ exp_avg,
                                                    T* __restrict__ exp_avg_sq, size_t n, AdamCoeffs k) {
     const size_t step = (size_t)gridDim.x * blockDim.x;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += step) {
-        const float g = (float)grad[i];
-        float m = (float)exp_avg[i], v = (float)exp_avg_sq[i];
-        // lerp(m, g, w1): torch's two forms around w = 0.5
-        m = k.w1 < 0.5f ? rnd<T>(m + k.w1 * (g - m)) : rnd<T>(g - (g - m) * (1.0f - k.w1));
-        v = rnd<T>(v * k.beta2);
-        v = rnd<T>(v + k.w2 * g * g);
-        const float denom = rnd<T>(rnd<T>(rnd<T>(sqrtf(v)) / k.bc2_sqrt) + k.eps);
-        const float p = rnd<T>((float)param[i] + k.neg_step_size * m / denom);
-        exp_avg[i] = (T)m;
-        exp_avg_sq[i] = (T)v;
-        param[i] = (T)p;
+        adam_element<T>(param, grad, exp_avg, exp_avg_sq, i, k);
     }
 }
 
@@ -148,8 +82,6 @@ hipError_t launch_ddim_step(const void* sample, const void* eps_a, const void* e
     });
     return hipGetLastError();
 }
-
-static size_t null_loss_blocks(size_t n) { return (n + INV_BLOCK_ELEMS - 1) / INV_BLOCK_ELEMS; }
 
 size_t null_loss_max_count() { return INV_BLOCK_ELEMS * (size_t)0x7fffffff; }   // a 32-bit grid of workgroups
 

@@ -340,6 +340,16 @@ hipError_t launch_null_loss_grad(const void* eps_uncond, const void* eps_cond, c
                                  double grad_scale, void* workspace, hipStream_t stream);
 hipError_t launch_adam_step(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, int dtype, size_t n, const float adam[6],
                             hipStream_t stream);
+// cs_inversion_frames.hip (the same on F frames of `per` elements each: cs_null_loss_grad_frames, cs_adam_step_frames).  active_in,
+// active: one byte per frame, non-zero = the frame still optimises; active_out: what the next inner step takes as active_in
+size_t null_loss_frames_max();
+size_t null_loss_frames_workspace_bytes(size_t frames, size_t per);
+hipError_t launch_null_loss_grad_frames(const void* eps_uncond, const void* eps_cond, const void* latent_cur, const void* latent_prev,
+                                        void* rec, float* loss, void* grad, const uint8_t* active_in, uint8_t* active_out, int dtype,
+                                        size_t frames, size_t per, float guidance, const float c[4], double grad_scale, double threshold,
+                                        void* workspace, hipStream_t stream);
+hipError_t launch_adam_step_frames(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, const uint8_t* active, int dtype,
+                                   size_t frames, size_t m, const float adam[6], hipStream_t stream);
 // cs_inpaintloop.hip (StereoDiffusion Fast mode's inpainting loop outside its models: cs_inpaint_image_prep,
 // cs_inpaint_latent_init, cs_inpaint_plms_step).  dtype, mean_dtype: enum cs_latent_dtype; kind: enum cs_plms_kind;
 // x [2n][9][hl][wl], the UNet's persistent input

@@ -861,6 +861,126 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, lr, step, beta1=0.9, beta2=0.999
     return param
 
 
+# ---- null-text optimisation on F frames at once (cs_null_loss_grad_frames, cs_adam_step_frames) ----
+MAX_FRAMES = 65535                         # the grid's second dimension
+NULL_LOSS_MAX_COUNT = 32768 * 0x7fffffff   # null_loss_max_count(): a 32-bit grid of 32768-element workgroups
+_NULL_LOSS_BLOCK = 32768                   # elements per workgroup of the loss: above it a frame needs the second stage
+
+
+def null_loss_frames_workspace_bytes(frames, per):
+    """cs_null_loss_frames_workspace_bytes, restated: two floats per block of 32 768 elements and frame when per > 32 768."""
+    blocks = (per + _NULL_LOSS_BLOCK - 1) // _NULL_LOSS_BLOCK
+    return frames * blocks * 8 if blocks > 1 else 0
+
+
+def _frames_like(first, tensors, what):
+    """_flat_like on tensors [F, ...]: -> (dtype code, F, elements per frame), within the kernels' limits."""
+    dtype, n = _flat_like(first, tensors, what)
+    name0, t0 = first
+    _tensor(name0, t0, dims=(range(2, 9), "be [F, ...] (frames first), got shape"))
+    frames, per = t0.shape[0], n // t0.shape[0]
+    if frames > MAX_FRAMES:
+        raise ValueError(f"{name0} has {frames} frames, more than the {MAX_FRAMES} of one launch")
+    if per > NULL_LOSS_MAX_COUNT:
+        raise ValueError(f"{name0} has {per} elements per frame, more than the {NULL_LOSS_MAX_COUNT} of a 32-bit grid")
+    return dtype, frames, per
+
+
+def _frame_flags(name, t, frames, first):
+    _tensor(name, t, dtypes=((torch.uint8,), "uint8"), shape=((frames,), f"be [F] = {(frames,)}, got shape"), contiguous=True)
+    _same_device(first, (name, t))
+    return t
+
+
+def null_loss_grad_frames(eps_uncond, eps_cond, latent_cur, latent_prev, guidance, coeffs, active_in, threshold, active_out=None,
+                          loss=None, rec=None, grad=None, workspace=None):
+    """cs_null_loss_grad_frames: null_loss_grad on F frames in one launch -> (rec, loss [F] float32, grad, active_out).  Tensors
+    [F, ...]; a frame's rec, grad and loss are bit for bit null_loss_grad's on that frame alone.  active_in uint8 [F]: a frame whose
+    flag is 0 gets a zero grad, its rec and loss are not touched.  active_out uint8 [F], another buffer than active_in:
+    active_in[f] and not float64(loss[f]) < threshold -- the reference's early stop, left on the device.  active_out, loss, rec,
+    grad, workspace (uint8, null_loss_frames_workspace_bytes(F, per) bytes): buffers to write, or None for new ones (a new loss
+    is NaNs, a new rec zeros: what an inactive frame then shows).  Nothing here waits for the device."""
+    first = ("eps_uncond", eps_uncond)
+    dtype, frames, per = _frames_like(first, [("eps_cond", eps_cond), ("latent_cur", latent_cur), ("latent_prev", latent_prev)]
+                                      + [(n, t) for n, t in (("rec", rec), ("grad", grad)) if t is not None],
+                                      "eps_uncond, eps_cond, latent_cur, latent_prev, rec and grad")
+    g, c1, c2, c3, c4 = _step_scalars(guidance, coeffs)
+    threshold = float(threshold)
+    if math.isnan(threshold):
+        raise ValueError("threshold must not be a NaN")
+    _frame_flags("active_in", active_in, frames, first)
+    if active_out is not None:
+        _frame_flags("active_out", active_out, frames, first)
+        if active_out is active_in or active_out.data_ptr() == active_in.data_ptr():
+            raise ValueError("active_out must be another buffer than active_in (swap two buffers between inner steps)")
+    if loss is not None:
+        _tensor("loss", loss, dtypes=((torch.float32,), "float32"), shape=((frames,), f"be [F] = {(frames,)}, got shape"), contiguous=True)
+        _same_device(first, ("loss", loss))
+    need = null_loss_frames_workspace_bytes(frames, per)
+    if workspace is not None:
+        _tensor("workspace", workspace, dtypes=((torch.uint8,), "uint8"), contiguous=True)
+        _same_device(first, ("workspace", workspace))
+        if workspace.numel() < need:
+            raise ValueError(f"workspace has {workspace.numel()} bytes, {need} are needed")
+    _on_gpu(eps_uncond, no_gpu_error=True)
+    L = _native.lib()
+    dev = eps_uncond.device
+    rec = torch.zeros_like(eps_uncond) if rec is None else rec
+    grad = torch.empty_like(eps_uncond) if grad is None else grad
+    loss = torch.full((frames,), math.nan, dtype=torch.float32, device=dev) if loss is None else loss
+    active_out = torch.empty((frames,), dtype=torch.uint8, device=dev) if active_out is None else active_out
+    if workspace is None:
+        workspace, _ = _workspace(need, dev)
+    _launch(dev, L.cs_null_loss_grad_frames, _ptr(eps_uncond), _ptr(eps_cond), _ptr(latent_cur), _ptr(latent_prev), _ptr(rec), _ptr(loss),
+            _ptr(grad), _ptr(active_in), _ptr(active_out), dtype, frames, per, g, c1, c2, c3, c4, threshold,
+            _ptr(workspace) if need else None, need)
+    return rec, loss, grad, active_out
+
+
+class NullTextLossFrames(torch.autograd.Function):
+    """loss [F] = NullTextLossFrames.apply(eps_uncond, eps_cond, latent_cur, latent_prev, guidance, coeffs, active_in, threshold,
+    active_out): NullTextLoss per frame, one cs_null_loss_grad_frames launch.  The backward hands the kept gradient to eps_uncond;
+    the incoming gradient of the loss is taken as ones (loss.sum().backward(), or grad_outputs of ones) and any other value is
+    refused -- a per-frame scale would be one more pass over the tensor, and null-text optimisation has none.  ctx.rec, ctx.active_out:
+    the reconstructed latents and the flags of the next inner step."""
+
+    @staticmethod
+    def forward(ctx, eps_uncond, eps_cond, latent_cur, latent_prev, guidance, coeffs, active_in, threshold, active_out=None):
+        rec, loss, grad, active_out = null_loss_grad_frames(eps_uncond.detach(), eps_cond, latent_cur, latent_prev, guidance, coeffs,
+                                                            active_in, threshold, active_out)
+        ctx.save_for_backward(grad)
+        ctx.rec, ctx.active_out = rec, active_out
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        (grad,) = ctx.saved_tensors
+        if not bool((grad_output == 1).all()):
+            raise ValueError("NullTextLossFrames takes the gradient of its loss as ones (loss.sum().backward()); got another value")
+        return (grad,) + (None,) * 8
+
+
+def adam_step_frames(param, grad, exp_avg, exp_avg_sq, active, lr, step, beta1=0.9, beta2=0.999, eps=1e-8):
+    """cs_adam_step_frames: adam_step, with one lr and one step number, on the rows [f] of four tensors [F, ...] whose active[f]
+    (uint8 [F]) is set; the rows of every other frame are not written at all.  One launch.  -> param"""
+    first = ("param", param)
+    dtype, frames, per = _frames_like(first, [("grad", grad), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)],
+                                      "param, grad, exp_avg and exp_avg_sq")
+    if isinstance(step, bool) or not isinstance(step, int) or step < 1:
+        raise ValueError(f"step must be an int counting from 1, got {step!r}")
+    lr, beta1, beta2, eps = float(lr), float(beta1), float(beta2), float(eps)
+    if not (math.isfinite(lr) and math.isfinite(eps) and eps >= 0 and 0 <= beta1 < 1 and 0 <= beta2 < 1):
+        raise ValueError(f"lr and eps must be finite, eps >= 0 and the betas in [0, 1), got {lr}, {eps}, {beta1}, {beta2}")
+    for name, t in (("grad", grad), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
+        _tensor(name, t, no_grad="")
+    _frame_flags("active", active, frames, first)
+    _on_gpu(param, no_gpu_error=True)
+    _launch(param.device, _native.lib().cs_adam_step_frames, _ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(active), dtype,
+            frames, per, lr, beta1, beta2, eps, step)
+    return param
+
+
 # ---- StereoDiffusion Fast mode's inpainting loop outside its models (cs_inpaint_*; DESIGN.md section 2) ----
 def _unet_input(x, n, hl, wl, like=None):
     """x: the persistent UNet input [2n, 9, hl, wl], contiguous, of a latent dtype (of `like`'s, when given)."""

@@ -11,6 +11,9 @@ duck-typed); everything between two UNet calls runs in one HIP launch each:
   latent2image        (image / 2 + 0.5).clamp(0, 1) * 255 -> uint8 (:100-102)    engine.decode_to_codes
   invert              register_attention_control(model, None) (:216)             diffusion_utils' fused attention hook
 
+`NullInversion.invert_frames` is not in the reference: F frames in one UNet batch (video in Standard mode), every frame with its
+own loss, early stop and Adam state (engine.null_loss_grad_frames, engine.adam_step_frames), bit for bit what invert gives it alone.
+
 The step's coefficients sqrt(1 - a_t), sqrt(a_t), sqrt(1 - a_other), sqrt(a_other) are the reference's own expressions on
 scheduler.alphas_cumprod, evaluated once per timestep on the host and cached.  The inner loop reads the loss once per inner step,
 for the early stop; nothing else waits for the device.
@@ -252,6 +255,121 @@ class NullInversion:
 
         return (given if as_array else image, image_rec), ddim_latents[-1], uncond_embeddings
 
+    # ---- F frames in one UNet batch: every frame its own loss, its own early stop and its own Adam state ----
+    @torch.no_grad()
+    def _images2latent(self, images):
+        """image2latent on uint8 [F,512,512,3]: the same host arithmetic, one VAE call."""
+        device = self._get_device()
+        model_dtype = next(self.model.vae.parameters()).dtype
+        images = images.cpu().float() / 127.5 - 1
+        images = images.permute(0, 3, 1, 2).to(device).to(dtype=model_dtype)
+        latents = self.model.vae.encode(images)['latent_dist'].mean
+        return (latents * 0.18215).to(device)
+
+    def _frame_contexts(self, frames):
+        """(uncond [F,77,D], cond [F,77,D]): the prompt's two embeddings, one row per frame."""
+        uncond_embeddings, cond_embeddings = self.context.chunk(2)
+        return tuple(e.expand(frames, *e.shape[1:]).contiguous() for e in (uncond_embeddings, cond_embeddings))
+
+    @torch.no_grad()
+    def ddim_loop_frames(self, latent):
+        """ddim_loop on [F,C,h,w]: engine.ddim_step is elementwise, the UNet runs at batch F."""
+        _, cond_embeddings = self._frame_contexts(latent.shape[0])
+        all_latent = [latent]
+        latent = latent.clone().detach()
+        for i in range(self.num_ddim_steps):
+            t = self.model.scheduler.timesteps[len(self.model.scheduler.timesteps) - i - 1]
+            noise_pred = self.get_noise_pred_single(latent, t, cond_embeddings)
+            latent = self.next_step(noise_pred, t, latent)
+            all_latent.append(latent)
+        return all_latent
+
+    def null_optimization_frames(self, latents, num_inner_steps, epsilon):
+        """null_optimization on latents [F,C,h,w]: per outer step one conditional UNet call at batch F; per inner step one
+        unconditional UNet call at batch F, one cs_null_loss_grad_frames launch, the UNet's backward from its gradient, one
+        cs_adam_step_frames launch and one read of the flags and losses -- the inner step's single wait.  A frame whose loss
+        falls below the threshold stops there, as it would alone: its flag is cleared on the device, its later gradients are
+        zeros and Adam no longer writes it.  -> [F,77,D] per outer step; inner_steps_taken[i][f], losses[i][f][j]."""
+        frames = latents[-1].shape[0]
+        uncond_embeddings, cond_embeddings = self._frame_contexts(frames)
+        uncond_embeddings_list = []
+        latent_cur = latents[-1]
+        self.inner_steps_taken, self.losses = [], []
+        device = latent_cur.device
+        # everything the inner loop writes, allocated once.  state: F float32 losses, then the two flag buffers, which swap roles
+        # every inner step -- one tensor, so that one copy brings the losses and the flags to the host
+        state = torch.zeros((6 * frames,), dtype=torch.uint8, device=device)
+        loss = state[:4 * frames].view(torch.float32)
+        flags = [state[4 * frames:5 * frames], state[5 * frames:]]
+        rec, grad = torch.empty_like(latent_cur.contiguous()), torch.empty_like(latent_cur.contiguous())
+        per = latent_cur[0].numel()
+        workspace = torch.empty((max(engine.null_loss_frames_workspace_bytes(frames, per), 256),), dtype=torch.uint8, device=device)
+        exp_avg, exp_avg_sq = torch.empty_like(uncond_embeddings), torch.empty_like(uncond_embeddings)
+        for i in range(self.num_ddim_steps):
+            uncond_embeddings = uncond_embeddings.clone().detach().contiguous()
+            uncond_embeddings.requires_grad = True
+            # a fresh Adam per outer step (:192): zero moments, step numbers from 1; every frame starts active
+            lr = 1e-2 * (1. - i / 100.)
+            exp_avg.zero_()
+            exp_avg_sq.zero_()
+            latent_prev = latents[len(latents) - i - 2].detach().contiguous()
+            latent_cur = latent_cur.detach().contiguous()
+            t = self.model.scheduler.timesteps[i]
+            coeffs = self._step_coeffs("prev", t, latent_cur.dtype)
+            threshold = epsilon + i * 2e-5
+            with torch.no_grad():
+                noise_pred_cond = self.get_noise_pred_single(latent_cur, t, cond_embeddings).contiguous()
+            cur = 0
+            flags[cur].fill_(1)
+            active = [True] * frames
+            losses = [[] for _ in range(frames)]
+            for j in range(num_inner_steps):
+                noise_pred_uncond = self.get_noise_pred_single(latent_cur, t, uncond_embeddings).contiguous()
+                engine.null_loss_grad_frames(noise_pred_uncond.detach(), noise_pred_cond, latent_cur, latent_prev, self.guidance_scale,
+                                             coeffs, flags[cur], threshold, active_out=flags[1 - cur], loss=loss, rec=rec, grad=grad,
+                                             workspace=workspace)
+                (emb_grad,) = torch.autograd.grad(noise_pred_uncond, [uncond_embeddings], grad_outputs=grad)
+                engine.adam_step_frames(uncond_embeddings, emb_grad.contiguous(), exp_avg, exp_avg_sq, flags[cur], lr, j + 1)
+                host = state.cpu()   # the one wait per inner step: the early stops need it
+                loss_host = host[:4 * frames].view(torch.float32).tolist()
+                for f in range(frames):
+                    if active[f]:
+                        losses[f].append(loss_host[f])
+                cur = 1 - cur
+                active = [bool(a) for a in host[(4 + cur) * frames:(5 + cur) * frames].tolist()]
+                if not any(active):
+                    break
+            self.inner_steps_taken.append([len(row) for row in losses])
+            self.losses.append(losses)
+            uncond_embeddings_list.append(uncond_embeddings.detach())
+            with torch.no_grad():
+                context = torch.cat([uncond_embeddings, cond_embeddings])
+                latent_cur = self.get_noise_pred(latent_cur, t, False, context)
+        return uncond_embeddings_list
+
+    def invert_frames(self, images, prompt: str, num_inner_steps=10, early_stop_epsilon=1e-5, null_text_optimization=True):
+        """invert on F frames at once: images uint8 [F,512,512,3] on the device -> (x_t [F,C,h,w], uncond_embeddings): one
+        [F,77,D] tensor per outer step, or None where invert returns plain copies of the empty prompt's embedding (no
+        optimisation asked for, or a ComfyUI model without torch.func).  Every frame's x_t, embeddings, losses and inner-step
+        counts are what invert gives on that frame alone wherever the model's own arithmetic does not depend on the batch."""
+        if not (isinstance(images, torch.Tensor) and images.dtype == torch.uint8 and images.dim() == 4
+                and tuple(images.shape[1:]) == (512, 512, 3) and images.shape[0] > 0):
+            raise ValueError("images must be a uint8 tensor [F,512,512,3]")
+        self.init_prompt(prompt)
+        diffusion_utils.register_attention_control(self.model, None)
+        ddim_latents = self.ddim_loop_frames(self._images2latent(images))
+        uncond_embeddings = None
+        if null_text_optimization:
+            if not self._is_comfyui:
+                uncond_embeddings = self.null_optimization_frames(ddim_latents, num_inner_steps, early_stop_epsilon)
+            elif functional_call is not None:
+                self.model.unet.enable_gradient_mode()
+                try:
+                    uncond_embeddings = self.null_optimization_frames(ddim_latents, num_inner_steps, early_stop_epsilon)
+                finally:
+                    self.model.unet.disable_gradient_mode()
+        return ddim_latents[-1], uncond_embeddings
+
 
 def make_invert(model, num_ddim_steps, guidance_scale, null_text_optimization=True, num_inner_steps=10, early_stop_epsilon=1e-5):
     """-> invert(image_u8 [512,512,3]) -> (x_t, uncond_embeddings): the callable stereodiffusion_nodes.generate_stereo_standard
@@ -271,3 +389,19 @@ def make_invert(model, num_ddim_steps, guidance_scale, null_text_optimization=Tr
         return x_t, uncond_embeddings
 
     return invert
+
+
+def make_invert_frames(model, num_ddim_steps, guidance_scale, null_text_optimization=True, num_inner_steps=10, early_stop_epsilon=1e-5):
+    """-> invert_frames(images_u8 [F,512,512,3]) -> (x_t [F,C,h,w], uncond_embeddings): make_invert for
+    stereodiffusion_nodes.generate_stereo_standard_frames, F frames in one UNet batch."""
+    from . import stereo_utils
+
+    def invert_frames(images_u8):
+        inversion = NullInversion(model, num_ddim_steps, guidance_scale)
+        try:
+            return inversion.invert_frames(images_u8, "", num_inner_steps=num_inner_steps, early_stop_epsilon=early_stop_epsilon,
+                                           null_text_optimization=null_text_optimization)
+        finally:
+            stereo_utils.restore_attention(model)
+
+    return invert_frames

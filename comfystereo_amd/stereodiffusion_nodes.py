@@ -11,6 +11,8 @@ Standard mode, around its UNet, VAE and scheduler (_generate_stereo_impl and _te
 
     generate_stereo_standard  the tensor work of the mode: codes, gray, the resizes to 512 x 512, the disparity, the loop, the
                               resizes back into the side-by-side float frame (:249-307), with the inversion as a callback
+    generate_stereo_standard_frames  the same on every frame, groups of frames as one batch through the inversion, the loop and the
+                              VAE (not in the reference, which stops after the first frame; the node takes it under STANDARD_ALL_FRAMES)
     text2stereoimage          the denoising loop with BNAttention installed, the latent shift at 20 % of the steps and its
                               re-application every 20 %, the VAE decode and the uint8 codes (:576-682)
 
@@ -187,10 +189,13 @@ class _StandardLoop:
     """What the loop of _text2stereoimage carries from step to step (:624-667): the shift table, made once; the mask the
     first shift stores; the noise of `deblur`.  step() is one iteration; it launches kernels and nothing else."""
 
-    def __init__(self, model, disp_latent, scale_factor, deblur, num_inference_steps, guidance_scale, noise):
+    def __init__(self, model, disp_latent, scale_factor, deblur, num_inference_steps, guidance_scale, noise, per_frame=False):
         self.model, self.guidance_scale, self.controller = model, guidance_scale, _EmptyControl()
         self.shift_step, self.reshift_interval = _shift_steps(num_inference_steps)
-        self.src_col = engine.latent_shift_plan(disp_latent, scale_factor)
+        # the plan normalises with the range of the tensor it is given, as the reference's stereo_shift_torch does: frames that
+        # are to come out as they would alone (per_frame) get a plan each
+        self.src_col = (torch.cat([engine.latent_shift_plan(d[None], scale_factor) for d in disp_latent]) if per_frame
+                        else engine.latent_shift_plan(disp_latent, scale_factor))
         self.mask = torch.zeros(tuple(disp_latent.shape), dtype=torch.uint8, device=disp_latent.device)
         self.noise = noise if deblur else None   # [1,C,h,w]: the right view's
         self.shifted = False
@@ -385,6 +390,137 @@ def generate_stereo_standard(image, depth_map, scale_factor, direction, deblur, 
     return stereo, stereo[:, :, :w], stereo[:, :, w:]
 
 
+# Standard mode on every frame of a batch (not in the reference, which processes the first frame only: on its hardware one
+# null-text inversion takes minutes).  False: StereoDiffusionNode behaves as the reference's; True: Standard mode with more than one
+# frame goes through generate_stereo_standard_frames.  A module switch, like stereo_utils.HALF_ATTENTION.
+STANDARD_ALL_FRAMES = False
+
+
+def _norm_depth_frames(depth):
+    """_norm_depth on [F,H,W] with every frame's own range."""
+    flat = depth.flatten(1)
+    mn, mx = flat.min(1).values[:, None, None], flat.max(1).values[:, None, None]
+    rng = mx - mn
+    return torch.where(rng > torch.finfo(torch.float32).eps, 1 * (depth - mn) / rng, torch.zeros_like(depth))
+
+
+@torch.no_grad()
+def _stereo_latents_frames(model, uncond_embeddings, x_t, disparity, scale_factor, direction, deblur, num_inference_steps,
+                           guidance_scale, noise):
+    """_stereo_latents on F frames down the fused path (the model's scheduler is our DDIMScheduler): x_t [F,C,h,w], disparity
+    float32 [F,512,512], uncond_embeddings a list of [F,77,D] or None, noise [F,C,h,w] (the right views') or None ->
+    latents [2F,C,h,w], the left views, then the right views.  The UNet's persistent input is [4F,C,h,w] as standard_step lays it
+    out; BNAttention sees chunks = 2 and samples = F."""
+    frames, steps = x_t.shape[0], num_inference_steps
+    stereo_utils._need_gpu()
+    editor = stereo_utils.BNAttention(start_step=max(1, int(steps * 0.2)), total_steps=steps, direction=direction)
+    stereo_utils.register_attention_editor_diffusers(model, editor)
+    try:
+        tok = model.tokenizer
+        text_input = tok([""] * (2 * frames), padding="max_length", max_length=tok.model_max_length, truncation=True, return_tensors="pt")
+        text_embeddings = model.text_encoder(text_input.input_ids.to(model.device))[0]
+        if tuple(text_embeddings.shape[:1]) != (2 * frames,):
+            raise ValueError(f"the text encoder answered {tuple(text_embeddings.shape)} to {2 * frames} prompts")
+        latents = torch.cat([x_t, x_t]).to(model.device)
+        if not latents.is_cuda:
+            raise ValueError(f"the model's device must be the GPU, got latents on {latents.device}")
+        if latents.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise ValueError(f"latents must be float32, float16 or bfloat16, got {latents.dtype}")
+        model.scheduler.set_timesteps(steps)
+        disp_latent = _disparity_to_latent(disparity.to(latents.device), latents.shape[-2:])
+        if deblur:
+            noise = noise.to(latents.device, latents.dtype).contiguous()
+        loop = _StandardLoop(model, disp_latent, scale_factor, deblur, steps, guidance_scale, noise, per_frame=True)
+        timesteps = model.scheduler.timesteps[-steps:]
+        if uncond_embeddings is None:
+            uncond_input = tok([""] * (2 * frames), padding="max_length", max_length=tok.model_max_length, return_tensors="pt")
+            uncond_emb = model.text_encoder(uncond_input.input_ids.to(model.device))[0]
+            contexts = [torch.cat([uncond_emb, text_embeddings])] * len(timesteps)
+        else:
+            # frame f's own null-text embedding for both of its views: rows f and F + f of either half
+            contexts = [torch.cat([uncond_embeddings[i], uncond_embeddings[i], text_embeddings]) for i in range(len(timesteps))]
+        latents = loop.begin(latents, timesteps)
+        for i in range(len(timesteps)):
+            loop.fused_step(i, contexts[i])
+        return latents
+    finally:
+        stereo_utils.restore_attention(model)
+
+
+def generate_stereo_standard_frames(image, depth_map, scale_factor, direction, deblur, num_inference_steps, guidance_scale, model,
+                                    invert_frames, frames_per_batch=4, noise=None, generator=None):
+    """generate_stereo_standard on every frame: groups of up to `frames_per_batch` frames go through the inversion, the loop and
+    the VAE as one batch.  invert_frames(images_u8 [F,512,512,3] uint8, on the device) -> (x_t [F,C,64,64], uncond_embeddings:
+    a list of [F,77,D] per step, or None): inversion.make_invert_frames builds it.  noise: the deblur fill of the right views,
+    [N,C,64,64]; None: drawn per frame as text2stereoimage draws it ([2,C,64,64] from `generator`, the right view's half), in frame
+    order, so that a batch equals N successive single-frame calls on that generator.  Every frame has its own depth range.
+    A model whose scheduler is not our DDIMScheduler runs frame by frame through generate_stereo_standard.
+    -> (stereo [N,H,2W,3], left [N,H,W,3], right [N,H,W,3]) float32, left and right being the two halves of stereo."""
+    if not (isinstance(image, torch.Tensor) and isinstance(depth_map, torch.Tensor)):
+        raise ValueError("image and depth_map must be torch tensors")
+    if not callable(invert_frames):
+        raise ValueError("invert_frames must be callable: invert_frames(images_u8 [F,512,512,3]) -> (x_t, uncond_embeddings)")
+    if image.dim() != 4 or image.shape[-1] != 3 or not image.is_floating_point():
+        raise ValueError(f"image must be a float tensor [N,H,W,3], got {image.dtype} {tuple(image.shape)}")
+    if depth_map.dim() == 3:
+        depth_map = depth_map.unsqueeze(-1)
+    if (depth_map.dim() != 4 or depth_map.shape[-1] not in (1, 3) or not depth_map.is_floating_point()
+            or tuple(depth_map.shape[:3]) != tuple(image.shape[:3])):
+        raise ValueError(f"depth_map must be a float tensor [N,H,W,3], [N,H,W,1] or [N,H,W] matching image {tuple(image.shape)}, "
+                         f"got {depth_map.dtype} {tuple(depth_map.shape)}")
+    if image.numel() == 0:
+        raise ValueError(f"empty image {tuple(image.shape)}")
+    if direction not in ("uni", "bi"):
+        raise ValueError(f"direction must be 'uni' or 'bi', got {direction!r}")
+    if not isinstance(num_inference_steps, int) or isinstance(num_inference_steps, bool) or num_inference_steps < 1:
+        raise ValueError(f"num_inference_steps must be a positive int, got {num_inference_steps!r}")
+    if isinstance(frames_per_batch, bool) or not isinstance(frames_per_batch, int) or frames_per_batch < 1:
+        raise ValueError(f"frames_per_batch must be a positive int, got {frames_per_batch!r}")
+    n, h, w, _ = image.shape
+    if noise is not None and not (isinstance(noise, torch.Tensor) and noise.dim() == 4 and noise.shape[0] == n):
+        raise ValueError(f"noise must be None or a tensor [N,C,h,w] like the inverted latents, one right view per frame (N = {n})")
+    host = not image.is_cuda
+    dev = _device_for(image, depth_map)
+    stereo = torch.empty((n, h, 2 * w, 3), dtype=torch.float32, device=dev)
+    if not isinstance(model.scheduler, DDIMScheduler):
+        for k in range(n):
+            one = generate_stereo_standard(image[k:k + 1], depth_map[k:k + 1], scale_factor, direction, deblur, num_inference_steps,
+                                           guidance_scale, model, lambda image_u8: invert_frames(image_u8[None]),
+                                           None if noise is None else torch.cat([noise[k:k + 1]] * 2), generator)
+            stereo[k:k + 1] = one[0].to(dev)
+    else:
+        image, depth_map = image.to(dev, torch.float32), depth_map.to(dev, torch.float32)
+        s = (WORK_SIZE, WORK_SIZE)
+        for k in range(0, n, frames_per_batch):
+            group = slice(k, min(k + frames_per_batch, n))
+            frames = group.stop - group.start
+            img_u8 = engine.pil_resize(image[group], s)
+            depth_u8 = engine.pil_resize(depth_map[group], s, gray=depth_map.shape[-1] == 3)
+            disp = _norm_depth_frames(depth_u8[..., 0].float() / 255.0)
+            x_t, uncond_embeddings = invert_frames(img_u8)
+            if not isinstance(x_t, torch.Tensor) or x_t.dim() != 4 or x_t.shape[0] != frames:
+                raise ValueError(f"invert_frames must return (x_t [F,C,h,w], uncond_embeddings) for its F = {frames} frames")
+            fill = None
+            if deblur and noise is not None:
+                if tuple(noise.shape[1:]) != tuple(x_t.shape[1:]):
+                    raise ValueError(f"noise {tuple(noise.shape)} must be [N,C,h,w] with the latents' {tuple(x_t.shape[1:])}")
+                fill = noise[group]
+            elif deblur:
+                # a generator draws on its own device (the reference's is a CPU one); the result goes to the latents'
+                where = generator.device if generator is not None else x_t.device
+                fill = torch.cat([torch.randn((2,) + tuple(x_t.shape[1:]), generator=generator, device=where, dtype=x_t.dtype)[1:]
+                                  for _ in range(frames)])
+            latents = _stereo_latents_frames(model, uncond_embeddings, x_t, disp, scale_factor, direction, deblur, num_inference_steps,
+                                             guidance_scale, fill)
+            with torch.no_grad():
+                codes = engine.decode_to_codes(model.vae.decode(1 / 0.18215 * latents)["sample"].contiguous())
+            engine.pil_resize(codes[:frames], (w, h), f32="nhwc", codes=False, f32_out=stereo[group, :, :w])
+            engine.pil_resize(codes[frames:], (w, h), f32="nhwc", codes=False, f32_out=stereo[group, :, w:])
+    if host:
+        stereo = stereo.cpu()
+    return stereo, stereo[:, :, :w], stereo[:, :, w:]
+
+
 # ---- the ComfyUI node (reference :64-206, :685-692) -------------------------------------------------------------------------------
 FAST_MODE, STANDARD_MODE = "Fast (Warp + Inpaint)", "Standard (DDIM)"
 
@@ -463,6 +599,10 @@ class StereoDiffusionNode:
             ldm_stable = model_wrappers.ComfyUIModelWrapper(model, clip, vae)
             if not ldm_stable.is_supported():
                 raise ValueError(ldm_stable.get_unsupported_message())
+            if STANDARD_ALL_FRAMES and image.shape[0] > 1:
+                invert_frames = inversion.make_invert_frames(ldm_stable, int(num_inference_steps), guidance_scale, null_text_optimization)
+                return generate_stereo_standard_frames(image, depth_map, scale_factor, direction, deblur, int(num_inference_steps),
+                                                       guidance_scale, ldm_stable, invert_frames, generator=generator)
             invert = inversion.make_invert(ldm_stable, int(num_inference_steps), guidance_scale, null_text_optimization)
             return generate_stereo_standard(image, depth_map, scale_factor, direction, deblur, int(num_inference_steps), guidance_scale,
                                             ldm_stable, invert, generator=generator)

@@ -427,6 +427,32 @@ CS_API int cs_adam_step(void *param, const void *grad, void *exp_avg, void *exp_
                         double beta1, double beta2, double eps, int step, void *stream);
 
 /*
+ * Null-text optimisation on F frames at once: the two calls above with a frame axis, for a UNet that runs `frames` frames in one
+ * batch while every frame keeps its own loss, its own early stop and its own Adam state.  Tensors are [frames][per] contiguous.
+ *   cs_null_loss_grad_frames  per frame f with active_in[f] != 0: rec[f], grad[f] and loss[f] (float32 [frames]) are bit for bit
+ *     what cs_null_loss_grad gives on that frame's `per` elements alone (the same blocks counted from the frame's first element,
+ *     the same summation tree, count = per), and active_out[f] = !((double)loss[f] < threshold): the reference's early stop
+ *     `loss.item() < epsilon + i * 2e-5` (:205-208), made in float64 on the device -- a loss at the threshold, or a NaN, does not
+ *     stop the frame.  Per frame with active_in[f] == 0: grad[f] is zeros, rec[f] and loss[f] are not touched, active_out[f] = 0.
+ *     active_in and active_out are uint8 [frames] and two different buffers (swap them between inner steps).  One launch, and a
+ *     second one when per > 32 768; no atomics.  workspace: cs_null_loss_frames_workspace_bytes(frames, per): two floats per
+ *     block of 32 768 elements and frame when per > 32 768, else 0 (workspace may be NULL).
+ *   cs_adam_step_frames  cs_adam_step, with the same coefficients and step number for all frames, on the rows of the frames with
+ *     active[f] != 0; the four rows of every other frame are not written at all.  One launch.
+ * CS_EINVAL before any launch: null pointers, frames <= 0 or per <= 0, unknown dtype, active_out == active_in, a NaN threshold,
+ * and what the single-tensor calls refuse; CS_ELIMIT: frames > 65 535 (the grid's second dimension), per above
+ * cs_null_loss_grad's limit.
+ */
+CS_API size_t cs_null_loss_frames_workspace_bytes(long long frames, long long per);
+CS_API int cs_null_loss_grad_frames(const void *eps_uncond, const void *eps_cond, const void *latent_cur, const void *latent_prev,
+                                    void *rec, float *loss, void *grad, const uint8_t *active_in, uint8_t *active_out, int dtype,
+                                    long long frames, long long per, double guidance, double c1, double c2, double c3, double c4,
+                                    double threshold, void *workspace, size_t workspace_bytes, void *stream);
+CS_API int cs_adam_step_frames(void *param, const void *grad, void *exp_avg, void *exp_avg_sq, const uint8_t *active, int dtype,
+                               long long frames, long long per, double lr, double beta1, double beta2, double eps, int step,
+                               void *stream);
+
+/*
  * StereoDiffusion's Fast mode outside its models (reference model_wrappers.py ComfyUIInpaintRunner.__call__, :522-641): the tensor
  * work before and inside the inpainting loop, around ONE persistent UNet input
  *   x [2n][9][hl][wl] of `dtype` (enum cs_latent_dtype): the uncond half (n frames), then the cond half -- the layout of

@@ -9,6 +9,13 @@ The UNet is stood in for by `eps_uncond = embedding.sum() * 0 + eps`, the cheape
 launches: torch.profiler's device kernels of one step.  One JSON line per dtype.
 
   python tools/inversion_bench.py [--iters 200] [--warmup 20]
+
+--frames F: instead, null-text inversion of F frames on the stand-in model (tools/null_fake_model.py, form "exact", float32, 5 outer
+steps of up to 10 inner steps): NullInversion.invert on the F frames one after the other against NullInversion.invert_frames on all
+of them in one batch -- wall time of each (host clock around a device synchronise, the best of --repeats), device kernels and
+device-to-host copies of one run each, from torch.profiler (the batched loop's one read per inner step is such a copy; the
+single-frame loop's `loss.item()` does not always appear as one in the trace, so compare the kernels and the time, not the copies).  The stand-in's UNet costs next to nothing, so the time is
+launches and waits: what the batch saves on a real UNet is not measured here.  One JSON line.
 """
 import argparse
 import json
@@ -52,11 +59,58 @@ def launches(fn):
     return sum(1 for ev in prof.events() if ev.device_type == torch.autograd.DeviceType.CUDA and "memcpy" not in ev.name.lower())
 
 
+def frames_bench(frames, repeats):
+    import time
+
+    from torch.profiler import ProfilerActivity, profile
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import null_fake_model as nm
+    from comfystereo_amd import inversion, stereo_utils
+    steps, inner, guidance, epsilon = 5, 10, 7.5, 9.34e-3
+    images = torch.stack([torch.from_numpy(nm.seeded_image(11 + f)) for f in range(frames)]).cuda()
+    model = nm.NullModel("exact", "cuda")
+
+    def one_by_one():
+        for f in range(frames):
+            inversion.NullInversion(model, steps, guidance).invert(images[f], "a photo", num_inner_steps=inner, early_stop_epsilon=epsilon)
+        stereo_utils.restore_attention(model)
+
+    def batched():
+        inversion.NullInversion(model, steps, guidance).invert_frames(images, "a photo", num_inner_steps=inner, early_stop_epsilon=epsilon)
+        stereo_utils.restore_attention(model)
+
+    row = dict(frames=frames, outer_steps=steps, max_inner_steps=inner)
+    for name, fn in (("one_by_one", one_by_one), ("batched", batched)):
+        fn()
+        best = float("inf")
+        for _ in range(repeats):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            best = min(best, time.perf_counter() - t0)
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        names = [ev.name.lower().replace(" ", "").replace("->", "to") for ev in prof.events()
+                 if ev.device_type == torch.autograd.DeviceType.CUDA]
+        copies = [n for n in names if "memcpy" in n or "copy" in n and "kernel" not in n]
+        row[name] = dict(ms=best * 1e3, kernels=len(names) - len(copies),
+                         device_to_host_copies=sum("dtoh" in n or "devicetohost" in n for n in copies))
+    print(json.dumps(row))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--frames", type=int, default=0, help="time F frames one after the other against the batched inversion")
+    ap.add_argument("--repeats", type=int, default=5)
     args = ap.parse_args()
+    if args.frames:
+        if args.frames < 1:
+            ap.error("--frames must be positive")
+        return frames_bench(args.frames, args.repeats)
     for dtype in (torch.float32, torch.float16, torch.bfloat16):
         g = torch.Generator().manual_seed(0)
         lat = [torch.randn(1, 4, 64, 64, generator=g).to(dtype).cuda() for _ in range(4)]
