@@ -39,6 +39,9 @@ LATENT_DTYPE = {"float32": 0, "float16": 1, "bfloat16": 2}
 LATENT_OP = {"first": 0, "reshift": 1}
 # enum cs_standard_op (the shift cs_standard_step applies after its DDIM step)
 STANDARD_OP = {"none": 0, "first": 1, "reshift": 2}
+# enum cs_prediction (what the model's answer is: cs_ddim_step_pred, cs_null_loss_grad_pred, cs_null_loss_grad_frames_pred,
+# cs_standard_step_pred)
+PREDICTION = {"epsilon": 0, "v_prediction": 1}
 # enum cs_plms_kind (the linear multistep combination of cs_inpaint_plms_step)
 PLMS_KIND = {"first": 0, "second": 1, "order2": 2, "order3": 3, "order4": 4}
 
@@ -172,6 +175,11 @@ SIGNATURES = {
     "cs_inpaint_plms_step": (_int, [_vp, _vp] + [_int] * 5 + [_dbl] * 4 + [_vp] * 6 + [_vp]),
     # StereoDiffusion Standard mode between two UNet calls
     "cs_standard_step": (_int, [_vp, _vp] + [_int] * 5 + [_dbl] * 5 + [_int, _vp, _vp, _vp, _vp]),
+    # the same four steps with the model's prediction type (epsilon, v)
+    "cs_ddim_step_pred": (_int, [_vp, _vp, _vp, _vp, _int, _ll] + [_dbl] * 5 + [_int, _vp]),
+    "cs_null_loss_grad_pred": (_int, [_vp] * 7 + [_int, _ll] + [_dbl] * 5 + [_int, _vp, _size, _vp]),
+    "cs_null_loss_grad_frames_pred": (_int, [_vp] * 9 + [_int, _ll, _ll] + [_dbl] * 5 + [_int, _dbl, _vp, _size, _vp]),
+    "cs_standard_step_pred": (_int, [_vp, _vp] + [_int] * 5 + [_dbl] * 5 + [_int, _int, _vp, _vp, _vp, _vp]),
     # the stereo attention, its differentiable form, their float16 / bfloat16 forms
     "cs_stereo_attention_max_head_dim": (_int, []),
     "cs_stereo_attention": (_int, [_vp] * 4 + [_int] * 7 + [_dbl, _int, _vp]),

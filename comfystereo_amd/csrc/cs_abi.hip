@@ -1411,39 +1411,52 @@ int cs_decode_to_codes(const void* image, int dtype, int n, int c, int h, int w,
 // ---- null-text inversion outside the UNet (cs_inversion.hip) ----
 static bool finite_d(double x) { return x - x == 0.0; }
 
-// the checks cs_ddim_step and cs_null_loss_grad share; c2 divides
-static const char* step_args_error(int dtype, long long count, double guidance, const double c[4]) {
+// the checks cs_ddim_step and cs_null_loss_grad share; c2 divides under CS_PRED_EPSILON and only multiplies under CS_PRED_V
+static const char* step_args_error(int dtype, long long count, double guidance, const double c[4], int prediction) {
     if (count <= 0) return "non-positive count";
     if (!latent_dtype_ok(dtype)) return "unknown dtype (CS_LATENT_F32 / F16 / BF16)";
+    if (prediction != CS_PRED_EPSILON && prediction != CS_PRED_V) return "unknown prediction (CS_PRED_EPSILON / CS_PRED_V)";
     if (!finite_d(guidance) || !finite_d(c[0]) || !finite_d(c[1]) || !finite_d(c[2]) || !finite_d(c[3]))
         return "guidance and c1..c4 must be finite";
-    if ((float)c[1] == 0.0f) return "c2 (the square root of alpha_t) must not be 0";
+    if (prediction == CS_PRED_EPSILON && (float)c[1] == 0.0f) return "c2 (the square root of alpha_t) must not be 0";
     return nullptr;
 }
 
-int cs_ddim_step(const void* sample, const void* eps_a, const void* eps_b, void* out, int dtype, long long count, double guidance,
-                 double c1, double c2, double c3, double c4, void* stream) {
+// d rec / d e of the step (cs_ddimstep.h), in double from the float32 coefficients
+static double step_slope(const float c[4], int prediction) {
+    if (prediction == CS_PRED_V) return (double)c[2] * (double)c[1] - (double)c[3] * (double)c[0];
+    return (double)c[2] - (double)c[3] * (double)c[0] / (double)c[1];
+}
+
+// The four *_pred entry points and their epsilon namesakes are one body each: the namesake passes CS_PRED_EPSILON.
+int cs_ddim_step_pred(const void* sample, const void* eps_a, const void* eps_b, void* out, int dtype, long long count, double guidance,
+                      double c1, double c2, double c3, double c4, int prediction, void* stream) {
     if (!sample || !eps_a || !out) return fail(CS_EINVAL, "null pointer");
     const coeffs4 c(c1, c2, c3, c4);
-    if (const char* msg = step_args_error(dtype, count, guidance, c.d)) return fail(CS_EINVAL, msg);
+    if (const char* msg = step_args_error(dtype, count, guidance, c.d, prediction)) return fail(CS_EINVAL, msg);
     const size_t eb = latent_elem_bytes(dtype), bytes = (size_t)count * eb;
     if (misaligned(eb, {sample, eps_a, eps_b, out})) return fail(CS_EINVAL, "cs_ddim_step: misaligned tensor");
     // out may be sample itself: then sample is no input to keep clear of
     const span o = {out, bytes}, ins[3] = {{out == sample ? nullptr : sample, bytes}, {eps_a, bytes}, {eps_b, bytes}};
     if (any_overlap(&o, 1, ins, 3)) return fail(CS_EINVAL, "cs_ddim_step: out may be sample itself; it must not overlap anything else");
-    hipError_t e = launch_ddim_step(sample, eps_a, eps_b, out, dtype, (size_t)count, (float)guidance, c.f, (hipStream_t)stream);
+    hipError_t e = launch_ddim_step(sample, eps_a, eps_b, out, dtype, (size_t)count, (float)guidance, c.f, prediction, (hipStream_t)stream);
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_ddim_step");
+}
+
+int cs_ddim_step(const void* sample, const void* eps_a, const void* eps_b, void* out, int dtype, long long count, double guidance,
+                 double c1, double c2, double c3, double c4, void* stream) {
+    return cs_ddim_step_pred(sample, eps_a, eps_b, out, dtype, count, guidance, c1, c2, c3, c4, CS_PRED_EPSILON, stream);
 }
 
 size_t cs_null_loss_workspace_bytes(long long count) { return count > 0 ? null_loss_workspace_bytes((size_t)count) : 0; }
 
-int cs_null_loss_grad(const void* eps_uncond, const void* eps_cond, const void* latent_cur, const void* latent_prev, void* rec,
-                      float* loss, void* grad, int dtype, long long count, double guidance, double c1, double c2, double c3, double c4,
-                      void* workspace, size_t workspace_bytes, void* stream) {
+int cs_null_loss_grad_pred(const void* eps_uncond, const void* eps_cond, const void* latent_cur, const void* latent_prev, void* rec,
+                           float* loss, void* grad, int dtype, long long count, double guidance, double c1, double c2, double c3,
+                           double c4, int prediction, void* workspace, size_t workspace_bytes, void* stream) {
     if (!eps_uncond || !eps_cond || !latent_cur || !latent_prev || !rec || !loss || !grad) return fail(CS_EINVAL, "null pointer");
     const coeffs4 cc(c1, c2, c3, c4);
     const float* c = cc.f;
-    if (const char* msg = step_args_error(dtype, count, guidance, cc.d)) return fail(CS_EINVAL, msg);
+    if (const char* msg = step_args_error(dtype, count, guidance, cc.d, prediction)) return fail(CS_EINVAL, msg);
     if ((unsigned long long)count > null_loss_max_count()) return fail(CS_ELIMIT, "cs_null_loss_grad: too many elements for a 32-bit grid");
     const size_t eb = latent_elem_bytes(dtype), bytes = (size_t)count * eb, need = null_loss_workspace_bytes((size_t)count);
     if (misaligned(eb, {eps_uncond, eps_cond, latent_cur, latent_prev, rec, grad})) return fail(CS_EINVAL, "cs_null_loss_grad: misaligned tensor");
@@ -1455,10 +1468,17 @@ int cs_null_loss_grad(const void* eps_uncond, const void* eps_cond, const void* 
         if (any_overlap(&out, 1, ins, 4)) return fail(CS_EINVAL, "cs_null_loss_grad: outputs must not overlap inputs");
     if (any_overlap(outs, 3, nullptr, 0)) return fail(CS_EINVAL, "cs_null_loss_grad: outputs must not overlap each other");
     // d loss / d eps_uncond = (2 / n) * (rec - latent_prev) * d rec / d e * d e / d eps_uncond
-    const double grad_scale = 2.0 / (double)count * ((double)c[2] - (double)c[3] * (double)c[0] / (double)c[1]) * (1.0 - (double)(float)guidance);
+    const double grad_scale = 2.0 / (double)count * step_slope(c, prediction) * (1.0 - (double)(float)guidance);
     hipError_t e = launch_null_loss_grad(eps_uncond, eps_cond, latent_cur, latent_prev, rec, loss, grad, dtype, (size_t)count,
-                                         (float)guidance, c, grad_scale, workspace, (hipStream_t)stream);
+                                         (float)guidance, c, prediction, grad_scale, workspace, (hipStream_t)stream);
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_null_loss_grad");
+}
+
+int cs_null_loss_grad(const void* eps_uncond, const void* eps_cond, const void* latent_cur, const void* latent_prev, void* rec,
+                      float* loss, void* grad, int dtype, long long count, double guidance, double c1, double c2, double c3, double c4,
+                      void* workspace, size_t workspace_bytes, void* stream) {
+    return cs_null_loss_grad_pred(eps_uncond, eps_cond, latent_cur, latent_prev, rec, loss, grad, dtype, count, guidance, c1, c2, c3, c4,
+                                  CS_PRED_EPSILON, workspace, workspace_bytes, stream);
 }
 
 // the checks and the coefficients cs_adam_step and cs_adam_step_frames share
@@ -1512,17 +1532,17 @@ static const char* frames_error(long long frames, long long per, int* code) {
     return nullptr;
 }
 
-int cs_null_loss_grad_frames(const void* eps_uncond, const void* eps_cond, const void* latent_cur, const void* latent_prev, void* rec,
-                             float* loss, void* grad, const uint8_t* active_in, uint8_t* active_out, int dtype, long long frames,
-                             long long per, double guidance, double c1, double c2, double c3, double c4, double threshold,
-                             void* workspace, size_t workspace_bytes, void* stream) {
+int cs_null_loss_grad_frames_pred(const void* eps_uncond, const void* eps_cond, const void* latent_cur, const void* latent_prev, void* rec,
+                                  float* loss, void* grad, const uint8_t* active_in, uint8_t* active_out, int dtype, long long frames,
+                                  long long per, double guidance, double c1, double c2, double c3, double c4, int prediction,
+                                  double threshold, void* workspace, size_t workspace_bytes, void* stream) {
     if (!eps_uncond || !eps_cond || !latent_cur || !latent_prev || !rec || !loss || !grad || !active_in || !active_out)
         return fail(CS_EINVAL, "null pointer");
     const coeffs4 cc(c1, c2, c3, c4);
     const float* c = cc.f;
     int code;
     if (const char* msg = frames_error(frames, per, &code)) return fail_named(code, "cs_null_loss_grad_frames", msg);
-    if (const char* msg = step_args_error(dtype, per, guidance, cc.d)) return fail(CS_EINVAL, msg);
+    if (const char* msg = step_args_error(dtype, per, guidance, cc.d, prediction)) return fail(CS_EINVAL, msg);
     if ((unsigned long long)per > null_loss_max_count())
         return fail(CS_ELIMIT, "cs_null_loss_grad_frames: too many elements per frame for a 32-bit grid");
     if (active_in == active_out) return fail(CS_EINVAL, "cs_null_loss_grad_frames: active_out must not be active_in");
@@ -1539,11 +1559,19 @@ int cs_null_loss_grad_frames(const void* eps_uncond, const void* eps_cond, const
         if (any_overlap(&out, 1, ins, 5)) return fail(CS_EINVAL, "cs_null_loss_grad_frames: outputs must not overlap inputs");
     if (any_overlap(outs, 4, nullptr, 0)) return fail(CS_EINVAL, "cs_null_loss_grad_frames: outputs must not overlap each other");
     // per frame, as cs_null_loss_grad with count = per
-    const double grad_scale = 2.0 / (double)per * ((double)c[2] - (double)c[3] * (double)c[0] / (double)c[1]) * (1.0 - (double)(float)guidance);
+    const double grad_scale = 2.0 / (double)per * step_slope(c, prediction) * (1.0 - (double)(float)guidance);
     hipError_t e = launch_null_loss_grad_frames(eps_uncond, eps_cond, latent_cur, latent_prev, rec, loss, grad, active_in, active_out, dtype,
-                                                (size_t)frames, (size_t)per, (float)guidance, c, grad_scale, threshold, workspace,
+                                                (size_t)frames, (size_t)per, (float)guidance, c, prediction, grad_scale, threshold, workspace,
                                                 (hipStream_t)stream);
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_null_loss_grad_frames");
+}
+
+int cs_null_loss_grad_frames(const void* eps_uncond, const void* eps_cond, const void* latent_cur, const void* latent_prev, void* rec,
+                             float* loss, void* grad, const uint8_t* active_in, uint8_t* active_out, int dtype, long long frames,
+                             long long per, double guidance, double c1, double c2, double c3, double c4, double threshold,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+    return cs_null_loss_grad_frames_pred(eps_uncond, eps_cond, latent_cur, latent_prev, rec, loss, grad, active_in, active_out, dtype, frames,
+                                         per, guidance, c1, c2, c3, c4, CS_PRED_EPSILON, threshold, workspace, workspace_bytes, stream);
 }
 
 int cs_adam_step_frames(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, const uint8_t* active, int dtype, long long frames,
@@ -1629,13 +1657,14 @@ int cs_inpaint_plms_step(const void* noise_pred, void* x, int dtype, int n, int 
 }
 
 // ---- Standard mode between two UNet calls (cs_standardloop.hip) ----
-int cs_standard_step(void* x, const void* noise_pred, int dtype, int b, int c, int h, int w, double guidance, double c1, double c2,
-                     double c3, double c4, int op, const int32_t* src_col, uint8_t* mask, const void* noise, void* stream) {
+int cs_standard_step_pred(void* x, const void* noise_pred, int dtype, int b, int c, int h, int w, double guidance, double c1, double c2,
+                          double c3, double c4, int prediction, int op, const int32_t* src_col, uint8_t* mask, const void* noise,
+                          void* stream) {
     if (!x || !noise_pred) return fail(CS_EINVAL, "null pointer");
     if (b <= 0 || c <= 0 || h <= 0 || w <= 0) return fail(CS_EINVAL, "non-positive size");
     if (op < CS_STANDARD_NONE || op > CS_STANDARD_RESHIFT) return fail(CS_EINVAL, "cs_standard_step: unknown op (CS_STANDARD_NONE / FIRST / RESHIFT)");
     const coeffs4 cc(c1, c2, c3, c4);
-    if (const char* msg = step_args_error(dtype, 1, guidance, cc.d)) return fail(CS_EINVAL, msg);
+    if (const char* msg = step_args_error(dtype, 1, guidance, cc.d, prediction)) return fail(CS_EINVAL, msg);
     if (op != CS_STANDARD_NONE && (!src_col || !mask)) return fail(CS_EINVAL, "cs_standard_step: a shift op takes src_col and mask");
     if (noise && op != CS_STANDARD_FIRST) return fail(CS_EINVAL, "cs_standard_step: noise goes with CS_STANDARD_FIRST only");
     if (w > LATENT_MAX_WIDTH) return fail(CS_ELIMIT, "cs_standard_step: rows of more than 8192 columns");
@@ -1647,8 +1676,14 @@ int cs_standard_step(void* x, const void* noise_pred, int dtype, int b, int c, i
     const span outs[2] = {{x, 4 * view_bytes}, {mask, pixels}};
     const span ins[3] = {{noise_pred, 4 * view_bytes}, {src_col, pixels * 4}, {noise, view_bytes}};
     if (any_overlap(outs, 2, ins, 3)) return fail(CS_EINVAL, "cs_standard_step: x and mask must not overlap each other or an input");
-    hipError_t e = launch_standard_step(x, noise_pred, dtype, b, c, h, w, (float)guidance, cc.f, op, src_col, mask, noise, (hipStream_t)stream);
+    hipError_t e = launch_standard_step(x, noise_pred, dtype, b, c, h, w, (float)guidance, cc.f, prediction, op, src_col, mask, noise,
+                                        (hipStream_t)stream);
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_standard_step");
+}
+
+int cs_standard_step(void* x, const void* noise_pred, int dtype, int b, int c, int h, int w, double guidance, double c1, double c2,
+                     double c3, double c4, int op, const int32_t* src_col, uint8_t* mask, const void* noise, void* stream) {
+    return cs_standard_step_pred(x, noise_pred, dtype, b, c, h, w, guidance, c1, c2, c3, c4, CS_PRED_EPSILON, op, src_col, mask, noise, stream);
 }
 
 int cs_stereo_attention_max_head_dim(void) { return stereo_attention_max_head_dim(); }

@@ -41,15 +41,36 @@ __device__ __forceinline__ float guided(float a, float b, bool has_b, float guid
     return rnd<T>(a + gd);
 }
 
-// c4 * ((sample - c1 * e) / c2) + c3 * e, in the reference's order (inversion.py:62-64, :72-74)
-template <class T>
+// The step from the guided prediction e, by what the model predicts (PRED: enum cs_prediction; a template parameter, so the
+// epsilon instantiations are the code they were):
+//   CS_PRED_EPSILON  c4 * ((sample - c1 * e) / c2) + c3 * e, in the reference's order (inversion.py:62-64, :72-74)
+//   CS_PRED_V        e is v = c2 * eps - c1 * x0 (Salimans & Ho 2022):  x0 = c2 * sample - c1 * v;  eps = c2 * v + c1 * sample;
+//                    c4 * x0 + c3 * eps -- the operation order of diffusers' DDIMScheduler.step with prediction_type
+//                    "v_prediction", eta 0.  c2 is the first operand of two products here and divides nothing.
+template <class T, int PRED = CS_PRED_EPSILON>
 __device__ __forceinline__ float ddim_value(float s, float e, const StepCoeffs& k) {
+    if constexpr (PRED == CS_PRED_V) {
+        const float x0 = rnd<T>(mul_rnd<T>(k.c2, s) - mul_rnd<T>(k.c1, e));
+        const float eps = rnd<T>(mul_rnd<T>(k.c2, e) + mul_rnd<T>(k.c1, s));
+        return rnd<T>(mul_rnd<T>(k.c4, x0) + mul_rnd<T>(k.c3, eps));
+    }
     const float t = mul_rnd<T>(k.c1, e);
     const float num = rnd<T>(s - t);
     const float x0 = rnd<T>(num / k.c2);
     const float dir = mul_rnd<T>(k.c3, e);
     const float scaled = mul_rnd<T>(k.c4, x0);
     return rnd<T>(scaled + dir);
+}
+
+// the same from the prediction before its roundings to T, in float64: what the null-text loss is taken from (cs_nullloss.h)
+template <int PRED>
+__device__ __forceinline__ double ddim_value_f64(double s, double e, const StepCoeffs& k) {
+    if constexpr (PRED == CS_PRED_V) {
+        const double x0 = (double)k.c2 * s - (double)k.c1 * e;
+        const double eps = (double)k.c2 * e + (double)k.c1 * s;
+        return (double)k.c4 * x0 + (double)k.c3 * eps;
+    }
+    return (double)k.c4 * ((s - (double)k.c1 * e) / (double)k.c2) + (double)k.c3 * e;
 }
 
 }  // namespace cs

@@ -2,7 +2,8 @@
 // NullInversion.ddim_loop and NullInversion.null_optimization in one launch each.
 //
 //   k_ddim_step        classifier-free guidance (:88) and one DDIM step; one formula is prev_step (:57-65) and next_step (:67-75),
-//                      the host chooses the two alphas:  out = c4 * ((sample - c1 * e) / c2) + c3 * e
+//                      the host chooses the two alphas:  out = c4 * ((sample - c1 * e) / c2) + c3 * e; for a v-prediction model
+//                      (PRED = CS_PRED_V) the step of cs_ddimstep.h on v
 //   k_null_loss_grad   the inner step of null_optimization (:198-201) outside the UNet: the guided prediction, prev_step, the
 //                      mean squared error against latent_prev, and its closed-form gradient with respect to eps_uncond
 //   k_null_loss_final  the second reduction stage, for tensors of more than one workgroup's share
@@ -20,19 +21,19 @@
 
 namespace cs {
 
-template <class T>
+template <class T, int PRED>
 __global__ void __launch_bounds__(256) k_ddim_step(const T* sample, const T* __restrict__ eps_a, const T* __restrict__ eps_b, T* out,
                                                    size_t n, StepCoeffs k) {
     // out may be sample (neither is __restrict__): every element is read before it is written, by the same thread
     const size_t step = (size_t)gridDim.x * blockDim.x;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += step) {
         const float e = guided<T>((float)eps_a[i], eps_b ? (float)eps_b[i] : 0.0f, eps_b != nullptr, k.guidance);
-        out[i] = (T)ddim_value<T>((float)sample[i], e, k);
+        out[i] = (T)ddim_value<T, PRED>((float)sample[i], e, k);
     }
 }
 
 // grid: blocks of INV_BLOCK_ELEMS consecutive elements.  One block: it writes the loss.  More: partial[2 * block] = its pair.
-template <class T>
+template <class T, int PRED>
 __global__ void __launch_bounds__(INV_THREADS) k_null_loss_grad(const T* __restrict__ eps_uncond, const T* __restrict__ eps_cond,
                                                                 const T* __restrict__ latent_cur, const T* __restrict__ latent_prev,
                                                                 T* __restrict__ rec, T* __restrict__ grad, float* __restrict__ loss,
@@ -40,7 +41,7 @@ __global__ void __launch_bounds__(INV_THREADS) k_null_loss_grad(const T* __restr
                                                                 float count) {
     __shared__ float sh_hi[INV_THREADS], sh_lo[INV_THREADS];
     float hi = 0.0f, lo = 0.0f;
-    null_loss_block<T>(eps_uncond, eps_cond, latent_cur, latent_prev, rec, grad, blockIdx.x, n, k, grad_scale, hi, lo);
+    null_loss_block<T, PRED>(eps_uncond, eps_cond, latent_cur, latent_prev, rec, grad, blockIdx.x, n, k, grad_scale, hi, lo);
     block_reduce_pairs(hi, lo, sh_hi, sh_lo);
     if (threadIdx.x == 0) {
         if (gridDim.x == 1) {
@@ -73,12 +74,14 @@ __global__ void __launch_bounds__(256) k_adam_step(T* __restrict__ param, const 
 static StepCoeffs step_coeffs(float guidance, const float c[4]) { return StepCoeffs{guidance, c[0], c[1], c[2], c[3]}; }
 
 hipError_t launch_ddim_step(const void* sample, const void* eps_a, const void* eps_b, void* out, int dtype, size_t n, float guidance,
-                            const float c[4], hipStream_t stream) {
+                            const float c[4], int prediction, hipStream_t stream) {
     const StepCoeffs k = step_coeffs(guidance, c);
     with_latent_type(dtype, [&](auto tag) {
         using T = decltype(tag);
-        hipLaunchKernelGGL(k_ddim_step<T>, dim3(stream_grid(n)), dim3(256), 0, stream, as<T>(sample), as<T>(eps_a), as<T>(eps_b), as<T>(out),
-                           n, k);
+        with_prediction(prediction, [&](auto pred) {
+            hipLaunchKernelGGL((k_ddim_step<T, decltype(pred)::value>), dim3(stream_grid(n)), dim3(256), 0, stream, as<T>(sample),
+                               as<T>(eps_a), as<T>(eps_b), as<T>(out), n, k);
+        });
     });
     return hipGetLastError();
 }
@@ -92,7 +95,7 @@ size_t null_loss_workspace_bytes(size_t n) {
 
 hipError_t launch_null_loss_grad(const void* eps_uncond, const void* eps_cond, const void* latent_cur, const void* latent_prev,
                                  void* rec, float* loss, void* grad, int dtype, size_t n, float guidance, const float c[4],
-                                 double grad_scale, void* workspace, hipStream_t stream) {
+                                 int prediction, double grad_scale, void* workspace, hipStream_t stream) {
     const int blocks = (int)null_loss_blocks(n);
     const dim3 grid(blocks), block(INV_THREADS);
     const StepCoeffs k = step_coeffs(guidance, c);
@@ -100,8 +103,10 @@ hipError_t launch_null_loss_grad(const void* eps_uncond, const void* eps_cond, c
     const float count = (float)n;
     with_latent_type(dtype, [&](auto tag) {
         using T = decltype(tag);
-        hipLaunchKernelGGL(k_null_loss_grad<T>, grid, block, 0, stream, as<T>(eps_uncond), as<T>(eps_cond), as<T>(latent_cur),
-                           as<T>(latent_prev), as<T>(rec), as<T>(grad), loss, partial, n, k, grad_scale, count);
+        with_prediction(prediction, [&](auto pred) {
+            hipLaunchKernelGGL((k_null_loss_grad<T, decltype(pred)::value>), grid, block, 0, stream, as<T>(eps_uncond), as<T>(eps_cond),
+                               as<T>(latent_cur), as<T>(latent_prev), as<T>(rec), as<T>(grad), loss, partial, n, k, grad_scale, count);
+        });
     });
     if (blocks > 1) hipLaunchKernelGGL(k_null_loss_final, dim3(1), block, 0, stream, partial, blocks, loss, count);
     return hipGetLastError();

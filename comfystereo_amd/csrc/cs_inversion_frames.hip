@@ -29,7 +29,7 @@ __device__ __forceinline__ void frame_loss_and_flag(float hi, float lo, float co
     active_out[f] = (double)value < threshold ? 0 : 1;
 }
 
-template <class T>
+template <class T, int PRED>
 __global__ void __launch_bounds__(INV_THREADS) k_null_loss_grad_frames(
     const T* __restrict__ eps_uncond, const T* __restrict__ eps_cond, const T* __restrict__ latent_cur, const T* __restrict__ latent_prev,
     T* __restrict__ rec, T* __restrict__ grad, float* __restrict__ loss, float* __restrict__ partial,
@@ -45,8 +45,8 @@ __global__ void __launch_bounds__(INV_THREADS) k_null_loss_grad_frames(
         return;
     }
     float hi = 0.0f, lo = 0.0f;
-    null_loss_block<T>(eps_uncond + base, eps_cond + base, latent_cur + base, latent_prev + base, rec + base, grad + base, blockIdx.x, per,
-                       k, grad_scale, hi, lo);
+    null_loss_block<T, PRED>(eps_uncond + base, eps_cond + base, latent_cur + base, latent_prev + base, rec + base, grad + base,
+                             blockIdx.x, per, k, grad_scale, hi, lo);
     block_reduce_pairs(hi, lo, sh_hi, sh_lo);
     if (threadIdx.x == 0) {
         if (gridDim.x == 1) {
@@ -95,8 +95,8 @@ size_t null_loss_frames_workspace_bytes(size_t frames, size_t per) {
 
 hipError_t launch_null_loss_grad_frames(const void* eps_uncond, const void* eps_cond, const void* latent_cur, const void* latent_prev,
                                         void* rec, float* loss, void* grad, const uint8_t* active_in, uint8_t* active_out, int dtype,
-                                        size_t frames, size_t per, float guidance, const float c[4], double grad_scale, double threshold,
-                                        void* workspace, hipStream_t stream) {
+                                        size_t frames, size_t per, float guidance, const float c[4], int prediction, double grad_scale,
+                                        double threshold, void* workspace, hipStream_t stream) {
     const int blocks = (int)null_loss_blocks(per);
     const dim3 grid(blocks, (unsigned)frames), block(INV_THREADS);
     const StepCoeffs k{guidance, c[0], c[1], c[2], c[3]};
@@ -104,9 +104,11 @@ hipError_t launch_null_loss_grad_frames(const void* eps_uncond, const void* eps_
     const float count = (float)per;
     with_latent_type(dtype, [&](auto tag) {
         using T = decltype(tag);
-        hipLaunchKernelGGL(k_null_loss_grad_frames<T>, grid, block, 0, stream, as<T>(eps_uncond), as<T>(eps_cond), as<T>(latent_cur),
-                           as<T>(latent_prev), as<T>(rec), as<T>(grad), loss, partial, active_in, active_out, per, k, grad_scale, count,
-                           threshold);
+        with_prediction(prediction, [&](auto pred) {
+            hipLaunchKernelGGL((k_null_loss_grad_frames<T, decltype(pred)::value>), grid, block, 0, stream, as<T>(eps_uncond),
+                               as<T>(eps_cond), as<T>(latent_cur), as<T>(latent_prev), as<T>(rec), as<T>(grad), loss, partial, active_in,
+                               active_out, per, k, grad_scale, count, threshold);
+        });
     });
     if (blocks > 1)
         hipLaunchKernelGGL(k_null_loss_final_frames, dim3((unsigned)frames), block, 0, stream, partial, blocks, loss, active_in, active_out,

@@ -329,15 +329,16 @@ hipError_t launch_latent_shift_apply(const void* left, void* right, const int32_
                                      int dtype, int b, int c, int h, int w, int op, hipStream_t stream);
 hipError_t launch_decode_to_codes(const void* image, int dtype, int n, int c, int h, int w, uint8_t* codes, hipStream_t stream);
 // cs_inversion.hip (null-text inversion outside the UNet: cs_ddim_step, cs_null_loss_grad, cs_adam_step).  dtype: enum
-// cs_latent_dtype; c: the step's four coefficients c1..c4; grad_scale: (2 / n) * (c3 - c4 * c1 / c2) * (1 - guidance);
+// cs_latent_dtype; c: the step's four coefficients c1..c4; prediction: enum cs_prediction; grad_scale: (2 / n) * (c3 - c4 * c1 / c2)
+// * (1 - guidance), under CS_PRED_V (2 / n) * (c3 * c2 - c4 * c1) * (1 - guidance);
 // adam: w1 = 1 - beta1, beta2, w2 = 1 - beta2, sqrt(bias correction 2), eps, -lr / bias correction 1
 hipError_t launch_ddim_step(const void* sample, const void* eps_a, const void* eps_b, void* out, int dtype, size_t n, float guidance,
-                            const float c[4], hipStream_t stream);
+                            const float c[4], int prediction, hipStream_t stream);
 size_t null_loss_max_count();
 size_t null_loss_workspace_bytes(size_t n);
 hipError_t launch_null_loss_grad(const void* eps_uncond, const void* eps_cond, const void* latent_cur, const void* latent_prev,
                                  void* rec, float* loss, void* grad, int dtype, size_t n, float guidance, const float c[4],
-                                 double grad_scale, void* workspace, hipStream_t stream);
+                                 int prediction, double grad_scale, void* workspace, hipStream_t stream);
 hipError_t launch_adam_step(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, int dtype, size_t n, const float adam[6],
                             hipStream_t stream);
 // cs_inversion_frames.hip (the same on F frames of `per` elements each: cs_null_loss_grad_frames, cs_adam_step_frames).  active_in,
@@ -346,8 +347,8 @@ size_t null_loss_frames_max();
 size_t null_loss_frames_workspace_bytes(size_t frames, size_t per);
 hipError_t launch_null_loss_grad_frames(const void* eps_uncond, const void* eps_cond, const void* latent_cur, const void* latent_prev,
                                         void* rec, float* loss, void* grad, const uint8_t* active_in, uint8_t* active_out, int dtype,
-                                        size_t frames, size_t per, float guidance, const float c[4], double grad_scale, double threshold,
-                                        void* workspace, hipStream_t stream);
+                                        size_t frames, size_t per, float guidance, const float c[4], int prediction, double grad_scale,
+                                        double threshold, void* workspace, hipStream_t stream);
 hipError_t launch_adam_step_frames(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, const uint8_t* active, int dtype,
                                    size_t frames, size_t m, const float adam[6], hipStream_t stream);
 // cs_inpaintloop.hip (StereoDiffusion Fast mode's inpainting loop outside its models: cs_inpaint_image_prep,
@@ -363,7 +364,7 @@ hipError_t launch_inpaint_plms_step(const void* noise_pred, void* x, int dtype, 
 // cs_standardloop.hip (StereoDiffusion Standard mode between two UNet calls: cs_standard_step).  dtype: enum cs_latent_dtype;
 // op: enum cs_standard_op; cf: the step's four coefficients c1..c4; x [4b][c][h][w], the UNet's persistent input
 hipError_t launch_standard_step(void* x, const void* noise_pred, int dtype, int b, int c, int h, int w, float guidance, const float cf[4],
-                                int op, const int32_t* src_col, uint8_t* mask, const void* noise, hipStream_t stream);
+                                int prediction, int op, const int32_t* src_col, uint8_t* mask, const void* noise, hipStream_t stream);
 // lazy depth-blur tiles in k_gpuwarp (tilemap != nullptr): rows of at most this many columns, not the mesh-quality warp
 int gpuwarp_lazy_max_width();
 

@@ -5,6 +5,7 @@
 // that reaches only one of them.
 #pragma once
 #include <initializer_list>
+#include <type_traits>
 
 #include "cs_common.h"
 
@@ -74,6 +75,16 @@ void with_latent_type(int dtype, F&& f) {
         f(_Float16{});
     else
         f(__bf16{});
+}
+
+// f(tag) with decltype(tag)::value the prediction type (enum cs_prediction, checked by the caller), a compile-time constant:
+// with_prediction(prediction, [&](auto pred) { constexpr int P = decltype(pred)::value; ... })
+template <class F>
+void with_prediction(int prediction, F&& f) {
+    if (prediction == CS_PRED_V)
+        f(std::integral_constant<int, CS_PRED_V>{});
+    else
+        f(std::integral_constant<int, CS_PRED_EPSILON>{});
 }
 
 // a void* argument as the kernel's element pointer

@@ -44,8 +44,8 @@ __device__ __forceinline__ void block_reduce_pairs(float& hi, float& lo, float* 
 }
 
 // One thread's share of block `block` of a tensor of n elements: rec, grad and the thread's pair of the squares' sum.  The
-// pointers are the tensor's (a frame's) first element.
-template <class T>
+// pointers are the tensor's (a frame's) first element.  PRED: what the model predicts (cs_ddimstep.h).
+template <class T, int PRED = CS_PRED_EPSILON>
 __device__ __forceinline__ void null_loss_block(const T* __restrict__ eps_uncond, const T* __restrict__ eps_cond,
                                                 const T* __restrict__ latent_cur, const T* __restrict__ latent_prev,
                                                 T* __restrict__ rec, T* __restrict__ grad, size_t block, size_t n, const StepCoeffs& k,
@@ -54,12 +54,12 @@ __device__ __forceinline__ void null_loss_block(const T* __restrict__ eps_uncond
     const size_t end = begin + INV_BLOCK_ELEMS < n ? begin + INV_BLOCK_ELEMS : n;
     for (size_t i = begin + threadIdx.x; i < end; i += INV_THREADS) {
         const float e = guided<T>((float)eps_uncond[i], (float)eps_cond[i], true, k.guidance);
-        rec[i] = (T)ddim_value<T>((float)latent_cur[i], e, k);
+        rec[i] = (T)ddim_value<T, PRED>((float)latent_cur[i], e, k);
         // loss and gradient: from the reconstruction before its roundings to T (float64 per element, which the bound against a
         // float64 restatement asks for at small counts); each square enters the float32 sum rounded once
         const double a = (double)(float)eps_uncond[i];
         const double e64 = a + (double)k.guidance * ((double)(float)eps_cond[i] - a);
-        const double r64 = (double)k.c4 * (((double)(float)latent_cur[i] - (double)k.c1 * e64) / (double)k.c2) + (double)k.c3 * e64;
+        const double r64 = ddim_value_f64<PRED>((double)(float)latent_cur[i], e64, k);
         const double diff = r64 - (double)(float)latent_prev[i];
         grad[i] = (T)(float)(grad_scale * diff);
         two_sum_add(hi, lo, (float)(diff * diff));

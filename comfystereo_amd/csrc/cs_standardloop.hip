@@ -3,8 +3,8 @@
 //   x [4B][C][h][w]   rows 0..B-1 the left views, B..2B-1 the right views (the current latents), 2B..4B-1 their copy for the
 //                     conditional half (torch.cat([latents] * 2))
 //
-//   k_standard_step   e = u + guidance * (c - u), the DDIM step, then by `op` what k_latent_shift_apply does to the pair (new left,
-//                     new right); the result goes into both halves of x.
+//   k_standard_step   e = u + guidance * (c - u), the DDIM step (PRED: of an epsilon or a v-prediction model), then by `op` what
+//                     k_latent_shift_apply does to the pair (new left, new right); the result goes into both halves of x.
 //
 // Arithmetic: cs_ddimstep.h, the statement cs_ddim_step uses -- the results are the bits of cs_ddim_step on the two halves
 // followed by cs_latent_shift_apply.  The shift moves values and never computes.
@@ -30,14 +30,14 @@ constexpr size_t SL_LDS_BYTES = 49152;    // the LDS of one workgroup: at least 
 static_assert(LATENT_MAX_WIDTH * sizeof(float) <= SL_LDS_BYTES, "one row of the widest frame must fit");
 
 // the step of W consecutive elements at offset `at` of x's and noise_pred's first halves
-template <class T, int W>
+template <class T, int W, int PRED>
 __device__ __forceinline__ Chunk<T, W> step_chunk(const T* x, const T* __restrict__ noise_pred, size_t at, size_t half, const StepCoeffs& k) {
     const Chunk<T, W> s = load<T, W>(x + at), u = load<T, W>(noise_pred + at), c = load<T, W>(noise_pred + half + at);
     Chunk<T, W> out;
 #pragma unroll
     for (int q = 0; q < W; q++) {
         const float e = guided<T>((float)u.v[q], (float)c.v[q], true, k.guidance);
-        out.v[q] = (T)ddim_value<T>((float)s.v[q], e, k);
+        out.v[q] = (T)ddim_value<T, PRED>((float)s.v[q], e, k);
     }
     return out;
 }
@@ -46,7 +46,7 @@ __device__ __forceinline__ Chunk<T, W> step_chunk(const T* x, const T* __restric
 
 // grid: B * h workgroups, one per (b, row).  group: channels per pass, group * w elements of LDS.  x is read and written (not
 // __restrict__): every element of it is read by the one thread that writes it, before it does.
-template <class T, int W>
+template <class T, int W, int PRED>
 __global__ void __launch_bounds__(SL_THREADS) k_standard_step(T* x, const T* __restrict__ noise_pred, const int32_t* __restrict__ src_col,
                                                               uint8_t* mask, const T* __restrict__ noise, int nb, int c, int h, int w,
                                                               int group, int op, StepCoeffs k) {
@@ -65,7 +65,7 @@ __global__ void __launch_bounds__(SL_THREADS) k_standard_step(T* x, const T* __r
         for (int item = tid; item < gc * chunks; item += SL_THREADS) {
             const int g = item / chunks, col = (item - g * chunks) * W;
             const size_t at = left0 + (size_t)(g0 + g) * plane + col;
-            const Chunk<T, W> v = step_chunk<T, W>(x, noise_pred, at, half, k);
+            const Chunk<T, W> v = step_chunk<T, W, PRED>(x, noise_pred, at, half, k);
             store<T, W>(x + at, v);
             store<T, W>(x + half + at, v);
             if (op != CS_STANDARD_NONE) store<T, W>(row_left + (size_t)g * w + col, v);
@@ -76,7 +76,7 @@ __global__ void __launch_bounds__(SL_THREADS) k_standard_step(T* x, const T* __r
             const int g = item / chunks, col = (item - g * chunks) * W, ch = g0 + g;
             const size_t at = right0 + (size_t)ch * plane + col;
             Chunk<T, W> v;
-            if (op != CS_STANDARD_FIRST) v = step_chunk<T, W>(x, noise_pred, at, half, k);   // FIRST replaces every element
+            if (op != CS_STANDARD_FIRST) v = step_chunk<T, W, PRED>(x, noise_pred, at, half, k);   // FIRST replaces every element
             if (op != CS_STANDARD_NONE) {
                 Chunk<T, W> nz;
                 if (noise) nz = load<T, W>(noise + left0 + (size_t)ch * plane + col);
@@ -108,7 +108,7 @@ __global__ void __launch_bounds__(SL_THREADS) k_standard_step(T* x, const T* __r
     }
 }
 
-template <class T>
+template <class T, int PRED>
 static void standard_step(void* x, const void* noise_pred, const int32_t* src_col, uint8_t* mask, const void* noise, int b, int c, int h,
                           int w, int op, const StepCoeffs& k, hipStream_t stream) {
     constexpr int W = 16 / sizeof(T);
@@ -117,15 +117,19 @@ static void standard_step(void* x, const void* noise_pred, const int32_t* src_co
     const int group = op == CS_STANDARD_NONE ? c : (int)(fit < (size_t)c ? fit : (size_t)c);
     const size_t lds = op == CS_STANDARD_NONE ? 0 : (size_t)group * row_bytes;
     // whole chunks per row, and every row then starts on the 16-byte grid
-    launch_wide_or_narrow(w % W == 0 && aligned16({x, noise_pred, noise}), k_standard_step<T, W>, k_standard_step<T, 1>,
+    launch_wide_or_narrow(w % W == 0 && aligned16({x, noise_pred, noise}), k_standard_step<T, W, PRED>, k_standard_step<T, 1, PRED>,
                           dim3((unsigned)((size_t)b * h)), dim3(SL_THREADS), lds, stream, as<T>(x), as<T>(noise_pred), src_col, mask,
                           as<T>(noise), b, c, h, w, group, op, k);
 }
 
 hipError_t launch_standard_step(void* x, const void* noise_pred, int dtype, int b, int c, int h, int w, float guidance, const float cf[4],
-                                int op, const int32_t* src_col, uint8_t* mask, const void* noise, hipStream_t stream) {
+                                int prediction, int op, const int32_t* src_col, uint8_t* mask, const void* noise, hipStream_t stream) {
     const StepCoeffs k{guidance, cf[0], cf[1], cf[2], cf[3]};
-    with_latent_type(dtype, [&](auto tag) { standard_step<decltype(tag)>(x, noise_pred, src_col, mask, noise, b, c, h, w, op, k, stream); });
+    with_latent_type(dtype, [&](auto tag) {
+        with_prediction(prediction, [&](auto pred) {
+            standard_step<decltype(tag), decltype(pred)::value>(x, noise_pred, src_col, mask, noise, b, c, h, w, op, k, stream);
+        });
+    });
     return hipGetLastError();
 }
 

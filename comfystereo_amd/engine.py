@@ -776,47 +776,66 @@ def _flat_like(first, tensors, what):
     return _dtype_code(t0, _native.LATENT_DTYPE), t0.numel()
 
 
-def _step_scalars(guidance, coeffs):
+def _prediction(prediction):
+    """`prediction` in enum cs_prediction, or ValueError: the first check of every wrapper that takes it, before any tensor is
+    looked at."""
+    if not isinstance(prediction, str) or prediction not in _native.PREDICTION:
+        raise ValueError(f"unknown prediction {prediction!r} ({', '.join(_native.PREDICTION)})")
+    return _native.PREDICTION[prediction]
+
+
+def _step_scalars(guidance, coeffs, prediction=0):
     vals = _numbers((guidance,), coeffs, ("c1", "c2", "c3", "c4"), counted=True)
-    if vals[2] == 0.0:
+    if vals[2] == 0.0 and prediction == _native.PREDICTION["epsilon"]:   # (under v-prediction c2 multiplies and divides nothing)
         raise ValueError("coeffs[1] (the square root of alpha_t) must not be 0")
     return vals
 
 
 def ddim_step(sample, eps_a, eps_b, guidance, coeffs, out=None):
-    """cs_ddim_step: guidance and one DDIM step in one launch.  e = eps_a + guidance * (eps_b - eps_a), or eps_a when eps_b is
+    """ddim_step_pred for an epsilon model (the signature this function always had; a v-prediction model takes ddim_step_pred)."""
+    return ddim_step_pred(sample, eps_a, eps_b, guidance, coeffs, out)
+
+
+def ddim_step_pred(sample, eps_a, eps_b, guidance, coeffs, out=None, prediction="epsilon"):
+    """cs_ddim_step_pred: guidance and one DDIM step in one launch.  e = eps_a + guidance * (eps_b - eps_a), or eps_a when eps_b is
     None; out = c4 * ((sample - c1 * e) / c2) + c3 * e with coeffs = (c1, c2, c3, c4) = (sqrt(1 - a_t), sqrt(a_t),
     sqrt(1 - a_other), sqrt(a_other)) as float32 values: NullInversion.prev_step and next_step (reference inversion.py:57-75) are
     this formula with their two alphas.  Tensors of one shape and dtype (float32, float16, bfloat16), contiguous; every operation is
     rounded to the dtype as torch rounds the reference's expression.  out: None (a new tensor) or a tensor to write, which may be
-    `sample` itself.  -> out"""
+    `sample` itself.  prediction "v_prediction": eps_a and eps_b are the answers of a v-prediction model (Salimans & Ho 2022), and
+    with v the guided one, x0 = c2 * sample - c1 * v; e = c2 * v + c1 * sample; out = c4 * x0 + c3 * e (c2 a first operand: rounded
+    to a half dtype like c1, c3 and c4, and free to be 0).  -> out"""
+    pred = _prediction(prediction)
     ins = [("eps_a", eps_a)] + ([("eps_b", eps_b)] if eps_b is not None else []) + ([("out", out)] if out is not None else [])
     dtype, n = _flat_like(("sample", sample), ins, "sample, eps_a, eps_b and out")
-    g, c1, c2, c3, c4 = _step_scalars(guidance, coeffs)
+    g, c1, c2, c3, c4 = _step_scalars(guidance, coeffs, pred)
     for name, t in [("sample", sample)] + ins:
         _tensor(name, t, no_grad="cs_ddim_step is not differentiable (detach it, or run under no_grad on detached tensors)")
     _on_gpu(sample, no_gpu_error=True)
     if out is None:
         out = torch.empty_like(sample)
-    _launch(sample.device, _native.lib().cs_ddim_step, _ptr(sample), _ptr(eps_a), _opt_ptr(eps_b), _ptr(out), dtype, n, g, c1, c2, c3, c4)
+    _launch(sample.device, _native.lib().cs_ddim_step_pred, _ptr(sample), _ptr(eps_a), _opt_ptr(eps_b), _ptr(out), dtype, n, g, c1, c2, c3,
+            c4, pred)
     return out
 
 
-def null_loss_grad(eps_uncond, eps_cond, latent_cur, latent_prev, guidance, coeffs):
+def null_loss_grad(eps_uncond, eps_cond, latent_cur, latent_prev, guidance, coeffs, prediction="epsilon"):
     """cs_null_loss_grad: the inner step of null-text optimisation outside the UNet (reference inversion.py:198-201) in one
     launch -> (rec, loss, grad): rec = prev_step(eps_uncond + guidance * (eps_cond - eps_uncond), t, latent_cur) bit for bit,
     loss = mean((rec - latent_prev)^2) as a float32 tensor [] (a fixed summation order: the same bits on every run), grad =
-    d loss / d eps_uncond in the tensors' dtype.  Nothing here waits for the device."""
+    d loss / d eps_uncond in the tensors' dtype.  prediction: as for ddim_step (the gradient is then with respect to the
+    unconditional v).  Nothing here waits for the device."""
+    pred = _prediction(prediction)
     dtype, n = _flat_like(("eps_uncond", eps_uncond), [("eps_cond", eps_cond), ("latent_cur", latent_cur), ("latent_prev", latent_prev)],
                           "eps_uncond, eps_cond, latent_cur and latent_prev")
-    g, c1, c2, c3, c4 = _step_scalars(guidance, coeffs)
+    g, c1, c2, c3, c4 = _step_scalars(guidance, coeffs, pred)
     _on_gpu(eps_uncond, no_gpu_error=True)
     L = _native.lib()
     rec, grad = torch.empty_like(eps_uncond), torch.empty_like(eps_uncond)
     loss = torch.empty((), dtype=torch.float32, device=eps_uncond.device)
     ws, nb = _workspace(L.cs_null_loss_workspace_bytes(n), eps_uncond.device)
-    _launch(eps_uncond.device, L.cs_null_loss_grad, _ptr(eps_uncond), _ptr(eps_cond), _ptr(latent_cur), _ptr(latent_prev), _ptr(rec),
-            _ptr(loss), _ptr(grad), dtype, n, g, c1, c2, c3, c4, _ptr(ws) if nb else None, nb)
+    _launch(eps_uncond.device, L.cs_null_loss_grad_pred, _ptr(eps_uncond), _ptr(eps_cond), _ptr(latent_cur), _ptr(latent_prev), _ptr(rec),
+            _ptr(loss), _ptr(grad), dtype, n, g, c1, c2, c3, c4, pred, _ptr(ws) if nb else None, nb)
     return rec, loss, grad
 
 
@@ -828,8 +847,8 @@ class NullTextLoss(torch.autograd.Function):
     whatever the dtype.  ctx.rec: the reconstructed latent, for callers that want it."""
 
     @staticmethod
-    def forward(ctx, eps_uncond, eps_cond, latent_cur, latent_prev, guidance, coeffs):
-        rec, loss, grad = null_loss_grad(eps_uncond.detach(), eps_cond, latent_cur, latent_prev, guidance, coeffs)
+    def forward(ctx, eps_uncond, eps_cond, latent_cur, latent_prev, guidance, coeffs, prediction="epsilon"):
+        rec, loss, grad = null_loss_grad(eps_uncond.detach(), eps_cond, latent_cur, latent_prev, guidance, coeffs, prediction)
         ctx.save_for_backward(grad)
         ctx.rec = rec
         return loss
@@ -838,7 +857,7 @@ class NullTextLoss(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_output):
         (grad,) = ctx.saved_tensors
-        return (grad * grad_output.to(grad.dtype)), None, None, None, None, None
+        return (grad * grad_output.to(grad.dtype)), None, None, None, None, None, None
 
 
 def adam_step(param, grad, exp_avg, exp_avg_sq, lr, step, beta1=0.9, beta2=0.999, eps=1e-8):
@@ -893,18 +912,20 @@ def _frame_flags(name, t, frames, first):
 
 
 def null_loss_grad_frames(eps_uncond, eps_cond, latent_cur, latent_prev, guidance, coeffs, active_in, threshold, active_out=None,
-                          loss=None, rec=None, grad=None, workspace=None):
+                          loss=None, rec=None, grad=None, workspace=None, prediction="epsilon"):
     """cs_null_loss_grad_frames: null_loss_grad on F frames in one launch -> (rec, loss [F] float32, grad, active_out).  Tensors
     [F, ...]; a frame's rec, grad and loss are bit for bit null_loss_grad's on that frame alone.  active_in uint8 [F]: a frame whose
     flag is 0 gets a zero grad, its rec and loss are not touched.  active_out uint8 [F], another buffer than active_in:
     active_in[f] and not float64(loss[f]) < threshold -- the reference's early stop, left on the device.  active_out, loss, rec,
     grad, workspace (uint8, null_loss_frames_workspace_bytes(F, per) bytes): buffers to write, or None for new ones (a new loss
-    is NaNs, a new rec zeros: what an inactive frame then shows).  Nothing here waits for the device."""
+    is NaNs, a new rec zeros: what an inactive frame then shows).  prediction: as for ddim_step.  Nothing here waits for the
+    device."""
+    pred = _prediction(prediction)
     first = ("eps_uncond", eps_uncond)
     dtype, frames, per = _frames_like(first, [("eps_cond", eps_cond), ("latent_cur", latent_cur), ("latent_prev", latent_prev)]
                                       + [(n, t) for n, t in (("rec", rec), ("grad", grad)) if t is not None],
                                       "eps_uncond, eps_cond, latent_cur, latent_prev, rec and grad")
-    g, c1, c2, c3, c4 = _step_scalars(guidance, coeffs)
+    g, c1, c2, c3, c4 = _step_scalars(guidance, coeffs, pred)
     threshold = float(threshold)
     if math.isnan(threshold):
         raise ValueError("threshold must not be a NaN")
@@ -931,8 +952,8 @@ def null_loss_grad_frames(eps_uncond, eps_cond, latent_cur, latent_prev, guidanc
     active_out = torch.empty((frames,), dtype=torch.uint8, device=dev) if active_out is None else active_out
     if workspace is None:
         workspace, _ = _workspace(need, dev)
-    _launch(dev, L.cs_null_loss_grad_frames, _ptr(eps_uncond), _ptr(eps_cond), _ptr(latent_cur), _ptr(latent_prev), _ptr(rec), _ptr(loss),
-            _ptr(grad), _ptr(active_in), _ptr(active_out), dtype, frames, per, g, c1, c2, c3, c4, threshold,
+    _launch(dev, L.cs_null_loss_grad_frames_pred, _ptr(eps_uncond), _ptr(eps_cond), _ptr(latent_cur), _ptr(latent_prev), _ptr(rec),
+            _ptr(loss), _ptr(grad), _ptr(active_in), _ptr(active_out), dtype, frames, per, g, c1, c2, c3, c4, pred, threshold,
             _ptr(workspace) if need else None, need)
     return rec, loss, grad, active_out
 
@@ -945,9 +966,10 @@ class NullTextLossFrames(torch.autograd.Function):
     the reconstructed latents and the flags of the next inner step."""
 
     @staticmethod
-    def forward(ctx, eps_uncond, eps_cond, latent_cur, latent_prev, guidance, coeffs, active_in, threshold, active_out=None):
+    def forward(ctx, eps_uncond, eps_cond, latent_cur, latent_prev, guidance, coeffs, active_in, threshold, active_out=None,
+                prediction="epsilon"):
         rec, loss, grad, active_out = null_loss_grad_frames(eps_uncond.detach(), eps_cond, latent_cur, latent_prev, guidance, coeffs,
-                                                            active_in, threshold, active_out)
+                                                            active_in, threshold, active_out, prediction=prediction)
         ctx.save_for_backward(grad)
         ctx.rec, ctx.active_out = rec, active_out
         return loss
@@ -958,7 +980,7 @@ class NullTextLossFrames(torch.autograd.Function):
         (grad,) = ctx.saved_tensors
         if not bool((grad_output == 1).all()):
             raise ValueError("NullTextLossFrames takes the gradient of its loss as ones (loss.sum().backward()); got another value")
-        return (grad,) + (None,) * 8
+        return (grad,) + (None,) * 9
 
 
 def adam_step_frames(param, grad, exp_avg, exp_avg_sq, active, lr, step, beta1=0.9, beta2=0.999, eps=1e-8):
@@ -1086,14 +1108,15 @@ def plms_step(noise_pred, x, kind, guidance, coeffs, e_out=None, history=(), cur
 
 
 # ---- StereoDiffusion Standard mode between two UNet calls (cs_standard_step) ----
-def standard_step(noise_pred, x, guidance, coeffs, op="none", src_col=None, mask=None, noise=None):
+def standard_step(noise_pred, x, guidance, coeffs, op="none", src_col=None, mask=None, noise=None, prediction="epsilon"):
     """cs_standard_step: classifier-free guidance, one DDIM step and the latent shift in one launch, in place on the UNet's
     persistent input.  x [4B,C,h,w]: rows 0..B-1 the left views, B..2B-1 the right views, 2B..4B-1 their copy for the conditional
     half; noise_pred [4B,C,h,w], the unconditional half first; both of one dtype (float32, float16, bfloat16), contiguous.
     e = u + guidance * (c - u); new = c4 * ((x - c1 * e) / c2) + c3 * e with coeffs = (c1, c2, c3, c4) as for ddim_step; then by
     `op` ("none", "first", "reshift") what latent_shift_apply does to (new left, new right) with src_col int32 [B,h,w], mask uint8
     [B,h,w] and, for "first", an optional noise [B,C,h,w].  The result goes into both halves of x: bit for bit ddim_step on the
-    two halves, then latent_shift_apply, then the copy.  -> x"""
+    two halves, then latent_shift_apply, then the copy.  prediction: as for ddim_step, whose v-prediction step this then is.  -> x"""
+    pred = _prediction(prediction)
     if op not in _native.STANDARD_OP:
         raise ValueError(f"unknown op {op!r} (none, first, reshift)")
     if noise is not None and op != "first":
@@ -1120,9 +1143,9 @@ def standard_step(noise_pred, x, guidance, coeffs, op="none", src_col=None, mask
         src_col = mask = None
     if w > LATENT_MAX_WIDTH:
         raise ValueError(f"rows of {w} columns: cs_standard_step takes up to {LATENT_MAX_WIDTH} (latent_shift_plan's limit)")
-    g, c1, c2, c3, c4 = _step_scalars(guidance, coeffs)
+    g, c1, c2, c3, c4 = _step_scalars(guidance, coeffs, pred)
     _same_device(("x", x), *named)
     _on_gpu(x, no_gpu_error=True)
-    _launch(x.device, _native.lib().cs_standard_step, _ptr(x), _ptr(noise_pred), _dtype_code(x, _native.LATENT_DTYPE), b, c, h, w, g, c1, c2,
-            c3, c4, _native.STANDARD_OP[op], _opt_ptr(src_col), _opt_ptr(mask), _opt_ptr(noise))
+    _launch(x.device, _native.lib().cs_standard_step_pred, _ptr(x), _ptr(noise_pred), _dtype_code(x, _native.LATENT_DTYPE), b, c, h, w, g, c1,
+            c2, c3, c4, pred, _native.STANDARD_OP[op], _opt_ptr(src_col), _opt_ptr(mask), _opt_ptr(noise))
     return x

@@ -22,6 +22,11 @@ float16 / bfloat16: CPU torch -- the run the fixtures record -- converts a 0-dim
 product with a half tensor to the half dtype before it multiplies, and keeps the divisor's float32: c1, c3 and c4 are rounded to
 the tensors' dtype when the scheduler's alphas are tensors, c2 is not (`_operand`).  float32 needs none of this.
 
+A v-prediction model (scheduler.config.prediction_type == "v_prediction", the SD 2.x 768-v checkpoints): the same launches with
+prediction="v_prediction" -- x0 = c2 * x - c1 * v; e = c2 * v + c1 * x; out = c4 * x0 + c3 * e --, c2 then rounded like the other
+three (schedulers.step_coeffs).  A scheduler that does not say predicts epsilon.  NullInversion.work_size: the side of the square
+work frame, 512 unless the caller sets it (768 for those checkpoints); the methods keep the reference's signatures.
+
 No CPU fallback: without a GPU the first kernel raises RuntimeError, as the attention hook does.
 """
 import math
@@ -30,7 +35,7 @@ import numpy as np
 import torch
 
 from . import diffusion_utils, engine
-from .schedulers import _operand, _sqrt   # noqa: F401  (inpaint_runner imports them from here)
+from .schedulers import _operand, _sqrt, check_work_size, prediction_of, step_coeffs   # noqa: F401  (inpaint_runner imports the first two from here)
 
 try:
     from torch.func import functional_call
@@ -54,6 +59,11 @@ class EmptyControl:
 class NullInversion:
     """DDIM inversion with null-text optimisation for image-to-latent conversion (reference :42-255)."""
 
+    # The side of the square frame invert and invert_frames work on: the reference's 512; 768 for the SD 2.x 768-v checkpoints.  An
+    # attribute, not an argument: the methods keep the reference's signatures.  A positive multiple of 8, checked where it is used;
+    # make_invert and make_invert_frames set it from stereodiffusion_nodes.STANDARD_WORK_SIZE.
+    work_size = 512
+
     def __init__(self, model, num_ddim_steps: int = 50, guidance_scale: float = 7.5):
         self.model = model
         self.num_ddim_steps = num_ddim_steps
@@ -70,7 +80,8 @@ class NullInversion:
     def _step_coeffs(self, kind, timestep, dtype):
         sch = self.scheduler
         # the scheduler is the model's and shared: another set_timesteps, or another schedule, must not meet this one's values
-        key = (kind, int(timestep), dtype, sch.num_inference_steps, id(sch.alphas_cumprod))
+        prediction = prediction_of(sch)
+        key = (kind, int(timestep), dtype, sch.num_inference_steps, id(sch.alphas_cumprod), prediction)
         if key not in self._coeffs:
             ratio = sch.config.num_train_timesteps // sch.num_inference_steps
             if kind == "prev":   # (:58-63)
@@ -81,16 +92,15 @@ class NullInversion:
                 timestep, next_timestep = min(timestep - ratio, 999), timestep
                 alpha_prod_t = sch.alphas_cumprod[timestep] if timestep >= 0 else sch.final_alpha_cumprod
                 alpha_other = sch.alphas_cumprod[next_timestep]
-            beta_prod_t = 1 - alpha_prod_t
-            self._coeffs[key] = (_operand(_sqrt(beta_prod_t), dtype, True), _operand(_sqrt(alpha_prod_t), dtype, False),
-                                 _operand(_sqrt(1 - alpha_other), dtype, True), _operand(_sqrt(alpha_other), dtype, True))
+            self._coeffs[key] = step_coeffs(alpha_prod_t, alpha_other, dtype, prediction)
         return self._coeffs[key]
 
     def _step(self, kind, eps_a, eps_b, guidance, timestep, sample):
         sample = sample.detach().contiguous()
         eps_a = eps_a.detach().contiguous()
         eps_b = None if eps_b is None else eps_b.detach().contiguous()
-        return engine.ddim_step(sample, eps_a, eps_b, guidance, self._step_coeffs(kind, timestep, sample.dtype))
+        return engine.ddim_step_pred(sample, eps_a, eps_b, guidance, self._step_coeffs(kind, timestep, sample.dtype),
+                                     prediction=prediction_of(self.scheduler))
 
     # prev_step / next_step: the values of the reference's; not differentiable (the inputs are detached): inside the optimisation
     # the gradient goes through engine.NullTextLoss instead
@@ -197,12 +207,14 @@ class NullInversion:
             latent_cur = latent_cur.detach().contiguous()
             t = self.model.scheduler.timesteps[i]
             coeffs = self._step_coeffs("prev", t, latent_cur.dtype)
+            prediction = prediction_of(self.scheduler)
             with torch.no_grad():
                 noise_pred_cond = self.get_noise_pred_single(latent_cur, t, cond_embeddings).contiguous()
             losses = []
             for j in range(num_inner_steps):
                 noise_pred_uncond = self.get_noise_pred_single(latent_cur, t, uncond_embeddings).contiguous()
-                loss = engine.NullTextLoss.apply(noise_pred_uncond, noise_pred_cond, latent_cur, latent_prev, self.guidance_scale, coeffs)
+                loss = engine.NullTextLoss.apply(noise_pred_uncond, noise_pred_cond, latent_cur, latent_prev, self.guidance_scale, coeffs,
+                                                 prediction)
                 (grad,) = torch.autograd.grad(loss, [uncond_embeddings])
                 engine.adam_step(uncond_embeddings, grad.contiguous(), exp_avg, exp_avg_sq, lr, j + 1)
                 loss_item = loss.item()   # the one wait per inner step: the early stop needs it
@@ -218,6 +230,7 @@ class NullInversion:
         return uncond_embeddings_list
 
     def invert(self, image, prompt: str, num_inner_steps=10, early_stop_epsilon=1e-5, null_text_optimization=True):
+        work_size = check_work_size(self.work_size)
         self.init_prompt(prompt)
         diffusion_utils.register_attention_control(self.model, None)
 
@@ -227,8 +240,8 @@ class NullInversion:
             given = image
             image = torch.from_numpy(image)
         if isinstance(image, torch.Tensor) and image.dim() == 3:
-            if image.shape[0] != 512 or image.shape[1] != 512:
-                image = engine.pil_resize(image.to(self._get_device())[None], (512, 512))[0]
+            if image.shape[0] != work_size or image.shape[1] != work_size:
+                image = engine.pil_resize(image.to(self._get_device())[None], (work_size, work_size))[0]
             if image.max() <= 1:
                 image = (image * 255).to(torch.uint8)
         if as_array:
@@ -316,6 +329,7 @@ class NullInversion:
             latent_cur = latent_cur.detach().contiguous()
             t = self.model.scheduler.timesteps[i]
             coeffs = self._step_coeffs("prev", t, latent_cur.dtype)
+            prediction = prediction_of(self.scheduler)
             threshold = epsilon + i * 2e-5
             with torch.no_grad():
                 noise_pred_cond = self.get_noise_pred_single(latent_cur, t, cond_embeddings).contiguous()
@@ -327,7 +341,7 @@ class NullInversion:
                 noise_pred_uncond = self.get_noise_pred_single(latent_cur, t, uncond_embeddings).contiguous()
                 engine.null_loss_grad_frames(noise_pred_uncond.detach(), noise_pred_cond, latent_cur, latent_prev, self.guidance_scale,
                                              coeffs, flags[cur], threshold, active_out=flags[1 - cur], loss=loss, rec=rec, grad=grad,
-                                             workspace=workspace)
+                                             workspace=workspace, prediction=prediction)
                 (emb_grad,) = torch.autograd.grad(noise_pred_uncond, [uncond_embeddings], grad_outputs=grad)
                 engine.adam_step_frames(uncond_embeddings, emb_grad.contiguous(), exp_avg, exp_avg_sq, flags[cur], lr, j + 1)
                 host = state.cpu()   # the one wait per inner step: the early stops need it
@@ -348,13 +362,15 @@ class NullInversion:
         return uncond_embeddings_list
 
     def invert_frames(self, images, prompt: str, num_inner_steps=10, early_stop_epsilon=1e-5, null_text_optimization=True):
-        """invert on F frames at once: images uint8 [F,512,512,3] on the device -> (x_t [F,C,h,w], uncond_embeddings): one
+        """invert on F frames at once: images uint8 [F,512,512,3] on the device (512: self.work_size) -> (x_t [F,C,h,w],
+        uncond_embeddings): one
         [F,77,D] tensor per outer step, or None where invert returns plain copies of the empty prompt's embedding (no
         optimisation asked for, or a ComfyUI model without torch.func).  Every frame's x_t, embeddings, losses and inner-step
         counts are what invert gives on that frame alone wherever the model's own arithmetic does not depend on the batch."""
+        work_size = check_work_size(self.work_size)
         if not (isinstance(images, torch.Tensor) and images.dtype == torch.uint8 and images.dim() == 4
-                and tuple(images.shape[1:]) == (512, 512, 3) and images.shape[0] > 0):
-            raise ValueError("images must be a uint8 tensor [F,512,512,3]")
+                and tuple(images.shape[1:]) == (work_size, work_size, 3) and images.shape[0] > 0):
+            raise ValueError(f"images must be a uint8 tensor [F,{work_size},{work_size},3]")
         self.init_prompt(prompt)
         diffusion_utils.register_attention_control(self.model, None)
         ddim_latents = self.ddim_loop_frames(self._images2latent(images))
@@ -371,15 +387,24 @@ class NullInversion:
         return ddim_latents[-1], uncond_embeddings
 
 
+def _standard_work_size():
+    """stereodiffusion_nodes.STANDARD_WORK_SIZE as it stands now, checked: the one switch of Standard mode's work frame."""
+    from . import stereodiffusion_nodes
+    return check_work_size(stereodiffusion_nodes.STANDARD_WORK_SIZE)
+
+
 def make_invert(model, num_ddim_steps, guidance_scale, null_text_optimization=True, num_inner_steps=10, early_stop_epsilon=1e-5):
-    """-> invert(image_u8 [512,512,3]) -> (x_t, uncond_embeddings): the callable stereodiffusion_nodes.generate_stereo_standard
+    """-> invert(image_u8 [512,512,3]) -> (x_t, uncond_embeddings), 512 being stereodiffusion_nodes.STANDARD_WORK_SIZE when the
+    callable runs: the callable stereodiffusion_nodes.generate_stereo_standard
     takes where the reference runs NullInversion(ldm_stable, steps, guidance_scale).invert(image, "", ...)
     (stereodiffusion_nodes.py:267-273).  The attention hook invert installs is removed again before it returns: the Standard
     loop installs its own."""
     from . import stereo_utils
 
     def invert(image_u8):
+        work_size = _standard_work_size()   # (refused before the model is touched)
         inversion = NullInversion(model, num_ddim_steps, guidance_scale)
+        inversion.work_size = work_size
         try:
             _, x_t, uncond_embeddings = inversion.invert(image_u8, "", num_inner_steps=num_inner_steps,
                                                          early_stop_epsilon=early_stop_epsilon,
@@ -392,12 +417,15 @@ def make_invert(model, num_ddim_steps, guidance_scale, null_text_optimization=Tr
 
 
 def make_invert_frames(model, num_ddim_steps, guidance_scale, null_text_optimization=True, num_inner_steps=10, early_stop_epsilon=1e-5):
-    """-> invert_frames(images_u8 [F,512,512,3]) -> (x_t [F,C,h,w], uncond_embeddings): make_invert for
+    """-> invert_frames(images_u8 [F,512,512,3]) -> (x_t [F,C,h,w], uncond_embeddings), 512 being
+    stereodiffusion_nodes.STANDARD_WORK_SIZE when the callable runs: make_invert for
     stereodiffusion_nodes.generate_stereo_standard_frames, F frames in one UNet batch."""
     from . import stereo_utils
 
     def invert_frames(images_u8):
+        work_size = _standard_work_size()   # (refused before the model is touched)
         inversion = NullInversion(model, num_ddim_steps, guidance_scale)
+        inversion.work_size = work_size
         try:
             return inversion.invert_frames(images_u8, "", num_inner_steps=num_inner_steps, early_stop_epsilon=early_stop_epsilon,
                                            null_text_optimization=null_text_optimization)

@@ -176,8 +176,11 @@ class ComfyUIModelWrapper:
         self.text_encoder = TextEncoderWrapper(clip, device)
         self.tokenizer = TokenizerWrapper(clip)
         self._model_type = self._detect_model_type()
+        self._prediction_kind = detect_prediction_kind(model)
+        # the steps between two UNet calls restate epsilon and v-prediction; any other kind is refused by is_supported, and its
+        # scheduler is never stepped
         self.scheduler = DDIMScheduler(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear", clip_sample=False,
-                                       set_alpha_to_one=False)
+                                       set_alpha_to_one=False, prediction_type=self.prediction_type or "epsilon")
 
     def _detect_model_type(self):
         """By the name of the model configuration's class; an unknown name with a 4-channel UNet counts as SD1."""
@@ -200,13 +203,39 @@ class ComfyUIModelWrapper:
     def model_type(self):
         return self._model_type
 
+    @property
+    def prediction_type(self):
+        """"epsilon" or "v_prediction" (the scheduler's prediction_type); None for a kind of model the steps do not restate."""
+        return _PREDICTION_OF_KIND.get(self._prediction_kind)
+
     def is_supported(self, pipeline_mode="standard"):
+        if self.prediction_type is None:
+            return False
         return self._model_type in (FAST_PIPELINE_MODEL_TYPES if pipeline_mode == "fast" else SUPPORTED_MODEL_TYPES)
 
     def get_unsupported_message(self):
+        if self.prediction_type is None:
+            return (f"Model sampling type '{self._prediction_kind}' is not supported for stereo generation: the DDIM steps are "
+                    "stated for epsilon (EPS) and v-prediction (V_PREDICTION) models only.")
         return (f"Model type '{self._model_type}' is not yet supported for stereo generation. "
                 f"Currently supported: {', '.join(SUPPORTED_MODEL_TYPES)}. "
                 f"SDXL and FLUX support may be added in future updates.")
+
+
+_PREDICTION_OF_KIND = {"EPS": "epsilon", "V_PREDICTION": "v_prediction"}
+
+
+def detect_prediction_kind(model):
+    """ComfyUI's model.model.model_type, duck-typed -> its name, upper case: an enum member (comfy.model_base.ModelType: EPS,
+    V_PREDICTION, EDM, FLOW, ...) gives its .name, a string itself.  A model that does not say is an epsilon model: "EPS"."""
+    kind = getattr(getattr(model, "model", None), "model_type", None)
+    if kind is None:
+        return "EPS"
+    name = kind if isinstance(kind, str) else getattr(kind, "name", None)
+    if not isinstance(name, str):
+        return str(kind).upper()
+    name = name.upper()
+    return {"EPSILON": "EPS", "V_PRED": "V_PREDICTION"}.get(name, name)
 
 
 def make_inpaint_runner(model, clip, vae, device="cuda"):
@@ -217,5 +246,9 @@ def make_inpaint_runner(model, clip, vae, device="cuda"):
     if in_ch != 9:   # before anything is loaded
         raise ValueError(f"Connected model has {in_ch} UNet input channels, but inpainting requires 9 channels. "
                          f"Please use an inpainting checkpoint (e.g., sd-v1-5-inpainting).")
+    kind = detect_prediction_kind(model)
+    if kind != "EPS":   # the PLMS step restates epsilon prediction only (the published SD2 inpainting checkpoint is an epsilon model)
+        raise ValueError(f"Connected inpainting model declares {'v-prediction' if kind == 'V_PREDICTION' else kind} "
+                         f"(model_type {kind}); Fast mode's inpainting loop supports epsilon-prediction models only.")
     _load_to_gpu(model)
     return inpaint_runner.InpaintRunner(unet, VAEWrapper(vae, device), TextEncoderWrapper(clip, device), TokenizerWrapper(clip))

@@ -39,7 +39,7 @@ import torch.nn.functional as F
 
 from . import engine, stereo_utils
 from .diffusion_utils import diffusion_step, init_latent
-from .schedulers import DDIMScheduler
+from .schedulers import DDIMScheduler, check_work_size, prediction_of
 
 
 def prepare_inpaint(image, depth, scale_factor, threshold=0.05):
@@ -201,6 +201,7 @@ class _StandardLoop:
         self.shifted = False
         # the fused path: our own DDIM scheduler, whose step the kernel restates; any other scheduler keeps diffusion_step
         self.fused = isinstance(model.scheduler, DDIMScheduler)
+        self.prediction = prediction_of(model.scheduler) if self.fused else "epsilon"   # what the fused step is told
         self.x = None
 
     def _op(self, i):
@@ -232,7 +233,7 @@ class _StandardLoop:
             noise_pred = noise_pred.contiguous()
         op = self._op(i)
         engine.standard_step(noise_pred, self.x, self.guidance_scale, self.coeffs[i], op, self.src_col, self.mask,
-                             self.noise if op == "first" else None)
+                             self.noise if op == "first" else None, prediction=self.prediction)
         self.shifted = self.shifted or op == "first"
 
     def step(self, i, t, latents, context):
@@ -252,6 +253,7 @@ def _stereo_latents(model, prompt, uncond_embeddings, latent, disparity, scale_f
     reached the shift step).  on_step(i, latents) sees the latents after every iteration."""
     if not (isinstance(prompt, (list, tuple)) and len(prompt) == 2 and all(isinstance(p, str) for p in prompt)):
         raise ValueError("prompt must be a list of two strings (the left and the right view)")
+    work_size = check_work_size(STANDARD_WORK_SIZE)
     if direction not in ("uni", "bi"):
         raise ValueError(f"direction must be 'uni' or 'bi', got {direction!r}")
     if not isinstance(num_inference_steps, int) or isinstance(num_inference_steps, bool) or num_inference_steps < 1:
@@ -268,7 +270,7 @@ def _stereo_latents(model, prompt, uncond_embeddings, latent, disparity, scale_f
     stereo_utils.register_attention_editor_diffusers(model, editor)
     try:
         batch_size = len(prompt)
-        height = width = WORK_SIZE
+        height = width = work_size
         tok = model.tokenizer
         text_input = tok(list(prompt), padding="max_length", max_length=tok.model_max_length, truncation=True, return_tensors="pt")
         text_embeddings = model.text_encoder(text_input.input_ids.to(model.device))[0]
@@ -327,7 +329,11 @@ def text2stereoimage(model, prompt, uncond_embeddings, latent, disparity, scale_
     device (a CPU generator, the reference's kind, also serves init_latent when latent is None; a device generator needs a
     latent), moved to the latents' --, on the latents' device otherwise.
     Runs under torch.no_grad() like the reference (:575), the VAE decode included: a caller that has gradients enabled for the
-    inversion need not switch them off.  The loop does not wait for the device."""
+    inversion need not switch them off.  The loop does not wait for the device.
+    The side of the square work frame is the module switch STANDARD_WORK_SIZE, a positive multiple of 8 (768 for the SD 2.x 768-v
+    checkpoints), read when the function runs; every 512 above is then that size and every 64 an eighth of it.  A scheduler whose
+    config.prediction_type is "v_prediction" makes every step the
+    v-prediction step, still one launch."""
     latents, _ = _stereo_latents(model, prompt, uncond_embeddings, latent, disparity, scale_factor, direction, deblur,
                                  num_inference_steps, guidance_scale, noise, generator)
     image = model.vae.decode(1 / 0.18215 * latents)["sample"]
@@ -349,11 +355,13 @@ def generate_stereo_standard(image, depth_map, scale_factor, direction, deblur, 
     is processed, as in the reference.  invert(image_u8 [512,512,3] uint8, on the device) -> (x_t [1,C,64,64], uncond_embeddings
     or None): it stands where the reference calls NullInversion.invert.  model, direction, deblur, noise, generator: as for
     text2stereoimage.  -> (stereo [1,H,2W,3], left [1,H,W,3], right [1,H,W,3]) float32, left and right being the two halves of
-    stereo.  Host tensors go to the device and the results come back to the host; device tensors stay where they are."""
+    stereo.  Host tensors go to the device and the results come back to the host; device tensors stay where they are.
+    STANDARD_WORK_SIZE, read when the function runs, is the side of the work frame where the text above says 512 (64: an eighth)."""
+    work_size = check_work_size(STANDARD_WORK_SIZE)
     if not (isinstance(image, torch.Tensor) and isinstance(depth_map, torch.Tensor)):
         raise ValueError("image and depth_map must be torch tensors")
     if not callable(invert):
-        raise ValueError("invert must be callable: invert(image_u8 [512,512,3]) -> (x_t, uncond_embeddings)")
+        raise ValueError(f"invert must be callable: invert(image_u8 [{work_size},{work_size},3]) -> (x_t, uncond_embeddings)")
     if image.dim() != 4 or image.shape[-1] != 3 or not image.is_floating_point():
         raise ValueError(f"image must be a float tensor [N,H,W,3], got {image.dtype} {tuple(image.shape)}")
     if depth_map.dim() == 3:
@@ -373,7 +381,7 @@ def generate_stereo_standard(image, depth_map, scale_factor, direction, deblur, 
     dev = _device_for(image, depth_map)
     image, depth_map = image[:1].to(dev, torch.float32), depth_map[:1].to(dev, torch.float32)
     _, h, w, _ = image.shape
-    s = (WORK_SIZE, WORK_SIZE)
+    s = (work_size, work_size)
     img_u8 = engine.pil_resize(image, s)
     depth_u8 = engine.pil_resize(depth_map, s, gray=depth_map.shape[-1] == 3)
     disp = _norm_depth(depth_u8[..., 0].float() / 255.0)
@@ -394,6 +402,12 @@ def generate_stereo_standard(image, depth_map, scale_factor, direction, deblur, 
 # null-text inversion takes minutes).  False: StereoDiffusionNode behaves as the reference's; True: Standard mode with more than one
 # frame goes through generate_stereo_standard_frames.  A module switch, like stereo_utils.HALF_ATTENTION.
 STANDARD_ALL_FRAMES = False
+
+# The side of the square frame Standard mode works on.  512 is the reference's constant; the SD 2.x 768-v checkpoints are trained
+# at 768.  A positive multiple of 8, checked and read whenever generate_stereo_standard, generate_stereo_standard_frames,
+# text2stereoimage or the callables of inversion.make_invert / make_invert_frames run: their signatures, and the node's INPUT_TYPES,
+# stay what they were.  Fast mode keeps WORK_SIZE.  A module switch like the one above.
+STANDARD_WORK_SIZE = 512
 
 
 def _norm_depth_frames(depth):
@@ -455,11 +469,13 @@ def generate_stereo_standard_frames(image, depth_map, scale_factor, direction, d
     [N,C,64,64]; None: drawn per frame as text2stereoimage draws it ([2,C,64,64] from `generator`, the right view's half), in frame
     order, so that a batch equals N successive single-frame calls on that generator.  Every frame has its own depth range.
     A model whose scheduler is not our DDIMScheduler runs frame by frame through generate_stereo_standard.
+    STANDARD_WORK_SIZE, read when the function runs, is the side of the work frame where the text above says 512 (64: an eighth).
     -> (stereo [N,H,2W,3], left [N,H,W,3], right [N,H,W,3]) float32, left and right being the two halves of stereo."""
+    work_size = check_work_size(STANDARD_WORK_SIZE)
     if not (isinstance(image, torch.Tensor) and isinstance(depth_map, torch.Tensor)):
         raise ValueError("image and depth_map must be torch tensors")
     if not callable(invert_frames):
-        raise ValueError("invert_frames must be callable: invert_frames(images_u8 [F,512,512,3]) -> (x_t, uncond_embeddings)")
+        raise ValueError(f"invert_frames must be callable: invert_frames(images_u8 [F,{work_size},{work_size},3]) -> (x_t, uncond_embeddings)")
     if image.dim() != 4 or image.shape[-1] != 3 or not image.is_floating_point():
         raise ValueError(f"image must be a float tensor [N,H,W,3], got {image.dtype} {tuple(image.shape)}")
     if depth_map.dim() == 3:
@@ -490,7 +506,7 @@ def generate_stereo_standard_frames(image, depth_map, scale_factor, direction, d
             stereo[k:k + 1] = one[0].to(dev)
     else:
         image, depth_map = image.to(dev, torch.float32), depth_map.to(dev, torch.float32)
-        s = (WORK_SIZE, WORK_SIZE)
+        s = (work_size, work_size)
         for k in range(0, n, frames_per_batch):
             group = slice(k, min(k + frames_per_batch, n))
             frames = group.stop - group.start

@@ -520,6 +520,34 @@ CS_API int cs_standard_step(void *x, const void *noise_pred, int dtype, int b, i
                             void *stream);
 
 /*
+ * The same four steps for a model that predicts something else than the noise (`prediction`: enum cs_prediction).  With
+ * CS_PRED_EPSILON each is its namesake above, bit for bit.  With CS_PRED_V the model's answer is v = c2 * eps - c1 * x0 (Salimans &
+ * Ho, "Progressive Distillation for Fast Sampling of Diffusion Models", 2022; the SD 2.x 768-v checkpoints); guidance is applied
+ * to the raw answers as before, v = eps_a + guidance * (eps_b - eps_a), and the step is
+ *     x0 = c2 * sample - c1 * v;   e = c2 * v + c1 * sample;   out = c4 * x0 + c3 * e
+ * -- the operation order of diffusers' DDIMScheduler.step with prediction_type "v_prediction", eta 0 -- every operation rounded
+ * once to the dtype as above.  c2 is the first operand of two products and divides nothing: c2 = 0 is no error under CS_PRED_V.
+ * The loss of cs_null_loss_grad_pred is taken from that formula in float64 in the same fixed order, and
+ * grad = d loss / d eps_uncond = (2 / count) * (rec - latent_prev) * (c3 * c2 - c4 * c1) * (1 - guidance).
+ * CS_EINVAL before any launch: an unknown prediction, and everything the namesake refuses (c2 = 0 under CS_PRED_EPSILON only).
+ */
+enum cs_prediction { CS_PRED_EPSILON = 0, CS_PRED_V = 1 };
+CS_API int cs_ddim_step_pred(const void *sample, const void *eps_a, const void *eps_b, void *out, int dtype, long long count,
+                             double guidance, double c1, double c2, double c3, double c4, int prediction, void *stream);
+CS_API int cs_null_loss_grad_pred(const void *eps_uncond, const void *eps_cond, const void *latent_cur, const void *latent_prev,
+                                  void *rec, float *loss, void *grad, int dtype, long long count, double guidance, double c1,
+                                  double c2, double c3, double c4, int prediction, void *workspace, size_t workspace_bytes,
+                                  void *stream);
+CS_API int cs_null_loss_grad_frames_pred(const void *eps_uncond, const void *eps_cond, const void *latent_cur,
+                                         const void *latent_prev, void *rec, float *loss, void *grad, const uint8_t *active_in,
+                                         uint8_t *active_out, int dtype, long long frames, long long per, double guidance,
+                                         double c1, double c2, double c3, double c4, int prediction, double threshold,
+                                         void *workspace, size_t workspace_bytes, void *stream);
+CS_API int cs_standard_step_pred(void *x, const void *noise_pred, int dtype, int b, int c, int h, int w, double guidance,
+                                 double c1, double c2, double c3, double c4, int prediction, int op, const int32_t *src_col,
+                                 uint8_t *mask, const void *noise, void *stream);
+
+/*
  * Stereo attention (reference stereo_utils.py BNAttention :91-188, the hot path of StereoDiffusion's Standard mode): one fused
  * flash-style forward attention, float32 in and out, float32 accumulation on the f32-input MFMA; no score matrix is written,
  * there is no workspace, nothing is allocated, everything runs on the caller's stream.

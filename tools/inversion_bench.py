@@ -32,8 +32,10 @@ COEFFS = (0.8, 0.6, 0.7, 0.714)
 GUIDANCE = 7.5
 
 
-def stock_step(c, e, x):
+def stock_step(c, e, x, prediction="epsilon"):
     c1, c2, c3, c4 = c
+    if prediction == "v_prediction":   # e is the model's v
+        return c4 * (c2 * x - c1 * e) + c3 * (c2 * e + c1 * x)
     return c4 * ((x - c1 * e) / c2) + c3 * e
 
 
@@ -59,7 +61,7 @@ def launches(fn):
     return sum(1 for ev in prof.events() if ev.device_type == torch.autograd.DeviceType.CUDA and "memcpy" not in ev.name.lower())
 
 
-def frames_bench(frames, repeats):
+def frames_bench(frames, repeats, prediction="epsilon"):
     import time
 
     from torch.profiler import ProfilerActivity, profile
@@ -69,6 +71,7 @@ def frames_bench(frames, repeats):
     steps, inner, guidance, epsilon = 5, 10, 7.5, 9.34e-3
     images = torch.stack([torch.from_numpy(nm.seeded_image(11 + f)) for f in range(frames)]).cuda()
     model = nm.NullModel("exact", "cuda")
+    model.scheduler.config.prediction_type = prediction   # (NullInversion reads it from the scheduler)
 
     def one_by_one():
         for f in range(frames):
@@ -79,7 +82,7 @@ def frames_bench(frames, repeats):
         inversion.NullInversion(model, steps, guidance).invert_frames(images, "a photo", num_inner_steps=inner, early_stop_epsilon=epsilon)
         stereo_utils.restore_attention(model)
 
-    row = dict(frames=frames, outer_steps=steps, max_inner_steps=inner)
+    row = dict(frames=frames, prediction=prediction, outer_steps=steps, max_inner_steps=inner)
     for name, fn in (("one_by_one", one_by_one), ("batched", batched)):
         fn()
         best = float("inf")
@@ -106,11 +109,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--frames", type=int, default=0, help="time F frames one after the other against the batched inversion")
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--prediction", choices=["epsilon", "v"], default="epsilon",
+                    help="what the model predicts: v = a v-prediction model, the SD 2.x 768-v checkpoints")
     args = ap.parse_args()
+    prediction = {"epsilon": "epsilon", "v": "v_prediction"}[args.prediction]
     if args.frames:
         if args.frames < 1:
             ap.error("--frames must be positive")
-        return frames_bench(args.frames, args.repeats)
+        return frames_bench(args.frames, args.repeats, prediction)
     for dtype in (torch.float32, torch.float16, torch.bfloat16):
         g = torch.Generator().manual_seed(0)
         lat = [torch.randn(1, 4, 64, 64, generator=g).to(dtype).cuda() for _ in range(4)]
@@ -124,7 +130,7 @@ def main():
         def fused():
             state["k"] += 1
             e = emb_f.sum() * 0 + eps
-            loss = engine.NullTextLoss.apply(e, eps_cond, cur, prev, GUIDANCE, COEFFS)
+            loss = engine.NullTextLoss.apply(e, eps_cond, cur, prev, GUIDANCE, COEFFS, prediction)
             (grad,) = torch.autograd.grad(loss, [emb_f])
             engine.adam_step(emb_f, grad.contiguous(), m, v, 1e-2, state["k"])
 
@@ -134,19 +140,22 @@ def main():
         def stock():
             e = emb_s.sum() * 0 + eps
             pred = e + GUIDANCE * (eps_cond - e)
-            loss = torch.nn.functional.mse_loss(stock_step(c, pred, cur), prev)
+            loss = torch.nn.functional.mse_loss(stock_step(c, pred, cur, prediction), prev)
             opt.zero_grad()
             loss.backward()
             opt.step()
 
         out = torch.empty_like(cur)
-        row = dict(dtype=str(dtype).split(".")[-1],
+        def fused_step():
+            return engine.ddim_step_pred(cur, eps, None, 1.0, COEFFS, out=out, prediction=prediction)
+
+        row = dict(dtype=str(dtype).split(".")[-1], prediction=prediction,
                    inner_step_fused_us=timed(fused, args.iters, args.warmup), inner_step_stock_us=timed(stock, args.iters, args.warmup),
                    inner_step_fused_launches=launches(fused), inner_step_stock_launches=launches(stock),
-                   ddim_step_fused_us=timed(lambda: engine.ddim_step(cur, eps, None, 1.0, COEFFS, out=out), args.iters, args.warmup),
-                   ddim_step_stock_us=timed(lambda: stock_step(c, eps, cur), args.iters, args.warmup),
-                   ddim_step_fused_launches=launches(lambda: engine.ddim_step(cur, eps, None, 1.0, COEFFS, out=out)),
-                   ddim_step_stock_launches=launches(lambda: stock_step(c, eps, cur)))
+                   ddim_step_fused_us=timed(fused_step, args.iters, args.warmup),
+                   ddim_step_stock_us=timed(lambda: stock_step(c, eps, cur, prediction), args.iters, args.warmup),
+                   ddim_step_fused_launches=launches(fused_step),
+                   ddim_step_stock_launches=launches(lambda: stock_step(c, eps, cur, prediction)))
         print(json.dumps(row))
 
 

@@ -120,7 +120,7 @@ class NullUNet(nn.Module):
         late = 0.5 if int(t) >= 500 else 0.25
         sample = late * torch.roll(x, 1, dims=-1) - 0.25 * torch.flip(x, dims=[-2])
         sample = sample + 0.125 * torch.roll(x, 1, dims=1)
-        plane = ctx[:, :64, :64]
+        plane = ctx[:, :x.shape[-2], :x.shape[-1]]   # [64,64] at the reference's latents; smaller work frames take their corner
         planes = torch.stack([plane, torch.roll(plane, 1, -1), torch.flip(plane, [-2]), torch.roll(plane, 3, -2)], 1)
         sample = sample + CONTEXT_GAIN * planes
         if self.form == "attn":

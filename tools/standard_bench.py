@@ -107,7 +107,7 @@ def ddim_main(args):
         noise = torch.randn((1, 4, 64, 64), generator=g).to(dtype).cuda()
         disp = torch.rand((1, 64, 64), generator=g).cuda()
         context = torch.zeros((4, 77, 8), dtype=dtype, device="cuda")
-        sched = schedulers.DDIMScheduler()
+        sched = schedulers.DDIMScheduler(prediction_type=args.prediction)
         sched.set_timesteps(steps)
         model = types.SimpleNamespace(unet=FixedUNet(pred), scheduler=sched)
         loop = sdn._StandardLoop(model, disp, 8.0, True, steps, guidance, noise)
@@ -135,7 +135,12 @@ def ddim_main(args):
                 e = u + guidance * (c - u)
                 prev_t = int(t) - 1000 // steps
                 a_t, a_p = acp[int(t)], (acp[prev_t] if prev_t >= 0 else final)
-                lat = a_p ** 0.5 * ((lat - (1 - a_t) ** 0.5 * e) / a_t ** 0.5) + (1 - a_p) ** 0.5 * e
+                if args.prediction == "v_prediction":   # e is the guided v
+                    x0 = a_t ** 0.5 * lat - (1 - a_t) ** 0.5 * e
+                    e = a_t ** 0.5 * e + (1 - a_t) ** 0.5 * lat
+                    lat = a_p ** 0.5 * x0 + (1 - a_p) ** 0.5 * e
+                else:
+                    lat = a_p ** 0.5 * ((lat - (1 - a_t) ** 0.5 * e) / a_t ** 0.5) + (1 - a_p) ** 0.5 * e
                 if i == loop.shift_step:
                     lat, bmask = torch_first(lat, src, noise)
                 elif bmask is not None and i > loop.shift_step and i % loop.reshift_interval == 0:
@@ -148,7 +153,7 @@ def ddim_main(args):
             for _ in range(args.rounds):   # alternating, so that drift falls on all three alike
                 for name, fn in (("fused", fused), ("unfused", unfused), ("stock", stock)):
                     times[name].append(loop_time(fn) / steps)
-            out = dict(bench="standard_loop_ddim", dtype=str(dtype).split(".")[-1], latents=[2, 4, 64, 64], steps=steps, rounds=args.rounds)
+            out = dict(bench="standard_loop_ddim", prediction=args.prediction, dtype=str(dtype).split(".")[-1], latents=[2, 4, 64, 64], steps=steps, rounds=args.rounds)
             for name, fn in (("fused", fused), ("unfused", unfused), ("stock", stock)):
                 out[f"{name}_us_per_step"] = round(float(np.median(times[name])), 2)
                 out[f"{name}_launches_per_step"] = round(launches(fn) / steps, 2)
@@ -161,8 +166,13 @@ def main():
     ap.add_argument("--scheduler", choices=["ddim"], default=None)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=20)
+    ap.add_argument("--prediction", choices=["epsilon", "v"], default="epsilon",
+                    help="what the model predicts (with --scheduler ddim): v = a v-prediction model, the SD 2.x 768-v checkpoints")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "standard_bench.py needs a GPU"
+    args.prediction = {"epsilon": "epsilon", "v": "v_prediction"}[args.prediction]
+    if args.prediction != "epsilon" and args.scheduler != "ddim":
+        ap.error("--prediction v goes with --scheduler ddim (the shift kernels alone do not step)")
     if args.scheduler == "ddim":
         return ddim_main(args)
     rows = []
