@@ -44,6 +44,8 @@ STANDARD_OP = {"none": 0, "first": 1, "reshift": 2}
 PREDICTION = {"epsilon": 0, "v_prediction": 1}
 # enum cs_plms_kind (the linear multistep combination of cs_inpaint_plms_step)
 PLMS_KIND = {"first": 0, "second": 1, "order2": 2, "order3": 3, "order4": 4}
+# enum cs_fewstep_sampler (the samplers of cs_inpaint_fewstep_init / cs_inpaint_fewstep_step)
+FEWSTEP_SAMPLER = {"euler": 0, "lcm": 1}
 
 # the ABI version the ctypes signatures below were written for (include/comfystereo_amd.h CS_ABI_VERSION)
 ABI_VERSION = 4
@@ -173,6 +175,9 @@ SIGNATURES = {
     "cs_inpaint_image_prep": (_int, [_vp, _vp] + [_int] * 6 + [_vp, _vp, _vp, _vp]),
     "cs_inpaint_latent_init": (_int, [_vp, _vp, _int, _vp, _int] + _nhw + [_dbl, _dbl, _vp, _vp, _vp, _vp]),
     "cs_inpaint_plms_step": (_int, [_vp, _vp] + [_int] * 5 + [_dbl] * 4 + [_vp] * 6 + [_vp]),
+    # ... and its loop for few-step models (Euler, LCM)
+    "cs_inpaint_fewstep_init": (_int, [_vp, _vp, _vp] + [_int] * 7 + [_dbl, _dbl, _vp, _vp, _vp, _vp]),
+    "cs_inpaint_fewstep_step": (_int, [_vp, _vp] + [_int] * 8 + [_dbl] * 7 + [_vp] * 6 + [_vp]),
     # StereoDiffusion Standard mode between two UNet calls
     "cs_standard_step": (_int, [_vp, _vp] + [_int] * 5 + [_dbl] * 5 + [_int, _vp, _vp, _vp, _vp]),
     # the same four steps with the model's prediction type (epsilon, v)

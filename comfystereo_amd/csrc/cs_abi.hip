@@ -1656,6 +1656,73 @@ int cs_inpaint_plms_step(const void* noise_pred, void* x, int dtype, int n, int 
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_inpaint_plms_step");
 }
 
+// ---- Fast mode's loop for few-step models (cs_fewstep.hip) ----
+static const char* fewstep_args_error(int dtype, int channels, int sampler) {
+    if (!latent_dtype_ok(dtype)) return "unknown dtype (CS_LATENT_F32 / F16 / BF16)";
+    if (sampler != CS_FEWSTEP_EULER && sampler != CS_FEWSTEP_LCM) return "unknown sampler (CS_FEWSTEP_EULER / CS_FEWSTEP_LCM)";
+    if (channels != 4 && channels != 9) return "channels must be 9 (an inpainting UNet) or 4";
+    return nullptr;
+}
+
+int cs_inpaint_fewstep_init(const void* img_latent, const void* noise, const void* x9, int dtype, int n, int hl, int wl, int channels,
+                            int cfg, int sampler, double k0, double k1, void* x, void* state, void* mask_l, void* stream) {
+    if (!img_latent || !x) return fail(CS_EINVAL, "null pointer");
+    if (n <= 0 || hl <= 0 || wl <= 0) return fail(CS_EINVAL, "non-positive size");
+    if (const char* msg = fewstep_args_error(dtype, channels, sampler)) return fail_named(CS_EINVAL, "cs_inpaint_fewstep_init", msg);
+    if (channels == 4 && (!x9 || !mask_l))
+        return fail(CS_EINVAL, "cs_inpaint_fewstep_init: 4 channels take x9 (the mask's source) and mask_l");
+    if (sampler == CS_FEWSTEP_EULER && !state) return fail(CS_EINVAL, "cs_inpaint_fewstep_init: null state (CS_FEWSTEP_EULER keeps the un-scaled sample)");
+    if (!finite_d(k0) || !finite_d(k1)) return fail(CS_EINVAL, "cs_inpaint_fewstep_init: k0 and k1 must be finite");
+    if (noise && sampler == CS_FEWSTEP_EULER && (float)k1 == 0.0f) return fail(CS_EINVAL, "cs_inpaint_fewstep_init: k1 (the input scale) must not be 0");
+    if (channels == 9) x9 = nullptr, mask_l = nullptr;   // (a pointer the layout does not use is not passed on)
+    const int halves = cfg ? 2 : 1;
+    const size_t eb = latent_elem_bytes(dtype), plane = (size_t)n * hl * wl * eb, bytes = 4 * plane;
+    if (misaligned(eb, {img_latent, noise, x9, x, state, mask_l})) return fail(CS_EINVAL, "cs_inpaint_fewstep_init: misaligned tensor");
+    const span outs[3] = {{x, (size_t)halves * channels * plane}, {state, bytes}, {mask_l, plane}};
+    const span ins[3] = {{img_latent, bytes}, {noise, bytes}, {x9, 18 * plane}};
+    if (any_overlap(outs, 3, ins, 3)) return fail(CS_EINVAL, "cs_inpaint_fewstep_init: x, state and mask_l must not overlap each other or an input");
+    hipError_t e = launch_inpaint_fewstep_init(img_latent, noise, x9, dtype, n, hl, wl, channels, halves, sampler, (float)k0, (float)k1, x, state,
+                                               mask_l, (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_inpaint_fewstep_init");
+}
+
+int cs_inpaint_fewstep_step(const void* noise_pred, void* x, int dtype, int n, int hl, int wl, int channels, int sampler, int cfg, int last,
+                            double guidance, double k0, double k1, double k2, double k3, double k4, double k5, void* state,
+                            const void* step_noise, const void* img_latent, const void* noise0, const void* mask_l, void* decode_in,
+                            void* stream) {
+    if (!noise_pred || !x) return fail(CS_EINVAL, "null pointer");
+    if (n <= 0 || hl <= 0 || wl <= 0) return fail(CS_EINVAL, "non-positive size");
+    if (const char* msg = fewstep_args_error(dtype, channels, sampler)) return fail_named(CS_EINVAL, "cs_inpaint_fewstep_step", msg);
+    // what the sampler and the layout read and write
+    if (sampler == CS_FEWSTEP_EULER && !state) return fail(CS_EINVAL, "cs_inpaint_fewstep_step: null state (CS_FEWSTEP_EULER reads and writes the un-scaled sample)");
+    if (sampler == CS_FEWSTEP_LCM && !last && !step_noise)
+        return fail(CS_EINVAL, "cs_inpaint_fewstep_step: null step_noise (every CS_FEWSTEP_LCM step but the last adds fresh noise)");
+    if (channels == 4 && (!img_latent || !mask_l || (!last && !noise0)))
+        return fail(CS_EINVAL, "cs_inpaint_fewstep_step: 4 channels take img_latent, mask_l and, before the last step, noise0 (the blend)");
+    const double kd[6] = {k0, k1, k2, k3, k4, k5};
+    for (double v : kd)
+        if (!finite_d(v)) return fail(CS_EINVAL, "cs_inpaint_fewstep_step: guidance and k0..k5 must be finite");
+    if (!finite_d(guidance)) return fail(CS_EINVAL, "cs_inpaint_fewstep_step: guidance and k0..k5 must be finite");
+    if ((float)k1 == 0.0f) return fail(CS_EINVAL, "cs_inpaint_fewstep_step: k1 (Euler: the input scale, LCM: sqrt(a_t)) must not be 0");
+    // (a pointer the sampler, the layout or the step does not use is not passed on, whatever it holds)
+    if (sampler == CS_FEWSTEP_LCM) state = nullptr;
+    if (sampler == CS_FEWSTEP_EULER || last) step_noise = nullptr;
+    if (channels == 9) img_latent = nullptr, noise0 = nullptr, mask_l = nullptr;
+    if (last) noise0 = nullptr;
+    const int halves = cfg ? 2 : 1;
+    const size_t eb = latent_elem_bytes(dtype), plane = (size_t)n * hl * wl * eb, bytes = 4 * plane;
+    if (misaligned(eb, {noise_pred, x, state, step_noise, img_latent, noise0, mask_l, decode_in}))
+        return fail(CS_EINVAL, "cs_inpaint_fewstep_step: misaligned tensor");
+    const span outs[3] = {{x, (size_t)halves * channels * plane}, {state, bytes}, {decode_in, bytes}};
+    const span ins[5] = {{noise_pred, halves * bytes}, {step_noise, bytes}, {img_latent, bytes}, {noise0, bytes}, {mask_l, plane}};
+    if (any_overlap(outs, 3, ins, 5))
+        return fail(CS_EINVAL, "cs_inpaint_fewstep_step: x, state and decode_in must not overlap each other or an input");
+    const float kf[6] = {(float)k0, (float)k1, (float)k2, (float)k3, (float)k4, (float)k5};
+    hipError_t e = launch_inpaint_fewstep_step(noise_pred, x, dtype, n, hl, wl, channels, sampler, cfg ? 1 : 0, last ? 1 : 0, (float)guidance, kf,
+                                               state, step_noise, img_latent, noise0, mask_l, decode_in, (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_inpaint_fewstep_step");
+}
+
 // ---- Standard mode between two UNet calls (cs_standardloop.hip) ----
 int cs_standard_step_pred(void* x, const void* noise_pred, int dtype, int b, int c, int h, int w, double guidance, double c1, double c2,
                           double c3, double c4, int prediction, int op, const int32_t* src_col, uint8_t* mask, const void* noise,

@@ -361,6 +361,15 @@ hipError_t launch_inpaint_latent_init(const void* mean_img, const void* mean_mas
 hipError_t launch_inpaint_plms_step(const void* noise_pred, void* x, int dtype, int n, int hl, int wl, int kind, float guidance, float sc,
                                     float da, float denom, void* e_out, const void* e1, const void* e2, const void* e3, void* cur_sample,
                                     void* decode_in, hipStream_t stream);
+// cs_fewstep.hip (Fast mode's loop for few-step models: cs_inpaint_fewstep_init, cs_inpaint_fewstep_step).  dtype: enum
+// cs_latent_dtype; sampler: enum cs_fewstep_sampler; channels: 9 or 4; halves: 2 under classifier-free guidance, 1 without;
+// x [halves * n][channels][hl][wl], the UNet's persistent input; x9 [2n][9][hl][wl], what launch_inpaint_image_prep wrote
+hipError_t launch_inpaint_fewstep_init(const void* img_latent, const void* noise, const void* x9, int dtype, int n, int hl, int wl,
+                                       int channels, int halves, int sampler, float k0, float k1, void* x, void* state, void* mask_l,
+                                       hipStream_t stream);
+hipError_t launch_inpaint_fewstep_step(const void* noise_pred, void* x, int dtype, int n, int hl, int wl, int channels, int sampler, int cfg,
+                                       int last, float guidance, const float k[6], void* state, const void* step_noise,
+                                       const void* img_latent, const void* noise0, const void* mask_l, void* decode_in, hipStream_t stream);
 // cs_standardloop.hip (StereoDiffusion Standard mode between two UNet calls: cs_standard_step).  dtype: enum cs_latent_dtype;
 // op: enum cs_standard_op; cf: the step's four coefficients c1..c4; x [4b][c][h][w], the UNet's persistent input
 hipError_t launch_standard_step(void* x, const void* noise_pred, int dtype, int b, int c, int h, int w, float guidance, const float cf[4],

@@ -1107,6 +1107,138 @@ def plms_step(noise_pred, x, kind, guidance, coeffs, e_out=None, history=(), cur
     return x
 
 
+# ---- Fast mode's loop for few-step models (cs_inpaint_fewstep_*) ----
+FEWSTEP_COEFFS = {"euler": ("sigma_next - sigma_t", "sqrt(sigma_next^2 + 1)", "sigma_next"),
+                  "lcm": ("sqrt(1 - a_t)", "sqrt(a_t)", "c_out", "c_skip", "sqrt(a_next)", "sqrt(1 - a_next)")}
+
+
+def _fewstep_sampler(sampler):
+    if sampler not in _native.FEWSTEP_SAMPLER:
+        raise ValueError(f"unknown sampler {sampler!r} ({', '.join(_native.FEWSTEP_SAMPLER)})")
+    return _native.FEWSTEP_SAMPLER[sampler]
+
+
+def _fewstep_numbers(lead, coeffs, names):
+    """_numbers for any count of coefficients."""
+    try:
+        vals = [float(v) for v in lead] + [float(c) for c in coeffs]
+    except (TypeError, ValueError):
+        vals = None
+    if vals is None or len(vals) != len(lead) + len(names):
+        raise ValueError(f"coeffs must be {len(names)} numbers ({', '.join(names)})")
+    if not all(math.isfinite(v) for v in vals):
+        raise ValueError(f"{'guidance and ' if lead else ''}coeffs must be finite, got {tuple(vals)}")
+    return vals
+
+
+def _fewstep_input(x, n, hl, wl, cfg):
+    """x: the persistent UNet input [2n or n, 9 or 4, hl, wl] of a latent dtype, contiguous -> its channel count."""
+    _tensor("x", x, dtypes=(_FLOATS, _FLOATS_TEXT), dims=((4,), "be [2N or N,C,hl,wl], got shape"), contiguous=True,
+            no_grad="the inpainting loop works in place")
+    channels = x.shape[1]
+    if channels not in (4, 9):
+        raise ValueError(f"x must have 9 channels (an inpainting UNet) or 4, got shape {tuple(x.shape)}")
+    shape = ((2 if cfg else 1) * n, channels, hl, wl)
+    _tensor("x", x, shape=(shape, f"be [{'2N' if cfg else 'N'},{channels},hl,wl] = {shape} {'under' if cfg else 'without'} guidance, got shape"))
+    return channels
+
+
+def fewstep_latent_init(img_latent, noise, coeffs, x, sampler, cfg, state=None, prep=None, mask_l=None):
+    """cs_inpaint_fewstep_init: the first latents of a few-step loop.  img_latent [N,4,hl,wl] (inpaint_latent_init's), noise
+    the same or None (no timestep left: x = img_latent); x [2N,C,hl,wl] with cfg, [N,C,hl,wl] without, C = 9 or 4; sampler
+    "euler": coeffs = (sigma_0, sqrt(sigma_0^2 + 1)), state [N,4,hl,wl] receives img_latent + sigma_0 * noise and channels 0..3
+    of x that divided by the second coefficient; "lcm": coeffs = add_noise's (sa, sb), x = sa * img_latent + sb * noise as
+    inpaint_latent_init forms it.  C = 4: mask_l [N,1,hl,wl] receives channel 4 of prep [2N,9,hl,wl], the mask
+    inpaint_image_prep put there.  -> x"""
+    code = _fewstep_sampler(sampler)
+    _tensor("img_latent", img_latent, dtypes=(_FLOATS, _FLOATS_TEXT), dims=((4,), "be [N,4,hl,wl], got shape"), not_empty="img_latent",
+            contiguous=True, no_grad="")
+    n, c, hl, wl = img_latent.shape
+    if c != 4:
+        raise ValueError(f"img_latent must be [N,4,hl,wl], got shape {tuple(img_latent.shape)}")
+    channels = _fewstep_input(x, n, hl, wl, cfg)
+    _tensor("x", x, like=(img_latent.dtype, f"x and img_latent must share one dtype, got {{got}} and {img_latent.dtype}"))
+    what = f"have img_latent's shape {tuple(img_latent.shape)}, got"
+    named = [("x", x)]
+    for name, t in (("noise", noise), ("state", state)):
+        if t is not None:
+            _like_x(name, t, x, img_latent.shape, what)
+            named.append((name, t))
+    if sampler == "euler" and state is None:
+        raise ValueError("sampler 'euler' takes state, the un-scaled sample")
+    if channels == 4:
+        if prep is None or mask_l is None:
+            raise ValueError("a 4-channel x takes prep (inpaint_image_prep's x) and mask_l")
+        _unet_input(prep, n, hl, wl, like=("img_latent", img_latent))
+        _like_x("mask_l", mask_l, x, (n, 1, hl, wl), f"be [N,1,hl,wl] = {(n, 1, hl, wl)}, got shape")
+        named += [("prep", prep), ("mask_l", mask_l)]
+    else:
+        prep = mask_l = None
+    k0, k1 = (1.0, 1.0) if noise is None else _fewstep_numbers((), coeffs, ("sigma_0", "sqrt(sigma_0^2 + 1)") if sampler == "euler" else ("sa", "sb"))
+    if noise is not None and sampler == "euler" and k1 == 0.0:
+        raise ValueError("coeffs[1] (the input scale) must not be 0")
+    _same_device(("img_latent", img_latent), *named)
+    _on_gpu(img_latent, no_gpu_error=True)
+    _launch(x.device, _native.lib().cs_inpaint_fewstep_init, _ptr(img_latent), _opt_ptr(noise), _opt_ptr(prep),
+            _dtype_code(x, _native.LATENT_DTYPE), n, hl, wl, channels, int(bool(cfg)), code, k0, k1, _ptr(x), _opt_ptr(state), _opt_ptr(mask_l))
+    return x
+
+
+def fewstep_step(noise_pred, x, sampler, guidance, coeffs, cfg, last=False, state=None, step_noise=None, img_latent=None, noise0=None,
+                 mask_l=None, decode_in=None):
+    """cs_inpaint_fewstep_step: guidance and one Euler or LCM step in one launch, in place on the UNet's input.  With cfg
+    noise_pred [2N,4,hl,wl] (uncond, cond), x [2N,C,hl,wl] and e = u + guidance * (t - u) in the dtype; without, noise_pred
+    [N,4,hl,wl] is e and x [N,C,hl,wl].  After e everything is float32 with one rounding per stored tensor (tools/fewstep_oracle.py
+    is the specification).  coeffs: FEWSTEP_COEFFS[sampler].
+      "euler"  prev = state + e * (sigma_next - sigma_t); state (the un-scaled sample, [N,4,hl,wl]) = lat; channels 0..3 of x =
+               lat / sqrt(sigma_next^2 + 1), the next step's scaled input
+      "lcm"    s = channels 0..3 of x; x0 = (s - sqrt(1 - a_t) e) / sqrt(a_t); den = c_out x0 + c_skip s; prev = sqrt(a_next) den +
+               sqrt(1 - a_next) step_noise, den on the last step; channels 0..3 of x = lat
+    C = 9: lat = prev.  C = 4: lat = mask_l != 0 ? prev : keep -- a select: values are moved, not multiplied -- with keep the
+    image's latents at the next noise level from img_latent and noise0 (the initial noise), img_latent itself on the last step;
+    mask_l [N,1,hl,wl].  decode_in, when given, receives lat / 0.18215.  -> x"""
+    code = _fewstep_sampler(sampler)
+    _tensor("noise_pred", noise_pred, dtypes=(_FLOATS, _FLOATS_TEXT), dims=((4,), "be [2N or N,4,hl,wl], got shape"), not_empty="noise_pred",
+            contiguous=True, no_grad="cs_inpaint_fewstep_step is not differentiable")
+    rows, c, hl, wl = noise_pred.shape
+    if c != 4 or (cfg and rows % 2):
+        raise ValueError(f"noise_pred must be [{'2N' if cfg else 'N'},4,hl,wl], got shape {tuple(noise_pred.shape)}")
+    n = rows // 2 if cfg else rows
+    channels = _fewstep_input(x, n, hl, wl, cfg)
+    _tensor("x", x, like=(noise_pred.dtype, f"x and noise_pred must share one dtype, got {{got}} and {noise_pred.dtype}"))
+    last = bool(last)
+    if (state is None) != (sampler != "euler"):
+        raise ValueError("state goes with sampler 'euler' only, which keeps the un-scaled sample there")
+    if (step_noise is None) != (sampler != "lcm" or last):
+        raise ValueError("step_noise goes with every step of sampler 'lcm' but the last, and with no other")
+    if channels == 4 and (img_latent is None or mask_l is None or (noise0 is None and not last)):
+        raise ValueError("a 4-channel x takes img_latent, mask_l and, before the last step, noise0 (the blend)")
+    if channels == 9:
+        img_latent = noise0 = mask_l = None
+    if last:
+        noise0 = None
+    shape = (n, 4, hl, wl)
+    what = f"be [N,4,hl,wl] = {shape}, got shape"
+    named = [(name, t) for name, t in (("state", state), ("step_noise", step_noise), ("img_latent", img_latent), ("noise0", noise0),
+                                       ("decode_in", decode_in)) if t is not None]
+    for name, t in named:
+        _like_x(name, t, x, shape, what)
+    if mask_l is not None:
+        _like_x("mask_l", mask_l, x, (n, 1, hl, wl), f"be [N,1,hl,wl] = {(n, 1, hl, wl)}, got shape")
+        named.append(("mask_l", mask_l))
+    names = FEWSTEP_COEFFS[sampler]
+    vals = _fewstep_numbers((guidance,), coeffs, names)
+    g, k = vals[0], vals[1:] + [0.0] * (6 - len(names))
+    if k[1] == 0.0:
+        raise ValueError(f"coeffs[1] ({names[1]}) must not be 0")
+    _same_device(("noise_pred", noise_pred), ("x", x), *named)
+    _on_gpu(noise_pred, no_gpu_error=True)
+    _launch(x.device, _native.lib().cs_inpaint_fewstep_step, _ptr(noise_pred), _ptr(x), _dtype_code(x, _native.LATENT_DTYPE), n, hl, wl,
+            channels, code, int(bool(cfg)), int(last), g, *k, _opt_ptr(state), _opt_ptr(step_noise), _opt_ptr(img_latent), _opt_ptr(noise0),
+            _opt_ptr(mask_l), _opt_ptr(decode_in))
+    return x
+
+
 # ---- StereoDiffusion Standard mode between two UNet calls (cs_standard_step; DESIGN.md section 2) ----
 def standard_step(noise_pred, x, guidance, coeffs, op="none", src_col=None, mask=None, noise=None, prediction="epsilon"):
     """cs_standard_step: classifier-free guidance, one DDIM step and the latent shift in one launch, in place on the UNet's

@@ -8,13 +8,15 @@ tokenizer, text_encoder, unet, vae, scheduler, device.
                         torch.func.functional_call on cloned parameters and buffers, so that gradients reach an embedding although
                         ComfyUI created the weights under inference mode (null-text optimisation needs this)
   ComfyUIModelWrapper   the five above plus our DDIMScheduler, the model type by the reference's class-name rules
-  make_inpaint_runner   inpaint_runner.InpaintRunner around a 9-channel MODEL, for Fast mode
+  make_inpaint_runner   inpaint_runner.InpaintRunner around a 9-channel MODEL (a 4-channel one with the few-step samplers), for
+                        Fast mode
 
 comfy.model_management.load_models_gpu is called where the reference calls it, inside the constructors, and skipped when `comfy`
 cannot be imported: every class works on duck-typed stand-ins.  Importing this module needs neither comfy nor diffusers.
 
-Not here: the reference's set_scheduler_for_mode and its Euler scheduler.  Nothing in the reference calls the first, and no model
-type it detects selects the second.
+Not here: the reference's set_scheduler_for_mode, which nothing in the reference calls.  Its Euler scheduler with trailing spacing
+(:419-459), which no model type the reference detects selects, lives as the sampler "euler" of inpaint_runner.InpaintRunner
+(fewstep_timesteps, fewstep_coeffs, FewStepLoop; the step is cs_inpaint_fewstep_step), next to the "lcm" sampler.
 """
 import types
 
@@ -238,12 +240,15 @@ def detect_prediction_kind(model):
     return {"EPSILON": "EPS", "V_PRED": "V_PREDICTION"}.get(name, name)
 
 
-def make_inpaint_runner(model, clip, vae, device="cuda"):
+def make_inpaint_runner(model, clip, vae, device="cuda", sampler="plms"):
     """-> inpaint_runner.InpaintRunner around the MODEL's diffusion model and the wrapped VAE and CLIP (the reference's
-    ComfyUIInpaintRunner.__init__, :496-520).  ValueError with the reference's message unless the UNet takes 9 channels."""
+    ComfyUIInpaintRunner.__init__, :496-520).  ValueError with the reference's message unless the UNet takes 9 channels; the
+    few-step samplers ("euler", "lcm") take a 4-channel UNet too.  An unknown sampler is refused by name."""
+    if sampler not in inpaint_runner.SAMPLERS:
+        raise ValueError(f"unknown sampler {sampler!r} ({', '.join(inpaint_runner.SAMPLERS)})")
     unet = model.model.diffusion_model
     in_ch = _in_channels(unet)
-    if in_ch != 9:   # before anything is loaded
+    if in_ch != 9 and not (in_ch == 4 and sampler != "plms"):   # before anything is loaded
         raise ValueError(f"Connected model has {in_ch} UNet input channels, but inpainting requires 9 channels. "
                          f"Please use an inpainting checkpoint (e.g., sd-v1-5-inpainting).")
     kind = detect_prediction_kind(model)
@@ -251,4 +256,5 @@ def make_inpaint_runner(model, clip, vae, device="cuda"):
         raise ValueError(f"Connected inpainting model declares {'v-prediction' if kind == 'V_PREDICTION' else kind} "
                          f"(model_type {kind}); Fast mode's inpainting loop supports epsilon-prediction models only.")
     _load_to_gpu(model)
-    return inpaint_runner.InpaintRunner(unet, VAEWrapper(vae, device), TextEncoderWrapper(clip, device), TokenizerWrapper(clip))
+    return inpaint_runner.InpaintRunner(unet, VAEWrapper(vae, device), TextEncoderWrapper(clip, device), TokenizerWrapper(clip),
+                                        sampler=sampler)

@@ -409,6 +409,12 @@ STANDARD_ALL_FRAMES = False
 # stay what they were.  Fast mode keeps WORK_SIZE.  A module switch like the one above.
 STANDARD_WORK_SIZE = 512
 
+# Fast mode's sampler: "plms", the reference's loop, or for the few-step models its tooltips name (SD-Turbo, the LCM checkpoints)
+# "euler" / "lcm" (inpaint_runner.SAMPLERS), which also take a 4-channel model and drop the unconditional batch when guidance_scale
+# <= 1.  Read when generate_stereo runs and passed to make_inpaint_runner and make_inpaint, which refuse an unknown value by name;
+# the node's INPUT_TYPES and signature stay the reference's.  A module switch like the two above.
+FAST_SAMPLER = "plms"
+
 
 def _norm_depth_frames(depth):
     """_norm_depth on [F,H,W] with every frame's own range."""
@@ -609,8 +615,9 @@ class StereoDiffusionNode:
         with torch.inference_mode(False):
             if pipeline_mode == FAST_MODE:
                 # a model that is no inpainting model raises the 9-channel message (the reference falls back to a download)
-                runner = model_wrappers.make_inpaint_runner(model, clip, vae)
-                inpaint = inpaint_runner.make_inpaint(runner, prompt, int(num_inference_steps), guidance_scale, denoise_strength, seed)
+                runner = model_wrappers.make_inpaint_runner(model, clip, vae, sampler=FAST_SAMPLER)
+                inpaint = inpaint_runner.make_inpaint(runner, prompt, int(num_inference_steps), guidance_scale, denoise_strength, seed,
+                                                      sampler=FAST_SAMPLER)
                 return generate_stereo_fast(image, depth_map, scale_factor, inpaint)
             ldm_stable = model_wrappers.ComfyUIModelWrapper(model, clip, vae)
             if not ldm_stable.is_supported():

@@ -493,6 +493,45 @@ CS_API int cs_inpaint_plms_step(const void *noise_pred, void *x, int dtype, int 
                                 void *cur_sample, void *decode_in, void *stream);
 
 /*
+ * Fast mode's loop for few-step models (SD-Turbo, LCM checkpoints): the samplers such a model was trained for, around the same
+ * persistent UNet input, one launch per step.
+ *   x [halves * n][channels][hl][wl] of `dtype`: halves = 2 under classifier-free guidance (cfg != 0: uncond half, cond half), 1
+ *   without (the conditional batch alone; noise_pred is then the prediction itself).  channels = 9: an inpainting UNet, channels
+ *   4..8 written once as above.  channels = 4: an ordinary UNet used RePaint-style -- after every step
+ *   lat = mask_l != 0 ? prev : keep, a select (values are moved, not multiplied), keep being the image's latents at the next
+ *   noise level: Euler img_latent + sigma_next * noise0, LCM sqrt(a_next) * img_latent + sqrt(1 - a_next) * noise0, on the last
+ *   step img_latent.
+ * Arithmetic: e = u + guidance * (t - u) in the dtype as in cs_inpaint_plms_step; everything after it in float32 on the dtype's
+ * values with the coefficients as float32, one IEEE operation each, no contraction, and one rounding to the dtype per stored
+ * tensor.  The specification of the bits is tools/fewstep_oracle.py on CPU torch.
+ *   CS_FEWSTEP_EULER  (Karras et al. 2022, Alg. 1 without churn)  k0 = sigma_next - sigma_t, k1 = sqrt(sigma_next^2 + 1),
+ *     k2 = sigma_next:  prev = state + e * k0;  state = lat (the un-scaled sample, a buffer of its own);  channels 0..3 of x =
+ *     lat / k1, the NEXT step's scale_model_input (on the last step sigma_next = 0, k1 = 1).
+ *   CS_FEWSTEP_LCM  (Luo et al. 2023, multistep consistency sampling)  k0 = sqrt(1 - a_t), k1 = sqrt(a_t), k2 = c_out,
+ *     k3 = c_skip, k4 = sqrt(a_next), k5 = sqrt(1 - a_next); s = channels 0..3 of x's first half:  x0 = (s - k0 * e) / k1;
+ *     den = k2 * x0 + k3 * s;  prev = k4 * den + k5 * step_noise, with last != 0 prev = den;  channels 0..3 of x = lat.
+ *   decode_in != NULL: also decode_in = lat / 0.18215 (float32 lat, rounded once).  state, step_noise, img_latent, noise0,
+ *   decode_in: [n][4][hl][wl]; mask_l [n][hl][wl], 0 / 1 in `dtype`.  Pointers the sampler, the layout or the step does not use
+ *   may be NULL.
+ *   cs_inpaint_fewstep_init: the first latents from img_latent (cs_inpaint_latent_init's) and the initial noise.  Euler (k0 =
+ *     sigma_0, k1 = sqrt(sigma_0^2 + 1)): state = img_latent + k0 * noise, x = that / k1.  LCM (k0, k1 = add_noise's two roots in
+ *     the dtype): x = k0 * img_latent + k1 * noise, every operation rounded to the dtype as in cs_inpaint_latent_init.  noise
+ *     NULL (no timestep left): x = img_latent.  channels = 4: mask_l = channel 4 of x9 [2n][9][hl][wl], where
+ *     cs_inpaint_image_prep put the mask at the latents' size.
+ * CS_EINVAL before any launch: null pointers, non-positive sizes, unknown dtype or sampler, channels other than 9 or 4, a pointer
+ * the sampler, layout or step needs missing (state for Euler, step_noise for an LCM step that is not the last, img_latent / mask_l /
+ * noise0 for 4 channels), misaligned tensors, outputs that overlap each other or an input, non-finite coefficients, k1 == 0.
+ */
+enum cs_fewstep_sampler { CS_FEWSTEP_EULER = 0, CS_FEWSTEP_LCM = 1 };
+CS_API int cs_inpaint_fewstep_init(const void *img_latent, const void *noise, const void *x9, int dtype, int n, int hl, int wl,
+                                   int channels, int cfg, int sampler, double k0, double k1, void *x, void *state, void *mask_l,
+                                   void *stream);
+CS_API int cs_inpaint_fewstep_step(const void *noise_pred, void *x, int dtype, int n, int hl, int wl, int channels, int sampler,
+                                   int cfg, int last, double guidance, double k0, double k1, double k2, double k3, double k4,
+                                   double k5, void *state, const void *step_noise, const void *img_latent, const void *noise0,
+                                   const void *mask_l, void *decode_in, void *stream);
+
+/*
  * StereoDiffusion's Standard mode between two UNet calls (reference stereodiffusion_nodes.py:624-667 with diffusion_utils.py:29-66):
  * classifier-free guidance, the DDIM step and the latent shift in ONE launch, around one persistent UNet input
  *   x [4b][c][h][w] of `dtype` (enum cs_latent_dtype): rows 0..b-1 the left views, b..2b-1 the right views -- the current
