@@ -203,6 +203,7 @@ SIGNATURES = {
     "cs_test_powf": (_int, [_vp, _flt, _vp, _size, _vp]),
     "cs_test_exp": (_int, [_vp, _vp, _size, _vp]),
     "cs_test_edge_threshold": (_flt, [_flt]),
+    "cs_test_blur_plan": (_int, [_dbl, _dbl, _int, _dbl] + _nhw + [_int]),
 }
 EXPORTS = list(SIGNATURES)
 

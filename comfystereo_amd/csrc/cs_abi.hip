@@ -1938,6 +1938,13 @@ int cs_test_powf(const float* x, float y, float* out, size_t count, void* stream
 
 float cs_test_edge_threshold(float den) { return blur_edge_threshold_host(den); }
 
+int cs_test_blur_plan(double blur_strength, double blur_mask_width, int vert_smooth_px, double falloff_exponent, int n, int h, int w,
+                      int flags) {
+    if (n <= 0 || h <= 0 || w <= 0) return CS_EINVAL;
+    const BlurParams prm = {blur_strength, 20.0, blur_mask_width, falloff_exponent, vert_smooth_px};
+    return blur_plan_describe(prm, n, h, w, flags);
+}
+
 int cs_test_exp(const double* x, double* out, size_t count, void* stream) {
     if (!x || !out) return fail(CS_EINVAL, "null pointer");
     hipLaunchKernelGGL(k_test_exp, dim3(grid_for(count, 256)), dim3(256), 0, (hipStream_t)stream, x, out, count);

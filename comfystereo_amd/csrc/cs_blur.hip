@@ -100,13 +100,14 @@ __global__ void __launch_bounds__(1024) k_blur_weights(BlurArgs A) {
     for (int x = tid; x < w; x += nt) {
         float dl = ll[x] >= 0 ? (float)(x - ll[x]) : large;
         float dr = lr[x] < BIG ? (float)(lr[x] - x) : large;
+        // (mask radius 0: an edge pixel's 0 / 0 is a NaN that torch.clamp hands on, reference :1168 -- fminf / fmaxf would drop it)
         float t = 1.0f - fminf(dl, dr) / rad;
-        t = fminf(fmaxf(t, 0.0f), 1.0f);
+        t = t < 0.0f ? 0.0f : (t > 1.0f ? 1.0f : t);
         wl[x] = falloff_pow(t, A.fall_mode, A.fall32, T);
         dl = rl[x] >= 0 ? (float)(x - rl[x]) : large;
         dr = rr[x] < BIG ? (float)(rr[x] - x) : large;
         t = 1.0f - fminf(dl, dr) / rad;
-        t = fminf(fmaxf(t, 0.0f), 1.0f);
+        t = t < 0.0f ? 0.0f : (t > 1.0f ? 1.0f : t);
         wr[x] = falloff_pow(t, A.fall_mode, A.fall32, T);
     }
 }
@@ -1324,12 +1325,19 @@ static void launch_fused(const BlurArgs& A, const BlurScratch& S, size_t lds, co
                        (const unsigned long long*)S.bits_r, S.MW, count, list, tstat);
 }
 
+// the two-pass kernels' LDS: k_blur_weights keeps four scan rows of the frame's width, k_blur_apply both weight tiles with their
+// vertical halo and the depth tile with the box's
+static bool blur_two_pass_lds(int w, int vert, int bs, size_t* ldsA, size_t* ldsB) {
+    *ldsA = 4 * (size_t)w * 4 + 32 * 4 + sizeof(csm::PowfTables) + 64;
+    *ldsB = ((size_t)(BLUR_TR + 2 * vert) * BLUR_TW * 2 + (size_t)BLUR_TR * (BLUR_TW + bs - 1)) * 4;
+    return *ldsA <= CS_LDS_BYTES && *ldsB <= CS_LDS_BYTES;
+}
+
 static int launch_blur_two_pass(const BlurArgs& A, hipStream_t stream) {
     const int n = A.n, h = A.h, w = A.w;
     int threads = w <= 256 ? 256 : (w <= 1024 ? 512 : 1024);
-    size_t ldsA = 4 * (size_t)w * 4 + 32 * 4 + sizeof(csm::PowfTables) + 64;
-    size_t ldsB = ((size_t)(BLUR_TR + 2 * A.vert) * BLUR_TW * 2 + (size_t)BLUR_TR * (BLUR_TW + A.bs - 1)) * 4;
-    if (ldsA > CS_LDS_BYTES || ldsB > CS_LDS_BYTES) return CS_ELIMIT;
+    size_t ldsA, ldsB;
+    if (!blur_two_pass_lds(w, A.vert, A.bs, &ldsA, &ldsB)) return CS_ELIMIT;
     hipError_t e = hipFuncSetAttribute((const void*)k_blur_weights, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsA);
     if (e != hipSuccess) return CS_EHIP;
     e = hipFuncSetAttribute((const void*)k_blur_apply, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsB);
@@ -1337,6 +1345,10 @@ static int launch_blur_two_pass(const BlurArgs& A, hipStream_t stream) {
     hipLaunchKernelGGL(k_blur_weights, dim3(h, n), dim3(threads), ldsA, stream, A);
     hipLaunchKernelGGL(k_blur_apply, dim3((w + BLUR_TW - 1) / BLUR_TW, (h + BLUR_TR - 1) / BLUR_TR, n), dim3(256), ldsB, stream, A);
     return CS_OK;
+}
+
+static int blur_fall_mode(double falloff) {
+    return falloff == 1.0 ? 0 : falloff == 0.5 ? 1 : falloff == 2.0 ? 2 : falloff == 3.0 ? 3 : falloff == 0.0 ? 5 : 4;
 }
 
 int launch_blur(const BlurPlan& P, const float* depth, float* out_l, float* out_r, uint32_t* stats, hipStream_t stream, uint32_t* tilemap,
@@ -1354,7 +1366,7 @@ int launch_blur(const BlurPlan& P, const float* depth, float* out_l, float* out_
     if (A.bs < 1) return CS_EINVAL;  // torch raises on a zero-width kernel
     const double falloff = P.prm.falloff;
     A.fall32 = (float)falloff;
-    A.fall_mode = falloff == 1.0 ? 0 : falloff == 0.5 ? 1 : falloff == 2.0 ? 2 : falloff == 3.0 ? 3 : falloff == 0.0 ? 5 : 4;
+    A.fall_mode = blur_fall_mode(falloff);
     A.wl = S.wl; A.wr = S.wr;
     A.out_l = out_l; A.out_r = out_r;
     A.dbg = dev_switch(CS_DEBUG_DBG);
@@ -1399,6 +1411,21 @@ int launch_blur(const BlurPlan& P, const float* depth, float* out_l, float* out_
         hipLaunchKernelGGL(k_blur_tile_stats, dim3(4, n), dim3(256), 0, stream, (const uint32_t*)S.work_count, (const uint32_t*)S.worklist,
                            (const float4*)tstat, A.stats_rw);
     return CS_OK;
+}
+
+// What blur_plan and launch_blur decide for a call, without a launch (cs_test_blur_plan).  flags: bit 0 the caller has a tile
+// map, 1 node path, 2 RGB depth at the frames' size, 3 the depth map is 16-byte aligned.
+int blur_plan_describe(const BlurParams& prm, int n, int h, int w, int flags) {
+    const BlurPlan P = blur_plan(prm, n, h, w, nullptr, nullptr, flags & 1, flags & 2, flags & 4);
+    if (P.bs < 1) return CS_EINVAL;
+    BlurArgs A = {};
+    A.depth = reinterpret_cast<const float*>((uintptr_t)((flags & 8) ? 16 : 4));   // (only its alignment is looked at)
+    A.n = n; A.h = h; A.w = w; A.bs = P.bs; A.radius = P.radius; A.vert = P.vert;
+    size_t ldsA, ldsB;
+    int r = (P.fused ? 1 : 0) | (P.listed ? 2 : 0) | (P.lazy ? 4 : 0) | (P.pre_edges ? 8 : 0) | (blur_fall_mode(prm.falloff) << 8);
+    if (P.listed && blur_fast_ok(A)) r |= 16;
+    if (!P.fused && !blur_two_pass_lds(w, P.vert, P.bs, &ldsA, &ldsB)) r |= 32;
+    return r;
 }
 
 }  // namespace cs

@@ -241,6 +241,8 @@ float blur_edge_threshold_host(float den);   // the largest t with fl(t / den) <
 // completes the maps.
 int launch_blur(const BlurPlan& P, const float* depth, float* out_l, float* out_r, uint32_t* stats, hipStream_t stream,
                 uint32_t* tilemap = nullptr, int* lazy_used = nullptr);
+// blur_plan's and launch_blur's decisions for a call as bits (cs_test_blur_plan, include/comfystereo_amd.h); no launch, no GPU
+int blur_plan_describe(const BlurParams& prm, int n, int h, int w, int flags);
 int blur_tilemap_words(int w);                 // 32-bit words per tile row, including the pad word the readers rely on
 size_t blur_tilemap_bytes(int n, int h, int w);
 // the rows of `list` (frame * h + row, *count of them; null: all `total` rows) complete in out_l / out_r: gray * scale for

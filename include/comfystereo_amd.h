@@ -706,6 +706,17 @@ CS_API int cs_test_exp(const double *x, double *out, size_t count, void *stream)
  * fl(t / den) <= 0.5, so that clamp(|g| / den, 0, 1) > 0.5 (reference stereoimage_generation.py:1213-1222) <=> |g| > t;
  * negative when den is not positive and finite (the kernels then keep the division). */
 CS_API float cs_test_edge_threshold(float den);
+/* Host only (no GPU, no launch): the kernels the depth blur would run for a call of these parameters and this shape, as the
+ * library's own plan decides it (the development switches in force included).
+ * flags: bit 0 the caller keeps a tile map (cs_generate unless CS_DEBUG_BLUR_FULL_COPY), 1 node path (cs_generate; clear:
+ * cs_directional_blur), 2 RGB depth at the frames' size, 3 the depth map is 16-byte aligned.
+ * Returns CS_EINVAL when the strength rounds to a box of 0 columns or a size is not positive, else the bits
+ *   1 fused kernel (clear: the two-pass kernels)      2 edge-free tiles copied, the others on a worklist (clear: every tile)
+ *   4 lazy: classification + tile map                  8 edge bit rows made by the gray conversion
+ *  16 the worklist runs the one-item-per-lane loader  32 refused with CS_ELIMIT (two-pass and its LDS does not fit)
+ *  bits 8..10: the falloff's evaluation, 0: x, 1: sqrt, 2: x*x, 3: x*x*x, 4: powf, 5: ones */
+CS_API int cs_test_blur_plan(double blur_strength, double blur_mask_width, int vert_smooth_px, double falloff_exponent, int n, int h,
+                             int w, int flags);
 
 #ifdef __cplusplus
 }
