@@ -195,6 +195,9 @@ SIGNATURES = {
     "cs_attention_half_fwd_lse": (_int, [_vp] * 5 + [_int] + _bhnnd + [_dbl, _vp]),
     "cs_attention_half_bwd_workspace_bytes": (_size, _bhnnd),
     "cs_attention_half_bwd": (_int, [_vp] * 9 + [_int] + _bhnnd + [_dbl, _vp, _size, _vp]),
+    # temporal depth stabilisation of a video batch
+    "cs_temporal_depth_workspace_bytes": (_size, [_int] * 4),
+    "cs_temporal_depth": (_int, [_vp] + [_int] * 4 + [_dbl] * 3 + [_vp] * 7 + [_size, _vp]),
     # profiling, development switches, test hooks
     "cs_profile": (_int, [_int]),
     "cs_profile_read": (_int, [_dp, _ip]),

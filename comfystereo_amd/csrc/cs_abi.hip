@@ -75,10 +75,10 @@ __global__ void __launch_bounds__(256) k_gray(const float* __restrict__ depth, f
         for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < hw / 4; q += stride) {
             float4 a = s4[3 * q], b = s4[3 * q + 1], cc = s4[3 * q + 2];
             float4 g;
-            g.x = (0.2989f * a.x + 0.5870f * a.y) + 0.1140f * a.z;
-            g.y = (0.2989f * a.w + 0.5870f * b.x) + 0.1140f * b.y;
-            g.z = (0.2989f * b.z + 0.5870f * b.w) + 0.1140f * cc.x;
-            g.w = (0.2989f * cc.y + 0.5870f * cc.z) + 0.1140f * cc.w;
+            g.x = gray_of(a.x, a.y, a.z);
+            g.y = gray_of(a.w, b.x, b.y);
+            g.z = gray_of(b.z, b.w, cc.x);
+            g.w = gray_of(cc.y, cc.z, cc.w);
             d4[q] = g;
             mn = fminf(fminf(mn, g.x), fminf(g.y, fminf(g.z, g.w)));
             mx = fmaxf(fmaxf(mx, g.x), fmaxf(g.y, fmaxf(g.z, g.w)));
@@ -86,7 +86,7 @@ __global__ void __launch_bounds__(256) k_gray(const float* __restrict__ depth, f
     } else {
         for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < hw; i += stride) {
             float g;
-            if (c == 3) g = (0.2989f * src[3 * i] + 0.5870f * src[3 * i + 1]) + 0.1140f * src[3 * i + 2];
+            if (c == 3) g = gray_of(src[3 * i], src[3 * i + 1], src[3 * i + 2]);
             else g = src[(size_t)i * c];
             dst[i] = g;
             mn = fminf(mn, g);
@@ -1861,6 +1861,40 @@ int cs_attention_half_bwd(const void* q, const void* k, const void* v, const voi
     hipError_t e = launch_attention_half_bwd(q, k, v, out, lse, d_out, dq, dk, dv, dtype, b, h, n, n_k, d, (float)scale, workspace,
                                              (hipStream_t)stream);
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_attention_half_bwd");
+}
+
+size_t cs_temporal_depth_workspace_bytes(int n, int h, int w, int c) {
+    return (n <= 0 || h <= 0 || w <= 0 || c <= 0) ? 0 : temporal_workspace_bytes(n, h, w);
+}
+
+int cs_temporal_depth(const float* depth, int n, int h, int w, int c, double alpha, double motion_threshold, double cut_threshold,
+                      float* state_prev_raw, float* state_prev, int32_t* state_valid, float* out, float* m_out, int32_t* cut_out,
+                      void* workspace, size_t workspace_bytes, void* stream) {
+    if (!depth || !state_prev_raw || !state_prev || !state_valid || !out || !m_out || !cut_out || !workspace)
+        return fail(CS_EINVAL, "null pointer");
+    if (n <= 0 || h <= 0 || w <= 0 || c <= 0) return fail(CS_EINVAL, "non-positive size");
+    if (!(alpha >= 0.0 && alpha <= 1.0)) return fail(CS_EINVAL, "cs_temporal_depth: alpha must lie in [0, 1]");
+    if (!(motion_threshold >= 0.0)) return fail(CS_EINVAL, "cs_temporal_depth: motion_threshold must be >= 0 (+inf allowed)");
+    if (!(cut_threshold >= 0.0)) return fail(CS_EINVAL, "cs_temporal_depth: cut_threshold must be >= 0 (+inf allowed)");
+    if (((uintptr_t)depth | (uintptr_t)state_prev_raw | (uintptr_t)state_prev | (uintptr_t)state_valid | (uintptr_t)out |
+         (uintptr_t)m_out | (uintptr_t)cut_out | (uintptr_t)workspace) & 3)
+        return fail(CS_EINVAL, "cs_temporal_depth: every buffer needs 4-byte alignment");
+    if (n > 65535) return fail(CS_ELIMIT, "cs_temporal_depth: more than 65535 frames in one call");
+    if ((size_t)h * w >= (1ull << 31)) return fail(CS_ELIMIT, "cs_temporal_depth: frame of 2^31 pixels or more");
+    const size_t px = (size_t)n * h * w;
+    const size_t need = cs_temporal_depth_workspace_bytes(n, h, w, c);
+    // the kernels read and write all eight buffers through pointers they take as distinct
+    const struct { const void* p; size_t bytes; } buf[] = {
+        {depth, px * c * 4}, {out, px * 4}, {state_prev_raw, (size_t)h * w * 4}, {state_prev, (size_t)h * w * 4}, {state_valid, 4},
+        {m_out, (size_t)n * 4}, {cut_out, (size_t)n * 4}, {workspace, need}};
+    for (int i = 0; i < 8; i++)
+        for (int j = i + 1; j < 8; j++)
+            if (overlaps(buf[i].p, buf[i].bytes, buf[j].p, buf[j].bytes))
+                return fail(CS_EINVAL, "cs_temporal_depth: depth, out, the state arrays, m_out, cut_out and workspace must not overlap");
+    if (workspace_bytes < need) return fail(CS_EWORKSPACE, "workspace too small");
+    hipError_t e = launch_temporal(depth, n, h, w, c, (float)alpha, (float)motion_threshold, (float)cut_threshold, state_prev_raw,
+                                   state_prev, state_valid, out, m_out, cut_out, (float*)workspace, (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_temporal_depth");
 }
 
 int cs_profile(int enable) {

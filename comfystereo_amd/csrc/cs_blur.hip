@@ -368,7 +368,6 @@ __global__ void __launch_bounds__(64) k_gray_edges(const float* __restrict__ rgb
     const bool nb_lane = (lane == 0 && x > 0 && incol) || (lane == 63 && x + 4 < w);
     struct Row { float4 v; float nb, lo, hi; };   // lo / hi: extremes of everything the row contributes to this lane's Sobel taps
     const bool pad0 = x == 0 || x + 4 >= w;   // a zero-padded neighbour column
-    auto gray_of = [](float r, float g, float b) { return (0.2989f * r + 0.5870f * g) + 0.1140f * b; };
     auto load_row = [&](int yy, float4& a, float4& b, float4& c, float& n0, float& n1, float& n2) {
         // (loads from a clamped, always valid address; the VALUES are selected: a conditional load of a float4 becomes a
         // load through a selected pointer with the zero vector in scratch memory)

@@ -76,6 +76,10 @@ namespace cs {
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 __device__ __forceinline__ int wave_id() { return threadIdx.x >> 6; }
 
+// The gray value of an RGB depth pixel (GenerateStereo.py:134-139): two products, two sums, each rounded to
+// float32 on its own.  The one statement of it: k_gray, k_gray_edges and the temporal filter's kernels call this.
+__device__ __forceinline__ float gray_of(float r, float g, float b) { return (0.2989f * r + 0.5870f * g) + 0.1140f * b; }
+
 struct OpAdd {
     __device__ __forceinline__ int operator()(int a, int b) const { return a + b; }
 };

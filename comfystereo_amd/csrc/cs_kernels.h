@@ -376,6 +376,12 @@ hipError_t launch_inpaint_fewstep_step(const void* noise_pred, void* x, int dtyp
 // op: enum cs_standard_op; cf: the step's four coefficients c1..c4; x [4b][c][h][w], the UNet's persistent input
 hipError_t launch_standard_step(void* x, const void* noise_pred, int dtype, int b, int c, int h, int w, float guidance, const float cf[4],
                                 int prediction, int op, const int32_t* src_col, uint8_t* mask, const void* noise, hipStream_t stream);
+// cs_temporal.hip (temporal depth stabilisation: cs_temporal_depth).  partial: temporal_workspace_bytes(n, h, w) bytes, one
+// float32 per frame and 16 384-pixel range; valid: the state's flag, one int32 in device memory
+size_t temporal_workspace_bytes(int n, int h, int w);
+hipError_t launch_temporal(const float* depth, int n, int h, int w, int c, float alpha, float motion_thr, float cut_thr,
+                           float* prev_raw, float* prev, int32_t* valid, float* out, float* m, int32_t* cut, float* partial,
+                           hipStream_t stream);
 // lazy depth-blur tiles in k_gpuwarp (tilemap != nullptr): rows of at most this many columns, not the mesh-quality warp
 int gpuwarp_lazy_max_width();
 

@@ -447,6 +447,57 @@ def gaussian_blur(depth, sigma, op="plain", edge_threshold=None):
     return out.reshape(depth.shape)
 
 
+# ---- temporal depth stabilisation of a video batch (cs_temporal_depth) ----------------------------------
+class TemporalState:
+    """What cs_temporal_depth carries from one call to the next: prev_raw and prev, float32 [H,W] (the last frame's gray value
+    and its filtered value), and `valid`, one int32 on the device (0: no frame seen yet).  temporal_depth updates it in place."""
+
+    def __init__(self, h, w, device):
+        self.prev_raw = torch.empty((h, w), dtype=torch.float32, device=device)
+        self.prev = torch.empty((h, w), dtype=torch.float32, device=device)
+        self.valid = torch.zeros((1,), dtype=torch.int32, device=device)
+
+    @property
+    def shape(self):
+        return tuple(self.prev.shape)
+
+    @property
+    def device(self):
+        return self.prev.device
+
+    def clone(self):
+        other = TemporalState.__new__(TemporalState)
+        other.prev_raw, other.prev, other.valid = self.prev_raw.clone(), self.prev.clone(), self.valid.clone()
+        return other
+
+
+def temporal_depth(depth, state=None, alpha=0.5, motion_threshold=0.1, cut_threshold=0.08):
+    """cs_temporal_depth on a float32 device tensor [N,H,W,C] (C == 3: gray value, C == 1: the value, else channel 0) ->
+    (y float32 [N,H,W], m float32 [N], cut int32 [N] of 0 / 1, state).  state: the TemporalState of the clip's earlier frames,
+    updated in place and returned, or None for a clip's first frames (a new one is returned).  A clip fed in sub-batches gives
+    bit for bit what one call gives.  Nothing waits for the device; a call with a given state can be captured into a graph."""
+    L = _native.lib()
+    _tensor("depth", depth, dims=((4,), "be [N,H,W,C], got shape"), dtypes=((torch.float32,), "float32"), not_empty="depth",
+            contiguous=True, no_grad="")
+    _on_gpu(depth, no_gpu_error=True)
+    n, h, w, c = depth.shape
+    if state is None:
+        state = TemporalState(h, w, depth.device)
+    elif not isinstance(state, TemporalState):
+        raise ValueError("state must be a TemporalState or None")
+    elif state.shape != (h, w):
+        raise ValueError(f"state is for frames of {state.shape}, depth has {(h, w)}")
+    else:
+        _same_device(("depth", depth), ("state", state.prev), ("state", state.prev_raw), ("state", state.valid))
+    y = torch.empty((n, h, w), dtype=torch.float32, device=depth.device)
+    m = torch.empty((n,), dtype=torch.float32, device=depth.device)
+    cut = torch.empty((n,), dtype=torch.int32, device=depth.device)
+    ws, nb = _workspace(L.cs_temporal_depth_workspace_bytes(n, h, w, c), depth.device)
+    _launch(depth.device, L.cs_temporal_depth, _ptr(depth), n, h, w, c, float(alpha), float(motion_threshold), float(cut_threshold),
+            _ptr(state.prev_raw), _ptr(state.prev), _ptr(state.valid), _ptr(y), _ptr(m), _ptr(cut), _ptr(ws), nb)
+    return y, m, cut, state
+
+
 # ---- StereoDiffusion Fast mode's warp, inpaint mask and gap pre-fill (cs_inpaint_prepare; DESIGN.md section 2) ---------------
 def inpaint_prepare(image, depth, scale_factor, threshold=0.05, codes=False):
     """cs_inpaint_prepare on device tensors: image [B,3,H,W] (values k / 255), depth [B,H,W], every frame on its own ->

@@ -328,3 +328,36 @@ def right_direction_aware_blur_depth_map(depth, sigma, edge_threshold):
     """reference :1329-1344: the blend with w = min(|g| / edge_threshold, 1) where g is negative, else 0 -> float32 [H,W].
     Input that is not float32 is converted to float32 first."""
     return _gaussian(depth, sigma, "right", edge_threshold)
+
+
+# ---- temporal depth stabilisation of a video batch (cs_temporal_depth; DESIGN.md section 5) -------------------------------------
+def stabilize_depth(depth, state=None, alpha=0.5, motion_threshold=0.1, cut_threshold=0.08, batch_size=16, cuts=None):
+    """The causal, motion-adaptive, scene-cut-aware temporal filter over the depth maps of a clip, run in front of the stereo
+    step.  depth: a host or device tensor [N,H,W] or [N,H,W,C] (other dtypes are converted to float32) -> (the filtered depth in
+    the input's layout, on the input's device, float32; state).  [N,H,W] and one channel keep their shape, any other C gets y in
+    all of its channels.  state: what an earlier call returned for the clip's earlier frames (engine.TemporalState, kept on
+    the device), or None.  Host input is uploaded in sub-batches of at most batch_size frames with the state carried on the
+    device; the result is bit for bit the one of a single call.  cuts: a list that receives every sub-batch's cut flags (int32 [k]
+    on the input's device), for callers that want them -- the node's scene-cut mask."""
+    dev = _device()
+    if not isinstance(depth, torch.Tensor):
+        depth = torch.from_numpy(np.ascontiguousarray(depth))
+    if depth.dim() not in (3, 4) or depth.numel() == 0:
+        raise ValueError(f"depth must be a non-empty [N,H,W] or [N,H,W,C], got shape {tuple(depth.shape)}")
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError(f"batch_size must be at least 1, got {batch_size}")
+    d4 = depth if depth.dim() == 4 else depth.unsqueeze(-1)
+    n, c = d4.shape[0], d4.shape[3]
+    step = n if depth.is_cuda else batch_size
+    parts = []
+    for b0 in range(0, n, step):
+        chunk = d4[b0:b0 + step].to(depth.device if depth.is_cuda else dev, torch.float32).contiguous()
+        y, _, cut, state = engine.temporal_depth(chunk, state, alpha, motion_threshold, cut_threshold)
+        parts.append(y if depth.is_cuda else y.cpu())
+        if cuts is not None:
+            cuts.append(cut if depth.is_cuda else cut.cpu())
+    y = parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
+    if depth.dim() == 4:
+        y = y.unsqueeze(-1) if c == 1 else y.unsqueeze(-1).expand(-1, -1, -1, c).contiguous()
+    return y, state

@@ -663,6 +663,29 @@ CS_API int cs_attention_half_bwd(const void *q, const void *k, const void *v, co
                           void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * Temporal depth stabilisation of a video batch (not in the reference, which normalises every frame alone): a causal,
+ * motion-adaptive, scene-cut-aware filter along t, run in front of cs_generate.  DESIGN.md section 5 has the specification,
+ * tools/temporal_oracle.py states it in numpy.  float32 throughout, every operation rounded once.
+ *   depth [n][h][w][c] float32; g = the gray value cs_params.depth_c describes (c == 3: gray, c == 1: the value, else channel 0)
+ *   m_t   = mean over the pixels of |g_t - g_{t-1}|; frame 0's predecessor is state_prev_raw if *state_valid, else there is none
+ *   cut_t = m_t > cut_threshold (a NaN mean is no cut); a frame without predecessor is a cut and has m = 0
+ *   y_t   = g_t  if cut_t or !(|g_t - y_{t-1}| < motion_threshold),  else  y_{t-1} + alpha * (g_t - y_{t-1});  y_{-1} = state_prev
+ * out [n][h][w] float32 = y; m_out [n] float32; cut_out [n] int32 (0 / 1).  The state -- state_prev_raw [h][w], state_prev [h][w]
+ * float32 and state_valid, one int32, all in DEVICE memory -- is read and then overwritten with the last frame's g and y and
+ * with 1, so a clip fed in sub-batches gives bit for bit what one call gives; the caller zeroes *state_valid to start a clip.
+ * m_t is added up in an order that depends on h * w alone, without atomics: bit-identical from run to run and for a frame pair
+ * inside one call or across two.  alpha, motion_threshold and cut_threshold are rounded to float32; alpha in [0, 1], the
+ * thresholds >= 0 (+inf allowed), else CS_EINVAL, as for a null pointer, a non-positive size or a buffer off the 4-byte grid.
+ * No two of depth, out, the three state buffers, m_out, cut_out and workspace may overlap (CS_EINVAL).  CS_ELIMIT: n > 65535 or h * w >= 2^31.  CS_EWORKSPACE: workspace_bytes <
+ * cs_temporal_depth_workspace_bytes(n, h, w, c) (0 for non-positive sizes).  Every refusal precedes the first launch; the
+ * three launches go to `stream`, nothing waits for the device, and the call can be captured into a graph.
+ */
+CS_API size_t cs_temporal_depth_workspace_bytes(int n, int h, int w, int c);
+CS_API int cs_temporal_depth(const float *depth, int n, int h, int w, int c, double alpha, double motion_threshold,
+                             double cut_threshold, float *state_prev_raw, float *state_prev, int32_t *state_valid, float *out,
+                             float *m_out, int32_t *cut_out, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Measurement hook for bench.py: while enabled, cs_generate brackets the launch of its dominant
  * kernel (the row warp + fill kernel of the selected technique) with HIP events on the caller's
  * stream.  cs_profile_read waits for the recorded events, returns the summed kernel time in
