@@ -198,6 +198,9 @@ SIGNATURES = {
     # temporal depth stabilisation of a video batch
     "cs_temporal_depth_workspace_bytes": (_size, [_int] * 4),
     "cs_temporal_depth": (_int, [_vp] + [_int] * 4 + [_dbl] * 3 + [_vp] * 7 + [_size, _vp]),
+    # depth range clipping of a video batch
+    "cs_depth_range_workspace_bytes": (_size, [_int] * 4),
+    "cs_depth_range": (_int, [_vp] + [_int] * 6 + [_dbl, _int] + [_vp] * 10 + [_size, _vp]),
     # profiling, development switches, test hooks
     "cs_profile": (_int, [_int]),
     "cs_profile_read": (_int, [_dp, _ip]),

@@ -1897,6 +1897,40 @@ int cs_temporal_depth(const float* depth, int n, int h, int w, int c, double alp
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_temporal_depth");
 }
 
+size_t cs_depth_range_workspace_bytes(int n, int h, int w, int c) {
+    return (n <= 0 || h <= 0 || w <= 0 || c <= 0) ? 0 : range_workspace_bytes(n);
+}
+
+int cs_depth_range(const float* depth, int n, int h, int w, int c, int rank_lo, int rank_hi, double beta, int normalize,
+                   const int32_t* cut_or_null, float* state_lo, float* state_hi, int32_t* state_valid, float* out, float* lo_out,
+                   float* hi_out, float* raw_lo_out, float* raw_hi_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!depth || !state_lo || !state_hi || !state_valid || !out || !lo_out || !hi_out || !raw_lo_out || !raw_hi_out || !workspace)
+        return fail(CS_EINVAL, "null pointer");
+    if (n <= 0 || h <= 0 || w <= 0 || c <= 0) return fail(CS_EINVAL, "non-positive size");
+    if (n > 65535) return fail(CS_ELIMIT, "cs_depth_range: more than 65535 frames in one call");
+    if ((size_t)h * w >= (1ull << 31)) return fail(CS_ELIMIT, "cs_depth_range: frame of 2^31 pixels or more");
+    if (rank_lo < 0 || rank_lo > rank_hi || (size_t)rank_hi >= (size_t)h * w)
+        return fail(CS_EINVAL, "cs_depth_range: the ranks must satisfy 0 <= rank_lo <= rank_hi < h * w");
+    if (!(beta >= 0.0 && beta <= 1.0)) return fail(CS_EINVAL, "cs_depth_range: beta must lie in [0, 1]");
+    if (((uintptr_t)depth | (uintptr_t)cut_or_null | (uintptr_t)state_lo | (uintptr_t)state_hi | (uintptr_t)state_valid |
+         (uintptr_t)out | (uintptr_t)lo_out | (uintptr_t)hi_out | (uintptr_t)raw_lo_out | (uintptr_t)raw_hi_out | (uintptr_t)workspace) & 3)
+        return fail(CS_EINVAL, "cs_depth_range: every buffer needs 4-byte alignment");
+    const size_t px = (size_t)n * h * w, per_frame = (size_t)n * 4;
+    const size_t need = cs_depth_range_workspace_bytes(n, h, w, c);
+    // the kernels read and write these buffers through pointers they take as distinct (an absent cut has no bytes)
+    const struct { const void* p; size_t bytes; } buf[] = {
+        {depth, px * c * 4}, {out, px * 4}, {state_lo, 4}, {state_hi, 4}, {state_valid, 4}, {lo_out, per_frame}, {hi_out, per_frame},
+        {raw_lo_out, per_frame}, {raw_hi_out, per_frame}, {workspace, need}, {cut_or_null, cut_or_null ? per_frame : 0}};
+    for (int i = 0; i < 11; i++)
+        for (int j = i + 1; j < 11; j++)
+            if (buf[i].bytes && buf[j].bytes && overlaps(buf[i].p, buf[i].bytes, buf[j].p, buf[j].bytes))
+                return fail(CS_EINVAL, "cs_depth_range: depth, out, the state words, the four bound arrays, cut and workspace must not overlap");
+    if (workspace_bytes < need) return fail(CS_EWORKSPACE, "workspace too small");
+    hipError_t e = launch_depth_range(depth, n, h, w, c, rank_lo, rank_hi, (float)beta, normalize != 0, cut_or_null, state_lo, state_hi,
+                                      state_valid, out, lo_out, hi_out, raw_lo_out, raw_hi_out, workspace, (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_depth_range");
+}
+
 int cs_profile(int enable) {
     std::lock_guard<std::mutex> lock(g_prof_mu);
     g_prof_on.store(enable != 0);

@@ -382,6 +382,12 @@ size_t temporal_workspace_bytes(int n, int h, int w);
 hipError_t launch_temporal(const float* depth, int n, int h, int w, int c, float alpha, float motion_thr, float cut_thr,
                            float* prev_raw, float* prev, int32_t* valid, float* out, float* m, int32_t* cut, float* partial,
                            hipStream_t stream);
+// cs_depthrange.hip (depth range clipping: cs_depth_range).  workspace: range_workspace_bytes(n) bytes, the frames' digit
+// histograms and selections; cut: null or [n] int32; the state's three words live in device memory
+size_t range_workspace_bytes(int n);
+hipError_t launch_depth_range(const float* depth, int n, int h, int w, int c, int rank_lo, int rank_hi, float beta, int normalize,
+                              const int32_t* cut, float* state_lo, float* state_hi, int32_t* state_valid, float* out, float* lo,
+                              float* hi, float* raw_lo, float* raw_hi, void* workspace, hipStream_t stream);
 // lazy depth-blur tiles in k_gpuwarp (tilemap != nullptr): rows of at most this many columns, not the mesh-quality warp
 int gpuwarp_lazy_max_width();
 

@@ -498,6 +498,75 @@ def temporal_depth(depth, state=None, alpha=0.5, motion_threshold=0.1, cut_thres
     return y, m, cut, state
 
 
+# ---- depth range clipping of a video batch (cs_depth_range) ------------------------------------------------
+class RangeState:
+    """What cs_depth_range carries from one call to the next: lo and hi, one float32 each (the last frame's bounds), and `valid`,
+    one int32 (0: no frame seen yet), all on the device.  `shape` is the frame size the clip has.  depth_range updates it in place."""
+
+    def __init__(self, h, w, device):
+        self.shape = (int(h), int(w))
+        self.lo = torch.zeros((1,), dtype=torch.float32, device=device)
+        self.hi = torch.zeros((1,), dtype=torch.float32, device=device)
+        self.valid = torch.zeros((1,), dtype=torch.int32, device=device)
+
+    @property
+    def device(self):
+        return self.lo.device
+
+    def clone(self):
+        other = RangeState.__new__(RangeState)
+        other.shape = self.shape
+        other.lo, other.hi, other.valid = self.lo.clone(), self.hi.clone(), self.valid.clone()
+        return other
+
+
+def clip_ranks(clip_low, clip_high, count):
+    """The two 0-based ranks among `count` keys that the clip fractions stand for (float64, as tools/range_oracle.py states it):
+    floor(clip_low * (count - 1)) and (count - 1) - floor(clip_high * (count - 1)); ValueError outside 0 <= clip < 0.5."""
+    clip_low, clip_high = float(clip_low), float(clip_high)
+    if not (0.0 <= clip_low < 0.5 and 0.0 <= clip_high < 0.5):
+        raise ValueError(f"clip_low and clip_high must lie in [0, 0.5), got {clip_low} and {clip_high}")
+    last = int(count) - 1
+    return int(math.floor(clip_low * last)), last - int(math.floor(clip_high * last))
+
+
+def depth_range(depth, state=None, clip_low=0.005, clip_high=0.005, beta=1.0, cut=None, normalize=False):
+    """cs_depth_range on a float32 device tensor [N,H,W,C] (C == 3: gray value, C == 1: the value, else channel 0) ->
+    (y float32 [N,H,W], lo, hi, raw_lo, raw_hi float32 [N], state).  raw_lo / raw_hi: per frame the values at the clip fractions'
+    ranks (exact order statistics); lo / hi: those smoothed along t with weight beta, restarted where cut [N] (int32, device;
+    what temporal_depth returns) is non-zero; y: the gray depth clamped to [lo, hi], and with normalize mapped to 0..1.  state:
+    the RangeState of the clip's earlier frames, updated in place and returned, or None for a clip's first frames (a new one is
+    returned).  A clip fed in sub-batches gives bit for bit what one call gives.  Nothing waits for the device; a call with a given
+    state can be captured into a graph."""
+    L = _native.lib()
+    _tensor("depth", depth, dims=((4,), "be [N,H,W,C], got shape"), dtypes=((torch.float32,), "float32"), not_empty="depth",
+            contiguous=True, no_grad="")
+    n, h, w, c = depth.shape
+    rank_lo, rank_hi = clip_ranks(clip_low, clip_high, h * w)
+    beta = float(beta)
+    if not 0.0 <= beta <= 1.0:
+        raise ValueError(f"beta must lie in [0, 1], got {beta}")
+    if cut is not None:
+        _tensor("cut", cut, shape=((n,), f"be [{n}], one flag per frame, got shape"), dtypes=((torch.int32,), "int32"), contiguous=True)
+    _on_gpu(depth, no_gpu_error=True)
+    if state is None:
+        state = RangeState(h, w, depth.device)
+    elif not isinstance(state, RangeState):
+        raise ValueError("state must be a RangeState or None")
+    elif state.shape != (h, w):
+        raise ValueError(f"state is for frames of {state.shape}, depth has {(h, w)}")
+    else:
+        _same_device(("depth", depth), ("state", state.lo), ("state", state.hi), ("state", state.valid))
+    if cut is not None:
+        _same_device(("depth", depth), ("cut", cut))
+    y = torch.empty((n, h, w), dtype=torch.float32, device=depth.device)
+    lo, hi, raw_lo, raw_hi = (torch.empty((n,), dtype=torch.float32, device=depth.device) for _ in range(4))
+    ws, nb = _workspace(L.cs_depth_range_workspace_bytes(n, h, w, c), depth.device)
+    _launch(depth.device, L.cs_depth_range, _ptr(depth), n, h, w, c, rank_lo, rank_hi, beta, int(bool(normalize)), _opt_ptr(cut),
+            _ptr(state.lo), _ptr(state.hi), _ptr(state.valid), _ptr(y), _ptr(lo), _ptr(hi), _ptr(raw_lo), _ptr(raw_hi), _ptr(ws), nb)
+    return y, lo, hi, raw_lo, raw_hi, state
+
+
 # ---- StereoDiffusion Fast mode's warp, inpaint mask and gap pre-fill (cs_inpaint_prepare; DESIGN.md section 2) ---------------
 def inpaint_prepare(image, depth, scale_factor, threshold=0.05, codes=False):
     """cs_inpaint_prepare on device tensors: image [B,3,H,W] (values k / 255), depth [B,H,W], every frame on its own ->

@@ -361,3 +361,49 @@ def stabilize_depth(depth, state=None, alpha=0.5, motion_threshold=0.1, cut_thre
     if depth.dim() == 4:
         y = y.unsqueeze(-1) if c == 1 else y.unsqueeze(-1).expand(-1, -1, -1, c).contiguous()
     return y, state
+
+
+# ---- depth range clipping of a video batch (cs_depth_range) ------------------------------------------------
+def clip_depth_range(depth, state=None, clip_low=0.005, clip_high=0.005, beta=1.0, normalize=False, batch_size=16, cuts=None,
+                     bounds=None):
+    """Percentile clipping of the near and far end of the depth maps of a clip, with the two bounds smoothed over time, run in
+    front of the stereo step (behind stabilize_depth, if that runs).  depth: a host or device tensor [N,H,W] or [N,H,W,C] (other
+    dtypes are converted to float32) -> (the clamped depth in the input's layout, on the input's device, float32; state).
+    [N,H,W] and one channel keep their shape, any other C gets y in all of its channels.  clip_low / clip_high: the fractions of
+    the pixels below / above the bounds, 0 <= clip < 0.5; beta: the weight of a frame's own bounds against the preceding
+    frame's, 1 = no smoothing; normalize: map [lo, hi] to 0..1.  state: what an earlier call returned for the clip's earlier
+    frames (engine.RangeState, kept on the device), or None.  Host input is uploaded in sub-batches of at most batch_size frames
+    with the state carried on the device; the result is bit for bit the one of a single call.  cuts: the list stabilize_depth
+    filled for the same frames (int32 flags, in any split): the bounds restart at every flagged frame.  bounds: a list that
+    receives every sub-batch's (lo, hi, raw_lo, raw_hi), float32 [k] on the input's device."""
+    if not isinstance(depth, torch.Tensor):
+        depth = torch.from_numpy(np.ascontiguousarray(depth))
+    if depth.dim() not in (3, 4) or depth.numel() == 0:
+        raise ValueError(f"depth must be a non-empty [N,H,W] or [N,H,W,C], got shape {tuple(depth.shape)}")
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError(f"batch_size must be at least 1, got {batch_size}")
+    engine.clip_ranks(clip_low, clip_high, 1)   # (the fractions' refusal, before anything is uploaded)
+    d4 = depth if depth.dim() == 4 else depth.unsqueeze(-1)
+    n, c = d4.shape[0], d4.shape[3]
+    cut = None
+    if cuts is not None:
+        cut = torch.cat([torch.as_tensor(k).reshape(-1) for k in cuts]) if len(cuts) else torch.zeros((0,), dtype=torch.int32)
+        if cut.numel() != n:
+            raise ValueError(f"cuts hold {cut.numel()} flags, depth has {n} frames")
+    where = depth.device if depth.is_cuda else _device()
+    if cut is not None:
+        cut = cut.to(where, torch.int32)
+    step = n if depth.is_cuda else batch_size
+    parts = []
+    for b0 in range(0, n, step):
+        chunk = d4[b0:b0 + step].to(where, torch.float32).contiguous()
+        y, *four, state = engine.depth_range(chunk, state, clip_low, clip_high, beta, None if cut is None else cut[b0:b0 + step].contiguous(),
+                                             normalize)
+        parts.append(y if depth.is_cuda else y.cpu())
+        if bounds is not None:
+            bounds.append(tuple(t if depth.is_cuda else t.cpu() for t in four))
+    y = parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
+    if depth.dim() == 4:
+        y = y.unsqueeze(-1) if c == 1 else y.unsqueeze(-1).expand(-1, -1, -1, c).contiguous()
+    return y, state

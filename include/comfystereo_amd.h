@@ -686,6 +686,34 @@ CS_API int cs_temporal_depth(const float *depth, int n, int h, int w, int c, dou
                              float *m_out, int32_t *cut_out, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * Depth range clipping of a video batch (not in the reference, which normalises every frame by its own extremes, so a few outlier
+ * pixels flatten the scene and flickering extremes make it pump): two order statistics of the gray depth per frame, smoothed
+ * along t, and a clamp to them, run in front of cs_generate.  DESIGN.md section 5 has the specification, tools/range_oracle.py
+ * states it in numpy.  float32 throughout, every operation rounded once.
+ *   depth [n][h][w][c] float32; g = the gray value cs_params.depth_c describes (c == 3: gray, c == 1: the value, else channel 0)
+ *   key(x)   = bits(x) ^ 0x80000000 if the sign bit is clear, else ~bits(x) (uint32; -0 below +0, NaNs where their bits put them)
+ *   raw_lo_t = the element of g_t whose key has rank rank_lo (0-based) among the frame's h * w keys; raw_hi_t likewise for rank_hi
+ *   lo_t     = raw_lo_t if frame t has no predecessor (t == 0 and !*state_valid), if cut[t] != 0, or if s is not finite, else
+ *              s = lo_{t-1} + beta * (raw_lo_t - lo_{t-1}); lo_{-1} = *state_lo.  hi_t likewise.  cut_or_null: [n] int32 or NULL
+ *   y        = g where g is NaN; else g < lo_t ? lo_t : g, and then hi_t where that exceeds hi_t (a NaN bound clamps nothing)
+ *   normalize != 0:  y = hi_t == lo_t ? 0 : (y - lo_t) / (hi_t - lo_t), one subtraction, one IEEE division
+ * out [n][h][w] float32 = y; lo_out, hi_out, raw_lo_out, raw_hi_out [n] float32.  The state -- state_lo, state_hi, one float32
+ * each, and state_valid, one int32, all in DEVICE memory -- is read and then overwritten with the last frame's lo, hi and with 1,
+ * so a clip fed in sub-batches gives bit for bit what one call gives; the caller zeroes *state_valid to start a clip.
+ * The selection is exact (a radix selection over the key: integer counts, the same in any order).  CS_EINVAL: a null pointer
+ * (cut_or_null excepted), a non-positive size, ranks outside 0 <= rank_lo <= rank_hi < h * w, beta not in [0, 1] (NaN included),
+ * a buffer off the 4-byte grid, or any two of depth, out, the three state words, the four bound arrays, cut and workspace
+ * overlapping.  CS_ELIMIT: n > 65535 or h * w >= 2^31.  CS_EWORKSPACE: workspace_bytes < cs_depth_range_workspace_bytes(n, h, w, c)
+ * (0 for non-positive sizes).  Every refusal precedes the first launch; the seven launches (one a memset of the workspace) go to
+ * `stream`, nothing waits for the device or is read back, and the call can be captured into a graph.
+ */
+CS_API size_t cs_depth_range_workspace_bytes(int n, int h, int w, int c);
+CS_API int cs_depth_range(const float *depth, int n, int h, int w, int c, int rank_lo, int rank_hi, double beta, int normalize,
+                          const int32_t *cut_or_null, float *state_lo, float *state_hi, int32_t *state_valid, float *out,
+                          float *lo_out, float *hi_out, float *raw_lo_out, float *raw_hi_out, void *workspace,
+                          size_t workspace_bytes, void *stream);
+
+/*
  * Measurement hook for bench.py: while enabled, cs_generate brackets the launch of its dominant
  * kernel (the row warp + fill kernel of the selected technique) with HIP events on the caller's
  * stream.  cs_profile_read waits for the recorded events, returns the summed kernel time in
