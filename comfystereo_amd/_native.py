@@ -201,6 +201,10 @@ SIGNATURES = {
     # depth range clipping of a video batch
     "cs_depth_range_workspace_bytes": (_size, [_int] * 4),
     "cs_depth_range": (_int, [_vp] + [_int] * 6 + [_dbl, _int] + [_vp] * 10 + [_size, _vp]),
+    # image-guided depth upsampling: the plan of a geometry, made once, and the pass over a batch
+    "cs_guided_depth_plan_bytes": (_size, [_int] * 5),
+    "cs_guided_depth_plan": (_int, [_int] * 5 + [_dbl, _dbl, _vp, _size, _vp]),
+    "cs_guided_depth_apply": (_int, [_vp, _vp] + [_int] * 7 + [_vp, _size, _vp, _vp]),
     # profiling, development switches, test hooks
     "cs_profile": (_int, [_int]),
     "cs_profile_read": (_int, [_dp, _ip]),

@@ -1931,6 +1931,50 @@ int cs_depth_range(const float* depth, int n, int h, int w, int c, int rank_lo, 
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_depth_range");
 }
 
+static int guided_geometry(int h, int w, int dh, int dw, int radius) {
+    if (h <= 0 || w <= 0 || dh <= 0 || dw <= 0) return fail(CS_EINVAL, "non-positive size");
+    if (radius < 1 || radius > 3) return fail(CS_EINVAL, "cs_guided_depth: the radius must be 1, 2 or 3");
+    if (dh > h || dw > w) return fail(CS_ELIMIT, "cs_guided_depth: the depth map is larger than the image");
+    if ((size_t)h * w >= (1ull << 31)) return fail(CS_ELIMIT, "cs_guided_depth: frame of 2^31 pixels or more");
+    return CS_OK;
+}
+
+size_t cs_guided_depth_plan_bytes(int h, int w, int dh, int dw, int radius) {
+    return (h <= 0 || w <= 0 || dh <= 0 || dw <= 0 || radius < 1 || radius > 3) ? 0 : guided_plan_bytes(h, w, dh, dw, radius);
+}
+
+int cs_guided_depth_plan(int h, int w, int dh, int dw, int radius, double sigma_s, double sigma_r, void* plan, size_t plan_bytes,
+                         void* stream) {
+    if (!plan) return fail(CS_EINVAL, "null pointer");
+    if (int rc = guided_geometry(h, w, dh, dw, radius)) return rc;
+    if (!(sigma_s > 0.0) || !(sigma_r > 0.0)) return fail(CS_EINVAL, "cs_guided_depth_plan: sigma_s and sigma_r must be positive");
+    if ((uintptr_t)plan & 3) return fail(CS_EINVAL, "cs_guided_depth_plan: every buffer needs 4-byte alignment");
+    if (plan_bytes < guided_plan_bytes(h, w, dh, dw, radius)) return fail(CS_EWORKSPACE, "plan buffer too small");
+    hipError_t e = launch_guided_plan(h, w, dh, dw, radius, sigma_s, sigma_r, plan, (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_guided_depth_plan");
+}
+
+int cs_guided_depth_apply(const float* image, const float* depth, int n, int h, int w, int dh, int dw, int c, int radius, const void* plan,
+                          size_t plan_bytes, float* out, void* stream) {
+    if (!image || !depth || !plan || !out) return fail(CS_EINVAL, "null pointer");
+    if (n <= 0 || c <= 0) return fail(CS_EINVAL, "non-positive size");
+    if (int rc = guided_geometry(h, w, dh, dw, radius)) return rc;
+    if (n > 65535) return fail(CS_ELIMIT, "cs_guided_depth_apply: more than 65535 frames in one call");
+    if (((uintptr_t)image | (uintptr_t)depth | (uintptr_t)plan | (uintptr_t)out) & 3)
+        return fail(CS_EINVAL, "cs_guided_depth_apply: every buffer needs 4-byte alignment");
+    const size_t px = (size_t)n * h * w, need = guided_plan_bytes(h, w, dh, dw, radius);
+    // the kernel reads and writes these buffers through pointers it takes as distinct
+    const struct { const void* p; size_t bytes; } buf[] = {
+        {image, px * 3 * 4}, {depth, (size_t)n * dh * dw * c * 4}, {plan, need}, {out, px * 4}};
+    for (int i = 0; i < 4; i++)
+        for (int j = i + 1; j < 4; j++)
+            if (overlaps(buf[i].p, buf[i].bytes, buf[j].p, buf[j].bytes))
+                return fail(CS_EINVAL, "cs_guided_depth_apply: image, depth, plan and out must not overlap");
+    if (plan_bytes < need) return fail(CS_EWORKSPACE, "plan buffer too small");
+    hipError_t e = launch_guided_apply(image, depth, n, h, w, dh, dw, c, radius, plan, out, (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_guided_depth_apply");
+}
+
 int cs_profile(int enable) {
     std::lock_guard<std::mutex> lock(g_prof_mu);
     g_prof_on.store(enable != 0);

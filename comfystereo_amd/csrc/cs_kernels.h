@@ -388,6 +388,12 @@ size_t range_workspace_bytes(int n);
 hipError_t launch_depth_range(const float* depth, int n, int h, int w, int c, int rank_lo, int rank_hi, float beta, int normalize,
                               const int32_t* cut, float* state_lo, float* state_hi, int32_t* state_valid, float* out, float* lo,
                               float* hi, float* raw_lo, float* raw_hi, void* workspace, hipStream_t stream);
+// cs_guideddepth.hip (image-guided depth upsampling: cs_guided_depth_plan, cs_guided_depth_apply).  plan: guided_plan_bytes(...)
+// bytes of device memory, written by launch_guided_plan once per geometry and read by every launch_guided_apply of it
+size_t guided_plan_bytes(int h, int w, int dh, int dw, int radius);
+hipError_t launch_guided_plan(int h, int w, int dh, int dw, int radius, double sigma_s, double sigma_r, void* plan, hipStream_t stream);
+hipError_t launch_guided_apply(const float* image, const float* depth, int n, int h, int w, int dh, int dw, int c, int radius,
+                               const void* plan, float* out, hipStream_t stream);
 // lazy depth-blur tiles in k_gpuwarp (tilemap != nullptr): rows of at most this many columns, not the mesh-quality warp
 int gpuwarp_lazy_max_width();
 

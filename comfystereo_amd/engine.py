@@ -567,6 +567,121 @@ def depth_range(depth, state=None, clip_low=0.005, clip_high=0.005, beta=1.0, cu
     return y, lo, hi, raw_lo, raw_hi, state
 
 
+# ---- image-guided depth upsampling (cs_guided_depth_plan / cs_guided_depth_apply) --------------------------
+GUIDED_RADII = (1, 2, 3)
+_GUIDED_WR_WORDS = 768   # the range table's block in the plan: 766 weights and two words of padding (cs_guideddepth.hip)
+
+
+class GuidedPlan:
+    """What cs_guided_depth_plan writes for one geometry (h, w, dh, dw, radius) and two sigmas: the taps' centres and spatial
+    weights per column and row, the range table and the guide positions of the low-resolution samples, in one device buffer.
+    Made once (guided_depth_plan) and read by every guided_depth call of that geometry.  The accessors return the blocks by
+    value, whatever the buffer's byte layout: cx, cy int32 [w], [h]; wx, wy float32 [w,K], [h,K]; wr float32 [766]; gx, gy
+    int32 [dw], [dh]."""
+
+    def __init__(self, h, w, dh, dw, radius, sigma_s, sigma_r, buffer, nbytes):
+        self.h, self.w, self.dh, self.dw, self.radius = h, w, dh, dw, radius
+        self.sigma_s, self.sigma_r = sigma_s, sigma_r
+        self.buffer, self.nbytes = buffer, nbytes
+
+    @property
+    def device(self):
+        return self.buffer.device
+
+    @property
+    def taps(self):
+        return 2 * self.radius + 1
+
+    def _block(self, name):
+        k = self.taps
+        sizes = (("wr", _GUIDED_WR_WORDS), ("cx", self.w), ("cy", self.h), ("gx", self.dw), ("gy", self.dh), ("wx", self.w * k),
+                 ("wy", self.h * k))
+        at = 0
+        for block, words in sizes:
+            if block == name:
+                return self.buffer[4 * at:4 * (at + words)]
+            at += words
+        raise KeyError(name)
+
+    def _ints(self, name):
+        return self._block(name).view(torch.int32).clone()
+
+    def _floats(self, name):
+        return self._block(name).view(torch.float32).clone()
+
+    cx = property(lambda self: self._ints("cx"))
+    cy = property(lambda self: self._ints("cy"))
+    gx = property(lambda self: self._ints("gx"))
+    gy = property(lambda self: self._ints("gy"))
+    wx = property(lambda self: self._floats("wx").view(self.w, self.taps))
+    wy = property(lambda self: self._floats("wy").view(self.h, self.taps))
+    wr = property(lambda self: self._floats("wr")[:766])
+
+
+def _guided_geometry(h, w, dh, dw, radius):
+    h, w, dh, dw, radius = int(h), int(w), int(dh), int(dw), int(radius)
+    if min(h, w, dh, dw) < 1:
+        raise ValueError(f"the sizes must be positive, got an image of {(h, w)} and a depth map of {(dh, dw)}")
+    if dh > h or dw > w:
+        raise ValueError(f"the depth map {(dh, dw)} is larger than the image {(h, w)}: guided upsampling only enlarges")
+    if radius not in GUIDED_RADII:
+        raise ValueError(f"radius must be 1, 2 or 3, got {radius}")
+    return h, w, dh, dw, radius
+
+
+def _guided_sigmas(sigma_s, sigma_r):
+    sigma_s, sigma_r = float(sigma_s), float(sigma_r)
+    if not (sigma_s > 0.0 and sigma_r > 0.0):
+        raise ValueError(f"sigma_s and sigma_r must be positive, got {sigma_s} and {sigma_r}")
+    return sigma_s, sigma_r
+
+
+def guided_depth_plan(h, w, dh, dw, radius=2, sigma_s=1.0, sigma_r=0.1, device=None):
+    """cs_guided_depth_plan: the plan of the guided upsampling of depth maps of dh x dw to frames of h x w (dh <= h, dw <= w) ->
+    GuidedPlan on `device` (None: the current GPU).  radius: 1, 2 or 3, K = 2 radius + 1 taps per axis; sigma_s > 0: the spatial
+    Gaussian's width in low-resolution pixels; sigma_r > 0: the range Gaussian's width in units of the summed colour difference
+    (inf: no range term, a pure spatial filter).  One small launch; nothing waits for the device."""
+    L = _native.lib()
+    h, w, dh, dw, radius = _guided_geometry(h, w, dh, dw, radius)
+    sigma_s, sigma_r = _guided_sigmas(sigma_s, sigma_r)
+    if not torch.cuda.is_available():
+        raise RuntimeError("comfystereo_amd needs an MI355X (PyTorch-ROCm `cuda` device); there is no CPU fallback")
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if device.type != "cuda":
+        raise ValueError("comfystereo_amd engine calls need device-resident tensors (there is no CPU path)")
+    buffer, nbytes = _workspace(L.cs_guided_depth_plan_bytes(h, w, dh, dw, radius), device)
+    _launch(device, L.cs_guided_depth_plan, h, w, dh, dw, radius, sigma_s, sigma_r, _ptr(buffer), nbytes)
+    return GuidedPlan(h, w, dh, dw, radius, sigma_s, sigma_r, buffer, nbytes)
+
+
+def guided_depth(image, depth, plan):
+    """cs_guided_depth_apply on float32 device tensors: image [N,H,W,3], the guide, and depth [N,dh,dw,C] (C == 3: gray value,
+    C == 1: the value, else channel 0) -> float32 [N,H,W], the depth at the image's size with its edges on the image's edges.
+    plan: the GuidedPlan of this geometry (guided_depth_plan), reused for every batch.  One launch; nothing waits for the device;
+    a call can be captured into a graph."""
+    L = _native.lib()
+    _tensor("image", image, dims=((4,), "be [N,H,W,3], got shape"), dtypes=((torch.float32,), "float32"), not_empty="image",
+            contiguous=True, no_grad="")
+    _tensor("depth", depth, dims=((4,), "be [N,dh,dw,C], got shape"), dtypes=((torch.float32,), "float32"), not_empty="depth",
+            contiguous=True, no_grad="")
+    n, h, w, ic = image.shape
+    if ic != 3:
+        raise ValueError(f"image must be [N,H,W,3], got shape {tuple(image.shape)}")
+    if depth.shape[0] != n:
+        raise ValueError(f"image has {n} frames, depth has {depth.shape[0]}")
+    _, dh, dw, c = depth.shape
+    if not isinstance(plan, GuidedPlan):
+        raise ValueError("plan must be a GuidedPlan (guided_depth_plan)")
+    if (plan.h, plan.w, plan.dh, plan.dw) != (h, w, dh, dw):
+        raise ValueError(f"plan is for depth maps of {(plan.dh, plan.dw)} and frames of {(plan.h, plan.w)}, got {(dh, dw)} and {(h, w)}")
+    _on_gpu(image, no_gpu_error=True)
+    _same_device(("image", image), ("depth", depth), ("plan", plan.buffer))
+    out = torch.empty((n, h, w), dtype=torch.float32, device=image.device)
+    _launch(image.device, L.cs_guided_depth_apply, _ptr(image), _ptr(depth), n, h, w, dh, dw, c, plan.radius, _ptr(plan.buffer),
+            plan.nbytes, _ptr(out))
+    return out
+
+
 # ---- StereoDiffusion Fast mode's warp, inpaint mask and gap pre-fill (cs_inpaint_prepare; DESIGN.md section 2) ---------------
 def inpaint_prepare(image, depth, scale_factor, threshold=0.05, codes=False):
     """cs_inpaint_prepare on device tensors: image [B,3,H,W] (values k / 255), depth [B,H,W], every frame on its own ->

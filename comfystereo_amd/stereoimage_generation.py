@@ -407,3 +407,46 @@ def clip_depth_range(depth, state=None, clip_low=0.005, clip_high=0.005, beta=1.
     if depth.dim() == 4:
         y = y.unsqueeze(-1) if c == 1 else y.unsqueeze(-1).expand(-1, -1, -1, c).contiguous()
     return y, state
+
+
+# ---- image-guided depth upsampling (cs_guided_depth_plan / cs_guided_depth_apply) --------------------------
+def upsample_depth_guided(image, depth, radius=2, sigma_s=1.0, sigma_r=0.1, batch_size=16):
+    """Joint bilateral upsampling of depth maps to their frames' size, guided by the frames, run in front of the stereo step
+    (behind stabilize_depth and clip_depth_range, which are cheaper at the estimator's resolution).  image: a host or device
+    tensor [N,H,W,3], the frames; depth: [N,dh,dw] or [N,dh,dw,C] with dh <= H and dw <= W, where image is (other dtypes are
+    converted to float32) -> the depth at H x W, float32, on the input's device: [N,dh,dw] gives [N,H,W], [N,dh,dw,C] gives
+    [N,H,W,C] with the result in every channel.  radius: 1, 2 or 3 (K = 2 radius + 1 taps per axis); sigma_s: the spatial
+    Gaussian's width in low-resolution pixels; sigma_r: the range Gaussian's width in units of the summed 8-bit colour difference
+    over 255 (inf: no range term).  Host input is uploaded in sub-batches of at most batch_size frames; the plan is made once."""
+    if not isinstance(image, torch.Tensor):
+        image = torch.from_numpy(np.ascontiguousarray(image))
+    if not isinstance(depth, torch.Tensor):
+        depth = torch.from_numpy(np.ascontiguousarray(depth))
+    if image.dim() != 4 or image.shape[3] != 3 or image.numel() == 0:
+        raise ValueError(f"image must be a non-empty [N,H,W,3], got shape {tuple(image.shape)}")
+    if depth.dim() not in (3, 4) or depth.numel() == 0:
+        raise ValueError(f"depth must be a non-empty [N,dh,dw] or [N,dh,dw,C], got shape {tuple(depth.shape)}")
+    if depth.shape[0] != image.shape[0]:
+        raise ValueError(f"image has {image.shape[0]} frames, depth has {depth.shape[0]}")
+    if depth.device != image.device:
+        raise ValueError("image and depth must be on the same device")
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError(f"batch_size must be at least 1, got {batch_size}")
+    d4 = depth if depth.dim() == 4 else depth.unsqueeze(-1)
+    n, h, w = image.shape[:3]
+    dh, dw, c = d4.shape[1:]
+    engine._guided_geometry(h, w, dh, dw, radius)   # (the refusals, before anything is uploaded)
+    engine._guided_sigmas(sigma_s, sigma_r)
+    where = image.device if image.is_cuda else _device()
+    plan = engine.guided_depth_plan(h, w, dh, dw, radius, sigma_s, sigma_r, device=where)
+    step = n if image.is_cuda else batch_size
+    parts = []
+    for b0 in range(0, n, step):
+        y = engine.guided_depth(image[b0:b0 + step].to(where, torch.float32).contiguous(),
+                                d4[b0:b0 + step].to(where, torch.float32).contiguous(), plan)
+        parts.append(y if image.is_cuda else y.cpu())
+    y = parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
+    if depth.dim() == 4:
+        y = y.unsqueeze(-1) if c == 1 else y.unsqueeze(-1).expand(-1, -1, -1, c).contiguous()
+    return y

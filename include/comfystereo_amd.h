@@ -714,6 +714,40 @@ CS_API int cs_depth_range(const float *depth, int n, int h, int w, int c, int ra
                           size_t workspace_bytes, void *stream);
 
 /*
+ * Image-guided depth upsampling (not in the reference, which stretches a smaller depth map bilinearly, so every silhouette
+ * becomes a ramp that the warp smears into a halo): joint bilateral upsampling (Kopf, Cohen, Lischinski, Uyttendaele, SIGGRAPH
+ * 2007), run in front of cs_generate.  Each full-resolution pixel is a weighted mean of the K x K nearest low-resolution depth
+ * samples, K = 2 * radius + 1; a sample counts as far as the frame's colour at its position resembles the colour at the pixel.
+ * DESIGN.md section 5 has the specification, tools/guided_oracle.py states it in numpy.
+ *   image [n][h][w][3] float32, the guide; depth [n][dh][dw][c] float32, dh <= h, dw <= w; g = the gray value cs_params.depth_c
+ *   describes (c == 3: gray, c == 1: the value, else channel 0); out [n][h][w] float32
+ * The plan depends on h, w, dh, dw, radius, sigma_s (in low-resolution pixels) and sigma_r only: cs_guided_depth_plan writes it
+ * once into cs_guided_depth_plan_bytes(...) bytes of device memory (0 for a non-positive size or a radius outside 1..3), and every
+ * cs_guided_depth_apply of that geometry reads it.  float64, every operation rounded once, integers in 64 bits:
+ *   u        = ((2x + 1) dw - w) / (2w)   one division;   cx[x] = floor(u + 0.5)
+ *   wx[x][j] = float32(exp(-(t t) / ((2 sigma_s) sigma_s))),  t = (cx[x] + j - radius) - u,  j = 0..K-1;   cy, wy likewise from h, dh
+ *   wr[d]    = float32(exp(-(a a) / ((2 sigma_r) sigma_r))),  a = d / 255.0,  d = 0..765;   sigma_r = +inf gives wr = 1
+ *   gx[qx]   = min(w - 1, ((2 qx + 1) w) / (2 dw)) in integers, gy likewise: the guide pixel under a low-resolution sample's centre
+ * The pass, float32, every operation rounded once.  code(v) = uint8(trunc(min(max(v, 0), 1) * 255 + 0.5)), NaN -> 0, per
+ * channel.  For pixel (y, x), p = code(image[y][x]), i = 0..K-1 outer, j = 0..K-1 inner:
+ *   qy = clamp(cy[y] + i - radius, 0, dh - 1);  qx = clamp(cx[x] + j - radius, 0, dw - 1);  ws = wy[y][i] * wx[x][j]
+ *   d  = |p.r - q.r| + |p.g - q.g| + |p.b - q.b|,  q = code(image[gy[qy]][gx[qx]]);  wg = ws * wr[d];  v = g[qy][qx]
+ *   num += wg * v;  den += wg;  ns += ws * v;  ds += ws;        out = den > 0 ? num / den : ns / ds   (IEEE division)
+ * The spatial weight uses the unclamped tap position and the index is clamped (border samples are replicated); the fallback,
+ * reached where every weight has rounded to zero, is the spatial mean; non-finite depth follows the arithmetic.
+ * CS_EINVAL: a null pointer, a non-positive size, a radius outside 1..3, a sigma that is not positive (NaN included), a buffer
+ * off the 4-byte grid, or any two of image, depth, plan and out overlapping.  CS_ELIMIT: dh > h, dw > w, n > 65535 or
+ * h * w >= 2^31.  CS_EWORKSPACE: plan_bytes < cs_guided_depth_plan_bytes(h, w, dh, dw, radius).  Every refusal precedes the first
+ * launch; each call is one launch on `stream`, nothing waits for the device, and a call can be captured into a graph.  A plan
+ * handed to an apply of another geometry gives wrong values, never an access outside the buffers.
+ */
+CS_API size_t cs_guided_depth_plan_bytes(int h, int w, int dh, int dw, int radius);
+CS_API int cs_guided_depth_plan(int h, int w, int dh, int dw, int radius, double sigma_s, double sigma_r, void *plan,
+                                size_t plan_bytes, void *stream);
+CS_API int cs_guided_depth_apply(const float *image, const float *depth, int n, int h, int w, int dh, int dw, int c, int radius,
+                                 const void *plan, size_t plan_bytes, float *out, void *stream);
+
+/*
  * Measurement hook for bench.py: while enabled, cs_generate brackets the launch of its dominant
  * kernel (the row warp + fill kernel of the selected technique) with HIP events on the caller's
  * stream.  cs_profile_read waits for the recorded events, returns the summed kernel time in
