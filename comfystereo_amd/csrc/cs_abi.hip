@@ -1205,6 +1205,40 @@ static bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
     return a && b && pa < pb + nb && pb < pa + na;
 }
 
+// ---- the buffer checks that entry points share --------------------------------------------------------------------------------
+// some pointer (null ones aside) is off the grid of `elem_bytes`, a power of two
+static bool misaligned(size_t elem_bytes, std::initializer_list<const void*> ptrs) {
+    uintptr_t bits = 0;
+    for (const void* p : ptrs) bits |= (uintptr_t)p;
+    return (bits & (elem_bytes - 1)) != 0;
+}
+
+struct span { const void* p; size_t bytes; };
+
+// some written region overlaps another one or a read one (a null region overlaps nothing).  An entry point that refuses overlap
+// between any two of its buffers, read-only pairs included, passes them all as `outs`.
+static bool any_overlap(const span* outs, int n_out, const span* ins, int n_in) {
+    for (int i = 0; i < n_out; i++) {
+        for (int j = i + 1; j < n_out; j++)
+            if (overlaps(outs[i].p, outs[i].bytes, outs[j].p, outs[j].bytes)) return true;
+        for (int j = 0; j < n_in; j++)
+            if (overlaps(outs[i].p, outs[i].bytes, ins[j].p, ins[j].bytes)) return true;
+    }
+    return false;
+}
+
+// an entry point's buffers as one table (the depth pre-passes): a null pointer among the first n, one off the grid of `elem_bytes`
+static bool any_null(const span* bufs, int n) {
+    for (int i = 0; i < n; i++)
+        if (!bufs[i].p) return true;
+    return false;
+}
+static bool misaligned(size_t elem_bytes, const span* bufs, int n) {
+    uintptr_t bits = 0;
+    for (int i = 0; i < n; i++) bits |= (uintptr_t)bufs[i].p;
+    return (bits & (elem_bytes - 1)) != 0;
+}
+
 int cs_pil_resize(const void* in, int n, int h, int w, int c, int oh, int ow, int flags, uint8_t* out_u8, float* out_f32,
                   size_t f32_row_pitch, void* workspace, size_t workspace_bytes, void* stream) {
     if (!in || !workspace) return fail(CS_EINVAL, "null pointer");
@@ -1351,26 +1385,6 @@ int cs_latent_shift_plan(const float* disp, int b, int h, int w, double scale_fa
 
 // ---- the checks the latent loops' entry points share (element size and width limit: cs_latent.h) ----
 static bool latent_dtype_ok(int dtype) { return dtype >= CS_LATENT_F32 && dtype <= CS_LATENT_BF16; }
-
-// some pointer (null ones aside) is off the grid of `elem_bytes`, a power of two
-static bool misaligned(size_t elem_bytes, std::initializer_list<const void*> ptrs) {
-    uintptr_t bits = 0;
-    for (const void* p : ptrs) bits |= (uintptr_t)p;
-    return (bits & (elem_bytes - 1)) != 0;
-}
-
-struct span { const void* p; size_t bytes; };
-
-// some written region overlaps another one or a read one (a null region overlaps nothing)
-static bool any_overlap(const span* outs, int n_out, const span* ins, int n_in) {
-    for (int i = 0; i < n_out; i++) {
-        for (int j = i + 1; j < n_out; j++)
-            if (overlaps(outs[i].p, outs[i].bytes, outs[j].p, outs[j].bytes)) return true;
-        for (int j = 0; j < n_in; j++)
-            if (overlaps(outs[i].p, outs[i].bytes, ins[j].p, ins[j].bytes)) return true;
-    }
-    return false;
-}
 
 // c1..c4 as the kernels take them
 struct coeffs4 {
@@ -1863,6 +1877,18 @@ int cs_attention_half_bwd(const void* q, const void* k, const void* v, const voi
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_attention_half_bwd");
 }
 
+// ---- the depth pre-passes (cs_temporal_depth, cs_depth_range, cs_guided_depth_*) ------------------------------------------------
+// Each entry point lists its buffers once, in a span table, and checks null pointers, alignment and overlap off it.  The kernels
+// take every buffer through a pointer they treat as distinct, so any two overlapping ones are refused, read-only pairs included.
+// (The table is made before the sizes are checked; a refused call never uses its byte counts.)
+
+// the limits they share: the frames are the grid's second dimension, a frame's pixel index fits 31 bits
+static int depth_limits(const char* entry, int n, int h, int w) {
+    if (n > 65535) return fail_named(CS_ELIMIT, entry, "more than 65535 frames in one call");
+    if ((size_t)h * w >= (1ull << 31)) return fail_named(CS_ELIMIT, entry, "frame of 2^31 pixels or more");
+    return CS_OK;
+}
+
 size_t cs_temporal_depth_workspace_bytes(int n, int h, int w, int c) {
     return (n <= 0 || h <= 0 || w <= 0 || c <= 0) ? 0 : temporal_workspace_bytes(n, h, w);
 }
@@ -1870,27 +1896,18 @@ size_t cs_temporal_depth_workspace_bytes(int n, int h, int w, int c) {
 int cs_temporal_depth(const float* depth, int n, int h, int w, int c, double alpha, double motion_threshold, double cut_threshold,
                       float* state_prev_raw, float* state_prev, int32_t* state_valid, float* out, float* m_out, int32_t* cut_out,
                       void* workspace, size_t workspace_bytes, void* stream) {
-    if (!depth || !state_prev_raw || !state_prev || !state_valid || !out || !m_out || !cut_out || !workspace)
-        return fail(CS_EINVAL, "null pointer");
+    const size_t frame = (size_t)h * w * 4, px = (size_t)n * h * w, need = cs_temporal_depth_workspace_bytes(n, h, w, c);
+    const span buf[8] = {{depth, px * c * 4}, {out, px * 4}, {state_prev_raw, frame}, {state_prev, frame}, {state_valid, 4},
+                         {m_out, (size_t)n * 4}, {cut_out, (size_t)n * 4}, {workspace, need}};
+    if (any_null(buf, 8)) return fail(CS_EINVAL, "null pointer");
     if (n <= 0 || h <= 0 || w <= 0 || c <= 0) return fail(CS_EINVAL, "non-positive size");
     if (!(alpha >= 0.0 && alpha <= 1.0)) return fail(CS_EINVAL, "cs_temporal_depth: alpha must lie in [0, 1]");
     if (!(motion_threshold >= 0.0)) return fail(CS_EINVAL, "cs_temporal_depth: motion_threshold must be >= 0 (+inf allowed)");
     if (!(cut_threshold >= 0.0)) return fail(CS_EINVAL, "cs_temporal_depth: cut_threshold must be >= 0 (+inf allowed)");
-    if (((uintptr_t)depth | (uintptr_t)state_prev_raw | (uintptr_t)state_prev | (uintptr_t)state_valid | (uintptr_t)out |
-         (uintptr_t)m_out | (uintptr_t)cut_out | (uintptr_t)workspace) & 3)
-        return fail(CS_EINVAL, "cs_temporal_depth: every buffer needs 4-byte alignment");
-    if (n > 65535) return fail(CS_ELIMIT, "cs_temporal_depth: more than 65535 frames in one call");
-    if ((size_t)h * w >= (1ull << 31)) return fail(CS_ELIMIT, "cs_temporal_depth: frame of 2^31 pixels or more");
-    const size_t px = (size_t)n * h * w;
-    const size_t need = cs_temporal_depth_workspace_bytes(n, h, w, c);
-    // the kernels read and write all eight buffers through pointers they take as distinct
-    const struct { const void* p; size_t bytes; } buf[] = {
-        {depth, px * c * 4}, {out, px * 4}, {state_prev_raw, (size_t)h * w * 4}, {state_prev, (size_t)h * w * 4}, {state_valid, 4},
-        {m_out, (size_t)n * 4}, {cut_out, (size_t)n * 4}, {workspace, need}};
-    for (int i = 0; i < 8; i++)
-        for (int j = i + 1; j < 8; j++)
-            if (overlaps(buf[i].p, buf[i].bytes, buf[j].p, buf[j].bytes))
-                return fail(CS_EINVAL, "cs_temporal_depth: depth, out, the state arrays, m_out, cut_out and workspace must not overlap");
+    if (misaligned(4, buf, 8)) return fail(CS_EINVAL, "cs_temporal_depth: every buffer needs 4-byte alignment");
+    if (int rc = depth_limits("cs_temporal_depth", n, h, w)) return rc;
+    if (any_overlap(buf, 8, nullptr, 0))
+        return fail(CS_EINVAL, "cs_temporal_depth: depth, out, the state arrays, m_out, cut_out and workspace must not overlap");
     if (workspace_bytes < need) return fail(CS_EWORKSPACE, "workspace too small");
     hipError_t e = launch_temporal(depth, n, h, w, c, (float)alpha, (float)motion_threshold, (float)cut_threshold, state_prev_raw,
                                    state_prev, state_valid, out, m_out, cut_out, (float*)workspace, (hipStream_t)stream);
@@ -1904,27 +1921,20 @@ size_t cs_depth_range_workspace_bytes(int n, int h, int w, int c) {
 int cs_depth_range(const float* depth, int n, int h, int w, int c, int rank_lo, int rank_hi, double beta, int normalize,
                    const int32_t* cut_or_null, float* state_lo, float* state_hi, int32_t* state_valid, float* out, float* lo_out,
                    float* hi_out, float* raw_lo_out, float* raw_hi_out, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!depth || !state_lo || !state_hi || !state_valid || !out || !lo_out || !hi_out || !raw_lo_out || !raw_hi_out || !workspace)
-        return fail(CS_EINVAL, "null pointer");
+    const size_t px = (size_t)n * h * w, per_frame = (size_t)n * 4, need = cs_depth_range_workspace_bytes(n, h, w, c);
+    // (cut stands last: it may be absent, which is no null pointer, and a null region overlaps nothing)
+    const span buf[11] = {{depth, px * c * 4}, {out, px * 4}, {state_lo, 4}, {state_hi, 4}, {state_valid, 4}, {lo_out, per_frame},
+                          {hi_out, per_frame}, {raw_lo_out, per_frame}, {raw_hi_out, per_frame}, {workspace, need},
+                          {cut_or_null, per_frame}};
+    if (any_null(buf, 10)) return fail(CS_EINVAL, "null pointer");
     if (n <= 0 || h <= 0 || w <= 0 || c <= 0) return fail(CS_EINVAL, "non-positive size");
-    if (n > 65535) return fail(CS_ELIMIT, "cs_depth_range: more than 65535 frames in one call");
-    if ((size_t)h * w >= (1ull << 31)) return fail(CS_ELIMIT, "cs_depth_range: frame of 2^31 pixels or more");
+    if (int rc = depth_limits("cs_depth_range", n, h, w)) return rc;
     if (rank_lo < 0 || rank_lo > rank_hi || (size_t)rank_hi >= (size_t)h * w)
         return fail(CS_EINVAL, "cs_depth_range: the ranks must satisfy 0 <= rank_lo <= rank_hi < h * w");
     if (!(beta >= 0.0 && beta <= 1.0)) return fail(CS_EINVAL, "cs_depth_range: beta must lie in [0, 1]");
-    if (((uintptr_t)depth | (uintptr_t)cut_or_null | (uintptr_t)state_lo | (uintptr_t)state_hi | (uintptr_t)state_valid |
-         (uintptr_t)out | (uintptr_t)lo_out | (uintptr_t)hi_out | (uintptr_t)raw_lo_out | (uintptr_t)raw_hi_out | (uintptr_t)workspace) & 3)
-        return fail(CS_EINVAL, "cs_depth_range: every buffer needs 4-byte alignment");
-    const size_t px = (size_t)n * h * w, per_frame = (size_t)n * 4;
-    const size_t need = cs_depth_range_workspace_bytes(n, h, w, c);
-    // the kernels read and write these buffers through pointers they take as distinct (an absent cut has no bytes)
-    const struct { const void* p; size_t bytes; } buf[] = {
-        {depth, px * c * 4}, {out, px * 4}, {state_lo, 4}, {state_hi, 4}, {state_valid, 4}, {lo_out, per_frame}, {hi_out, per_frame},
-        {raw_lo_out, per_frame}, {raw_hi_out, per_frame}, {workspace, need}, {cut_or_null, cut_or_null ? per_frame : 0}};
-    for (int i = 0; i < 11; i++)
-        for (int j = i + 1; j < 11; j++)
-            if (buf[i].bytes && buf[j].bytes && overlaps(buf[i].p, buf[i].bytes, buf[j].p, buf[j].bytes))
-                return fail(CS_EINVAL, "cs_depth_range: depth, out, the state words, the four bound arrays, cut and workspace must not overlap");
+    if (misaligned(4, buf, 11)) return fail(CS_EINVAL, "cs_depth_range: every buffer needs 4-byte alignment");
+    if (any_overlap(buf, 11, nullptr, 0))
+        return fail(CS_EINVAL, "cs_depth_range: depth, out, the state words, the four bound arrays, cut and workspace must not overlap");
     if (workspace_bytes < need) return fail(CS_EWORKSPACE, "workspace too small");
     hipError_t e = launch_depth_range(depth, n, h, w, c, rank_lo, rank_hi, (float)beta, normalize != 0, cut_or_null, state_lo, state_hi,
                                       state_valid, out, lo_out, hi_out, raw_lo_out, raw_hi_out, workspace, (hipStream_t)stream);
@@ -1935,8 +1945,7 @@ static int guided_geometry(int h, int w, int dh, int dw, int radius) {
     if (h <= 0 || w <= 0 || dh <= 0 || dw <= 0) return fail(CS_EINVAL, "non-positive size");
     if (radius < 1 || radius > 3) return fail(CS_EINVAL, "cs_guided_depth: the radius must be 1, 2 or 3");
     if (dh > h || dw > w) return fail(CS_ELIMIT, "cs_guided_depth: the depth map is larger than the image");
-    if ((size_t)h * w >= (1ull << 31)) return fail(CS_ELIMIT, "cs_guided_depth: frame of 2^31 pixels or more");
-    return CS_OK;
+    return depth_limits("cs_guided_depth", 1, h, w);   // (the frame's limit; the geometry has no frame count)
 }
 
 size_t cs_guided_depth_plan_bytes(int h, int w, int dh, int dw, int radius) {
@@ -1956,20 +1965,14 @@ int cs_guided_depth_plan(int h, int w, int dh, int dw, int radius, double sigma_
 
 int cs_guided_depth_apply(const float* image, const float* depth, int n, int h, int w, int dh, int dw, int c, int radius, const void* plan,
                           size_t plan_bytes, float* out, void* stream) {
-    if (!image || !depth || !plan || !out) return fail(CS_EINVAL, "null pointer");
+    const size_t px = (size_t)n * h * w, need = cs_guided_depth_plan_bytes(h, w, dh, dw, radius);
+    const span buf[4] = {{image, px * 3 * 4}, {depth, (size_t)n * dh * dw * c * 4}, {plan, need}, {out, px * 4}};
+    if (any_null(buf, 4)) return fail(CS_EINVAL, "null pointer");
     if (n <= 0 || c <= 0) return fail(CS_EINVAL, "non-positive size");
     if (int rc = guided_geometry(h, w, dh, dw, radius)) return rc;
-    if (n > 65535) return fail(CS_ELIMIT, "cs_guided_depth_apply: more than 65535 frames in one call");
-    if (((uintptr_t)image | (uintptr_t)depth | (uintptr_t)plan | (uintptr_t)out) & 3)
-        return fail(CS_EINVAL, "cs_guided_depth_apply: every buffer needs 4-byte alignment");
-    const size_t px = (size_t)n * h * w, need = guided_plan_bytes(h, w, dh, dw, radius);
-    // the kernel reads and writes these buffers through pointers it takes as distinct
-    const struct { const void* p; size_t bytes; } buf[] = {
-        {image, px * 3 * 4}, {depth, (size_t)n * dh * dw * c * 4}, {plan, need}, {out, px * 4}};
-    for (int i = 0; i < 4; i++)
-        for (int j = i + 1; j < 4; j++)
-            if (overlaps(buf[i].p, buf[i].bytes, buf[j].p, buf[j].bytes))
-                return fail(CS_EINVAL, "cs_guided_depth_apply: image, depth, plan and out must not overlap");
+    if (int rc = depth_limits("cs_guided_depth_apply", n, h, w)) return rc;
+    if (misaligned(4, buf, 4)) return fail(CS_EINVAL, "cs_guided_depth_apply: every buffer needs 4-byte alignment");
+    if (any_overlap(buf, 4, nullptr, 0)) return fail(CS_EINVAL, "cs_guided_depth_apply: image, depth, plan and out must not overlap");
     if (plan_bytes < need) return fail(CS_EWORKSPACE, "plan buffer too small");
     hipError_t e = launch_guided_apply(image, depth, n, h, w, dh, dw, c, radius, plan, out, (hipStream_t)stream);
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_guided_depth_apply");

@@ -2,7 +2,7 @@
 // "Depth range clipping").  Not in the reference, which normalises every frame by its own extremes: two order statistics of the
 // gray depth per frame, smoothed along t, and a clamp to them, in front of cs_generate.  tools/range_oracle.py states it in numpy.
 //
-//   g_t      = gray value of frame t (gray_of for C == 3, the value for C == 1, channel 0 otherwise: as cs_temporal.hip)
+//   g_t      = gray value of frame t (gray_of for C == 3, the value for C == 1, channel 0 otherwise: cs_gray4.h)
 //   key(x)   = bits(x) ^ 0x80000000 if the sign bit is clear, else ~bits(x): uint32, monotone in x, -0 below +0
 //   raw_lo_t = the element of g_t whose key has rank rank_lo (0-based) among the frame's h * w keys; raw_hi_t: rank_hi
 //   lo_t     = raw_lo_t if there is no predecessor, cut[t] != 0 or s is not finite, else s = lo_{t-1} + beta * (raw_lo_t - lo_{t-1})
@@ -57,6 +57,7 @@
 //   k_range_apply<true>                  16     22        0        8
 //   k_range_apply<false>                 22     28        0        8
 #include "cs_common.h"
+#include "cs_gray4.h"
 #include "cs_kernels.h"
 
 namespace cs {
@@ -66,48 +67,6 @@ enum { RH_THREADS = 256, RH_TRIPS = 32, RH_TRIP_PX = RH_THREADS * 4, RH_CHUNK = 
 
 size_t range_chunks(size_t hw) { return (hw + RH_CHUNK - 1) / RH_CHUNK; }
 size_t range_workspace_bytes(int n) { return al256((size_t)n * (RH_HIST_WORDS + RH_SEL_WORDS) * 4); }
-
-struct RPx4 { float v[4]; };
-
-// Four consecutive gray values from pixel i (a multiple of 4) of a frame; pixels at or behind hw read as 0.  The treatment of C
-// and the two access paths are cs_temporal.hip's load_gray4 / store4, restated here because that file keeps its own.
-template <int CM, bool VEC>
-__device__ __forceinline__ RPx4 range_load4(const float* frame, size_t i, size_t hw, int c) {
-    RPx4 g;
-    if (VEC && CM == 1) {
-        const float4 a = *reinterpret_cast<const float4*>(frame + i);
-        g.v[0] = a.x; g.v[1] = a.y; g.v[2] = a.z; g.v[3] = a.w;
-    } else if (VEC && CM == 3) {
-        const float4* q = reinterpret_cast<const float4*>(frame + 3 * i);
-        const float4 a = q[0], b = q[1], cc = q[2];
-        g.v[0] = gray_of(a.x, a.y, a.z); g.v[1] = gray_of(a.w, b.x, b.y);
-        g.v[2] = gray_of(b.z, b.w, cc.x); g.v[3] = gray_of(cc.y, cc.z, cc.w);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const size_t p = i + k;
-            float x = 0.0f;
-            if (p < hw) {
-                if (CM == 1) x = frame[p];
-                else if (CM == 3) x = gray_of(frame[3 * p], frame[3 * p + 1], frame[3 * p + 2]);
-                else x = frame[p * (size_t)c];
-            }
-            g.v[k] = x;
-        }
-    }
-    return g;
-}
-
-template <bool VEC>
-__device__ __forceinline__ void range_store4(float* frame, size_t i, size_t hw, const RPx4& g) {
-    if (VEC) {
-        *reinterpret_cast<float4*>(frame + i) = make_float4(g.v[0], g.v[1], g.v[2], g.v[3]);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            if (i + k < hw) frame[i + k] = g.v[k];
-    }
-}
 
 __device__ __forceinline__ uint32_t key_of(float x) {
     const uint32_t u = __builtin_bit_cast(uint32_t, x);
@@ -202,10 +161,10 @@ __global__ void __launch_bounds__(RH_THREADS) k_range_hist(const float* __restri
         if (chunk + (size_t)j * RH_TRIP_PX >= hw) break;          // (uniform over the workgroup: wave_count needs whole waves)
         const size_t i = chunk + (size_t)j * RH_TRIP_PX + 4 * (size_t)tid;
         const bool inside = i < hw;                               // (VEC: h * w is a multiple of 4, so i + 3 < hw as well)
-        RPx4 g;
+        Px4 g;
         g.v[0] = g.v[1] = g.v[2] = g.v[3] = 0.0f;
-        if (inside) g = range_load4<CM, VEC>(cur, i, hw, c);
-        if (P == 1 && CM != 1 && inside) range_store4<VEC>(gout, i, hw, g);
+        if (inside) g = load_gray4<CM, VEC>(cur, i, hw, c);
+        if (P == 1 && CM != 1 && inside) store4<VEC>(gout, i, hw, g);
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             const bool live = VEC ? inside : i + k < hw;
@@ -294,7 +253,7 @@ __global__ void __launch_bounds__(RH_THREADS) k_range_apply(const float* src, fl
     for (int j = 0; j < RA_TRIPS; j++) {
         const size_t i = ((size_t)blockIdx.x * RA_TRIPS + j) * RH_TRIP_PX + 4 * (size_t)threadIdx.x;
         if (i >= hw) break;
-        RPx4 g = range_load4<1, VEC>(cur, i, hw, 1);
+        Px4 g = load_gray4<1, VEC>(cur, i, hw, 1);
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             const float x = g.v[k];
@@ -303,7 +262,7 @@ __global__ void __launch_bounds__(RH_THREADS) k_range_apply(const float* src, fl
             if (normalize) y = flat ? 0.0f : (y - l) / span;
             g.v[k] = y;
         }
-        range_store4<VEC>(dst, i, hw, g);
+        store4<VEC>(dst, i, hw, g);
     }
 }
 
@@ -311,8 +270,7 @@ hipError_t launch_depth_range(const float* depth, int n, int h, int w, int c, in
                               const int32_t* cut, float* state_lo, float* state_hi, int32_t* state_valid, float* out, float* lo,
                               float* hi, float* raw_lo, float* raw_hi, void* workspace, hipStream_t stream) {
     const size_t hw = (size_t)h * w;
-    auto on16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    const bool vec = (hw & 3) == 0 && on16(depth) && on16(out);
+    const bool vec = vec4_path(hw, {depth, out});
     int32_t* hist = (int32_t*)workspace;
     int32_t* sel = hist + (size_t)n * RH_HIST_WORDS;
     hipError_t e = hipMemsetAsync(workspace, 0, (size_t)n * (RH_HIST_WORDS + RH_SEL_WORDS) * 4, stream);

@@ -57,6 +57,7 @@
 //   k_guided_apply<3, 0, true>           92     54    17152        5
 //   k_guided_apply<3, 0, false>          94     54    17152        5
 #include "cs_common.h"
+#include "cs_gray4.h"
 #include "cs_kernels.h"
 #include "cs_math.h"
 
@@ -259,8 +260,7 @@ static void guided_apply_r(const float* image, const float* depth, int n, int h,
 
 hipError_t launch_guided_apply(const float* image, const float* depth, int n, int h, int w, int dh, int dw, int c, int radius,
                                const void* plan, float* out, hipStream_t stream) {
-    auto on16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    const bool vec = (w & 3) == 0 && on16(image) && on16(out);
+    const bool vec = vec4_path((size_t)w, {image, out});   // (a lane's pixels lie in one row: every row must start on the grid)
     if (radius == 1) guided_apply_r<1>(image, depth, n, h, w, dh, dw, c, (const uint32_t*)plan, out, vec, stream);
     else if (radius == 2) guided_apply_r<2>(image, depth, n, h, w, dh, dw, c, (const uint32_t*)plan, out, vec, stream);
     else guided_apply_r<3>(image, depth, n, h, w, dh, dw, c, (const uint32_t*)plan, out, vec, stream);

@@ -2,7 +2,7 @@
 // stabilisation").  Not in the reference, which treats every frame alone: a causal, motion-adaptive, scene-cut-aware filter
 // along t over the gray depth, with its state carried from call to call.  tools/temporal_oracle.py states it in numpy.
 //
-//   g_t   = gray value of frame t (gray_of for C == 3, the value for C == 1, channel 0 otherwise)
+//   g_t   = gray value of frame t (gray_of for C == 3, the value for C == 1, channel 0 otherwise: cs_gray4.h, Px4 / load_gray4 / store4)
 //   m_t   = mean over the pixels of |g_t - g_{t-1}|          (t == 0: g_{-1} = the state's prev_raw)
 //   cut_t = m_t > cut_threshold, or no predecessor
 //   y_t   = g_t  if cut_t or !(|g_t - y_{t-1}| < motion_threshold),  else  y_{t-1} + alpha * (g_t - y_{t-1})
@@ -46,6 +46,7 @@
 //   k_temporal_recur<true>               40     43        0        8
 //   k_temporal_recur<false>              27     51        0        8
 #include "cs_common.h"
+#include "cs_gray4.h"
 #include "cs_kernels.h"
 
 namespace cs {
@@ -53,48 +54,6 @@ namespace cs {
 enum { TS_THREADS = 256, TS_TRIPS = 16, TS_TRIP_PX = TS_THREADS * 4, TS_CHUNK = TS_TRIP_PX * TS_TRIPS, TF_STAGE = 1024 };
 
 size_t temporal_partials(size_t hw) { return (hw + TS_CHUNK - 1) / TS_CHUNK; }
-
-struct Px4 { float v[4]; };
-
-// Four consecutive gray values from pixel i (a multiple of 4) of a frame whose first element is `frame`; pixels at or behind hw
-// read as 0.  CM: 1 -- one channel; 3 -- RGB; 0 -- channel 0 of c.  VEC: 16-byte loads (the caller guarantees i + 3 < hw).
-template <int CM, bool VEC>
-__device__ __forceinline__ Px4 load_gray4(const float* frame, size_t i, size_t hw, int c) {
-    Px4 g;
-    if (VEC && CM == 1) {
-        const float4 a = *reinterpret_cast<const float4*>(frame + i);
-        g.v[0] = a.x; g.v[1] = a.y; g.v[2] = a.z; g.v[3] = a.w;
-    } else if (VEC && CM == 3) {
-        const float4* q = reinterpret_cast<const float4*>(frame + 3 * i);
-        const float4 a = q[0], b = q[1], cc = q[2];
-        g.v[0] = gray_of(a.x, a.y, a.z); g.v[1] = gray_of(a.w, b.x, b.y);
-        g.v[2] = gray_of(b.z, b.w, cc.x); g.v[3] = gray_of(cc.y, cc.z, cc.w);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const size_t p = i + k;
-            float x = 0.0f;
-            if (p < hw) {
-                if (CM == 1) x = frame[p];
-                else if (CM == 3) x = gray_of(frame[3 * p], frame[3 * p + 1], frame[3 * p + 2]);
-                else x = frame[p * (size_t)c];
-            }
-            g.v[k] = x;
-        }
-    }
-    return g;
-}
-
-template <bool VEC>
-__device__ __forceinline__ void store4(float* frame, size_t i, size_t hw, const Px4& g) {
-    if (VEC) {
-        *reinterpret_cast<float4*>(frame + i) = make_float4(g.v[0], g.v[1], g.v[2], g.v[3]);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            if (i + k < hw) frame[i + k] = g.v[k];
-    }
-}
 
 template <int CM, bool VEC>
 __global__ void __launch_bounds__(TS_THREADS) k_temporal_stat(const float* __restrict__ depth, int c, size_t hw,
@@ -203,8 +162,7 @@ hipError_t launch_temporal(const float* depth, int n, int h, int w, int c, float
                            hipStream_t stream) {
     const size_t hw = (size_t)h * w;
     const int P = (int)temporal_partials(hw);
-    auto on16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    const bool vec = (hw & 3) == 0 && on16(depth) && on16(out) && on16(prev_raw) && on16(prev);
+    const bool vec = vec4_path(hw, {depth, out, prev_raw, prev});
     const dim3 sgrid((unsigned)P, (unsigned)n), block(TS_THREADS);
 #define CS_TEMPORAL_STAT(CM, VEC) \
     hipLaunchKernelGGL((k_temporal_stat<CM, VEC>), sgrid, block, 0, stream, depth, c, hw, (const float*)prev_raw, out, partial, P)

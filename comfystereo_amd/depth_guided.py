@@ -11,8 +11,6 @@ Its place in the chain is last: behind `StereoDepthStabilizer` and `StereoDepthR
 resolution, and directly in front of the Stereo Image Node, which then finds a depth map of the frame's size and resizes nothing.
 It keeps no state: every frame is upsampled on its own, stills included.
 """
-import torch
-
 from . import stereoimage_generation
 
 
@@ -42,8 +40,7 @@ class StereoDepthGuidedUpsample:
 
     def upsample(self, image, depth_map, radius=2, sigma_spatial=1.0, sigma_range=0.1, batch_size=16):
         """-> (the depth at the frames' size, in depth_map's channel layout and on its device,)."""
-        if not torch.cuda.is_available():
-            raise RuntimeError("comfystereo_amd needs an MI355X (PyTorch-ROCm `cuda` device); there is no CPU fallback")
+        stereoimage_generation._device_for(image)   # (without a GPU the package's RuntimeError, before anything else)
         return (stereoimage_generation.upsample_depth_guided(image, depth_map, radius, sigma_spatial, sigma_range, batch_size),)
 
 

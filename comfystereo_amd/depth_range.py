@@ -11,17 +11,14 @@ feeds a long clip: every execution continues where the last one stopped, bit for
 import torch
 
 from . import stereoimage_generation
+from .depth_nodes_common import ClipNode
 
 
 LIMIT = ("The stereo step's range equals these bounds only while a smoothed bound lies within the frame's own extremes (the "
          "ordinary case with a non-zero clip); otherwise the frame's own extreme rules, as without this node.")
 
 
-class StereoDepthRange:
-    def __init__(self):
-        self._state = None
-        self._key = None
-
+class StereoDepthRange(ClipNode):
     @classmethod
     def INPUT_TYPES(cls):
         return {
@@ -51,20 +48,11 @@ class StereoDepthRange:
     def clip(self, depth_map, scene_cut_mask=None, clip_low=0.005, clip_high=0.005, smoothing=0.2, normalize=False, batch_size=16,
              reset=False):
         """-> (the clamped depth in depth_map's layout and on its device,)."""
-        if not torch.cuda.is_available():
-            raise RuntimeError("comfystereo_amd needs an MI355X (PyTorch-ROCm `cuda` device); there is no CPU fallback")
-        n, h, w = depth_map.shape[:3]
-        device = depth_map.device if depth_map.is_cuda else torch.device("cuda", torch.cuda.current_device())
-        self._start_clip_if((h, w, device), reset)
+        n, _, _ = self._continue_clip(depth_map, reset)
         cuts = None if scene_cut_mask is None else [self._cuts_of(scene_cut_mask, n)]
         y, self._state = stereoimage_generation.clip_depth_range(depth_map, self._state, clip_low, clip_high, smoothing, normalize,
                                                                  batch_size, cuts=cuts)
         return (y,)
-
-    def _start_clip_if(self, key, reset):
-        """reset, another frame size or another device: the next frames start a new clip."""
-        if reset or key != self._key:
-            self._state, self._key = None, key
 
     @staticmethod
     def _cuts_of(mask, n):

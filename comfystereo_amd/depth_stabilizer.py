@@ -9,16 +9,13 @@ feeds a long clip: every execution continues where the last one stopped, bit for
 import torch
 
 from . import stereoimage_generation
+from .depth_nodes_common import ClipNode
 
 
 NEVER = 1000000.0   # the widgets' largest threshold: it and anything above it is passed on as +inf
 
 
-class StereoDepthStabilizer:
-    def __init__(self):
-        self._state = None
-        self._key = None
-
+class StereoDepthStabilizer(ClipNode):
     @classmethod
     def INPUT_TYPES(cls):
         return {
@@ -48,13 +45,7 @@ class StereoDepthStabilizer:
     def stabilize(self, depth_map, alpha=0.5, motion_threshold=0.1, cut_threshold=0.08, batch_size=16, reset=False):
         """-> (the filtered depth in depth_map's layout and on its device, a mask [N,H,W] that is 1 on every pixel of a frame the
         filter took for a scene cut -- the first frame of a clip among them -- and 0 elsewhere)."""
-        if not torch.cuda.is_available():
-            raise RuntimeError("comfystereo_amd needs an MI355X (PyTorch-ROCm `cuda` device); there is no CPU fallback")
-        n, h, w = depth_map.shape[:3]
-        device = depth_map.device if depth_map.is_cuda else torch.device("cuda", torch.cuda.current_device())
-        key = (h, w, device)
-        if reset or key != self._key:
-            self._state, self._key = None, key
+        n, h, w = self._continue_clip(depth_map, reset)
         motion_threshold = float("inf") if motion_threshold >= NEVER else motion_threshold
         cut_threshold = float("inf") if cut_threshold >= NEVER else cut_threshold
         cuts = []

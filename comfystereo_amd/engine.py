@@ -3,6 +3,7 @@
 Everything here takes and returns tensors that live on the MI355X (`cuda` device in PyTorch-ROCm);
 PyTorch only provides the memory and the stream -- the arithmetic is in the HIP kernels.
 """
+import copy
 import ctypes
 import math
 
@@ -447,28 +448,57 @@ def gaussian_blur(depth, sigma, op="plain", edge_threshold=None):
     return out.reshape(depth.shape)
 
 
+# ---- what the depth pre-passes share: the refusal of a frames argument, the state of a clip and its check -------------------------
+def _frames(name, t, layout="[N,H,W,C]"):
+    """The refusal of a pre-pass's frames argument (depth, or the guide image): float32 `layout`, not empty, contiguous, no grad.  -> t"""
+    return _tensor(name, t, dims=((4,), f"be {layout}, got shape"), dtypes=((torch.float32,), "float32"), not_empty=name,
+                   contiguous=True, no_grad="")
+
+
+class _ClipState:
+    """What a depth pre-pass carries from one call of a clip to the next: `shape`, the clip's frame size (h, w), and the device
+    tensors a subclass makes in its constructor, `valid` (one int32, 0: no frame seen yet) among them.  The pass updates them in
+    place."""
+
+    def __init__(self, h, w):
+        self.shape = (int(h), int(w))
+
+    @property
+    def tensors(self):
+        return [t for t in vars(self).values() if isinstance(t, torch.Tensor)]
+
+    @property
+    def device(self):
+        return self.valid.device
+
+    def clone(self):
+        return copy.deepcopy(self)   # (every tensor cloned, `shape` kept)
+
+
+def _clip_state(kind, state, depth):
+    """The state a call on `depth` [N,H,W,C] works with: a new one of `kind` for None (a clip's first frames), else `state`, or
+    ValueError unless it is one of `kind`, for frames of depth's size and on depth's device."""
+    h, w = depth.shape[1:3]
+    if state is None:
+        return kind(h, w, depth.device)
+    if not isinstance(state, kind):
+        raise ValueError(f"state must be a {kind.__name__} or None")
+    if state.shape != (h, w):
+        raise ValueError(f"state is for frames of {state.shape}, depth has {(h, w)}")
+    _same_device(("depth", depth), *(("state", t) for t in state.tensors))
+    return state
+
+
 # ---- temporal depth stabilisation of a video batch (cs_temporal_depth; DESIGN.md section 5) ----------------------------------
-class TemporalState:
+class TemporalState(_ClipState):
     """What cs_temporal_depth carries from one call to the next: prev_raw and prev, float32 [H,W] (the last frame's gray value
     and its filtered value), and `valid`, one int32 on the device (0: no frame seen yet).  temporal_depth updates it in place."""
 
     def __init__(self, h, w, device):
+        super().__init__(h, w)
         self.prev_raw = torch.empty((h, w), dtype=torch.float32, device=device)
         self.prev = torch.empty((h, w), dtype=torch.float32, device=device)
         self.valid = torch.zeros((1,), dtype=torch.int32, device=device)
-
-    @property
-    def shape(self):
-        return tuple(self.prev.shape)
-
-    @property
-    def device(self):
-        return self.prev.device
-
-    def clone(self):
-        other = TemporalState.__new__(TemporalState)
-        other.prev_raw, other.prev, other.valid = self.prev_raw.clone(), self.prev.clone(), self.valid.clone()
-        return other
 
 
 def temporal_depth(depth, state=None, alpha=0.5, motion_threshold=0.1, cut_threshold=0.08):
@@ -477,18 +507,9 @@ def temporal_depth(depth, state=None, alpha=0.5, motion_threshold=0.1, cut_thres
     updated in place and returned, or None for a clip's first frames (a new one is returned).  A clip fed in sub-batches gives
     bit for bit what one call gives.  Nothing waits for the device; a call with a given state can be captured into a graph."""
     L = _native.lib()
-    _tensor("depth", depth, dims=((4,), "be [N,H,W,C], got shape"), dtypes=((torch.float32,), "float32"), not_empty="depth",
-            contiguous=True, no_grad="")
-    _on_gpu(depth, no_gpu_error=True)
+    _on_gpu(_frames("depth", depth), no_gpu_error=True)
     n, h, w, c = depth.shape
-    if state is None:
-        state = TemporalState(h, w, depth.device)
-    elif not isinstance(state, TemporalState):
-        raise ValueError("state must be a TemporalState or None")
-    elif state.shape != (h, w):
-        raise ValueError(f"state is for frames of {state.shape}, depth has {(h, w)}")
-    else:
-        _same_device(("depth", depth), ("state", state.prev), ("state", state.prev_raw), ("state", state.valid))
+    state = _clip_state(TemporalState, state, depth)
     y = torch.empty((n, h, w), dtype=torch.float32, device=depth.device)
     m = torch.empty((n,), dtype=torch.float32, device=depth.device)
     cut = torch.empty((n,), dtype=torch.int32, device=depth.device)
@@ -499,25 +520,15 @@ def temporal_depth(depth, state=None, alpha=0.5, motion_threshold=0.1, cut_thres
 
 
 # ---- depth range clipping of a video batch (cs_depth_range) ------------------------------------------------
-class RangeState:
+class RangeState(_ClipState):
     """What cs_depth_range carries from one call to the next: lo and hi, one float32 each (the last frame's bounds), and `valid`,
     one int32 (0: no frame seen yet), all on the device.  `shape` is the frame size the clip has.  depth_range updates it in place."""
 
     def __init__(self, h, w, device):
-        self.shape = (int(h), int(w))
+        super().__init__(h, w)
         self.lo = torch.zeros((1,), dtype=torch.float32, device=device)
         self.hi = torch.zeros((1,), dtype=torch.float32, device=device)
         self.valid = torch.zeros((1,), dtype=torch.int32, device=device)
-
-    @property
-    def device(self):
-        return self.lo.device
-
-    def clone(self):
-        other = RangeState.__new__(RangeState)
-        other.shape = self.shape
-        other.lo, other.hi, other.valid = self.lo.clone(), self.hi.clone(), self.valid.clone()
-        return other
 
 
 def clip_ranks(clip_low, clip_high, count):
@@ -539,9 +550,7 @@ def depth_range(depth, state=None, clip_low=0.005, clip_high=0.005, beta=1.0, cu
     returned).  A clip fed in sub-batches gives bit for bit what one call gives.  Nothing waits for the device; a call with a given
     state can be captured into a graph."""
     L = _native.lib()
-    _tensor("depth", depth, dims=((4,), "be [N,H,W,C], got shape"), dtypes=((torch.float32,), "float32"), not_empty="depth",
-            contiguous=True, no_grad="")
-    n, h, w, c = depth.shape
+    n, h, w, c = _frames("depth", depth).shape
     rank_lo, rank_hi = clip_ranks(clip_low, clip_high, h * w)
     beta = float(beta)
     if not 0.0 <= beta <= 1.0:
@@ -549,14 +558,7 @@ def depth_range(depth, state=None, clip_low=0.005, clip_high=0.005, beta=1.0, cu
     if cut is not None:
         _tensor("cut", cut, shape=((n,), f"be [{n}], one flag per frame, got shape"), dtypes=((torch.int32,), "int32"), contiguous=True)
     _on_gpu(depth, no_gpu_error=True)
-    if state is None:
-        state = RangeState(h, w, depth.device)
-    elif not isinstance(state, RangeState):
-        raise ValueError("state must be a RangeState or None")
-    elif state.shape != (h, w):
-        raise ValueError(f"state is for frames of {state.shape}, depth has {(h, w)}")
-    else:
-        _same_device(("depth", depth), ("state", state.lo), ("state", state.hi), ("state", state.valid))
+    state = _clip_state(RangeState, state, depth)
     if cut is not None:
         _same_device(("depth", depth), ("cut", cut))
     y = torch.empty((n, h, w), dtype=torch.float32, device=depth.device)
@@ -660,10 +662,8 @@ def guided_depth(image, depth, plan):
     plan: the GuidedPlan of this geometry (guided_depth_plan), reused for every batch.  One launch; nothing waits for the device;
     a call can be captured into a graph."""
     L = _native.lib()
-    _tensor("image", image, dims=((4,), "be [N,H,W,3], got shape"), dtypes=((torch.float32,), "float32"), not_empty="image",
-            contiguous=True, no_grad="")
-    _tensor("depth", depth, dims=((4,), "be [N,dh,dw,C], got shape"), dtypes=((torch.float32,), "float32"), not_empty="depth",
-            contiguous=True, no_grad="")
+    _frames("image", image, "[N,H,W,3]")
+    _frames("depth", depth, "[N,dh,dw,C]")
     n, h, w, ic = image.shape
     if ic != 3:
         raise ValueError(f"image must be [N,H,W,3], got shape {tuple(image.shape)}")

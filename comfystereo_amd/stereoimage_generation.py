@@ -37,6 +37,11 @@ def _device():
     return torch.device("cuda", torch.cuda.current_device())
 
 
+def _device_for(t):
+    """Where a pass over the tensor `t` runs: t's device, else the current GPU (without one, _device's RuntimeError)."""
+    return t.device if t.is_cuda else _device()
+
+
 def _to_u8(x):
     """float32 outputs of the CPU-technique path are k/255 exactly -> recover k."""
     return torch.round(x * 255.0).to(torch.uint8)
@@ -330,6 +335,46 @@ def right_direction_aware_blur_depth_map(depth, sigma, edge_threshold):
     return _gaussian(depth, sigma, "right", edge_threshold)
 
 
+# ---- the depth pre-passes of a clip: one driver of their sub-batches ------------------------------------------
+class _DepthFrames:
+    """The depth argument of a pre-pass, a host or device tensor (or anything numpy takes) [N,H,W] or [N,H,W,C], and the loop that
+    feeds it to the device.  The steps run in the order the caller writes them, its own checks in between; none before run()
+    asks for a device."""
+
+    def __init__(self, depth, layout="[N,H,W]"):
+        if not isinstance(depth, torch.Tensor):
+            depth = torch.from_numpy(np.ascontiguousarray(depth))
+        if depth.dim() not in (3, 4) or depth.numel() == 0:
+            raise ValueError(f"depth must be a non-empty {layout} or {layout[:-1]},C], got shape {tuple(depth.shape)}")
+        self.depth = depth
+        self.d4 = depth if depth.dim() == 4 else depth.unsqueeze(-1)
+        self.n = depth.shape[0]
+
+    def in_batches_of(self, batch_size):
+        self.batch_size = int(batch_size)
+        if self.batch_size < 1:
+            raise ValueError(f"batch_size must be at least 1, got {self.batch_size}")
+        return self
+
+    def run(self, per_chunk, beside=()):
+        """per_chunk(b0, b1, frames b0..b1 of the depth as float32 [k,H,W,C] on the device, the same frames of every tensor of
+        `beside`) -> a tuple of device tensors, the first of them y [k,H',W'].  Device input goes in one call, host input in
+        sub-batches of batch_size whose results come back to the host.  -> (y of all frames in the caller's layout -- [N,H,W]
+        stays, C == 1 stays, any other C gets y in every channel --, the list of every call's other tensors)."""
+        where, on_device = _device_for(self.depth), self.depth.is_cuda
+        step = self.n if on_device else self.batch_size
+        parts, others = [], []
+        for b0 in range(0, self.n, step):
+            chunks = [t[b0:b0 + step].to(where, torch.float32).contiguous() for t in (self.d4,) + tuple(beside)]
+            y, *rest = (t if on_device else t.cpu() for t in per_chunk(b0, b0 + step, *chunks))
+            parts.append(y)
+            others.append(tuple(rest))
+        y = parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
+        if self.depth.dim() == 4:
+            y = y.unsqueeze(-1).expand(-1, -1, -1, self.d4.shape[3]).contiguous()
+        return y, others
+
+
 # ---- temporal depth stabilisation of a video batch (cs_temporal_depth; DESIGN.md section 5) -------------------------------------
 def stabilize_depth(depth, state=None, alpha=0.5, motion_threshold=0.1, cut_threshold=0.08, batch_size=16, cuts=None):
     """The causal, motion-adaptive, scene-cut-aware temporal filter over the depth maps of a clip, run in front of the stereo
@@ -339,27 +384,16 @@ def stabilize_depth(depth, state=None, alpha=0.5, motion_threshold=0.1, cut_thre
     the device), or None.  Host input is uploaded in sub-batches of at most batch_size frames with the state carried on the
     device; the result is bit for bit the one of a single call.  cuts: a list that receives every sub-batch's cut flags (int32 [k]
     on the input's device), for callers that want them -- the node's scene-cut mask."""
-    dev = _device()
-    if not isinstance(depth, torch.Tensor):
-        depth = torch.from_numpy(np.ascontiguousarray(depth))
-    if depth.dim() not in (3, 4) or depth.numel() == 0:
-        raise ValueError(f"depth must be a non-empty [N,H,W] or [N,H,W,C], got shape {tuple(depth.shape)}")
-    batch_size = int(batch_size)
-    if batch_size < 1:
-        raise ValueError(f"batch_size must be at least 1, got {batch_size}")
-    d4 = depth if depth.dim() == 4 else depth.unsqueeze(-1)
-    n, c = d4.shape[0], d4.shape[3]
-    step = n if depth.is_cuda else batch_size
-    parts = []
-    for b0 in range(0, n, step):
-        chunk = d4[b0:b0 + step].to(depth.device if depth.is_cuda else dev, torch.float32).contiguous()
+    frames = _DepthFrames(depth).in_batches_of(batch_size)
+
+    def filtered(b0, b1, chunk):
+        nonlocal state
         y, _, cut, state = engine.temporal_depth(chunk, state, alpha, motion_threshold, cut_threshold)
-        parts.append(y if depth.is_cuda else y.cpu())
-        if cuts is not None:
-            cuts.append(cut if depth.is_cuda else cut.cpu())
-    y = parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
-    if depth.dim() == 4:
-        y = y.unsqueeze(-1) if c == 1 else y.unsqueeze(-1).expand(-1, -1, -1, c).contiguous()
+        return y, cut
+
+    y, flags = frames.run(filtered)
+    if cuts is not None:
+        cuts.extend(cut for cut, in flags)
     return y, state
 
 
@@ -376,36 +410,24 @@ def clip_depth_range(depth, state=None, clip_low=0.005, clip_high=0.005, beta=1.
     with the state carried on the device; the result is bit for bit the one of a single call.  cuts: the list stabilize_depth
     filled for the same frames (int32 flags, in any split): the bounds restart at every flagged frame.  bounds: a list that
     receives every sub-batch's (lo, hi, raw_lo, raw_hi), float32 [k] on the input's device."""
-    if not isinstance(depth, torch.Tensor):
-        depth = torch.from_numpy(np.ascontiguousarray(depth))
-    if depth.dim() not in (3, 4) or depth.numel() == 0:
-        raise ValueError(f"depth must be a non-empty [N,H,W] or [N,H,W,C], got shape {tuple(depth.shape)}")
-    batch_size = int(batch_size)
-    if batch_size < 1:
-        raise ValueError(f"batch_size must be at least 1, got {batch_size}")
+    frames = _DepthFrames(depth).in_batches_of(batch_size)
     engine.clip_ranks(clip_low, clip_high, 1)   # (the fractions' refusal, before anything is uploaded)
-    d4 = depth if depth.dim() == 4 else depth.unsqueeze(-1)
-    n, c = d4.shape[0], d4.shape[3]
     cut = None
     if cuts is not None:
         cut = torch.cat([torch.as_tensor(k).reshape(-1) for k in cuts]) if len(cuts) else torch.zeros((0,), dtype=torch.int32)
-        if cut.numel() != n:
-            raise ValueError(f"cuts hold {cut.numel()} flags, depth has {n} frames")
-    where = depth.device if depth.is_cuda else _device()
-    if cut is not None:
-        cut = cut.to(where, torch.int32)
-    step = n if depth.is_cuda else batch_size
-    parts = []
-    for b0 in range(0, n, step):
-        chunk = d4[b0:b0 + step].to(where, torch.float32).contiguous()
-        y, *four, state = engine.depth_range(chunk, state, clip_low, clip_high, beta, None if cut is None else cut[b0:b0 + step].contiguous(),
-                                             normalize)
-        parts.append(y if depth.is_cuda else y.cpu())
-        if bounds is not None:
-            bounds.append(tuple(t if depth.is_cuda else t.cpu() for t in four))
-    y = parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
-    if depth.dim() == 4:
-        y = y.unsqueeze(-1) if c == 1 else y.unsqueeze(-1).expand(-1, -1, -1, c).contiguous()
+        if cut.numel() != frames.n:
+            raise ValueError(f"cuts hold {cut.numel()} flags, depth has {frames.n} frames")
+        cut = cut.to(_device_for(frames.depth), torch.int32)
+
+    def clipped(b0, b1, chunk):
+        nonlocal state
+        *y_and_four, state = engine.depth_range(chunk, state, clip_low, clip_high, beta, None if cut is None else cut[b0:b1].contiguous(),
+                                                normalize)
+        return y_and_four
+
+    y, fours = frames.run(clipped)
+    if bounds is not None:
+        bounds.extend(fours)
     return y, state
 
 
@@ -420,33 +442,17 @@ def upsample_depth_guided(image, depth, radius=2, sigma_s=1.0, sigma_r=0.1, batc
     over 255 (inf: no range term).  Host input is uploaded in sub-batches of at most batch_size frames; the plan is made once."""
     if not isinstance(image, torch.Tensor):
         image = torch.from_numpy(np.ascontiguousarray(image))
-    if not isinstance(depth, torch.Tensor):
-        depth = torch.from_numpy(np.ascontiguousarray(depth))
     if image.dim() != 4 or image.shape[3] != 3 or image.numel() == 0:
         raise ValueError(f"image must be a non-empty [N,H,W,3], got shape {tuple(image.shape)}")
-    if depth.dim() not in (3, 4) or depth.numel() == 0:
-        raise ValueError(f"depth must be a non-empty [N,dh,dw] or [N,dh,dw,C], got shape {tuple(depth.shape)}")
-    if depth.shape[0] != image.shape[0]:
-        raise ValueError(f"image has {image.shape[0]} frames, depth has {depth.shape[0]}")
-    if depth.device != image.device:
+    frames = _DepthFrames(depth, "[N,dh,dw]")
+    if frames.n != image.shape[0]:
+        raise ValueError(f"image has {image.shape[0]} frames, depth has {frames.n}")
+    if frames.depth.device != image.device:
         raise ValueError("image and depth must be on the same device")
-    batch_size = int(batch_size)
-    if batch_size < 1:
-        raise ValueError(f"batch_size must be at least 1, got {batch_size}")
-    d4 = depth if depth.dim() == 4 else depth.unsqueeze(-1)
-    n, h, w = image.shape[:3]
-    dh, dw, c = d4.shape[1:]
+    frames.in_batches_of(batch_size)
+    h, w = image.shape[1:3]
+    dh, dw = frames.d4.shape[1:3]
     engine._guided_geometry(h, w, dh, dw, radius)   # (the refusals, before anything is uploaded)
     engine._guided_sigmas(sigma_s, sigma_r)
-    where = image.device if image.is_cuda else _device()
-    plan = engine.guided_depth_plan(h, w, dh, dw, radius, sigma_s, sigma_r, device=where)
-    step = n if image.is_cuda else batch_size
-    parts = []
-    for b0 in range(0, n, step):
-        y = engine.guided_depth(image[b0:b0 + step].to(where, torch.float32).contiguous(),
-                                d4[b0:b0 + step].to(where, torch.float32).contiguous(), plan)
-        parts.append(y if image.is_cuda else y.cpu())
-    y = parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
-    if depth.dim() == 4:
-        y = y.unsqueeze(-1) if c == 1 else y.unsqueeze(-1).expand(-1, -1, -1, c).contiguous()
-    return y
+    plan = engine.guided_depth_plan(h, w, dh, dw, radius, sigma_s, sigma_r, device=_device_for(frames.depth))
+    return frames.run(lambda b0, b1, d, img: (engine.guided_depth(img, d, plan),), beside=(image,))[0]

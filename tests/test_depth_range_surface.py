@@ -34,9 +34,18 @@ def test_the_exports_are_in_the_header_and_in_the_bindings():
 
 
 def test_the_kernel_file_shares_the_gray_expression_and_records_its_resources():
-    with open(os.path.join(ROOT, "comfystereo_amd", "csrc", "cs_depthrange.hip")) as f:
-        text = f.read()
-    assert "gray_of(" in text and "0.2989" not in text
+    # the expression lives in the header the pre-passes share; no file of the family restates it or the access built on it
+    csrc = os.path.join(ROOT, "comfystereo_amd", "csrc")
+    texts = {}
+    for name in ("cs_gray4.h", "cs_temporal.hip", "cs_depthrange.hip", "cs_guideddepth.hip"):
+        with open(os.path.join(csrc, name)) as f:
+            texts[name] = f.read()
+        assert "0.2989" not in texts[name], name
+    assert "gray_of(" in texts["cs_gray4.h"] and len(re.findall(r"struct\s+\w*Px4\b", texts["cs_gray4.h"])) == 1
+    for name in ("cs_temporal.hip", "cs_depthrange.hip"):
+        assert '#include "cs_gray4.h"' in texts[name], name
+        assert not re.search(r"struct\s+\w*Px4\b|\bload_gray4\s*\(|range_load4|RPx4", texts[name]), name   # (a call names its <CM, VEC>)
+    text = texts["cs_depthrange.hip"]
     for kernel in ("k_range_hist<1, 1, true>", "k_range_hist<3, 1, false>", "k_range_pick", "k_range_smooth", "k_range_apply<true>"):
         assert re.search(r"//\s+" + re.escape(kernel) + r"\s+\d+\s+\d+\s+\d+\s+\d+", text), kernel
 

@@ -34,10 +34,17 @@ def test_the_exports_are_in_the_header_and_in_the_bindings():
 
 
 def test_the_kernel_file_shares_the_gray_expression():
+    # the expression lives in the header the pre-passes share; no file of the family restates it or the access built on it
     csrc = os.path.join(ROOT, "comfystereo_amd", "csrc")
-    with open(os.path.join(csrc, "cs_temporal.hip")) as f:
-        text = f.read()
-    assert "gray_of(" in text and "0.2989" not in text
+    text = {}
+    for name in ("cs_gray4.h", "cs_temporal.hip", "cs_depthrange.hip", "cs_guideddepth.hip"):
+        with open(os.path.join(csrc, name)) as f:
+            text[name] = f.read()
+        assert "0.2989" not in text[name], name
+    assert "gray_of(" in text["cs_gray4.h"] and len(re.findall(r"struct\s+\w*Px4\b", text["cs_gray4.h"])) == 1
+    for name in ("cs_temporal.hip", "cs_depthrange.hip"):
+        assert '#include "cs_gray4.h"' in text[name], name
+        assert not re.search(r"struct\s+\w*Px4\b|\bload_gray4\s*\(|range_load4|RPx4", text[name]), name   # (a call names its <CM, VEC>)
 
 
 # ---- refusals: all of them before any launch, so addresses that are never read will do ----------------------------------------------
