@@ -44,6 +44,9 @@ STANDARD_OP = {"none": 0, "first": 1, "reshift": 2}
 PREDICTION = {"epsilon": 0, "v_prediction": 1}
 # enum cs_plms_kind (the linear multistep combination of cs_inpaint_plms_step)
 PLMS_KIND = {"first": 0, "second": 1, "order2": 2, "order3": 3, "order4": 4}
+# enum cs_dilate_shape / cs_dilate_near (the foreground depth edge dilation, cs_depth_dilate)
+DILATE_SHAPE = {"square": 0, "disc": 1}
+DILATE_NEAR = {"bright": 0, "dark": 1}
 # enum cs_fewstep_sampler (the samplers of cs_inpaint_fewstep_init / cs_inpaint_fewstep_step)
 FEWSTEP_SAMPLER = {"euler": 0, "lcm": 1}
 
@@ -205,6 +208,8 @@ SIGNATURES = {
     "cs_guided_depth_plan_bytes": (_size, [_int] * 5),
     "cs_guided_depth_plan": (_int, [_int] * 5 + [_dbl, _dbl, _vp, _size, _vp]),
     "cs_guided_depth_apply": (_int, [_vp, _vp] + [_int] * 7 + [_vp, _size, _vp, _vp]),
+    # foreground depth edge dilation
+    "cs_depth_dilate": (_int, [_vp] + [_int] * 7 + [_flt, _vp, _vp]),
     # profiling, development switches, test hooks
     "cs_profile": (_int, [_int]),
     "cs_profile_read": (_int, [_dp, _ip]),

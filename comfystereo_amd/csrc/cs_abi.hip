@@ -1877,7 +1877,7 @@ int cs_attention_half_bwd(const void* q, const void* k, const void* v, const voi
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_attention_half_bwd");
 }
 
-// ---- the depth pre-passes (cs_temporal_depth, cs_depth_range, cs_guided_depth_*) ------------------------------------------------
+// ---- the depth pre-passes (cs_temporal_depth, cs_depth_range, cs_guided_depth_*, cs_depth_dilate) -------------------------------
 // Each entry point lists its buffers once, in a span table, and checks null pointers, alignment and overlap off it.  The kernels
 // take every buffer through a pointer they treat as distinct, so any two overlapping ones are refused, read-only pairs included.
 // (The table is made before the sizes are checked; a refused call never uses its byte counts.)
@@ -1976,6 +1976,23 @@ int cs_guided_depth_apply(const float* image, const float* depth, int n, int h, 
     if (plan_bytes < need) return fail(CS_EWORKSPACE, "plan buffer too small");
     hipError_t e = launch_guided_apply(image, depth, n, h, w, dh, dw, c, radius, plan, out, (hipStream_t)stream);
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_guided_depth_apply");
+}
+
+int cs_depth_dilate(const float* depth, int n, int h, int w, int c, int radius, int shape, int near, float threshold, float* out,
+                    void* stream) {
+    const size_t px = (size_t)n * h * w;
+    const span buf[2] = {{depth, px * c * 4}, {out, px * 4}};
+    if (any_null(buf, 2)) return fail(CS_EINVAL, "null pointer");
+    if (n <= 0 || h <= 0 || w <= 0 || c <= 0) return fail(CS_EINVAL, "non-positive size");
+    if (int rc = depth_limits("cs_depth_dilate", n, h, w)) return rc;
+    if (radius < 1 || radius > 8) return fail(CS_EINVAL, "cs_depth_dilate: the radius must lie in 1..8");
+    if (shape != CS_DILATE_SQUARE && shape != CS_DILATE_DISC) return fail(CS_EINVAL, "cs_depth_dilate: unknown shape");
+    if (near != CS_DILATE_NEAR_BRIGHT && near != CS_DILATE_NEAR_DARK) return fail(CS_EINVAL, "cs_depth_dilate: unknown near");
+    if (!(threshold >= 0.0f)) return fail(CS_EINVAL, "cs_depth_dilate: threshold must be >= 0 (+inf allowed)");
+    if (misaligned(4, buf, 2)) return fail(CS_EINVAL, "cs_depth_dilate: every buffer needs 4-byte alignment");
+    if (any_overlap(buf, 2, nullptr, 0)) return fail(CS_EINVAL, "cs_depth_dilate: out must not overlap depth (the halo reads neighbours)");
+    hipError_t e = launch_depth_dilate(depth, n, h, w, c, radius, shape, near, threshold, out, (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_depth_dilate");
 }
 
 int cs_profile(int enable) {

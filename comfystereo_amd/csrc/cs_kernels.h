@@ -394,6 +394,10 @@ size_t guided_plan_bytes(int h, int w, int dh, int dw, int radius);
 hipError_t launch_guided_plan(int h, int w, int dh, int dw, int radius, double sigma_s, double sigma_r, void* plan, hipStream_t stream);
 hipError_t launch_guided_apply(const float* image, const float* depth, int n, int h, int w, int dh, int dw, int c, int radius,
                                const void* plan, float* out, hipStream_t stream);
+// cs_depthdilate.hip (foreground depth edge dilation: cs_depth_dilate).  radius 1..8, shape and near of enum cs_dilate_shape /
+// cs_dilate_near; one launch, no workspace
+hipError_t launch_depth_dilate(const float* depth, int n, int h, int w, int c, int radius, int shape, int near, float threshold, float* out,
+                               hipStream_t stream);
 // lazy depth-blur tiles in k_gpuwarp (tilemap != nullptr): rows of at most this many columns, not the mesh-quality warp
 int gpuwarp_lazy_max_width();
 

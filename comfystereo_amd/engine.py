@@ -682,6 +682,39 @@ def guided_depth(image, depth, plan):
     return out
 
 
+# ---- foreground depth edge dilation (cs_depth_dilate) -------------------------------------------------------
+DILATE_RADII = tuple(range(1, 9))
+
+
+def _dilate_args(radius, shape, near, threshold):
+    """The refusals of depth_dilate's parameters -> (radius, shape code, near code, threshold)."""
+    if isinstance(radius, bool) or int(radius) != radius or int(radius) not in DILATE_RADII:
+        raise ValueError(f"radius must be an integer in 1..8, got {radius}")
+    if shape not in _native.DILATE_SHAPE:
+        raise ValueError(f"shape must be 'square' or 'disc', got {shape!r}")
+    if near not in _native.DILATE_NEAR:
+        raise ValueError(f"near must be 'bright' or 'dark', got {near!r}")
+    threshold = float(threshold)
+    if not threshold >= 0.0:
+        raise ValueError(f"threshold must be >= 0 (+inf allowed), got {threshold}")
+    return int(radius), _native.DILATE_SHAPE[shape], _native.DILATE_NEAR[near], threshold
+
+
+def depth_dilate(depth, radius=2, shape="disc", near="bright", threshold=0.04):
+    """cs_depth_dilate on a float32 device tensor [N,H,W,C] (C == 3: gray value, C == 1: the value, else channel 0) -> y float32
+    [N,H,W]: the near surface (near: 'bright' or 'dark' values) grown outward by `radius` pixels (1..8) over a 'square' or 'disc'
+    window, where the window's nearest value is at least `threshold` in front of the pixel; every other pixel keeps its gray value
+    bit for bit.  threshold 0 is plain grayscale dilation (dark: erosion).  One launch, no workspace; nothing waits for the device;
+    a call can be captured into a graph."""
+    L = _native.lib()
+    n, h, w, c = _frames("depth", depth).shape
+    radius, shape, near, threshold = _dilate_args(radius, shape, near, threshold)
+    _on_gpu(depth, no_gpu_error=True)
+    y = torch.empty((n, h, w), dtype=torch.float32, device=depth.device)
+    _launch(depth.device, L.cs_depth_dilate, _ptr(depth), n, h, w, c, radius, shape, near, threshold, _ptr(y))
+    return y
+
+
 # ---- StereoDiffusion Fast mode's warp, inpaint mask and gap pre-fill (cs_inpaint_prepare; DESIGN.md section 2) ---------------
 def inpaint_prepare(image, depth, scale_factor, threshold=0.05, codes=False):
     """cs_inpaint_prepare on device tensors: image [B,3,H,W] (values k / 255), depth [B,H,W], every frame on its own ->

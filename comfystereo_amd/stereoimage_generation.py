@@ -456,3 +456,18 @@ def upsample_depth_guided(image, depth, radius=2, sigma_s=1.0, sigma_r=0.1, batc
     engine._guided_sigmas(sigma_s, sigma_r)
     plan = engine.guided_depth_plan(h, w, dh, dw, radius, sigma_s, sigma_r, device=_device_for(frames.depth))
     return frames.run(lambda b0, b1, d, img: (engine.guided_depth(img, d, plan),), beside=(image,))[0]
+
+
+# ---- foreground depth edge dilation (cs_depth_dilate) -------------------------------------------------------
+def dilate_depth_edges(depth, radius=2, shape="disc", near="bright", threshold=0.04, batch_size=16):
+    """Grows the near surface of the depth maps outward by `radius` pixels at depth discontinuities, so the anti-aliased rim of an
+    object travels with the object in the warp and not with the background.  The last pre-pass in front of the stereo step, at
+    the frame's resolution (behind upsample_depth_guided, if that runs).  depth: a host or device tensor [N,H,W] or [N,H,W,C]
+    (other dtypes are converted to float32) -> the dilated depth in the input's layout, on the input's device, float32: [N,H,W]
+    and one channel keep their shape, any other C gets y in all of its channels.  radius: 1..8; shape: 'disc' or 'square'; near:
+    'bright' where larger values are nearer (ComfyUI's depth maps), 'dark' otherwise; threshold >= 0: a pixel takes its window's
+    nearest value only where that lies at least this far in front of it (0: plain dilation; +inf: nothing moves).  Every frame on
+    its own; host input is uploaded in sub-batches of at most batch_size frames."""
+    frames = _DepthFrames(depth).in_batches_of(batch_size)
+    engine._dilate_args(radius, shape, near, threshold)   # (the refusals, before anything is uploaded)
+    return frames.run(lambda b0, b1, d: (engine.depth_dilate(d, radius, shape, near, threshold),))[0]

@@ -748,6 +748,31 @@ CS_API int cs_guided_depth_apply(const float *image, const float *depth, int n, 
                                  const void *plan, size_t plan_bytes, float *out, void *stream);
 
 /*
+ * Foreground depth edge dilation (not in the reference): a frame's silhouettes are anti-aliased, so a depth edge that sits on
+ * the colour edge gives the outer, mixed pixels of an object the background's depth, and the warp leaves them behind as an outline
+ * beside every disocclusion.  The pass grows the near surface outward by `radius` pixels, at depth discontinuities only; it runs
+ * last in front of cs_generate, at the frame's resolution (behind cs_guided_depth_apply).  DESIGN.md section 5 has the
+ * specification, tools/dilate_oracle.py states it in numpy.
+ *   depth [n][h][w][c] float32; g = the gray value cs_params.depth_c describes (c == 3: gray, c == 1: the value, else channel 0)
+ *   window  CS_DILATE_SQUARE: |dx| <= radius and |dy| <= radius;  CS_DILATE_DISC: dx dx + dy dy <= radius radius, in integers
+ *           (radius 1: the 4-neighbour cross; radius 8: 197 taps).  Clipped to the frame: pixels outside take no part.
+ *   key(x)  = bits(x) ^ 0x80000000 if the sign bit is clear, else ~bits(x) (uint32: a total order, -0 below +0)
+ *   M(p)    = the non-NaN g(q) of largest key over p's window (CS_DILATE_NEAR_BRIGHT), of smallest key (CS_DILATE_NEAR_DARK)
+ *   y(p)    = M(p) if M(p) - g(p) >= threshold (dark: g(p) - M(p) >= threshold): one float32 subtraction, one comparison, which is
+ *             false for a NaN difference (a NaN centre, no candidate, inf - inf);  else g(p), bit for bit
+ * out [n][h][w] float32 = y.  threshold 0 is plain grayscale dilation (dark: erosion); a positive threshold leaves smooth slopes
+ * bit for bit and moves only discontinuities; dark(g) == -bright(-g) bit for bit.
+ * CS_EINVAL: a null pointer, a non-positive size, a radius outside 1..8, an unknown shape or near, a threshold that is negative or
+ * NaN (+inf allowed), a buffer off the 4-byte grid, or out overlapping depth (the halo reads neighbours).  CS_ELIMIT: n > 65535
+ * or h * w >= 2^31.  Every refusal precedes the launch; the call is one launch on `stream`, without workspace or atomics, nothing
+ * waits for the device, and the call can be captured into a graph.
+ */
+enum cs_dilate_shape { CS_DILATE_SQUARE = 0, CS_DILATE_DISC = 1 };
+enum cs_dilate_near { CS_DILATE_NEAR_BRIGHT = 0, CS_DILATE_NEAR_DARK = 1 };
+CS_API int cs_depth_dilate(const float *depth, int n, int h, int w, int c, int radius, int shape, int near, float threshold,
+                           float *out, void *stream);
+
+/*
  * Measurement hook for bench.py: while enabled, cs_generate brackets the launch of its dominant
  * kernel (the row warp + fill kernel of the selected technique) with HIP events on the caller's
  * stream.  cs_profile_read waits for the recorded events, returns the summed kernel time in
