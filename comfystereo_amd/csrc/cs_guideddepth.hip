@@ -58,6 +58,7 @@
 //   k_guided_apply<3, 0, false>          94     54    17152        5
 #include "cs_common.h"
 #include "cs_gray4.h"
+#include "cs_guidecode.h"
 #include "cs_kernels.h"
 #include "cs_math.h"
 
@@ -124,14 +125,7 @@ __global__ void __launch_bounds__(GD_THREADS) k_guided_plan(int h, int w, int dh
     }
 }
 
-// code(v) = uint8(trunc(min(max(v, 0), 1) * 255 + 0.5)), NaN -> 0 (a NaN fails the first comparison)
-__device__ __forceinline__ uint32_t guide_code(float v) {
-    float c = v > 0.0f ? v : 0.0f;
-    c = c < 1.0f ? c : 1.0f;
-    return (uint32_t)(c * 255.0f + 0.5f);
-}
-__device__ __forceinline__ uint32_t guide_pack(float r, float g, float b) { return guide_code(r) | (guide_code(g) << 8) | (guide_code(b) << 16); }
-
+// (guide_code, guide_pack: cs_guidecode.h)
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 template <int R, int CM, bool VEC>

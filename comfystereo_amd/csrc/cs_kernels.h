@@ -382,6 +382,14 @@ size_t temporal_workspace_bytes(int n, int h, int w);
 hipError_t launch_temporal(const float* depth, int n, int h, int w, int c, float alpha, float motion_thr, float cut_thr,
                            float* prev_raw, float* prev, int32_t* valid, float* out, float* m, int32_t* cut, float* partial,
                            hipStream_t stream);
+// cs_motiondepth.hip (motion-compensated temporal depth stabilisation: cs_motion_depth).  guide [n][h][w][3]; the state's fourth
+// buffer prev_luma is [h][w] uint8; vec [n][Hb][Wb][2] (dx, dy), sad and matched [n][Hb][Wb], Hb = ceil(h / 16), Wb = ceil(w / 16);
+// workspace: motion_workspace_bytes(n, h, w) bytes (cs_motiondepth.h MotionViews)
+size_t motion_workspace_bytes(int n, int h, int w);
+hipError_t launch_motion_depth(const float* depth, const float* guide, int n, int h, int w, int c, float alpha, float motion_thr,
+                               float cut_thr, int search_range, int smoothness, int match_thr, float* prev_raw, float* prev,
+                               uint8_t* prev_luma, int32_t* valid, float* out, float* m, int32_t* cut, int8_t* vec, int32_t* sad,
+                               uint8_t* matched, void* workspace, hipStream_t stream);
 // cs_depthrange.hip (depth range clipping: cs_depth_range).  workspace: range_workspace_bytes(n) bytes, the frames' digit
 // histograms and selections; cut: null or [n] int32; the state's three words live in device memory
 size_t range_workspace_bytes(int n);

@@ -48,68 +48,10 @@
 #include "cs_common.h"
 #include "cs_gray4.h"
 #include "cs_kernels.h"
+#include "cs_temporalstat.h"
 
+// (k_temporal_stat and k_temporal_final: cs_temporalstat.h, shared with cs_motiondepth.hip)
 namespace cs {
-
-enum { TS_THREADS = 256, TS_TRIPS = 16, TS_TRIP_PX = TS_THREADS * 4, TS_CHUNK = TS_TRIP_PX * TS_TRIPS, TF_STAGE = 1024 };
-
-size_t temporal_partials(size_t hw) { return (hw + TS_CHUNK - 1) / TS_CHUNK; }
-
-template <int CM, bool VEC>
-__global__ void __launch_bounds__(TS_THREADS) k_temporal_stat(const float* __restrict__ depth, int c, size_t hw,
-                                                              const float* __restrict__ prev_raw, float* __restrict__ gray_out,
-                                                              float* __restrict__ partial, int P) {
-    __shared__ float red[TS_THREADS];
-    const int tid = threadIdx.x, t = blockIdx.y;
-    const float* cur = depth + (size_t)t * hw * c;
-    const float* pre = depth + (size_t)(t > 0 ? t - 1 : 0) * hw * c;
-    float* gout = (CM != 1) ? gray_out + (size_t)t * hw : nullptr;
-    const size_t base = (size_t)blockIdx.x * TS_CHUNK + 4 * (size_t)tid;
-    float acc = 0.0f;
-#pragma unroll 4
-    for (int j = 0; j < TS_TRIPS; j++) {
-        const size_t i = base + (size_t)j * TS_TRIP_PX;
-        if (i >= hw) break;
-        const Px4 g = load_gray4<CM, VEC>(cur, i, hw, c);
-        // (uniform over the workgroup: frame 0's predecessor is the state's one-channel gray frame)
-        const Px4 p = t > 0 ? load_gray4<CM, VEC>(pre, i, hw, c) : load_gray4<1, VEC>(prev_raw, i, hw, 1);
-        if (CM != 1) store4<VEC>(gout, i, hw, g);
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            if (VEC || i + k < hw) acc = acc + fabsf(g.v[k] - p.v[k]);
-    }
-    red[tid] = acc;
-    __syncthreads();
-#pragma unroll
-    for (int half = TS_THREADS / 2; half > 0; half >>= 1) {
-        if (tid < half) red[tid] = red[tid] + red[tid + half];
-        __syncthreads();
-    }
-    if (tid == 0) partial[(size_t)t * P + blockIdx.x] = red[0];
-}
-
-__global__ void __launch_bounds__(TS_THREADS) k_temporal_final(const float* __restrict__ partial, int P, float count, float cut_thr,
-                                                               const int32_t* __restrict__ valid, float* __restrict__ m,
-                                                               int32_t* __restrict__ cut) {
-    __shared__ float stage[TF_STAGE];
-    const int tid = threadIdx.x, t = blockIdx.x;
-    const float* src = partial + (size_t)t * P;
-    float s = 0.0f;
-    for (int b0 = 0; b0 < P; b0 += TF_STAGE) {
-        const int len = min((int)TF_STAGE, P - b0);
-        for (int i = tid; i < len; i += TS_THREADS) stage[i] = src[b0 + i];
-        __syncthreads();
-        if (tid == 0)
-            for (int i = 0; i < len; i++) s = s + stage[i];
-        __syncthreads();
-    }
-    if (tid == 0) {
-        const float mean = s / count;
-        const bool has_pred = t > 0 || valid[0] != 0;
-        m[t] = has_pred ? mean : 0.0f;
-        cut[t] = has_pred ? (mean > cut_thr ? 1 : 0) : 1;   // (a NaN mean is not a cut)
-    }
-}
 
 // src and out are the same array for C != 1 (a lane reads frame t + 2 of its own pixels before it writes frame t): no __restrict__
 template <bool VEC>
@@ -161,17 +103,9 @@ hipError_t launch_temporal(const float* depth, int n, int h, int w, int c, float
                            float* prev_raw, float* prev, int32_t* valid, float* out, float* m, int32_t* cut, float* partial,
                            hipStream_t stream) {
     const size_t hw = (size_t)h * w;
-    const int P = (int)temporal_partials(hw);
     const bool vec = vec4_path(hw, {depth, out, prev_raw, prev});
-    const dim3 sgrid((unsigned)P, (unsigned)n), block(TS_THREADS);
-#define CS_TEMPORAL_STAT(CM, VEC) \
-    hipLaunchKernelGGL((k_temporal_stat<CM, VEC>), sgrid, block, 0, stream, depth, c, hw, (const float*)prev_raw, out, partial, P)
-    if (c == 1) { if (vec) CS_TEMPORAL_STAT(1, true); else CS_TEMPORAL_STAT(1, false); }
-    else if (c == 3) { if (vec) CS_TEMPORAL_STAT(3, true); else CS_TEMPORAL_STAT(3, false); }
-    else CS_TEMPORAL_STAT(0, false);   // (channel 0 of c: strided 4-byte loads on either grid)
-#undef CS_TEMPORAL_STAT
-    hipLaunchKernelGGL(k_temporal_final, dim3((unsigned)n), block, 0, stream, (const float*)partial, P, (float)hw, cut_thr,
-                       (const int32_t*)valid, m, cut);
+    const dim3 block(TS_THREADS);
+    launch_temporal_stat(depth, n, hw, c, cut_thr, prev_raw, valid, out, m, cut, partial, vec, stream);
     const float* src = c == 1 ? depth : out;
     const dim3 rgrid((unsigned)((hw + TS_TRIP_PX - 1) / TS_TRIP_PX));
     if (vec) hipLaunchKernelGGL(k_temporal_recur<true>, rgrid, block, 0, stream, src, out, n, hw, (const int32_t*)cut, alpha, motion_thr, prev_raw, prev, valid);

@@ -519,6 +519,82 @@ def temporal_depth(depth, state=None, alpha=0.5, motion_threshold=0.1, cut_thres
     return y, m, cut, state
 
 
+# ---- motion-compensated temporal depth stabilisation of a video batch (cs_motion_depth) ----------------------
+MOTION_BLOCK = 16
+MOTION_RANGES = {"search_range": 32, "smoothness": 4096, "match_threshold": 255}   # each an integer from 0 to this
+
+
+class MotionState(_ClipState):
+    """What cs_motion_depth carries from one call to the next: prev_raw and prev, float32 [H,W] (the last frame's gray value and
+    its filtered value), prev_luma, uint8 [H,W] (the luma of its colour frame), and `valid`, one int32 on the device (0: no frame
+    seen yet).  motion_depth updates it in place."""
+
+    def __init__(self, h, w, device):
+        super().__init__(h, w)
+        self.prev_raw = torch.empty((h, w), dtype=torch.float32, device=device)
+        self.prev = torch.empty((h, w), dtype=torch.float32, device=device)
+        self.prev_luma = torch.empty((h, w), dtype=torch.uint8, device=device)
+        self.valid = torch.zeros((1,), dtype=torch.int32, device=device)
+
+
+def _motion_args(search_range, smoothness, match_threshold):
+    """The refusals of motion_depth's three integer parameters -> them as ints."""
+    given = dict(search_range=search_range, smoothness=smoothness, match_threshold=match_threshold)
+    for name, v in given.items():
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or int(v) != v or not 0 <= int(v) <= MOTION_RANGES[name]:
+            raise ValueError(f"{name} must be an integer in 0..{MOTION_RANGES[name]}, got {v}")
+    return tuple(int(v) for v in given.values())
+
+
+def _motion_guide(guide, depth):
+    """The refusal of motion_depth's guide: float32 [N,H,W,3] with depth's N, H and W."""
+    _frames("guide", guide, "[N,H,W,3]")
+    if guide.shape[3] != 3 or tuple(guide.shape[:3]) != tuple(depth.shape[:3]):
+        raise ValueError(f"guide must be [N,H,W,3] at the depth's size {tuple(depth.shape[:3])}, got shape {tuple(guide.shape)}")
+
+
+def motion_depth(depth, guide, state=None, alpha=0.5, motion_threshold=0.1, cut_threshold=0.08, search_range=16, smoothness=32,
+                 match_threshold=12):
+    """motion_depth_detail without the SADs: -> (y, m, cut, state, vec, matched)."""
+    return motion_depth_detail(depth, guide, state, alpha, motion_threshold, cut_threshold, search_range, smoothness, match_threshold)[:6]
+
+
+def motion_depth_detail(depth, guide, state=None, alpha=0.5, motion_threshold=0.1, cut_threshold=0.08, search_range=16, smoothness=32,
+                        match_threshold=12):
+    """cs_motion_depth on float32 device tensors: depth [N,H,W,C] (C == 3: gray value, C == 1: the value, else channel 0) and
+    guide [N,H,W,3], the clip's colour frames at the depth's size -> (y float32 [N,H,W], m float32 [N], cut int32 [N] of 0 / 1,
+    state, vec int8 [N,Hb,Wb,2] of (dx, dy), matched uint8 [N,Hb,Wb] of 0 / 1, sad int32 [N,Hb,Wb]: the vectors' SADs),
+    Hb = ceil(H / 16), Wb = ceil(W / 16).
+    temporal_depth's filter with y_{t-1} read where the pixel's 16 x 16 block came from: a full-search block matcher on the guide's
+    8-bit luma over |dx|, |dy| <= search_range (0..32), cost SAD + smoothness (|dx| + |dy|) (0..4096); a block whose SAD exceeds
+    match_threshold (0..255) per pixel passes unfiltered.  The three defaults are starting values that nobody has tuned on
+    footage.  state: the MotionState of the clip's earlier frames, updated in place and returned, or None for a clip's first
+    frames (a new one is returned).  A clip fed in sub-batches gives bit for bit what one call gives; search_range 0 with
+    match_threshold 255 gives temporal_depth's y, m, cut and float state.  Nothing waits for the device; a call with a given state
+    can be captured into a graph."""
+    L = _native.lib()
+    _frames("depth", depth)
+    _motion_guide(guide, depth)
+    search_range, smoothness, match_threshold = _motion_args(search_range, smoothness, match_threshold)
+    _on_gpu(depth, no_gpu_error=True)
+    _same_device(("depth", depth), ("guide", guide))
+    n, h, w, c = depth.shape
+    state = _clip_state(MotionState, state, depth)
+    dev = depth.device
+    hb, wb = -(-h // MOTION_BLOCK), -(-w // MOTION_BLOCK)
+    y = torch.empty((n, h, w), dtype=torch.float32, device=dev)
+    m = torch.empty((n,), dtype=torch.float32, device=dev)
+    cut = torch.empty((n,), dtype=torch.int32, device=dev)
+    vec = torch.empty((n, hb, wb, 2), dtype=torch.int8, device=dev)
+    sad = torch.empty((n, hb, wb), dtype=torch.int32, device=dev)
+    matched = torch.empty((n, hb, wb), dtype=torch.uint8, device=dev)
+    ws, nb = _workspace(L.cs_motion_depth_workspace_bytes(n, h, w, c, search_range), dev)
+    _launch(dev, L.cs_motion_depth, _ptr(depth), _ptr(guide), n, h, w, c, float(alpha), float(motion_threshold), float(cut_threshold),
+            search_range, smoothness, match_threshold, _ptr(state.prev_raw), _ptr(state.prev), _ptr(state.prev_luma), _ptr(state.valid),
+            _ptr(y), _ptr(m), _ptr(cut), _ptr(vec), _ptr(sad), _ptr(matched), _ptr(ws), nb)
+    return y, m, cut, state, vec, matched, sad
+
+
 # ---- depth range clipping of a video batch (cs_depth_range; DESIGN.md section 5) ------------------------------------------------
 class RangeState(_ClipState):
     """What cs_depth_range carries from one call to the next: lo and hi, one float32 each (the last frame's bounds), and `valid`,

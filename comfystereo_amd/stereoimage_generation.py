@@ -397,6 +397,47 @@ def stabilize_depth(depth, state=None, alpha=0.5, motion_threshold=0.1, cut_thre
     return y, state
 
 
+# ---- motion-compensated temporal depth stabilisation of a video batch (cs_motion_depth) ----------------------
+def stabilize_depth_motion(depth, image, state=None, alpha=0.5, motion_threshold=0.1, cut_threshold=0.08, search_range=16, smoothness=32,
+                           match_threshold=12, batch_size=16, cuts=None, unmatched=None):
+    """stabilize_depth with the filter's state read where each 16 x 16 block came from, so that moving content is filtered too; the
+    motion is found on the clip's colour frames.  depth: as for stabilize_depth; image: a host or device tensor [N,H',W',3], the
+    frames the depth maps belong to, where depth is -> (the filtered depth in the input's layout, on the input's device, float32;
+    state: engine.MotionState).  An image at another size than the depth is brought there with engine.pil_resize (Pillow's 8-bit
+    bicubic); its codes go on as codes / 255, which the luma conversion maps back to the codes exactly (code(k / 255) = k).
+    search_range 0..32 pixels at the depth's resolution, smoothness 0..4096, match_threshold 0..255: engine.motion_depth; their
+    defaults are starting values that nobody has tuned on footage.  Host input is uploaded in sub-batches of at most batch_size
+    frames with the state carried on the device; the result is bit for bit the one of a single call.  cuts: a list that receives
+    every sub-batch's cut flags (int32 [k]); unmatched: one that receives every sub-batch's unmatched-block flags (uint8
+    [k,Hb,Wb], 1 where a block found no match and passed unfiltered), both on the input's device."""
+    frames = _DepthFrames(depth).in_batches_of(batch_size)
+    if not isinstance(image, torch.Tensor):
+        image = torch.from_numpy(np.ascontiguousarray(image))
+    if image.dim() != 4 or image.shape[3] != 3 or image.numel() == 0:
+        raise ValueError(f"image must be a non-empty [N,H,W,3], got shape {tuple(image.shape)}")
+    if frames.n != image.shape[0]:
+        raise ValueError(f"image has {image.shape[0]} frames, depth has {frames.n}")
+    if frames.depth.device != image.device:
+        raise ValueError("image and depth must be on the same device")
+    engine._motion_args(search_range, smoothness, match_threshold)   # (the refusals, before anything is uploaded)
+    h, w = frames.d4.shape[1:3]
+
+    def filtered(b0, b1, chunk, img):
+        nonlocal state
+        if tuple(img.shape[1:3]) != (h, w):
+            img = engine.pil_resize(img, (w, h), f32="nhwc", codes=True)[1]
+        y, _, cut, state, _, matched = engine.motion_depth(chunk, img, state, alpha, motion_threshold, cut_threshold, search_range,
+                                                           smoothness, match_threshold)
+        return y, cut, 1 - matched
+
+    y, flags = frames.run(filtered, beside=(image,))
+    if cuts is not None:
+        cuts.extend(cut for cut, _ in flags)
+    if unmatched is not None:
+        unmatched.extend(un for _, un in flags)
+    return y, state
+
+
 # ---- depth range clipping of a video batch (cs_depth_range; DESIGN.md section 5) ------------------------------------------------
 def clip_depth_range(depth, state=None, clip_low=0.005, clip_high=0.005, beta=1.0, normalize=False, batch_size=16, cuts=None,
                      bounds=None):

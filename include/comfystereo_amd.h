@@ -686,6 +686,41 @@ CS_API int cs_temporal_depth(const float *depth, int n, int h, int w, int c, dou
                              float *m_out, int32_t *cut_out, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * Motion-compensated temporal depth stabilisation of a video batch (not in the reference): cs_temporal_depth's filter, with
+ * y_{t-1} read where the pixel's block came from, so that moving content is filtered as well.  The motion is found on the 8-bit
+ * luma of the clip's colour frames by a full-search block matcher.  DESIGN.md section 5 has the specification,
+ * tools/motion_oracle.py states it in numpy.  Integers in the search; float32, every operation rounded once, in the filter.
+ *   depth [n][h][w][c] float32 and g, m_t, cut_t as for cs_temporal_depth; guide [n][h][w][3] float32, the colour frames at
+ *   the depth's size
+ *   code(v)  = uint8(trunc(min(max(v, 0), 1) * 255 + 0.5)), NaN -> 0;  L = (77 code(R) + 150 code(G) + 29 code(B) + 128) >> 8
+ *   blocks   16 x 16 from the top-left corner, clipped at the right and bottom edge: Hb = ceil(h / 16), Wb = ceil(w / 16)
+ *   v_t(b)   the (dx, dy) with |dx|, |dy| <= search_range for which every pixel of the block, displaced, lies inside the frame, that
+ *            minimises (sad + smoothness (|dx| + |dy|), |dx| + |dy|, |dy|, dy, dx) lexicographically;
+ *            sad = sum over the block of |L_t(p) - L_{t-1}(p + (dx, dy))|
+ *   matched  sad(v) <= match_threshold * (the block's pixel count)
+ *   q        = y_{t-1}(p + v_t(block(p)))
+ *   y_t(p)   = g_t(p)  if cut_t, the block is unmatched or !(|g_t(p) - q| < motion_threshold),  else  q + alpha * (g_t(p) - q)
+ * out [n][h][w] float32 = y; m_out [n] float32; cut_out [n] int32; vec_out [n][Hb][Wb][2] int8 (dx, dy); sad_out [n][Hb][Wb]
+ * int32; matched_out [n][Hb][Wb] uint8 (0 / 1).  The vectors of a cut frame are computed all the same.  The state -- state_prev_raw,
+ * state_prev [h][w] float32, state_prev_luma [h][w] uint8 and state_valid, one int32, all in DEVICE memory -- is read and then
+ * overwritten with the last frame's g, y and L and with 1, so a clip fed in sub-batches gives bit for bit what one call gives; the
+ * caller zeroes *state_valid to start a clip.  Frame 0 without a valid state is a cut with m = 0, vectors and SADs 0, every block
+ * matched.  With search_range 0 and match_threshold 255, out, m_out, cut_out and the two float state arrays are cs_temporal_depth's
+ * bit for bit.  alpha in [0, 1], the thresholds >= 0 (+inf allowed), search_range 0..32, smoothness 0..4096, match_threshold
+ * 0..255, else CS_EINVAL, as for a null pointer, a non-positive size, a buffer of 4-byte elements off the 4-byte grid, or any two
+ * buffers that overlap.  CS_ELIMIT: n > 65535 or h * w >= 2^31.  CS_EWORKSPACE: workspace_bytes <
+ * cs_motion_depth_workspace_bytes(n, h, w, c, search_range) (0 for non-positive sizes or a search_range out of range).  Every
+ * refusal precedes the first launch; the 3 + n launches (and, for n == 1, one device-to-device copy) go to `stream`, nothing waits
+ * for the device, nothing is allocated, and the call can be captured into a graph.
+ */
+CS_API size_t cs_motion_depth_workspace_bytes(int n, int h, int w, int c, int search_range);
+CS_API int cs_motion_depth(const float *depth, const float *guide, int n, int h, int w, int c, double alpha, double motion_threshold,
+                           double cut_threshold, int search_range, int smoothness, int match_threshold, float *state_prev_raw,
+                           float *state_prev, uint8_t *state_prev_luma, int32_t *state_valid, float *out, float *m_out,
+                           int32_t *cut_out, int8_t *vec_out, int32_t *sad_out, uint8_t *matched_out, void *workspace,
+                           size_t workspace_bytes, void *stream);
+
+/*
  * Depth range clipping of a video batch (not in the reference, which normalises every frame by its own extremes, so a few outlier
  * pixels flatten the scene and flickering extremes make it pump): two order statistics of the gray depth per frame, smoothed
  * along t, and a clamp to them, run in front of cs_generate.  DESIGN.md section 5 has the specification, tools/range_oracle.py
