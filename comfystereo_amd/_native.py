@@ -204,6 +204,9 @@ SIGNATURES = {
     # motion-compensated temporal depth stabilisation of a video batch
     "cs_motion_depth_workspace_bytes": (_size, [_int] * 5),
     "cs_motion_depth": (_int, [_vp] * 2 + [_int] * 4 + [_dbl] * 3 + [_int] * 3 + [_vp] * 11 + [_size, _vp]),
+    # the same with a coarse-to-fine motion search on a luma pyramid
+    "cs_motion_depth_pyramid_workspace_bytes": (_size, [_int] * 5),
+    "cs_motion_depth_pyramid": (_int, [_vp] * 2 + [_int] * 4 + [_dbl] * 3 + [_int] * 3 + [_vp] * 11 + [_size, _vp]),
     # depth range clipping of a video batch
     "cs_depth_range_workspace_bytes": (_size, [_int] * 4),
     "cs_depth_range": (_int, [_vp] + [_int] * 6 + [_dbl, _int] + [_vp] * 10 + [_size, _vp]),

@@ -13,6 +13,7 @@
 #include "cs_kernels.h"
 #include "cs_latent.h"
 #include "cs_motiondepth.h"
+#include "cs_motionpyramid.h"
 
 namespace cs {
 
@@ -1944,6 +1945,37 @@ int cs_motion_depth(const float* depth, const float* guide, int n, int h, int w,
                                        smoothness, match_threshold, state_prev_raw, state_prev, state_prev_luma, state_valid, out, m_out,
                                        cut_out, vec_out, sad_out, matched_out, workspace, (hipStream_t)stream);
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_motion_depth");
+}
+
+size_t cs_motion_depth_pyramid_workspace_bytes(int n, int h, int w, int c, int search_range) {
+    return (n <= 0 || h <= 0 || w <= 0 || c <= 0 || pyramid_args_error(search_range, 0, 0)) ? 0 : pyramid_workspace_bytes(n, h, w);
+}
+
+int cs_motion_depth_pyramid(const float* depth, const float* guide, int n, int h, int w, int c, double alpha, double motion_threshold,
+                            double cut_threshold, int search_range, int smoothness, int match_threshold, float* state_prev_raw,
+                            float* state_prev, uint8_t* state_prev_luma, int32_t* state_valid, float* out, float* m_out, int32_t* cut_out,
+                            int8_t* vec_out, int32_t* sad_out, uint8_t* matched_out, void* workspace, size_t workspace_bytes, void* stream) {
+    const size_t frame = (size_t)h * w, px = (size_t)n * frame, need = cs_motion_depth_pyramid_workspace_bytes(n, h, w, c, search_range);
+    const size_t blocks = (size_t)n * motion_blocks(h) * motion_blocks(w);
+    // (cs_motion_depth's table: the ten buffers of 4-byte elements first)
+    const span buf[13] = {{depth, px * c * 4}, {guide, px * 3 * 4}, {out, px * 4}, {state_prev_raw, frame * 4}, {state_prev, frame * 4},
+                          {state_valid, 4}, {m_out, (size_t)n * 4}, {cut_out, (size_t)n * 4}, {sad_out, blocks * 4}, {workspace, need},
+                          {state_prev_luma, frame}, {vec_out, blocks * 2}, {matched_out, blocks}};
+    if (any_null(buf, 13)) return fail(CS_EINVAL, "null pointer");
+    if (n <= 0 || h <= 0 || w <= 0 || c <= 0) return fail(CS_EINVAL, "non-positive size");
+    if (!(alpha >= 0.0 && alpha <= 1.0)) return fail(CS_EINVAL, "cs_motion_depth_pyramid: alpha must lie in [0, 1]");
+    if (!(motion_threshold >= 0.0)) return fail(CS_EINVAL, "cs_motion_depth_pyramid: motion_threshold must be >= 0 (+inf allowed)");
+    if (!(cut_threshold >= 0.0)) return fail(CS_EINVAL, "cs_motion_depth_pyramid: cut_threshold must be >= 0 (+inf allowed)");
+    if (const char* msg = pyramid_args_error(search_range, smoothness, match_threshold)) return fail_named(CS_EINVAL, "cs_motion_depth_pyramid", msg);
+    if (misaligned(4, buf, 10)) return fail(CS_EINVAL, "cs_motion_depth_pyramid: every buffer of 4-byte elements needs 4-byte alignment");
+    if (int rc = depth_limits("cs_motion_depth_pyramid", n, h, w)) return rc;
+    if (any_overlap(buf, 13, nullptr, 0))
+        return fail(CS_EINVAL, "cs_motion_depth_pyramid: depth, guide, out, the state arrays, the per-frame and per-block outputs and workspace must not overlap");
+    if (workspace_bytes < need) return fail(CS_EWORKSPACE, "workspace too small");
+    hipError_t e = launch_motion_depth_pyramid(depth, guide, n, h, w, c, (float)alpha, (float)motion_threshold, (float)cut_threshold,
+                                               search_range, smoothness, match_threshold, state_prev_raw, state_prev, state_prev_luma,
+                                               state_valid, out, m_out, cut_out, vec_out, sad_out, matched_out, workspace, (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_motion_depth_pyramid");
 }
 
 size_t cs_depth_range_workspace_bytes(int n, int h, int w, int c) {

@@ -390,6 +390,14 @@ hipError_t launch_motion_depth(const float* depth, const float* guide, int n, in
                                float cut_thr, int search_range, int smoothness, int match_thr, float* prev_raw, float* prev,
                                uint8_t* prev_luma, int32_t* valid, float* out, float* m, int32_t* cut, int8_t* vec, int32_t* sad,
                                uint8_t* matched, void* workspace, hipStream_t stream);
+// cs_motionpyramid.hip (the same filter with a coarse-to-fine search on a three-level luma pyramid: cs_motion_depth_pyramid).  The
+// arguments of launch_motion_depth, search_range a multiple of 4 in 4..120; workspace: pyramid_workspace_bytes(n, h, w) bytes
+// (cs_motionpyramid.h PyramidViews)
+size_t pyramid_workspace_bytes(int n, int h, int w);
+hipError_t launch_motion_depth_pyramid(const float* depth, const float* guide, int n, int h, int w, int c, float alpha, float motion_thr,
+                                       float cut_thr, int search_range, int smoothness, int match_thr, float* prev_raw, float* prev,
+                                       uint8_t* prev_luma, int32_t* valid, float* out, float* m, int32_t* cut, int8_t* vec, int32_t* sad,
+                                       uint8_t* matched, void* workspace, hipStream_t stream);
 // cs_depthrange.hip (depth range clipping: cs_depth_range).  workspace: range_workspace_bytes(n) bytes, the frames' digit
 // histograms and selections; cut: null or [n] int32; the state's three words live in device memory
 size_t range_workspace_bytes(int n);

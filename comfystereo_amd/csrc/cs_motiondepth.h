@@ -43,6 +43,11 @@ inline const char* motion_args_error(int search_range, int smoothness, int match
 
 inline int motion_blocks(int size) { return (size + MD_BLOCK - 1) / MD_BLOCK; }
 
+// the mask of a dword's first `count` bytes, count clamped to 0..4
+__host__ __device__ inline uint32_t low_bytes(int count) {
+    return count >= 4 ? 0xffffffffu : (count <= 0 ? 0u : (1u << (8 * count)) - 1u);
+}
+
 // The workspace's blocks, each on a 256-byte boundary (base == nullptr: the sizes alone):
 //   partial  [n][P] float32, the statistic's partial sums (cs_temporalstat.h)
 //   luma     [n + 1][h][pitch] uint8, pitch = w rounded up to 4: frame 0 is the state's, frame t + 1 is guide frame t
@@ -66,5 +71,15 @@ inline MotionViews motion_views(void* base, int n, int h, int w) {
     v.bytes = o;
     return v;
 }
+
+// cs_motiondepth.hip: the pass in its three parts (launch_motion_depth is the three in a row; cs_motionpyramid.hip puts a search of
+// its own between the first and the last).  luma: planes [n + 1][h][pitch] of h x w pixels; V: the workspace's views.
+void launch_motion_luma(const float* guide, int n, int h, int w, int pitch, const uint8_t* prev_luma, const int32_t* valid, uint8_t* luma,
+                        hipStream_t stream);
+void launch_motion_search(const uint8_t* luma, int n, int h, int w, int pitch, int search_range, int smoothness, int match_thr,
+                          const int32_t* valid, int8_t* vec, int32_t* sad, uint8_t* matched, hipStream_t stream);
+hipError_t launch_motion_filter(const float* depth, int n, int h, int w, int c, float alpha, float motion_thr, float cut_thr, float* prev_raw,
+                                float* prev, uint8_t* prev_luma, int32_t* valid, float* out, float* m, int32_t* cut, const int8_t* vec,
+                                const uint8_t* matched, const MotionViews& V, hipStream_t stream);
 
 }  // namespace cs

@@ -94,10 +94,6 @@ __global__ void __launch_bounds__(MD_THREADS) k_motion_luma(const float* __restr
     luma[(size_t)f * quads + q] = pk;
 }
 
-__device__ __forceinline__ uint32_t low_bytes(int count) {   // the mask of a dword's first `count` bytes, count clamped to 0..4
-    return count >= 4 ? 0xffffffffu : (count <= 0 ? 0u : (1u << (8 * count)) - 1u);
-}
-
 __global__ void __launch_bounds__(MD_THREADS) k_motion_search(const uint8_t* __restrict__ luma, int h, int w, int pitch, int S,
                                                              int smoothness, int match_thr, const int32_t* __restrict__ valid,
                                                              int hb, int wb, int groups, int8_t* __restrict__ vec,
@@ -242,22 +238,34 @@ __global__ void __launch_bounds__(MD_THREADS) k_motion_filter(const float* g_in,
 
 size_t motion_workspace_bytes(int n, int h, int w) { return motion_views(nullptr, n, h, w).bytes; }
 
-hipError_t launch_motion_depth(const float* depth, const float* guide, int n, int h, int w, int c, float alpha, float motion_thr,
-                               float cut_thr, int search_range, int smoothness, int match_thr, float* prev_raw, float* prev,
-                               uint8_t* prev_luma, int32_t* valid, float* out, float* m, int32_t* cut, int8_t* vec, int32_t* sad,
-                               uint8_t* matched, void* workspace, hipStream_t stream) {
-    const MotionViews V = motion_views(workspace, n, h, w);
-    const size_t hw = (size_t)h * w, quads = (size_t)h * (V.pitch / 4);
-    const int pitch = (int)V.pitch, hb = motion_blocks(h), wb = motion_blocks(w), groups = (wb + MD_GROUP - 1) / MD_GROUP;
-    const dim3 block(MD_THREADS), qgrid((unsigned)((quads + MD_THREADS - 1) / MD_THREADS));
-    // the luma of the whole batch, then every frame pair's vectors: they depend on the guide alone
-    const dim3 lgrid(qgrid.x, (unsigned)n + 1);
+// The pass in its three parts, which cs_motionpyramid.hip launches as well, with a search of its own between the first and the last.
+
+// the luma of the whole batch: luma [n + 1][h][pitch], frame 0 the state's
+void launch_motion_luma(const float* guide, int n, int h, int w, int pitch, const uint8_t* prev_luma, const int32_t* valid, uint8_t* luma,
+                        hipStream_t stream) {
+    const size_t quads = (size_t)h * (pitch / 4);
+    const dim3 block(MD_THREADS), lgrid((unsigned)((quads + MD_THREADS - 1) / MD_THREADS), (unsigned)n + 1);
     if (vec4_path((size_t)w, {guide}))
-        hipLaunchKernelGGL(k_motion_luma<true>, lgrid, block, 0, stream, guide, h, w, pitch, (const uint8_t*)prev_luma, (const int32_t*)valid, (uint32_t*)V.luma);
+        hipLaunchKernelGGL(k_motion_luma<true>, lgrid, block, 0, stream, guide, h, w, pitch, prev_luma, valid, (uint32_t*)luma);
     else
-        hipLaunchKernelGGL(k_motion_luma<false>, lgrid, block, 0, stream, guide, h, w, pitch, (const uint8_t*)prev_luma, (const int32_t*)valid, (uint32_t*)V.luma);
-    hipLaunchKernelGGL(k_motion_search, dim3((unsigned)groups * (unsigned)hb, (unsigned)n), block, 0, stream, (const uint8_t*)V.luma, h, w, pitch,
-                       search_range, smoothness, match_thr, (const int32_t*)valid, hb, wb, groups, vec, sad, matched);
+        hipLaunchKernelGGL(k_motion_luma<false>, lgrid, block, 0, stream, guide, h, w, pitch, prev_luma, valid, (uint32_t*)luma);
+}
+
+// every frame pair's vectors by full search on planes [n + 1][h][pitch] of h x w pixels: they depend on the guide alone
+void launch_motion_search(const uint8_t* luma, int n, int h, int w, int pitch, int search_range, int smoothness, int match_thr,
+                          const int32_t* valid, int8_t* vec, int32_t* sad, uint8_t* matched, hipStream_t stream) {
+    const int hb = motion_blocks(h), wb = motion_blocks(w), groups = (wb + MD_GROUP - 1) / MD_GROUP;
+    hipLaunchKernelGGL(k_motion_search, dim3((unsigned)groups * (unsigned)hb, (unsigned)n), dim3(MD_THREADS), 0, stream, luma, h, w, pitch,
+                       search_range, smoothness, match_thr, valid, hb, wb, groups, vec, sad, matched);
+}
+
+// m, cut and the filter along the vectors; V: the workspace's partial, luma and yprev
+hipError_t launch_motion_filter(const float* depth, int n, int h, int w, int c, float alpha, float motion_thr, float cut_thr, float* prev_raw,
+                                float* prev, uint8_t* prev_luma, int32_t* valid, float* out, float* m, int32_t* cut, const int8_t* vec,
+                                const uint8_t* matched, const MotionViews& V, hipStream_t stream) {
+    const size_t hw = (size_t)h * w, quads = (size_t)h * (V.pitch / 4);
+    const int pitch = (int)V.pitch, hb = motion_blocks(h), wb = motion_blocks(w);
+    const dim3 block(MD_THREADS), qgrid((unsigned)((quads + MD_THREADS - 1) / MD_THREADS));
     // m and cut, and g into `out` for C != 1: the plain filter's statistic, on the plain filter's choice of its path
     launch_temporal_stat(depth, n, hw, c, cut_thr, prev_raw, valid, out, m, cut, V.partial, vec4_path(hw, {depth, out, prev_raw, prev}), stream);
     const float* y_first = prev;
@@ -274,13 +282,24 @@ hipError_t launch_motion_depth(const float* depth, const float* guide, int n, in
         const uint8_t* lum = V.luma + (size_t)(t + 1) * h * V.pitch;
         const int last = t == n - 1;
 #define CS_MOTION_FILTER(VEC) \
-        hipLaunchKernelGGL(k_motion_filter<VEC>, qgrid, block, 0, stream, g_in, y_prev, out + (size_t)t * hw, h, w, (const int8_t*)vec + 2 * t * blocks, \
-                           (const uint8_t*)matched + t * blocks, wb, (const int32_t*)cut + t, alpha, motion_thr, last, lum, pitch, prev_raw, prev,   \
+        hipLaunchKernelGGL(k_motion_filter<VEC>, qgrid, block, 0, stream, g_in, y_prev, out + (size_t)t * hw, h, w, vec + 2 * t * blocks, \
+                           matched + t * blocks, wb, (const int32_t*)cut + t, alpha, motion_thr, last, lum, pitch, prev_raw, prev,        \
                            prev_luma, valid)
         if (fvec) CS_MOTION_FILTER(true); else CS_MOTION_FILTER(false);
 #undef CS_MOTION_FILTER
     }
     return hipGetLastError();
+}
+
+hipError_t launch_motion_depth(const float* depth, const float* guide, int n, int h, int w, int c, float alpha, float motion_thr,
+                               float cut_thr, int search_range, int smoothness, int match_thr, float* prev_raw, float* prev,
+                               uint8_t* prev_luma, int32_t* valid, float* out, float* m, int32_t* cut, int8_t* vec, int32_t* sad,
+                               uint8_t* matched, void* workspace, hipStream_t stream) {
+    const MotionViews V = motion_views(workspace, n, h, w);
+    launch_motion_luma(guide, n, h, w, (int)V.pitch, prev_luma, valid, V.luma, stream);
+    launch_motion_search(V.luma, n, h, w, (int)V.pitch, search_range, smoothness, match_thr, valid, vec, sad, matched, stream);
+    return launch_motion_filter(depth, n, h, w, c, alpha, motion_thr, cut_thr, prev_raw, prev, prev_luma, valid, out, m, cut, vec, matched, V,
+                                stream);
 }
 
 }  // namespace cs

@@ -572,10 +572,17 @@ def motion_depth_detail(depth, guide, state=None, alpha=0.5, motion_threshold=0.
     frames (a new one is returned).  A clip fed in sub-batches gives bit for bit what one call gives; search_range 0 with
     match_threshold 255 gives temporal_depth's y, m, cut and float state.  Nothing waits for the device; a call with a given state
     can be captured into a graph."""
-    L = _native.lib()
     _frames("depth", depth)
     _motion_guide(guide, depth)
     search_range, smoothness, match_threshold = _motion_args(search_range, smoothness, match_threshold)
+    return _motion_launch("cs_motion_depth", depth, guide, state, alpha, motion_threshold, cut_threshold, search_range, smoothness,
+                          match_threshold)
+
+
+def _motion_launch(entry, depth, guide, state, alpha, motion_threshold, cut_threshold, search_range, smoothness, match_threshold):
+    """What motion_depth_detail and motion_depth_pyramid_detail share behind their refusals: the device checks, the state, the
+    outputs, the workspace of `entry` and its launch."""
+    L = _native.lib()
     _on_gpu(depth, no_gpu_error=True)
     _same_device(("depth", depth), ("guide", guide))
     n, h, w, c = depth.shape
@@ -588,11 +595,48 @@ def motion_depth_detail(depth, guide, state=None, alpha=0.5, motion_threshold=0.
     vec = torch.empty((n, hb, wb, 2), dtype=torch.int8, device=dev)
     sad = torch.empty((n, hb, wb), dtype=torch.int32, device=dev)
     matched = torch.empty((n, hb, wb), dtype=torch.uint8, device=dev)
-    ws, nb = _workspace(L.cs_motion_depth_workspace_bytes(n, h, w, c, search_range), dev)
-    _launch(dev, L.cs_motion_depth, _ptr(depth), _ptr(guide), n, h, w, c, float(alpha), float(motion_threshold), float(cut_threshold),
+    ws, nb = _workspace(getattr(L, entry + "_workspace_bytes")(n, h, w, c, search_range), dev)
+    _launch(dev, getattr(L, entry), _ptr(depth), _ptr(guide), n, h, w, c, float(alpha), float(motion_threshold), float(cut_threshold),
             search_range, smoothness, match_threshold, _ptr(state.prev_raw), _ptr(state.prev), _ptr(state.prev_luma), _ptr(state.valid),
             _ptr(y), _ptr(m), _ptr(cut), _ptr(vec), _ptr(sad), _ptr(matched), _ptr(ws), nb)
     return y, m, cut, state, vec, matched, sad
+
+
+# ---- the same filter with a coarse-to-fine motion search (cs_motion_depth_pyramid) ---------------------------
+PYRAMID_SEARCH = (4, 120, 4)   # search_range: from, to, step
+
+
+def _pyramid_args(search_range, smoothness, match_threshold):
+    """The refusals of motion_depth_pyramid's three integer parameters -> them as ints."""
+    lo, hi, step = PYRAMID_SEARCH
+    v = search_range
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or int(v) != v or not lo <= int(v) <= hi or int(v) % step:
+        raise ValueError(f"search_range must be a multiple of {step} in {lo}..{hi}, got {v}")
+    return (int(v),) + _motion_args(0, smoothness, match_threshold)[1:]
+
+
+def motion_depth_pyramid(depth, guide, state=None, alpha=0.5, motion_threshold=0.1, cut_threshold=0.08, search_range=64, smoothness=32,
+                         match_threshold=12):
+    """motion_depth_pyramid_detail without the SADs: -> (y, m, cut, state, vec, matched)."""
+    return motion_depth_pyramid_detail(depth, guide, state, alpha, motion_threshold, cut_threshold, search_range, smoothness,
+                                       match_threshold)[:6]
+
+
+def motion_depth_pyramid_detail(depth, guide, state=None, alpha=0.5, motion_threshold=0.1, cut_threshold=0.08, search_range=64,
+                                smoothness=32, match_threshold=12):
+    """cs_motion_depth_pyramid: motion_depth_detail's arguments, returns, filter and state (a MotionState: the two may continue
+    each other's clip), with the vectors found coarse to fine on a three-level luma pyramid, so that they reach |dx|, |dy| <=
+    search_range + 3, search_range a multiple of 4 in 4..120: a full search over search_range / 4 on the quarter-size luma, then at
+    most 46 candidates per block on the half- and the full-size luma (twice the vectors of the block's parent and of the parent's
+    four neighbours, +-1, and (0, 0)).  tools/motion_pyramid_oracle.py states it.  Unlike the full search it can miss the best
+    vector: it follows what the coarse levels found.  The defaults are starting values that nobody has tuned on footage.  A clip
+    fed in sub-batches gives bit for bit what one call gives; nothing waits for the device; a call with a given state can be
+    captured into a graph."""
+    _frames("depth", depth)
+    _motion_guide(guide, depth)
+    search_range, smoothness, match_threshold = _pyramid_args(search_range, smoothness, match_threshold)
+    return _motion_launch("cs_motion_depth_pyramid", depth, guide, state, alpha, motion_threshold, cut_threshold, search_range, smoothness,
+                          match_threshold)
 
 
 # ---- depth range clipping of a video batch (cs_depth_range; DESIGN.md section 5) ------------------------------------------------

@@ -410,6 +410,25 @@ def stabilize_depth_motion(depth, image, state=None, alpha=0.5, motion_threshold
     frames with the state carried on the device; the result is bit for bit the one of a single call.  cuts: a list that receives
     every sub-batch's cut flags (int32 [k]); unmatched: one that receives every sub-batch's unmatched-block flags (uint8
     [k,Hb,Wb], 1 where a block found no match and passed unfiltered), both on the input's device."""
+    return _stabilize_with_motion(engine.motion_depth, engine._motion_args, depth, image, state, alpha, motion_threshold, cut_threshold,
+                                  search_range, smoothness, match_threshold, batch_size, cuts, unmatched)
+
+
+def stabilize_depth_motion_pyramid(depth, image, state=None, alpha=0.5, motion_threshold=0.1, cut_threshold=0.08, search_range=64,
+                                   smoothness=32, match_threshold=12, batch_size=16, cuts=None, unmatched=None):
+    """stabilize_depth_motion with the motion found coarse to fine on a three-level luma pyramid (engine.motion_depth_pyramid,
+    cs_motion_depth_pyramid), for motion beyond the full search's 32 pixels: search_range is a multiple of 4 in 4..120 and the
+    vectors reach search_range + 3 pixels at the depth's resolution.  Every other argument, the resize of an image at another size,
+    the sub-batches, the state (an engine.MotionState), cuts, unmatched and the returns are stabilize_depth_motion's.  The
+    defaults are starting values that nobody has tuned on footage."""
+    return _stabilize_with_motion(engine.motion_depth_pyramid, engine._pyramid_args, depth, image, state, alpha, motion_threshold,
+                                  cut_threshold, search_range, smoothness, match_threshold, batch_size, cuts, unmatched)
+
+
+def _stabilize_with_motion(motion_depth, check_args, depth, image, state, alpha, motion_threshold, cut_threshold, search_range, smoothness,
+                           match_threshold, batch_size, cuts, unmatched):
+    """stabilize_depth_motion and stabilize_depth_motion_pyramid: the engine function and the refusals of its three integer
+    parameters are what differs."""
     frames = _DepthFrames(depth).in_batches_of(batch_size)
     if not isinstance(image, torch.Tensor):
         image = torch.from_numpy(np.ascontiguousarray(image))
@@ -419,15 +438,15 @@ def stabilize_depth_motion(depth, image, state=None, alpha=0.5, motion_threshold
         raise ValueError(f"image has {image.shape[0]} frames, depth has {frames.n}")
     if frames.depth.device != image.device:
         raise ValueError("image and depth must be on the same device")
-    engine._motion_args(search_range, smoothness, match_threshold)   # (the refusals, before anything is uploaded)
+    check_args(search_range, smoothness, match_threshold)   # (the refusals, before anything is uploaded)
     h, w = frames.d4.shape[1:3]
 
     def filtered(b0, b1, chunk, img):
         nonlocal state
         if tuple(img.shape[1:3]) != (h, w):
             img = engine.pil_resize(img, (w, h), f32="nhwc", codes=True)[1]
-        y, _, cut, state, _, matched = engine.motion_depth(chunk, img, state, alpha, motion_threshold, cut_threshold, search_range,
-                                                           smoothness, match_threshold)
+        y, _, cut, state, _, matched = motion_depth(chunk, img, state, alpha, motion_threshold, cut_threshold, search_range, smoothness,
+                                                    match_threshold)
         return y, cut, 1 - matched
 
     y, flags = frames.run(filtered, beside=(image,))

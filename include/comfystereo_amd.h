@@ -721,6 +721,36 @@ CS_API int cs_motion_depth(const float *depth, const float *guide, int n, int h,
                            size_t workspace_bytes, void *stream);
 
 /*
+ * cs_motion_depth with a wide-range, coarse-to-fine motion search (not in the reference): the same filter, outputs, state and
+ * buffers, but the vectors reach |dx|, |dy| <= search_range + 3 with search_range a multiple of 4 in 4..120 (the full search stops
+ * at 32 and costs (2 S + 1)^2 SADs per block).  DESIGN.md section 5 has the specification, tools/motion_pyramid_oracle.py states
+ * it in numpy.
+ *   planes     L0 = L above;  L(k+1)(y, x) = (a + b + c + d + 2) >> 2 over the 2 x 2 cell of Lk, Lk edge-replicated to even sizes:
+ *              ceil(h_k / 2) x ceil(w_k / 2), levels 0, 1, 2
+ *   blocks     16 x 16 from the top-left corner of every level's own plane, clipped at the right and bottom edge; the parent of
+ *              level-k block (by, bx) is level-(k+1) block (by >> 1, bx >> 1)
+ *   level 2    cs_motion_depth's full search on L2 with search_range / 4
+ *   level 1, 0 a block's candidates are (0, 0) and 2 v + (ex, ey), |ex|, |ey| <= 1, for v the level above's vector of its parent and
+ *              of the parent's up, down, left and right neighbours that exist: at most 46 distinct ones.  Among those for which
+ *              every pixel of the block, displaced, lies inside the level's plane the winner minimises
+ *              (sad + smoothness (|dx| + |dy|), |dx| + |dy|, |dy|, dy, dx) on the level's own vector and SAD
+ *   vec_out, sad_out (without the penalty) and matched_out = sad <= match_threshold * (the block's pixel count) are level 0's
+ * The state is cs_motion_depth's (the two calls may continue each other's clip); the pyramid of its luma is rebuilt per call, so a
+ * clip fed in sub-batches gives bit for bit what one call gives.  Frame 0 without a valid state, the vectors of a cut frame, the
+ * ranges of the other parameters, every refusal and its code are cs_motion_depth's; search_range outside its set is CS_EINVAL.
+ * CS_EWORKSPACE: workspace_bytes < cs_motion_depth_pyramid_workspace_bytes(n, h, w, c, search_range) (0 for non-positive sizes or a
+ * search_range outside the set).  Every refusal precedes the first launch; the 6 + n launches (and, for n == 1, one
+ * device-to-device copy) go to `stream`, nothing waits for the device, nothing is allocated, no atomics, and the call can be
+ * captured into a graph.
+ */
+CS_API size_t cs_motion_depth_pyramid_workspace_bytes(int n, int h, int w, int c, int search_range);
+CS_API int cs_motion_depth_pyramid(const float *depth, const float *guide, int n, int h, int w, int c, double alpha,
+                                   double motion_threshold, double cut_threshold, int search_range, int smoothness, int match_threshold,
+                                   float *state_prev_raw, float *state_prev, uint8_t *state_prev_luma, int32_t *state_valid, float *out,
+                                   float *m_out, int32_t *cut_out, int8_t *vec_out, int32_t *sad_out, uint8_t *matched_out,
+                                   void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Depth range clipping of a video batch (not in the reference, which normalises every frame by its own extremes, so a few outlier
  * pixels flatten the scene and flickering extremes make it pump): two order statistics of the gray depth per frame, smoothed
  * along t, and a clamp to them, run in front of cs_generate.  DESIGN.md section 5 has the specification, tools/range_oracle.py

@@ -100,6 +100,28 @@ def clip(n, h, w, c):
     return depth, guide
 
 
+def pyramid_leg(args, sizes):
+    """--search pyramid: engine.motion_depth_pyramid at R = 32 / 64 / 120 next to engine.motion_depth at S = 16 / 32 on the same
+    batch, C = 1; `moved` is the fraction of blocks of frames 1.. on the clip's true vector (3, -2)."""
+    rows = []
+    prm = (0.5, 0.1, 0.6)
+    for name in args.sizes.split(","):
+        h, w = sizes[name]
+        depth, guide = clip(args.frames, h, w, 1)
+        for search, fn, ranges in (("full", engine.motion_depth, (16, 32)), ("pyramid", engine.motion_depth_pyramid, (32, 64, 120))):
+            for R in ranges:
+                state = engine.MotionState(h, w, depth.device)
+                vec = fn(depth, guide, state, *prm, R, 32, 12)[4]
+                on_true = float(((vec[1:, ..., 0] == 3) & (vec[1:, ..., 1] == -2)).float().mean())
+                ms = timed(lambda: fn(depth, guide, state, *prm, R, 32, 12), args.reps)
+                rows.append(dict(size=name, frames=args.frames, c=1, search=search, search_range=R, hip_ms=round(ms, 3),
+                                 blocks_on_true_vector=round(on_true, 4)))
+                print(json.dumps(rows[-1]))
+        del depth, guide
+        torch.cuda.empty_cache()
+    print(json.dumps({"motion_bench_pyramid": rows}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=64)
@@ -107,8 +129,12 @@ def main():
     ap.add_argument("--stock-frames", type=int, default=3)
     ap.add_argument("--sizes", default="1080p,4K")
     ap.add_argument("--ranges", default="8,16,32")
+    ap.add_argument("--search", default="full", choices=("full", "pyramid"),
+                    help="pyramid: time the coarse-to-fine search at R = 32 / 64 / 120 next to the full search at S = 16 / 32 instead")
     args = ap.parse_args()
     sizes = {"1080p": (1080, 1920), "4K": (2160, 3840)}
+    if args.search == "pyramid":
+        return pyramid_leg(args, sizes)
     rows = []
     prm = (0.5, 0.1, 0.6)
     for name in args.sizes.split(","):

@@ -146,10 +146,16 @@ def gather(prev, vec):
 
 
 def motion_depth(depth, guide, state=None, alpha=0.5, motion_threshold=0.1, cut_threshold=0.08, search_range=16, smoothness=32,
-                 match_threshold=12):
+                 match_threshold=12, search=None):
     """-> (y float32 [N,H,W], m float64 [N], cut int32 [N], the new State, vec int8 [N,Hb,Wb,2], sad int32 [N,Hb,Wb],
-    matched uint8 [N,Hb,Wb], blended bool [N,H,W]: the pixels that took the blend)."""
-    S, lam, thr = check_params(search_range, smoothness, match_threshold)
+    matched uint8 [N,Hb,Wb], blended bool [N,H,W]: the pixels that took the blend).
+    search: None for the full search above, or another one, search(cur, ref) -> (vec, sad, matched) on two uint8 [H,W] lumas with its
+    own parameters bound and checked (tools/motion_pyramid_oracle.py): the filter around it is stated here alone."""
+    if search is None:
+        S, lam, thr = check_params(search_range, smoothness, match_threshold)
+
+        def search(cur, ref):
+            return motion_search(cur, ref, S, lam, thr)
     g = temporal_oracle.gray(depth)
     lum = luma(guide)
     n, h, w = g.shape
@@ -171,7 +177,7 @@ def motion_depth(depth, guide, state=None, alpha=0.5, motion_threshold=0.1, cut_
             else:
                 m[t] = np.abs(g[t].astype(np.float64) - prev_raw.astype(np.float64)).mean()
                 is_cut = bool(m[t] > ct)
-                vec[t], sad[t], matched[t] = motion_search(lum[t], prev_luma, S, lam, thr)
+                vec[t], sad[t], matched[t] = search(lum[t], prev_luma)
             cut[t] = is_cut
             if is_cut:
                 y[t] = g[t]
